@@ -14,7 +14,9 @@ collectives are the weight broadcast at start-up (flat buckets), the metric redu
 and -- outside the timed region, reported as `end_to_end` -- the gather of every rank's
 decoded audio on rank 0 (BASELINE configs[3]).
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, ramps the context, warms up, times the K steps and prints ONE JSON line on rank 0.  --full also
+measures the secondary figures: per-kernel and roofline timings, the end-to-end and codec legs, and the CPU baselines.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -29,6 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "moss-ttsd_amd"))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
 
 
 def algorithmic_bytes_per_step(cfg, B, L):
@@ -217,6 +220,23 @@ def codec_leg(device, windows=8, T=375, reps=3):
             "vs_f32_mfma_peak": flop / dt / 157.3e12, "windows_per_call": windows, "codes_per_window": T}
 
 
+def dump_outputs(eng, out_dir, steps_done):
+    """What the last timed decode step handed its caller: `ids`, the frame of 8 codec ids it chose for every dialogue
+    [B,8], and the logits they were drawn from, `logits_ch0` [B,V] and `logits_ch1_7` [7,B,Vs] (bf16 values, exact in
+    float32).  Above DUMP_BYTES the logits keep a fixed, seeded sample of the dialogues, listed in `logits_rows`."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids = eng.read_generated(steps_done)[-1].astype(np.float64)
+    l0, l17 = eng.read_logits()
+    B = ids.shape[0]
+    fit = (DUMP_BYTES - ids.nbytes) // ((l0.shape[1] + 7 * l17.shape[2]) * 4)
+    arrays = {"ids": ids, "logits_ch0": l0, "logits_ch1_7": l17}
+    if fit < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, fit, replace=False))
+        arrays.update(logits_ch0=l0[rows], logits_ch1_7=l17[:, rows], logits_rows=rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n):
     """Start `n` ranks of this script (torch.distributed.run, one process per GPU, rendezvous on 127.0.0.1) as a child
     process tree and return its exit code.  The caller has not touched the GPU, and nothing is exec'd over it."""
@@ -294,7 +314,14 @@ def main():
     ap.add_argument("--fake-context", action="store_true",
                     help="PMC/profiling runs only: jump to the target context with mtts_debug_set_kv_len instead of "
                          "ramping (cache content is not meaningful; the result is marked invalid)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures: per-kernel and roofline timings (--profile-steps more "
+                         "steps), the end-to-end and codec legs, the CPU baselines; a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0: sampled ids and logits) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs the engine: not with --dry-run")
 
     # `python bench.py --gpus N` on its own (no launcher around it): start N fresh ranks, one per GPU, before this
     # process makes any GPU call, and hand its exit code back.  Under torchrun (WORLD_SIZE set) this IS one of the ranks.
@@ -337,6 +364,7 @@ def main():
     B, K, W, L = args.batch, args.steps, args.warmup, args.context
     T = args.prompt
     n_real = T - 7
+    # room for the --full profile steps is kept in a plain run too: the timed steps sit at the same KV lengths either way
     ramp = L - n_real - (K + W) - args.profile_steps
     assert ramp >= 0, "context too small for prompt + steps"
 
@@ -385,26 +413,29 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     assert not fin and st == (0 if args.fake_context else ramp) + W + K, (st, fin)
-    # roofline leg: per-kernel HIP events on the launch stream for a few more steps at the same context
-    eng.profile(True)
-    eng.step(args.profile_steps)
-    eng.sync_state()
-    prof = {}
-    for which, nm in ((0, "attn_scores_kernel"), (1, "attn_pv_kernel"), (3, "decode_step")):
-        ms, n, by = eng.profile_read(which)
-        prof[nm] = dict(ms=ms, launches=n, bytes=by)
-    eng.profile(False)
-    # dominant-kernel duration for the roofline: a train of back-to-back launches of each attention pass at the
-    # state the timed region ended in (KV length ~L), two HIP events on the launch stream
-    for ph, nm in ((1, "attn_scores_kernel"), (2, "attn_pv_kernel")):
-        ms, by = eng.attn_bench(ph, 4 * cfg["num_hidden_layers"])
-        prof[nm].update(train_ms=ms, train_bytes=by)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs, st)
+    prof, kv_pack = {}, None
+    if args.full:
+        # roofline leg: per-kernel HIP events on the launch stream for a few more steps at the same context
+        eng.profile(True)
+        eng.step(args.profile_steps)
+        eng.sync_state()
+        for which, nm in ((0, "attn_scores_kernel"), (1, "attn_pv_kernel"), (3, "decode_step")):
+            ms, n, by = eng.profile_read(which)
+            prof[nm] = dict(ms=ms, launches=n, bytes=by)
+        eng.profile(False)
+        # dominant-kernel duration for the roofline: a train of back-to-back launches of each attention pass at the
+        # state the timed region ended in (KV length ~L), two HIP events on the launch stream
+        for ph, nm in ((1, "attn_scores_kernel"), (2, "attn_pv_kernel")):
+            ms, by = eng.attn_bench(ph, 4 * cfg["num_hidden_layers"])
+            prof[nm].update(train_ms=ms, train_bytes=by)
+        try:                       # sealed KV pages: how many of this run's complete pages sealed, which layers read them
+            kv_pack = eng.kv_pack_stats()
+        except Exception:          # engine without sealed pages (MTTS_KV_PACK=0)
+            kv_pack = None
     t_decode_all = t_ramp + dt
     steps_all, _ = eng.sync_state()
-    try:                       # sealed KV pages: how many of this run's complete pages sealed, which layers read them
-        kv_pack = eng.kv_pack_stats()
-    except Exception:          # engine without sealed pages (MTTS_KV_PACK=0)
-        kv_pack = None
 
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     units = torch.tensor([float(B * K * 8)], dtype=torch.float64, device=device)
@@ -420,7 +451,7 @@ def main():
     # rank 0 receives all the audio (mtts.dist.gather_audio: one exact-size buffer per rank over its own xGMI link)
     e2e_sharded = None
     e2e_hung = False
-    if world > 1 and not args.no_codec and not args.fake_context:
+    if args.full and world > 1 and not args.no_codec and not args.fake_context:
         # The leg runs on a helper thread with a deadline: the headline line must be printed even if the codec or the
         # audio exchange (RCCL point-to-point, never run on hardware before the first 8-GPU bench) gets stuck.
         import threading
@@ -478,29 +509,6 @@ def main():
         value = total_ids / dt_max
         frames = value / 8.0
         ms_step = dt_max / K * 1e3
-        dom = max(("attn_scores_kernel", "attn_pv_kernel"), key=lambda k: prof[k]["train_ms"])
-        p = prof[dom]
-        avg_ms = p["train_ms"]
-        bytes_per_launch = p["train_bytes"]
-        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        # HBM traffic per launch from separate --pmc passes of the kernels as they are NOW (tools/pmc_summary.py; FETCH_SIZE
-        # doubled per the gfx950 correction).  Measured at B=32, L~4095: only quoted for that workload, and only from the
-        # file of the round that last touched csrc/attn.hip (r03: sealed pages, template arguments <G, fused, sealed>).
-        traffic, traffic_src = None, None
-        sealed = bool(kv_pack and kv_pack["k_layers_on"] == cfg["num_hidden_layers"] and kv_pack["v_layers_on"] == cfg["num_hidden_layers"])
-        for cand in ("r03_pmc_attention.json",):
-            try:
-                pmc = json.load(open(os.path.join(ROOT, "profiles", cand)))["kernels"]
-                if B == 32 and L == 4096 and not args.layers and sealed:
-                    # the file holds the variants that run at this size (GQA group 2; template arguments after the group:
-                    # fused q/k/v epilogue, sealed pages, ...): the full-context launches are the ones with the most calls
-                    keys = [k for k in pmc if k.startswith(dom + "<2,")]
-                    key = max(keys, key=lambda k: pmc[k]["launches"])
-                    traffic = pmc[key]["hbm_bytes_per_launch"]
-                    traffic_src = "profiles/" + cand + " : " + key
-                    break
-            except Exception:
-                traffic = None
         out = {
             "metric": "audio codec tokens/sec/node (decode, bf16, batch 32 @ 4k ctx)",
             "value": value, "unit": "codec_tokens/s", "n_gpus": world, "ranks": int(nranks.item()),
@@ -522,25 +530,51 @@ def main():
             # token of each dialogue only), against the dense bf16 MFMA peak
             "prefill": {"tokens": int(B * n_real), "tokens_per_s": B * n_real / t_prefill,
                         "tflops": 2.0 * stack_params * B * n_real / t_prefill / 1e12, "mfma_peak_tflops": 2500.0},
-            "roofline": {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "launches": 4 * cfg["num_hidden_layers"],
-                         "how": "train of back-to-back launches at the end-of-run KV length, 2 HIP events on the launch stream; "
-                                "`achieved` counts the ALGORITHMIC bytes (the bf16 K or V of every cached token, SURVEY 8d); the kernel "
-                                "reads complete pages in their sealed 13-bit form (kv_pack), so `traffic` is below them"},
-            "kv_pack": kv_pack,
-            "kernels": {k: {"avg_ms": v["ms"] / max(v["launches"], 1), "launches": v["launches"], "train_ms": v.get("train_ms"),
-                            "GBps": (v["bytes"] / max(v["launches"], 1)) / (v["ms"] / max(v["launches"], 1) * 1e-3) / 1e9
-                            if v["ms"] > 0 and v["bytes"] else None} for k, v in prof.items()},
         }
+        if args.full:
+            dom = max(("attn_scores_kernel", "attn_pv_kernel"), key=lambda k: prof[k]["train_ms"])
+            p = prof[dom]
+            avg_ms = p["train_ms"]
+            bytes_per_launch = p["train_bytes"]
+            achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            # HBM traffic per launch from separate --pmc passes of the kernels as they are NOW (tools/pmc_summary.py; FETCH_SIZE
+            # doubled per the gfx950 correction).  Measured at B=32, L~4095: only quoted for that workload, and only from the
+            # file of the round that last touched csrc/attn.hip (r03: sealed pages, template arguments <G, fused, sealed>).
+            traffic, traffic_src = None, None
+            sealed = bool(kv_pack and kv_pack["k_layers_on"] == cfg["num_hidden_layers"] and kv_pack["v_layers_on"] == cfg["num_hidden_layers"])
+            for cand in ("r03_pmc_attention.json",):
+                try:
+                    pmc = json.load(open(os.path.join(ROOT, "profiles", cand)))["kernels"]
+                    if B == 32 and L == 4096 and not args.layers and sealed:
+                        # the file holds the variants that run at this size (GQA group 2; template arguments after the group:
+                        # fused q/k/v epilogue, sealed pages, ...): the full-context launches are the ones with the most calls
+                        keys = [k for k in pmc if k.startswith(dom + "<2,")]
+                        key = max(keys, key=lambda k: pmc[k]["launches"])
+                        traffic = pmc[key]["hbm_bytes_per_launch"]
+                        traffic_src = "profiles/" + cand + " : " + key
+                        break
+                except Exception:
+                    traffic = None
+            out.update({
+                "roofline": {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                             "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": bytes_per_launch,
+                             "launches": 4 * cfg["num_hidden_layers"],
+                             "how": "train of back-to-back launches at the end-of-run KV length, 2 HIP events on the launch stream; "
+                                    "`achieved` counts the ALGORITHMIC bytes (the bf16 K or V of every cached token, SURVEY 8d); the kernel "
+                                    "reads complete pages in their sealed 13-bit form (kv_pack), so `traffic` is below them"},
+                "kv_pack": kv_pack,
+                "kernels": {k: {"avg_ms": v["ms"] / max(v["launches"], 1), "launches": v["launches"], "train_ms": v.get("train_ms"),
+                                "GBps": (v["bytes"] / max(v["launches"], 1)) / (v["ms"] / max(v["launches"], 1) * 1e-3) / 1e9
+                                if v["ms"] > 0 and v["bytes"] else None} for k, v in prof.items()},
+            })
         if args.layers:
             out["invalid"] = "depth overridden with --layers"
         if args.fake_context:
             out["invalid"] = "context faked with mtts_debug_set_kv_len (profiling run)"
         if e2e_sharded is not None:
             out["end_to_end"] = e2e_sharded
-        if world == 1 and not args.no_codec:
+        if args.full and world == 1 and not args.no_codec:
             if not args.fake_context:
                 out["end_to_end"] = end_to_end_leg(eng, device, B, T, t_prefill, t_decode_all, steps_all)
                 if not args.greedy:
@@ -551,7 +585,7 @@ def main():
             out["codec_decode"]["ms_per_window_at_32_per_call"] = codec_leg(device, windows=32, reps=2)["ms_per_window"]
             if not args.no_cpu_baseline:
                 out["codec_decode"]["cpu_baseline"] = codec_cpu_baseline()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cores = host_cores()
             st_time, per_layer, heads_t = cpu_baseline(cfg, B, L)
             out["cpu_baseline"] = {"value": B * 8 / st_time, "unit": "codec_tokens/s", "cores": cores, "kind": "port",

@@ -3,7 +3,7 @@
 VAR=$1; A=$2; B=$3; shift 3
 for i in 1 2; do
   for v in $A $B; do
-    env $VAR=$v python bench.py --steps 96 --warmup 16 --fake-context --no-codec --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --steps 96 --warmup 16 --fake-context --no-codec --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -4,7 +4,7 @@
 A=$1; B=$2; shift 2
 for v in "$A" "$B" "$A" "$B"; do
   MTTS_BUILD_FLAGS="$v" python moss-ttsd_amd/build.py --force > /dev/null 2>&1 || { echo "build failed for '$v'"; exit 1; }
-  python bench.py --steps 96 --warmup 16 --fake-context --no-codec --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  python bench.py --full --steps 96 --warmup 16 --fake-context --no-codec --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

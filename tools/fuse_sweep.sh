@@ -3,7 +3,7 @@
 for bc in "32 4096" "64 4096" "128 2048" "16 4096"; do
   set -- $bc
   for v in 1024 1000000; do
-    MTTS_FUSE_QKV_MAX=$v python bench.py --steps 64 --warmup 16 --fake-context --no-codec --no-cpu-baseline --batch $1 --context $2 2>/dev/null | python -c "
+    MTTS_FUSE_QKV_MAX=$v python bench.py --full --steps 64 --warmup 16 --fake-context --no-codec --no-cpu-baseline --batch $1 --context $2 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

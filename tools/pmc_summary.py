@@ -29,7 +29,7 @@ for k, v in fetch.items():
     f_kb, w_kb = sum(top) / len(top), sum(wtop) / len(wtop)
     out[k] = {"launches": len(v), "FETCH_SIZE_KB_raw": f_kb, "WRITE_SIZE_KB": w_kb,
               "hbm_bytes_per_launch": int((2 * f_kb + w_kb) * 1024)}
-json.dump({"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --output-format csv -- python3 bench.py --fake-context --layers 2 "
+json.dump({"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --output-format csv -- python3 bench.py --full --fake-context --layers 2 "
            "--prompt 40 --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-codec (two separate passes)",
            "note": "B=32 rows at KV length ~4095, one launch = one layer; see tools/pmc_summary.py for the correction",
            "kernels": out}, open(sys.argv[3], "w"), indent=1)
