@@ -152,6 +152,20 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* host_id
 /* Philox row ids of the rows of the NEXT mtts_begin / mtts_generate (consumed by it; default 0..B-1): one rank's share of
  * a sharded batch draws what its rows would draw inside the whole batch (host_row_ids int32 [n], n = that call's B). */
 int32_t mtts_set_row_ids(MttsEngine* e, const int32_t* host_row_ids, int32_t n);
+/* Takes per prompt of the NEXT mtts_begin / mtts_generate (consumed by it, failures included; default 1): HF
+ * generate(num_return_sequences=n) with sampling (GenerationMixin._expand_inputs_for_generation repeat-interleaves the
+ * batch).  B stays the number of prompts; the run has B*n rows, row b*n+j is take j of prompt b, and every per-row buffer
+ * of the run is in that row space (output ids, mtts_set_row_ids, mtts_read_generated / _logits / _seq_state,
+ * mtts_export_codes).  Only the B prompts are prefilled; the takes share their complete prompt pages (one owner count per
+ * KV page) and copy the partially filled last one.  The tokens equal those of the repeat-interleaved batch.
+ * MTTS_EINVAL: B*n > max_batch, or n > 1 with host_forced (the replay hook has no takes). */
+int32_t mtts_set_takes(MttsEngine* e, int32_t n);
+/* Scheduler mode: start a take of the dialogue just submitted to src_slot in the empty dst_slot: same prompt (its
+ * complete KV pages shared, the partially filled last one copied), drawing from (seed; step, row_id, channel).  The take's
+ * tokens equal those of mtts_slot_submit_row(dst_slot, the same prompt, seed, row_id).  Stream-ordered on `stream`.
+ * MTTS_ESTATE: src_slot was not submitted since the last mtts_step, or dst_slot is occupied; MTTS_ENOMEM: the prompt ends
+ * mid-page and no page is free for the copy. */
+int32_t mtts_slot_fork(MttsEngine* e, int32_t src_slot, int32_t dst_slot, uint64_t seed, int32_t row_id, void* stream);
 int32_t mtts_slot_states(MttsEngine* e, int32_t* host_state, void* stream);
 int32_t mtts_slot_read(MttsEngine* e, int32_t slot, int64_t* host_rows, int32_t capacity_steps, int32_t* n_steps);
 int32_t mtts_read_seq_state(MttsEngine* e, int32_t* host_nas, int32_t* host_unfinished, int32_t* host_kv_len, void* stream);

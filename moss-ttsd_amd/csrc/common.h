@@ -114,6 +114,20 @@ struct QkvFuse {
 #define MTTS_PKU 13
 struct KvPack { void* k; void* v; };             // this layer's sealed K / V pages ([kv head][page][13][64][16 B]), or null
 
+// Fork of a dialogue into take slots (engine.hip: mtts_begin with takes, mtts_slot_fork; layer.hip: fork_kernel), handed
+// over as launch arguments: `np` (src page -> dst page) pairs whose K and V blocks are copied in every layer and kv head,
+// and `nr` (src row -> dst row) pairs copied in each of `narr` per-row arrays (base, row stride and row length in bytes,
+// all multiples of 16).
+#define FORK_CAP 128
+#define FORK_ARR 4
+struct ForkJob {
+    int32_t np, nr, narr, pad;
+    int32_t psrc[FORK_CAP], pdst[FORK_CAP];
+    int32_t rsrc[FORK_CAP], rdst[FORK_CAP];
+    uint8_t* base[FORK_ARR];
+    int64_t stride[FORK_ARR], bytes[FORK_ARR];
+};
+
 // Per-row metadata of one forward pass.
 struct RowMeta {
     int32_t seq;     // sequence slot (page-table row), -1 = inactive row

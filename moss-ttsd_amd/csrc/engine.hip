@@ -93,6 +93,8 @@ void launch_f32_swiglu(const float* gu, float* act, int R, int I, int h16, hipSt
 #define MTTS_PF32CAP 256       // rows of a prefill pass in the fp32 engine (bounds its fp32 score scratch)
 struct PageEdits { int32_t n; int32_t idx[31]; int32_t val[31]; };     // page-table entries handed over as launch arguments
 void launch_set_pages(int32_t* table, const PageEdits& ed, hipStream_t st);
+void launch_fork(void* kc, void* vc, size_t layer_bytes, size_t head_bytes, int blk_bytes, int L, int nkv, const ForkJob& job,
+                 hipStream_t st);
 #define FLUSH_STEPS 7          // a dialogue whose EOS falls within 7 steps of max_length still runs its delay-pattern flush (modeling_asteroid.py:165-168)
 #define LINGER_STEPS 14        // static batch: a row finished BY max_length can be resurrected for a flush while another row's flush is still running (sampler.hip: update_kernel), so a batch runs up to 6 + 8 steps past max_length after ONE resurrection
 // Resurrections chain: a resurrected row's own 7-step flush keeps the batch alive, and every step of it re-tests the other
@@ -160,10 +162,13 @@ struct MttsEngine {
     // when it finishes (free list = stack; initial order ascending, or shuffled by MTTS_PAGE_SHUFFLE for the tests)
     std::vector<int32_t> free_pages;
     std::vector<int32_t> n_pages;       // pages each slot owns
+    std::vector<int32_t> page_owners;   // slots whose table holds the page (> 1: a prompt page shared by takes, pool_share)
     std::vector<char> slot_live;        // host's view: the slot holds a dialogue that may still step
     PageEdits pending_edits;            // table entries not yet on the device
     int forced_draw = 0;
     std::vector<int32_t> next_row_ids;  // Philox row ids of the next mtts_begin (mtts_set_row_ids); empty = 0..B-1
+    int next_takes = 1;                 // takes per prompt of the next mtts_begin / mtts_generate (mtts_set_takes)
+    int takes = 1;                      // of the current static run: row b*takes+j is take j of prompt b
     // ---- MTTS_DTYPE_F32 engine (f32path.hip): plain fp32 copies of everything, no packed layouts ----
     bool f32 = false;
     int h16 = 0;                        // MTTS_DTYPE_F16: the fp32 engine with fp16 rounding points (f32path.hip: r16)
@@ -227,7 +232,7 @@ struct MttsEngine {
 static hipStream_t S(void* s) { return (hipStream_t)s; }
 
 const char* mtts_last_error(void) { return g_err; }
-int32_t mtts_version(void) { return 200; }
+int32_t mtts_version(void) { return 201; }
 
 template <typename T>
 static int dalloc(T** p, size_t n, bool zero = true) {
@@ -279,6 +284,7 @@ static void pool_reset(MttsEngine* e) {
         }
     }
     std::fill(e->n_pages.begin(), e->n_pages.end(), 0);
+    e->page_owners.assign(e->total_pages, 0);
     e->pending_edits.n = 0;
 }
 // table entries reach the device as launch arguments of a one-wave kernel on the caller's stream: ordered with the
@@ -291,6 +297,18 @@ static int pool_flush(MttsEngine* e, hipStream_t st) {
     }
     return 0;
 }
+// append `page` to slot b's table (host copy now, device copy with the next flush)
+static int pool_append(MttsEngine* e, int b, int page, hipStream_t st) {
+    const int at = b * e->max_pages + e->n_pages[b]++;
+    e->h_page_table[at] = page;
+    // one batch is written by the lanes of ONE store (set_pages_kernel): an index must not appear twice in it
+    for (int i = 0; i < e->pending_edits.n; ++i)
+        if (e->pending_edits.idx[i] == at) { e->pending_edits.val[i] = page; return 0; }
+    if (e->pending_edits.n == 31) TRY(pool_flush(e, st));
+    e->pending_edits.idx[e->pending_edits.n] = at;
+    e->pending_edits.val[e->pending_edits.n++] = page;
+    return 0;
+}
 // make slot b own at least `need` pages; MTTS_ENOMEM when the pool runs dry (nothing is taken back)
 static int pool_grow(MttsEngine* e, int b, int need, hipStream_t st) {
     if (need > e->max_pages) return fail(MTTS_ENOMEM, "slot %d needs %d KV pages, a sequence holds at most %d (max_seq_len %d)", b, need, e->max_pages, e->cfg.max_seq_len);
@@ -298,22 +316,31 @@ static int pool_grow(MttsEngine* e, int b, int need, hipStream_t st) {
         if (e->free_pages.empty()) return fail(MTTS_ENOMEM, "KV page pool exhausted (%d pages of %d tokens): slot %d needs page %d", e->total_pages, MTTS_PAGE, b, e->n_pages[b]);
         const int page = e->free_pages.back();
         e->free_pages.pop_back();
-        const int at = b * e->max_pages + e->n_pages[b]++;
-        e->h_page_table[at] = page;
-        // one batch is written by the lanes of ONE store (set_pages_kernel): an index must not appear twice in it
-        int dup = -1;
-        for (int i = 0; i < e->pending_edits.n; ++i) if (e->pending_edits.idx[i] == at) dup = i;
-        if (dup >= 0) { e->pending_edits.val[dup] = page; continue; }
-        if (e->pending_edits.n == 31) TRY(pool_flush(e, st));
-        e->pending_edits.idx[e->pending_edits.n] = at;
-        e->pending_edits.val[e->pending_edits.n++] = page;
+        e->page_owners[page] = 1;
+        TRY(pool_append(e, b, page, st));
+    }
+    return 0;
+}
+// Takes of one prompt (mtts_begin with takes, mtts_slot_fork): slot dst (empty) gets slot src's first `npages` table
+// entries, and each of those pages one more owner.  Invariant: a slot writes only pages that it alone owns.  Only
+// COMPLETE prompt pages are shared: every K/V write of a dialogue goes to a position >= its prompt length, and their
+// sealed form was made once, by the source's prefill, in the same page numbering.  The partially filled last page is
+// copied into a private page (launch_fork_job).
+static int pool_share(MttsEngine* e, int src, int dst, int npages, hipStream_t st) {
+    for (int i = 0; i < npages; ++i) {
+        const int page = e->h_page_table[(size_t)src * e->max_pages + i];
+        e->page_owners[page]++;
+        TRY(pool_append(e, dst, page, st));
     }
     return 0;
 }
 // every launch that could touch the slot's pages must have been issued before (stream order protects the rest:
-// the next owner's writes are enqueued after them)
+// the next owner's writes are enqueued after them); a page goes back on the free list with its last owner
 static void pool_release(MttsEngine* e, int b) {
-    for (int i = e->n_pages[b] - 1; i >= 0; --i) e->free_pages.push_back(e->h_page_table[(size_t)b * e->max_pages + i]);
+    for (int i = e->n_pages[b] - 1; i >= 0; --i) {
+        const int page = e->h_page_table[(size_t)b * e->max_pages + i];
+        if (--e->page_owners[page] == 0) e->free_pages.push_back(page);
+    }
     e->n_pages[b] = 0;
     // table entries of this slot that never reached the device (a grow that ended in MTTS_ENOMEM) are void now
     int k = 0;
@@ -916,23 +943,54 @@ static int ensure_gen_storage(MttsEngine* e, int steps) {
     return 0;
 }
 
+// One launch of fork_kernel (layer.hip): the page pairs already in `job`, plus for its row pairs the rows of the logits
+// and, with `state_rows`, of the history bitmaps and the teacher-forcing tail.
+static int launch_fork_job(MttsEngine* e, ForkJob& job, bool state_rows, hipStream_t st) {
+    const int ew = e->f32 ? 4 : 2;                     // logits element bytes
+    job.narr = 0;
+    auto arr = [&](void* base, size_t stride, size_t bytes) {
+        job.base[job.narr] = (uint8_t*)base; job.stride[job.narr] = (int64_t)stride; job.bytes[job.narr++] = (int64_t)bytes;
+    };
+    arr(e->logits0, (size_t)e->V0_pad * ew, (size_t)e->V0_pad * ew);
+    arr(e->logits17, (size_t)7 * e->Vs_pad * ew, (size_t)7 * e->Vs_pad * ew);
+    if (state_rows) {
+        arr(e->d_bitmaps, (size_t)8 * e->bm_words * 4, (size_t)8 * e->bm_words * 4);
+        arr(e->d_tf, (size_t)7 * 8 * 4, (size_t)7 * 8 * 4);
+    }
+    for (int i = 0; i < job.np; ++i)
+        if (job.psrc[i] < 0 || job.psrc[i] >= e->total_pages || job.pdst[i] < 0 || job.pdst[i] >= e->total_pages)
+            return fail(MTTS_EINVAL, "fork: page outside the pool");
+    for (int i = 0; i < job.nr; ++i)
+        if (job.rsrc[i] < 0 || job.rsrc[i] >= e->cfg.max_batch || job.rdst[i] < 0 || job.rdst[i] >= e->cfg.max_batch)
+            return fail(MTTS_EINVAL, "fork: row outside the batch");
+    const size_t blk = (size_t)MTTS_PAGE * MTTS_HD * (e->f32 ? 4 : 2), layer = e->layer_stride * (e->f32 ? 4 : 2);
+    void* kc = e->f32 ? (void*)e->kcache_f : e->kcache;
+    void* vc = e->f32 ? (void*)e->vcache_f : e->vcache;
+    launch_fork(kc, vc, layer, (size_t)e->total_pages * blk, (int)blk, e->L, e->nkv, job, st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- begin: parse prompt, allocate pages, prefill --------------------------------------
-int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32_t B, int32_t T, int32_t max_length,
-                   const MttsSamplerCfg* sampler, uint64_t seed, void* stream) {
+static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32_t B, int32_t T, int32_t max_length,
+                     const MttsSamplerCfg* sampler, uint64_t seed, int takes, void* stream) {
     if (!e || !ids || !mask || !sampler) return fail(MTTS_EINVAL, "null argument");
     TRY(mtts_weights_ready(e));
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = S(stream);
-    if (B < 1 || B > e->cfg.max_batch) return fail(MTTS_EINVAL, "batch %d exceeds max_batch %d", B, e->cfg.max_batch);
+    // takes: row b*takes+j is take j of prompt b; only the B prompts are prefilled (into rows b*takes), the other takes
+    // share their complete prompt pages and get a copy of the rest (fork_kernel)
+    const int R = B * takes;
+    if (B < 1 || B > e->cfg.max_batch || R > e->cfg.max_batch) return fail(MTTS_EINVAL, "batch %d x %d takes exceeds max_batch %d", B, takes, e->cfg.max_batch);
     if (T < 8) return fail(MTTS_EINVAL, "T must be >= 8 (delay pattern adds 7 slots)");
     const int base = T - 7;
     if (max_length <= base) return fail(MTTS_EINVAL, "max_length %d leaves no room to generate (prompt slots %d)", max_length, base);
     // a dialogue whose EOS falls within 7 steps of max_length keeps stepping until its flush is through
     // (`unfinished | needs_additional_steps > 0`, modeling_asteroid.py:165-168)
     int max_steps = max_length - base + LINGER_STEPS;          // the least the engine must have room for; widened below
-    e->B = B; e->T = T; e->base_length = base; e->max_length = max_length;
+    e->B = R; e->T = T; e->base_length = base; e->max_length = max_length; e->takes = takes;
     e->seed = seed; e->steps_issued = 0; e->has_forced = false;
-    e->n_real.assign(B, 0);
+    e->n_real.assign(R, 0);
     e->max_real = 0;
     // attention_mask must be the left-padded form rpadding() produces (generation_utils.py:221-237)
     std::vector<int> pad(B, 0);
@@ -943,24 +1001,38 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
             if (!mask[(size_t)b * T + t]) return fail(MTTS_EINVAL, "attention_mask of row %d is not left-padded", b);
         if (p >= base) return fail(MTTS_EINVAL, "row %d has no real token in the first T-7 slots", b);
         pad[b] = p;
-        e->n_real[b] = base - p;
+        for (int j = 0; j < takes; ++j) e->n_real[b * takes + j] = base - p;
         e->max_real = std::max(e->max_real, base - p);
     }
     // pages: every earlier run has been synchronised by its caller or is ordered before us on `st`; the prompts'
     // pages are taken now, the rest on demand as the dialogues grow (issue_steps)
-    for (int b = 0; b < e->cfg.max_batch; ++b) { pool_release(e, b); e->slot_live[b] = b < B; }
+    for (int b = 0; b < e->cfg.max_batch; ++b) { pool_release(e, b); e->slot_live[b] = b < R; }
     e->pending_edits.n = 0;            // edits queued by a run that failed (MTTS_ENOMEM before its flush) belong to released pages
     TRY(pack_policy_reset(e, st));
+    ForkJob fork;
+    fork.np = 0; fork.nr = 0;
     for (int b = 0; b < B; ++b) {
-        const int need = (e->n_real[b] + max_steps + MTTS_PAGE - 1) / MTTS_PAGE;
-        if (need > e->max_pages) return fail(MTTS_ENOMEM, "row %d needs %d KV pages, a sequence holds at most %d (max_seq_len %d)", b, need, e->max_pages, e->cfg.max_seq_len);
-        TRY(pool_grow(e, b, (e->n_real[b] + MTTS_PAGE - 1) / MTTS_PAGE, st));
+        const int src = b * takes, len = e->n_real[src];
+        const int need = (len + max_steps + MTTS_PAGE - 1) / MTTS_PAGE;
+        if (need > e->max_pages) return fail(MTTS_ENOMEM, "row %d needs %d KV pages, a sequence holds at most %d (max_seq_len %d)", src, need, e->max_pages, e->cfg.max_seq_len);
+        TRY(pool_grow(e, src, (len + MTTS_PAGE - 1) / MTTS_PAGE, st));
+        for (int j = 1; j < takes; ++j) {
+            const int dst = src + j;
+            TRY(pool_share(e, src, dst, len / MTTS_PAGE, st));
+            if (len % MTTS_PAGE) {
+                TRY(pool_grow(e, dst, len / MTTS_PAGE + 1, st));
+                fork.psrc[fork.np] = e->h_page_table[(size_t)src * e->max_pages + len / MTTS_PAGE];
+                fork.pdst[fork.np++] = e->h_page_table[(size_t)dst * e->max_pages + len / MTTS_PAGE];
+            }
+            fork.rsrc[fork.nr] = src;
+            fork.rdst[fork.nr++] = dst;
+        }
     }
     TRY(pool_flush(e, st));
     if (e->max_real + max_steps > e->rope_rows)
         return fail(MTTS_EINVAL, "rope table has %d rows, need %d", e->rope_rows, e->max_real + max_steps);
     // room for chained resurrections (linger_bound) as far as the page-table width and the RoPE table allow
-    max_steps = std::max(max_steps, std::min(max_length - base + linger_bound(B),
+    max_steps = std::max(max_steps, std::min(max_length - base + linger_bound(R),
                                              std::min(e->max_pages * MTTS_PAGE, e->rope_rows) - e->max_real));
     e->max_steps = max_steps;
     // generation buffers
@@ -968,13 +1040,13 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
     // flattened prefill rows; every dialogue starts on a 32-row tile boundary so that a tile holds consecutive
     // positions of one dialogue (the prefill attention kernels share K/V pages across a tile); filler rows are idle
     size_t Mtot = 0;
-    for (int b = 0; b < B; ++b) Mtot += (size_t)round_up(e->n_real[b], MTTS_MAXR);
+    for (int b = 0; b < B; ++b) Mtot += (size_t)round_up(e->n_real[b * takes], MTTS_MAXR);
     size_t Mpad = (Mtot + MTTS_RCAP - 1) / MTTS_RCAP * MTTS_RCAP;
     std::vector<int32_t> toks(Mpad * 8, 0);
     std::vector<RowMeta> metas(Mpad, RowMeta{-1, 0, 0, 0});
     size_t r = 0;
     for (int b = 0; b < B; r = (r + MTTS_MAXR - 1) / MTTS_MAXR * MTTS_MAXR, ++b)
-        for (int i = 0; i < e->n_real[b]; ++i, ++r) {
+        for (int i = 0; i < e->n_real[b * takes]; ++i, ++r) {
             const int64_t* src = ids + ((size_t)b * T + pad[b] + i) * 8;
             for (int c = 0; c < 8; ++c) {
                 int64_t t = src[c];
@@ -982,7 +1054,7 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
                 if (t < 0 || t >= V) return fail(MTTS_EINVAL, "token %lld out of range on channel %d", (long long)t, c);
                 toks[r * 8 + c] = (int32_t)t;
             }
-            metas[r] = RowMeta{b, i, i == e->n_real[b] - 1 ? 1 : 0, 0};
+            metas[r] = RowMeta{b * takes, i, i == e->n_real[b * takes] - 1 ? 1 : 0, 0};
         }
     if (Mpad > e->pf_cap_rows) {
         if (e->d_pf_tokens) { hipFree(e->d_pf_tokens); hipFree(e->d_pf_meta); }
@@ -995,31 +1067,31 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
     // history bitmaps (HF repetition penalty sees the whole channel incl. pads: modeling_asteroid.py:129)
     {
         std::vector<uint32_t> bm((size_t)MTTS_RCAP * 8 * e->bm_words, 0u);
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < base; ++t)
+        for (int rw = 0; rw < R; ++rw)
+            for (int t = 0, b = rw / takes; t < base; ++t)
                 for (int c = 0; c < 8; ++c) {
                     int64_t tk = ids[((size_t)b * T + t) * 8 + c];
-                    if (tk >= 0 && tk < (int64_t)e->bm_words * 32) bm[((size_t)b * 8 + c) * e->bm_words + (tk >> 5)] |= 1u << (tk & 31);
+                    if (tk >= 0 && tk < (int64_t)e->bm_words * 32) bm[((size_t)rw * 8 + c) * e->bm_words + (tk >> 5)] |= 1u << (tk & 31);
                 }
         HIPCHK(hipMemcpyAsync(e->d_bitmaps, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, st));
         // teacher-forcing tail tf_inputs[:, base+s, :] for s = 0..6 (modeling_asteroid.py:143-145)
         std::vector<int32_t> tf((size_t)MTTS_RCAP * 7 * 8, 0);
-        for (int b = 0; b < B; ++b)
-            for (int s = 0; s < 7; ++s)
+        for (int rw = 0; rw < R; ++rw)
+            for (int s = 0, b = rw / takes; s < 7; ++s)
                 for (int c = 0; c < 8; ++c) {
                     int64_t tk = ids[((size_t)b * T + base + s) * 8 + c];
                     if (tk < 0 || tk >= (c == 0 ? e->V0 : e->Vs)) return fail(MTTS_EINVAL, "token %lld out of range on channel %d (delayed tail)", (long long)tk, c);
-                    tf[((size_t)b * 7 + s) * 8 + c] = (int32_t)tk;
+                    tf[((size_t)rw * 7 + s) * 8 + c] = (int32_t)tk;
                 }
         HIPCHK(hipMemcpyAsync(e->d_tf, tf.data(), tf.size() * 4, hipMemcpyHostToDevice, st));
         std::vector<SeqState> ss(MTTS_RCAP, SeqState{-1, 0, 0, 0, 0, 0, 0, 0, 0});
-        if (!e->next_row_ids.empty() && (int)e->next_row_ids.size() != B)
-            return fail(MTTS_EINVAL, "mtts_set_row_ids gave %d ids, the batch has %d rows", (int)e->next_row_ids.size(), B);
-        for (int b = 0; b < B; ++b)
+        if (!e->next_row_ids.empty() && (int)e->next_row_ids.size() != R)
+            return fail(MTTS_EINVAL, "mtts_set_row_ids gave %d ids, the batch has %d rows", (int)e->next_row_ids.size(), R);
+        for (int b = 0; b < R; ++b)
             ss[b] = SeqState{-1, 1, e->n_real[b], 0, base, max_length, e->next_row_ids.empty() ? b : e->next_row_ids[b], 1, seed};
         e->next_row_ids.clear();
         HIPCHK(hipMemcpyAsync(e->d_seqs, ss.data(), ss.size() * sizeof(SeqState), hipMemcpyHostToDevice, st));
-        LoopState ls{0, 0, 0, B, 0, e->gen_cap, e->forced_draw, e->f32 ? 1 : 0};
+        LoopState ls{0, 0, 0, R, 0, e->gen_cap, e->forced_draw, e->f32 ? 1 : 0};
         e->continuous = false;
         e->join_step.assign(MTTS_RCAP, 0);
         HIPCHK(hipMemcpyAsync(e->d_ls, &ls, sizeof(ls), hipMemcpyHostToDevice, st));
@@ -1041,8 +1113,26 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
         const bool lastc = off + rows >= Mpad;
         TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, lastc ? 2 : 0, st, 0));
     }
+    // takes: the partially filled last prompt page of each source row into its takes' private pages, and the source
+    // row's logits into theirs (bitmaps, teacher-forcing tails and states were uploaded for every row above)
+    if (fork.nr) TRY(launch_fork_job(e, fork, false, st));
     e->began = true;
     return MTTS_OK;
+}
+
+int32_t mtts_set_takes(MttsEngine* e, int32_t n) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    if (n < 1 || n > MTTS_RCAP) return fail(MTTS_EINVAL, "takes must be 1..%d (got %d)", MTTS_RCAP, n);
+    e->next_takes = n;
+    return MTTS_OK;
+}
+
+int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32_t B, int32_t T, int32_t max_length,
+                   const MttsSamplerCfg* sampler, uint64_t seed, void* stream) {
+    if (!e) return fail(MTTS_EINVAL, "null argument");
+    const int takes = e->next_takes;
+    e->next_takes = 1;                 // consumed by this call, whatever its outcome
+    return begin_run(e, ids, mask, B, T, max_length, sampler, seed, takes, stream);
 }
 
 // One decode step: sample from the previous logits, advance the per-dialogue state machine, run the stack.
@@ -1210,10 +1300,15 @@ int32_t mtts_read_logits(MttsEngine* e, uint16_t* l0, uint16_t* l17, void* strea
 int32_t mtts_generate(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32_t B, int32_t T, int32_t max_length,
                       const MttsSamplerCfg* sampler, uint64_t seed, int64_t* out, int32_t out_capacity, int32_t* out_len,
                       const int64_t* forced, int32_t forced_len, int64_t* decisions, void* stream) {
+    if (!e) return fail(MTTS_EINVAL, "null argument");
+    const int takes = e->next_takes;
+    e->next_takes = 1;                 // consumed by this call, whatever its outcome
     if (!out || !out_len) return fail(MTTS_EINVAL, "null output");
-    TRY(mtts_begin(e, ids, mask, B, T, max_length, sampler, seed, stream));
+    if (forced && takes > 1) return fail(MTTS_EINVAL, "forced replay (reference fixtures) has no takes: %d takes per prompt", takes);
+    TRY(begin_run(e, ids, mask, B, T, max_length, sampler, seed, takes, stream));
     hipStream_t st = S(stream);
     const int base = e->base_length;
+    const int R = e->B;
     if (forced) {
         if (!decisions) return fail(MTTS_EINVAL, "forced replay needs host_decisions");
         std::vector<int32_t> f((size_t)e->cfg.max_batch * e->gen_cap * 8, -1);
@@ -1239,17 +1334,18 @@ int32_t mtts_generate(MttsEngine* e, const int64_t* ids, const uint8_t* mask, in
     if (!forced && !done)
         return fail(MTTS_ESTATE, "the batch is still flushing after %d steps (%d past max_length): chained finished-row "
                     "resurrections (modeling_asteroid.py:140-141,168) outran the room max_seq_len %d leaves; raise it by %d",
-                    steps, steps - (max_length - base), e->cfg.max_seq_len, linger_bound(B) - LINGER_STEPS);
+                    steps, steps - (max_length - base), e->cfg.max_seq_len, linger_bound(R) - LINGER_STEPS);
     const int total = base + steps;
     if (total > out_capacity) return fail(MTTS_EINVAL, "out_capacity %d < %d", out_capacity, total);
-    std::vector<int64_t> gen((size_t)std::max(steps, 1) * B * 8);
+    std::vector<int64_t> gen((size_t)std::max(steps, 1) * R * 8);
     int ns = 0;
     TRY(read_rows(e, e->d_gen, gen.data(), steps, &ns));
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < R; ++b) {
+        const int p = b / takes;       // the row's prompt
         for (int t = 0; t < base; ++t)
-            for (int c = 0; c < 8; ++c) out[((size_t)b * out_capacity + t) * 8 + c] = ids[((size_t)b * T + t) * 8 + c];
+            for (int c = 0; c < 8; ++c) out[((size_t)b * out_capacity + t) * 8 + c] = ids[((size_t)p * T + t) * 8 + c];
         for (int s = 0; s < steps; ++s)
-            for (int c = 0; c < 8; ++c) out[((size_t)b * out_capacity + base + s) * 8 + c] = gen[((size_t)s * B + b) * 8 + c];
+            for (int c = 0; c < 8; ++c) out[((size_t)b * out_capacity + base + s) * 8 + c] = gen[((size_t)s * R + b) * 8 + c];
     }
     if (decisions) TRY(read_rows(e, e->d_declog, decisions, steps, &ns));
     *out_len = total;
@@ -1402,6 +1498,49 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
     e->n_real[slot] = n - e->steps_issued;          // so that n_real + steps_issued is this dialogue's current length
     e->join_step[slot] = e->steps_issued;
     e->slot_live[slot] = 1;
+    return MTTS_OK;
+}
+
+// Take of a just-submitted dialogue: dst starts where src starts (same prompt, KV, logits, history, teacher-forcing tail)
+// and draws from (seed; step, row_id, channel).  src's complete prompt pages are shared (pool_share), its partially filled
+// last page is copied into one fresh page; everything rides `stream` (one fork_kernel launch, one state upload).
+int32_t mtts_slot_fork(MttsEngine* e, int32_t src, int32_t dst, uint64_t seed, int32_t row_id, void* stream) {
+    if (!e || !e->began || !e->continuous) return fail(MTTS_ESTATE, "mtts_sched_open has not run");
+    if (src < 0 || src >= e->B || dst < 0 || dst >= e->B || src == dst) return fail(MTTS_EINVAL, "fork: slots %d -> %d out of range", src, dst);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = S(stream);
+    // src must have been submitted since the last mtts_step: its last prompt page has not been written past the prompt
+    if (!e->slot_live[src] || e->join_step[src] != e->steps_issued)
+        return fail(MTTS_ESTATE, "fork: slot %d holds no dialogue submitted since the last step", src);
+    HIPCHK(hipMemcpyAsync(e->h_seqs, e->d_seqs, (size_t)e->B * sizeof(SeqState), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!e->h_seqs[src].active || e->h_seqs[src].step) return fail(MTTS_ESTATE, "fork: slot %d has stepped", src);
+    if (e->h_seqs[dst].active) return fail(MTTS_ESTATE, "fork: slot %d is occupied", dst);
+    if (e->slot_live[dst]) { e->slot_live[dst] = 0; pool_release(e, dst); }      // finished, not collected yet
+    const int len = e->n_real[src] + e->steps_issued, full = len / MTTS_PAGE, tail = len % MTTS_PAGE != 0;
+    if ((int)e->free_pages.size() < tail)
+        return fail(MTTS_ENOMEM, "KV page pool: no free page for the take's copy of the last prompt page");
+    ForkJob job;
+    job.np = 0; job.nr = 1;
+    job.rsrc[0] = src; job.rdst[0] = dst;
+    int rc = pool_share(e, src, dst, full, st);
+    if (!rc && tail) {
+        rc = pool_grow(e, dst, full + 1, st);
+        job.psrc[0] = e->h_page_table[(size_t)src * e->max_pages + full];
+        job.pdst[0] = e->h_page_table[(size_t)dst * e->max_pages + full];
+        job.np = 1;
+    }
+    if (!rc) rc = pool_flush(e, st);
+    if (!rc) rc = launch_fork_job(e, job, true, st);
+    if (rc) { pool_release(e, dst); return rc; }    // the share is undone with the slot (counts, unshipped edits)
+    SeqState ns = e->h_seqs[src];
+    ns.row_id = row_id; ns.seed = seed;
+    e->h_seqs[dst] = ns;                            // pinned staging of the upload
+    HIPCHK(hipMemcpyAsync(e->d_seqs + dst, e->h_seqs + dst, sizeof(SeqState), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    e->n_real[dst] = e->n_real[src];
+    e->join_step[dst] = e->steps_issued;
+    e->slot_live[dst] = 1;
     return MTTS_OK;
 }
 

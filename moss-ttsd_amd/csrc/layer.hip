@@ -298,6 +298,56 @@ void launch_set_pages(int32_t* table, const PageEdits& ed, hipStream_t st) {
     hipLaunchKernelGGL(set_pages_kernel, dim3(1), dim3(64), 0, st, table, ed);
 }
 
+// Fork of a dialogue into take slots (engine.hip: launch_fork_job): the private copy of a partially filled last page and the
+// rows of per-row state that prefill wrote for the source row only (logits, and in scheduler mode the history bitmaps and
+// the teacher-forcing tail).  Blocks 0 .. np*L*nkv*2-1: one (pair, layer, kv head, K|V) page block each (`blk` 16-byte
+// units: 1024 for a bf16 page, 2048 for an fp32 one), every lane's loads in flight before its stores; the blocks after
+// that: FORK_ROW_BLOCKS per (row pair, array), strided over the row.  No allocation and no synchronisation: capturable.
+#define FORK_ROW_BLOCKS 8
+template <int N>
+__device__ __forceinline__ void fork_copy(const u32x4_t* __restrict__ s, u32x4_t* __restrict__ d, int tid) {
+    u32x4_t t[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) t[i] = s[i * 256 + tid];
+#pragma unroll
+    for (int i = 0; i < N; ++i) d[i * 256 + tid] = t[i];
+}
+__global__ __launch_bounds__(256) void fork_kernel(ForkJob job, u32x4_t* __restrict__ kc, u32x4_t* __restrict__ vc,
+                                                   size_t layer_u, size_t head_u, int blk, int L, int nkv) {
+    // the job is the first kernel argument: read in place (scalar loads of block-uniform entries); indexing the by-value
+    // copy would materialise all of it in VGPRs
+    const ForkJob* jp = (const ForkJob*)__builtin_amdgcn_kernarg_segment_ptr();
+    const int tid = threadIdx.x;
+    int b = blockIdx.x;
+    const int kv_blocks = jp->np * L * nkv * 2;
+    if (b < kv_blocks) {
+        const int which = b & 1; b >>= 1;
+        const int h = b % nkv; b /= nkv;
+        const int layer = b % L, p = b / L;
+        u32x4_t* base = (which ? vc : kc) + layer * layer_u + h * head_u;
+        const u32x4_t* s = base + (size_t)jp->psrc[p] * blk;
+        u32x4_t* d = base + (size_t)jp->pdst[p] * blk;
+        if (blk == 2048) fork_copy<8>(s, d, tid);
+        else fork_copy<4>(s, d, tid);
+        return;
+    }
+    b -= kv_blocks;
+    const int k = b % FORK_ROW_BLOCKS, a = (b / FORK_ROW_BLOCKS) % jp->narr, r = b / (FORK_ROW_BLOCKS * jp->narr);
+    const u32x4_t* s = (const u32x4_t*)(jp->base[a] + jp->stride[a] * jp->rsrc[r]);
+    u32x4_t* d = (u32x4_t*)(jp->base[a] + jp->stride[a] * jp->rdst[r]);
+    const int units = (int)(jp->bytes[a] >> 4);
+    for (int u = k * 256 + tid; u < units; u += FORK_ROW_BLOCKS * 256) d[u] = s[u];
+}
+// layer_bytes / head_bytes: distance between two layers' / two kv heads' page blocks in each cache; blk_bytes: one page
+// block (16 KiB bf16 or 32 KiB fp32: the two sizes the kernel is built for)
+void launch_fork(void* kc, void* vc, size_t layer_bytes, size_t head_bytes, int blk_bytes, int L, int nkv, const ForkJob& job,
+                 hipStream_t st) {
+    const int blocks = job.np * L * nkv * 2 + job.nr * job.narr * FORK_ROW_BLOCKS;
+    if (!blocks) return;
+    hipLaunchKernelGGL(fork_kernel, dim3(blocks), dim3(256), 0, st, job, (u32x4_t*)kc, (u32x4_t*)vc, layer_bytes >> 4,
+                       head_bytes >> 4, blk_bytes >> 4, L, nkv);
+}
+
 // Unit-test helper (mtts_k_paged_attn_decode): row-major K / V [seq][Lmax][nkv][128] bf16 -> the paged cache layouts
 // (K page [d/8][token][8], V page [token pair][d][2]) through an arbitrary page table.
 __global__ void pack_kv_pages_kernel(const uint16_t* __restrict__ K, const uint16_t* __restrict__ V, uint16_t* __restrict__ kcache,

@@ -66,6 +66,7 @@ class GenerationConfig:
         self.top_p = kw.get("top_p")
         self.repetition_penalty = kw.get("repetition_penalty")
         self.seed = kw.get("seed")
+        self.num_return_sequences = kw.get("num_return_sequences", 1)
 
     @classmethod
     def from_pretrained(cls, path):
@@ -169,12 +170,19 @@ class AsteroidTTSInstruct:
         return self._engine
 
     @torch.no_grad()
-    def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None, **_):
-        """LongTensor[B,T,8], mask[B,T] -> LongTensor[B, T-7+G, 8] (generation_utils.py:406-409)."""
+    def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,
+                 num_return_sequences=None, **_):
+        """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
+        num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
+        repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages."""
         gc = self.generation_config
         B, T, C = input_ids.shape
         if C != self.channels:
             raise ValueError(f"Expected {self.channels} channels, got {C}")
+        n = num_return_sequences if num_return_sequences is not None else getattr(gc, "num_return_sequences", 1)
+        n = 1 if n is None else int(n)
+        if n < 1:
+            raise ValueError(f"num_return_sequences must be >= 1 (got {n})")
         if attention_mask is None:
             attention_mask = torch.ones(B, T)
         # HF: max_length = max_new_tokens + input length when max_new_tokens is given
@@ -182,20 +190,26 @@ class AsteroidTTSInstruct:
         if max_length is None:
             max_length = (T + mnt) if mnt is not None else gc.max_length
         layers, do_samples = gc.channel_settings(C)
+        if n > 1 and not any(do_samples):
+            # HF GenerationMixin: greedy search returns one sequence per prompt
+            raise ValueError("Greedy methods (do_sample != True) without beam search do not support `num_return_sequences` "
+                             f"different than 1 (got {n}).")
         seed = self._next_seed(seed)
         ids = input_ids.detach().cpu().numpy()
         msk = attention_mask.detach().cpu().numpy()
         rows = list(range(B)) if self.sample_rows is None else [int(r) for r in self.sample_rows]
         if len(rows) != B:
             raise ValueError(f"sample_rows has {len(rows)} entries for a batch of {B}")
+        R = B * n                       # take j of prompt b is row b*n+j and draws as row rows[b]*n+j of the expanded job
         # room for the reference's finished-row flushes past max_length: 14 steps at least, the whole chain
         # (6 * B + 8, include/mtts.h: mtts_generate) where that is cheap
-        eng = self._get_engine(B, int(max_length) + 6 * min(B, self.MAX_ENGINE_BATCH) + 8)
-        if B <= self.MAX_ENGINE_BATCH:
+        eng = self._get_engine(R, int(max_length) + 6 * min(R, self.MAX_ENGINE_BATCH) + 8)
+        if R <= self.MAX_ENGINE_BATCH:
             # one static batch, the reference's semantics: finished rows emit (eos, 1024 x 7) until the batch ends
-            out = eng.generate(ids, msk, int(max_length), layers=layers, do_samples=do_samples, seed=seed, row_ids=rows)
+            out = eng.generate(ids, msk, int(max_length), layers=layers, do_samples=do_samples, seed=seed,
+                               row_ids=[r * n + j for r in rows for j in range(n)], takes=n)
         else:
-            out = self._generate_scheduled(eng, ids, msk, int(max_length), layers, do_samples, seed, rows)
+            out = self._generate_scheduled(eng, ids, msk, int(max_length), layers, do_samples, seed, rows, n)
         return torch.from_numpy(out).to(input_ids.device)
 
     def _next_seed(self, seed):
@@ -210,7 +224,7 @@ class AsteroidTTSInstruct:
         self._calls += 1
         return int(seed)
 
-    def _generate_scheduled(self, eng, ids, msk, max_length, layers, do_samples, seed, rows):
+    def _generate_scheduled(self, eng, ids, msk, max_length, layers, do_samples, seed, rows, takes=1):
         """More rows than one pass carries: the continuous batcher serves them through MAX_ENGINE_BATCH slots (a
         finished dialogue's slot and KV pages go to the next one).  Row i draws from the Philox stream
         (seed; step, rows[i], channel) -- the stream row i of one static batch would use, so the same seed and prompts
@@ -225,12 +239,13 @@ class AsteroidTTSInstruct:
         new = max_length - T
         cb = ContinuousBatcher(eng, slots=self.MAX_ENGINE_BATCH, gen_cap=max_length - base + 8, layers=layers,   # max_new + 7 flush steps
                                do_samples=do_samples)
-        res = cb.run(prompts, new, seeds=[seed] * B, row_ids=rows)
-        G = max(r.shape[0] - (T - pads[b] - 7) for b, r in enumerate(res))
-        full = np.full((B, base + G, C), self.config.speech_pad_token, dtype=np.int64)
+        res = cb.run(prompts, new, seeds=[seed] * B, row_ids=rows, takes=takes)     # row k = take k % takes of prompt k // takes
+        G = max(r.shape[0] - (T - pads[k // takes] - 7) for k, r in enumerate(res))
+        full = np.full((B * takes, base + G, C), self.config.speech_pad_token, dtype=np.int64)
         full[:, :, 0] = self.config.eos_token_id            # finished-row padding (modeling_asteroid.py:155-158)
-        for b, r in enumerate(res):
-            full[b, :base] = ids[b, :base]
+        for k, r in enumerate(res):
+            b = k // takes
+            full[k, :base] = ids[b, :base]
             gen = r[T - pads[b] - 7:]
-            full[b, base:base + gen.shape[0]] = gen
+            full[k, base:base + gen.shape[0]] = gen
         return full

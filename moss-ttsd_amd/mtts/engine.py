@@ -114,22 +114,33 @@ class Engine:
             assert r.shape == (B,)
             capi.check(self.lib.mtts_set_row_ids(self._h, r.ctypes.data, B))
 
+    def _set_takes(self, takes):
+        takes = int(takes)
+        if takes < 1:
+            raise ValueError(f"takes must be >= 1 (got {takes})")
+        capi.check(self.lib.mtts_set_takes(self._h, takes))
+        return takes
+
     def generate(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, forced=None,
-                 forced_as_draw=False, row_ids=None):
+                 forced_as_draw=False, row_ids=None, takes=1):
         """forced (verification hook): int64 [B,G,8] full sequences of a reference run.  -> (ids, decisions [steps,B,8]).
         forced_as_draw: the forced row replaces each step's raw draw before the state machine (replay of a SAMPLED
         run); decisions are then the raw draws.  forced_as_draw="all": also for rows that max_length has cut off (the
-        reference keeps evaluating them; scripted tests of chained resurrections)."""
+        reference keeps evaluating them; scripted tests of chained resurrections).
+        takes: sampled takes per prompt (HF num_return_sequences): B*takes rows, row b*takes+j is take j of prompt b,
+        equal to the run of the repeat-interleaved batch; row_ids then has B*takes entries."""
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
-        cap = int(max_length) + 6 * B + 8  # flushes that start at / run past max_length, chained (include/mtts.h: mtts_generate)
-        self._B = B
+        R = B * int(takes)
+        cap = int(max_length) + 6 * R + 8  # flushes that start at / run past max_length, chained (include/mtts.h: mtts_generate)
+        self._B = R
         mode = 0 if (forced is None or not forced_as_draw) else (2 if forced_as_draw == "all" else 1)
         capi.check(self.lib.mtts_set_forced_mode(self._h, mode))
-        out = np.zeros((B, cap, 8), dtype=np.int64)
+        out = np.zeros((R, cap, 8), dtype=np.int64)
         out_len = C.c_int32(0)
         scfg = sampler_cfgs(layers, do_samples)
-        self._set_row_ids(row_ids, B)       # Philox row id of each row (default: its position in this batch)
+        self._set_row_ids(row_ids, R)       # Philox row id of each row (default: its position in this batch)
+        self._set_takes(takes)
         fptr, flen, dptr, dec = None, 0, None, None
         if forced is not None:
             forced = np.ascontiguousarray(forced, dtype=np.int64)
@@ -144,11 +155,13 @@ class Engine:
             return res, dec[:out_len.value - (T - 7)].copy()
         return res
 
-    def begin(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, row_ids=None):
+    def begin(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, row_ids=None, takes=1):
+        """Prefill; takes as in generate() (the run then has B*takes rows)."""
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
-        self._B, self._T = B, T
-        self._set_row_ids(row_ids, B)
+        self._B, self._T = B * int(takes), T
+        self._set_row_ids(row_ids, B * int(takes))
+        self._set_takes(takes)
         capi.check(self.lib.mtts_begin(self._h, ids.ctypes.data, m.ctypes.data, B, T, int(max_length),
                                        sampler_cfgs(layers, do_samples), C.c_uint64(seed), None))
 
@@ -193,6 +206,11 @@ class Engine:
         assert ids.ndim == 2 and ids.shape[1] == 8
         capi.check(self.lib.mtts_slot_submit_row(self._h, int(slot), ids.ctypes.data, ids.shape[0], int(max_length),
                                                  C.c_uint64(seed), int(row_id), None))
+
+    def fork(self, src, dst, seed=0, row_id=0):
+        """Scheduler mode: a take of the dialogue just submitted to slot `src` in the empty slot `dst` (shared prompt
+        pages), drawing from (seed; step, row_id, channel) -- the tokens of submit(dst, that prompt, ..., seed, row_id)."""
+        capi.check(self.lib.mtts_slot_fork(self._h, int(src), int(dst), C.c_uint64(seed), int(row_id), None))
 
     def slot_states(self):
         """-> int32 [slots,4]: active, unfinished, rows generated, tokens cached."""

@@ -14,6 +14,11 @@ dialogues grow.  If the pool still runs dry mid-flight (`mtts_step` -> MTTS_ENOM
 generated rows is evicted and re-queued -- tokens are a function of (prompt, seed), so its re-run reproduces them --
 and nothing new is admitted until a resident dialogue has finished (otherwise the evicted prompt would take the freed
 pages straight back).
+
+Takes (`run(..., takes=n)`, HF num_return_sequences): when a prompt is admitted its other takes are forked into the
+slots free at that moment (`Engine.fork`: the complete prompt pages are shared, one page copied, no prefill), as far as
+pages allow; a take that gets no slot then, or is evicted later, is queued as a plain submission with its own row id
+and reproduces the same tokens.
 """
 from __future__ import annotations
 
@@ -29,21 +34,36 @@ class ContinuousBatcher:
         self.gen_cap = int(gen_cap)
         self.steps_per_poll = int(steps_per_poll)
         self.evictions = 0
+        self.forks = 0                                                # takes started by Engine.fork (no prefill of their own)
         engine.sched_open(self.slots, self.gen_cap, layers=layers, do_samples=do_samples)
 
-    def run(self, prompts, max_new_tokens, seeds=None, base_seed=0, row_ids=None):
+    def run(self, prompts, max_new_tokens, seeds=None, base_seed=0, row_ids=None, takes=1):
         """prompts: list of int64 [T_i,8] delay-shifted prompts (no padding); max_new_tokens: int or list
         (HF semantics: max_length = T_i + max_new).  seeds: one Philox key per dialogue (default base_seed + i, so
         that concurrent dialogues draw from different streams).  Returns a list of int64 [T_i-7+G_i, 8] in
         submission order.  row_ids: Philox row id per dialogue (default 0): with one shared seed and row_ids = the
-        dialogues' positions in a batch they draw what that static batch's rows draw."""
+        dialogues' positions in a batch they draw what that static batch's rows draw.
+        takes: sampled takes per prompt; take j of prompt i draws with seeds[i] and row id row_ids[i] * takes + j (the
+        row of the repeat-interleaved batch), and the result list holds len(prompts) * takes entries, take j of prompt
+        i at i * takes + j."""
+        takes = int(takes)
+        if takes < 1:
+            raise ValueError(f"takes must be >= 1 (got {takes})")
         n = len(prompts)
         mnt = [max_new_tokens] * n if np.isscalar(max_new_tokens) else list(max_new_tokens)
         seeds = list(seeds) if seeds is not None else [int(base_seed) + i for i in range(n)]
         row_ids = [0] * n if row_ids is None else [int(r) for r in row_ids]
+        # jobs k = i * takes + j; a queued job forks the prompt's other takes when it is admitted only if it is take 0 on
+        # its first admission
+        prompts = [prompts[k // takes] for k in range(n * takes)]
+        mnt = [mnt[k // takes] for k in range(n * takes)]
+        seeds = [seeds[k // takes] for k in range(n * takes)]
+        row_ids = [row_ids[k // takes] * takes + k % takes for k in range(n * takes)]
+        forks = set(range(0, n * takes, takes)) if takes > 1 else set()
+        n *= takes
         results = [None] * n
         owner = [-1] * self.slots
-        queue = list(range(n))
+        queue = list(range(n)) if takes == 1 else list(range(0, n, takes))
         steps = 0
         hold = False                                                  # after an eviction: wait for a dialogue to finish
         polls = 0
@@ -68,6 +88,9 @@ class ContinuousBatcher:
                         break                                         # wait for a resident dialogue to finish
                     queue.pop(0)
                     owner[s] = i
+                    if i in forks:
+                        forks.discard(i)
+                        self._fork_takes(s, i, takes, ids.shape[0], owner, queue, seeds, row_ids)
             try:
                 self.eng.step(self.steps_per_poll)
                 steps += self.steps_per_poll
@@ -96,3 +119,27 @@ class ContinuousBatcher:
                     hold = False
         self.engine_steps = steps
         return results
+
+    def _fork_takes(self, s, i, takes, T, owner, queue, seeds, row_ids):
+        """Take 0 of a prompt (job i) has just been submitted to slot s: fork takes 1.. into free slots while a page for
+        each take's copy of the last prompt page stays free next to the residents' headroom; the rest are queued (at the
+        front, in take order) as plain submissions."""
+        left = list(range(i + 1, i + takes))
+        own = 1 if (T - 7) % 64 else 0                                # private pages a take needs now
+        for d in range(self.slots):
+            if not left:
+                break
+            if owner[d] >= 0:
+                continue
+            live = sum(1 for o in owner if o >= 0)
+            if self.eng.kv_pool_state()[1] < own + live + 1:
+                break
+            try:
+                self.eng.fork(s, d, seed=int(seeds[left[0]]), row_id=row_ids[left[0]])
+            except capi.MttsError as err:
+                if err.code != capi.ENOMEM:
+                    raise
+                break
+            owner[d] = left.pop(0)
+            self.forks += 1
+        queue[:0] = left
