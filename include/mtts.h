@@ -133,6 +133,27 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* host_input_ids, const uint8_t* 
 int32_t mtts_step(MttsEngine* e, int32_t n_steps, void* stream);   /* n x (sample+update, forward); async */
 int32_t mtts_sync_state(MttsEngine* e, int32_t* steps_done, int32_t* all_finished, void* stream);
 int32_t mtts_read_generated(MttsEngine* e, int64_t* host_gen, int32_t capacity_steps, int32_t* n_steps);
+/* ---- output_scores: per-token log-probabilities (HF generate(output_scores=True) reduced to what
+ * compute_transition_scores(sequences, scores, normalize_logits=True) returns: one float per decision) ----
+ * lp[g][r][c] = log_softmax(S)[d]: S = the channel's processed score row of step g (hard-coded masks, repetition penalty,
+ * temperature, top-k, top-p; filtered tokens at -inf: modeling_asteroid.py:123-138 `next_token_scores`), d = the sampler's
+ * own raw decision for the slot.  On a sampled channel that is the log-probability with which the engine drew d (the kept
+ * set renormalised); on a greedy channel the log-softmax over all finite processed scores (a greedy channel applies no
+ * top-k / top-p).  A slot whose appended token is NOT a model decision holds NaN: the teacher-forced channels c > step of
+ * the first 7 steps, channels replaced by the EOS flush, finished-row padding, rows not evaluated.  The rule is the state
+ * machine's; in the forced replay modes lp is still taken at the engine's own decision.  Full score rows (8 x [B,V_c] per
+ * step) are not materialised.  Values are run-to-run bit-identical and do not depend on what else shares the batch.
+ * mtts_set_output_scores: sticky switch (default off), read by the next mtts_begin / mtts_generate / mtts_sched_open; off,
+ * the step is unchanged and no buffer exists.  MTTS_ESTATE when changed while a run is open (rows still unfinished on the
+ * device); setting the value it already has always succeeds.  A run the caller has abandoned mid-flight counts as open: end
+ * it first with mtts_sched_open (an empty scheduler run: no slot is occupied, so nothing is open), then set the switch
+ * and begin.
+ * mtts_read_scores: host_lp float [capacity_steps][rows][8], the row space and step range of mtts_read_generated;
+ * MTTS_ESTATE when the run was started with scores off.  mtts_slot_read_scores: scheduler mode, host_rows float [steps][8],
+ * like mtts_slot_read. */
+int32_t mtts_set_output_scores(MttsEngine* e, int32_t on);
+int32_t mtts_read_scores(MttsEngine* e, float* host_lp, int32_t capacity_steps, int32_t* n_steps);
+int32_t mtts_slot_read_scores(MttsEngine* e, int32_t slot, float* host_rows, int32_t capacity_steps, int32_t* n_steps);
 /* last forward's logits: bf16 bits, channel 0 [B,vocab_size], channels 1..7 [7,B,speech_vocab_size] */
 int32_t mtts_read_logits(MttsEngine* e, uint16_t* host_logits0, uint16_t* host_logits17, void* stream);
 /* the same for an MTTS_DTYPE_F32 engine: fp32 logits */
@@ -250,6 +271,11 @@ int32_t mtts_k_sample(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
                       const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
                       int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
                       int32_t* dev_tokens, void* stream);
+/* The same call that also leaves the log-probability of each row's token (see mtts_set_output_scores) in dev_logp float [rows]. */
+int32_t mtts_k_sample_scores(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
+                             const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
+                             int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
+                             int32_t* dev_tokens, float* dev_logp, void* stream);
 
 /* ======================================================================================
  * XY_Tokenizer decode path (codes -> 24 kHz waveform), fp32.

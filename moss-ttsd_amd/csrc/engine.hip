@@ -59,22 +59,22 @@ void launch_kv_pack_count(const void* kpack, const void* vpack, const int32_t* p
                           int total_pages, int nkv, int L, unsigned long long* out, hipStream_t st);
 struct SeqState { int32_t nas, unfinished, kv_len, step, base_length, max_length, row_id, active; uint64_t seed; };
 struct LoopState { int32_t step, done, continuous, B, error, gen_cap, forced_draw, logits_f32; };
-struct SampleScratch { uint32_t* hist; float* slice_val; int32_t* slice_idx; float* cand_val; int32_t* cand_idx; uint32_t* cand_n; int32_t* overflow; float* full_val; int32_t* full_idx; uint32_t* nuc_cnt; unsigned long long* nuc_mass; };
+struct SampleScratch { uint32_t* hist; float* slice_val; int32_t* slice_idx; float* cand_val; int32_t* cand_idx; uint32_t* cand_n; int32_t* overflow; float* full_val; int32_t* full_idx; uint32_t* nuc_cnt; unsigned long long* nuc_mass; float* slice_sum; float* lp; };
 #define SAMP_CAND 4096
 #define SAMP_NS 32
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps,
                    int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed,
                    int32_t* decisions, int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap,
-                   hipStream_t st);
+                   int emit_lp, hipStream_t st);
 void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
                           const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
-                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, hipStream_t st);
+                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp, hipStream_t st);
 static int alloc_scratch(SampleScratch& sc, int rows, int vocab);
 static int full_cap_for(int vocab) { int p = 1; while (p < vocab) p <<= 1; return vocab > SAMP_CAND ? p : 0; }
 static void free_scratch(SampleScratch& sc);
 void launch_update(const int32_t* decisions, int32_t* dec_log, const int32_t* forced, const int32_t* tf_tail,
                    int32_t* gen, int32_t* cur_tokens, SeqState* seqs, RowMeta* meta, uint32_t* bitmaps, int bm_words,
-                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, hipStream_t st);
+                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out, hipStream_t st);
 
 void launch_export_codes(const int32_t* gen, int64_t* codes, int B, int first, int n, int speech_offset, int clamp_hi,
                          int cap, hipStream_t st);
@@ -191,8 +191,14 @@ struct MttsEngine {
     uint32_t* d_bitmaps = nullptr;
     int bm_words = 0;
     MttsSamplerCfg* d_scfg = nullptr;
-    SampleScratch sscr = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    SampleScratch sscr = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int ch0_sampled = 0;
+    // output_scores: per-token log-probabilities [slot][gen_cap][8] fp32, laid out like d_gen; allocated on first use
+    float* d_lp = nullptr;
+    int lp_cap = 0;                     // gen_cap the buffer was allocated for
+    int scores_next = 0;                // mtts_set_output_scores: read by the next mtts_begin / mtts_generate / mtts_sched_open
+    int scores_on = 0;                  // of the current run
+    bool run_open = false;              // a run has begun and has not been seen to end (mtts_set_output_scores)
     int32_t* d_pf_tokens = nullptr;     // prefill staging
     RowMeta* d_pf_meta = nullptr;
     size_t pf_cap_rows = 0;
@@ -206,7 +212,7 @@ struct MttsEngine {
     uint64_t seed = 0;
     bool began = false, has_forced = false;
     // decode-step graphs: one captured step per (rows, KV page bound, ...) key, replayed by mtts_step
-    struct StepGraph { int B, pages, forced, ch0; hipGraphExec_t exec; };
+    struct StepGraph { int B, pages, forced, ch0, scores; hipGraphExec_t exec; };
     std::vector<StepGraph> graphs;
     hipStream_t cap_stream = nullptr;
     bool use_graphs = true;
@@ -232,7 +238,7 @@ struct MttsEngine {
 static hipStream_t S(void* s) { return (hipStream_t)s; }
 
 const char* mtts_last_error(void) { return g_err; }
-int32_t mtts_version(void) { return 201; }
+int32_t mtts_version(void) { return 202; }
 
 template <typename T>
 static int dalloc(T** p, size_t n, bool zero = true) {
@@ -262,11 +268,20 @@ static int alloc_scratch(SampleScratch& sc, int rows, int vocab) {
     TRY(dalloc(&sc.cand_val, (size_t)rows * SAMP_CAND));
     TRY(dalloc(&sc.cand_idx, (size_t)rows * SAMP_CAND));
     TRY(dalloc(&sc.cand_n, (size_t)rows));
+    sc.slice_sum = nullptr; sc.lp = nullptr;          // output_scores scratch: alloc_lp_scratch, only when asked for
+    return 0;
+}
+static int alloc_lp_scratch(SampleScratch& sc, int rows) {
+    if (sc.lp) return 0;
+    TRY(dalloc(&sc.slice_sum, (size_t)rows * SAMP_NS));
+    TRY(dalloc(&sc.lp, (size_t)rows * 8));
     return 0;
 }
 static void free_scratch(SampleScratch& sc) {
     hipFree(sc.hist); hipFree(sc.slice_val); hipFree(sc.slice_idx); hipFree(sc.cand_val); hipFree(sc.cand_idx); hipFree(sc.cand_n);
     hipFree(sc.overflow);
+    if (sc.slice_sum) hipFree(sc.slice_sum);
+    if (sc.lp) hipFree(sc.lp);
     if (sc.full_val) { hipFree(sc.full_val); hipFree(sc.full_idx); hipFree(sc.nuc_cnt); hipFree(sc.nuc_mass); }
 }
 
@@ -582,7 +597,7 @@ int32_t mtts_engine_destroy(MttsEngine* e) {
                     e->xn, e->xh, e->hlast, e->attn_p, e->act_p, e->qbuf, e->logits0, e->logits17, e->join_logits0, e->join_logits17, e->scores, e->stats,
                     e->opart, e->kcache, e->vcache, e->kpack, e->vpack, e->d_page_table, e->d_seqs, e->d_meta, e->d_ls, e->d_decisions,
                     e->d_cur, e->d_gen, e->d_declog, e->d_forced, e->d_tf, e->d_bitmaps, e->d_scfg, e->d_pf_tokens,
-                    e->d_pf_meta};
+                    e->d_pf_meta, e->d_lp};
     for (void* p : ptrs) if (p) hipFree(p);
     if (e->h_ls) hipHostFree(e->h_ls);
     if (e->h_seqs) hipHostFree(e->h_seqs);
@@ -943,6 +958,26 @@ static int ensure_gen_storage(MttsEngine* e, int steps) {
     return 0;
 }
 
+// output_scores: the switch of the run that starts now; its buffer exists only once a run asked for it, follows gen_cap,
+// and starts as NaN (0xff bytes) in every slot
+static int start_scores(MttsEngine* e, hipStream_t st) {
+    e->scores_on = e->scores_next;
+    if (!e->scores_on) return 0;
+    if (!e->sscr.lp) {
+        drop_graphs(e);                  // (captured steps hold the scratch pointers by value)
+        TRY(alloc_lp_scratch(e->sscr, e->cfg.max_batch));
+    }
+    const size_t n = (size_t)e->cfg.max_batch * e->gen_cap * 8;
+    if (!e->d_lp || e->lp_cap != e->gen_cap) {
+        if (e->d_lp) { hipFree(e->d_lp); e->d_lp = nullptr; }
+        drop_graphs(e);                  // captured steps hold the old pointer
+        TRY(dalloc(&e->d_lp, n, false));
+        e->lp_cap = e->gen_cap;
+    }
+    HIPCHK(hipMemsetAsync(e->d_lp, 0xff, n * sizeof(float), st));
+    return 0;
+}
+
 // One launch of fork_kernel (layer.hip): the page pairs already in `job`, plus for its row pairs the rows of the logits
 // and, with `state_rows`, of the history bitmaps and the teacher-forcing tail.
 static int launch_fork_job(MttsEngine* e, ForkJob& job, bool state_rows, hipStream_t st) {
@@ -1037,6 +1072,7 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
     e->max_steps = max_steps;
     // generation buffers
     TRY(ensure_gen_storage(e, max_steps));
+    TRY(start_scores(e, st));
     // flattened prefill rows; every dialogue starts on a 32-row tile boundary so that a tile holds consecutive
     // positions of one dialogue (the prefill attention kernels share K/V pages across a tile); filler rows are idle
     size_t Mtot = 0;
@@ -1117,6 +1153,7 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
     // row's logits into theirs (bitmaps, teacher-forcing tails and states were uploaded for every row above)
     if (fork.nr) TRY(launch_fork_job(e, fork, false, st));
     e->began = true;
+    e->run_open = true;
     return MTTS_OK;
 }
 
@@ -1142,17 +1179,18 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
 static int step_body(MttsEngine* e, int pages_bound, hipStream_t st, int64_t kvtok) {
     launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
                   e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, e->B, e->sscr, e->ch0_sampled,
-                  full_cap_for(e->V0), st);
+                  full_cap_for(e->V0), e->scores_on, st);
     launch_update(e->d_decisions, e->d_declog, e->has_forced ? e->d_forced : nullptr, e->d_tf, e->d_gen, e->d_cur,
                   e->d_seqs, e->d_meta, e->d_bitmaps, e->bm_words, e->d_ls, e->cfg.eos_token_id,
-                  e->cfg.speech_pad_token, e->cfg.speech_range_lo, e->cfg.speech_range_hi, st);
+                  e->cfg.speech_pad_token, e->cfg.speech_range_lo, e->cfg.speech_range_hi,
+                  e->scores_on ? e->sscr.lp : nullptr, e->scores_on ? e->d_lp : nullptr, st);
     return forward_rows(e, e->d_cur, e->d_meta, round_up(e->B, 32), pages_bound, 1, st, kvtok);
 }
 
 static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     const int forced = e->has_forced ? 1 : 0;
     for (auto& g : e->graphs)
-        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled) {
+        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled && g.scores == e->scores_on) {
             *out = g.exec;
             return MTTS_OK;
         }
@@ -1168,7 +1206,7 @@ static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     HIPCHK(ie);
-    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, exec});
+    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, e->scores_on, exec});
     *out = exec;
     return MTTS_OK;
 }
@@ -1242,6 +1280,7 @@ int32_t mtts_sync_state(MttsEngine* e, int32_t* steps_done, int32_t* all_finishe
     }
     if (steps_done) *steps_done = e->h_ls->step;
     if (all_finished) *all_finished = e->h_ls->done;
+    if (e->h_ls->done && !e->continuous) e->run_open = false;
     return MTTS_OK;
 }
 
@@ -1263,6 +1302,44 @@ int32_t mtts_read_generated(MttsEngine* e, int64_t* host_gen, int32_t capacity_s
     HIPCHK(hipSetDevice(e->device));
     TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
     return read_rows(e, e->d_gen, host_gen, capacity_steps, n_steps);
+}
+
+int32_t mtts_set_output_scores(MttsEngine* e, int32_t on) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    on = on ? 1 : 0;
+    if (on == e->scores_next) return MTTS_OK;
+    if (e->run_open) {                   // the device knows whether the run has ended: every row finished / every slot empty
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipDeviceSynchronize());
+        LoopState ls;
+        std::vector<SeqState> ss(MTTS_RCAP);
+        HIPCHK(hipMemcpy(&ls, e->d_ls, sizeof(ls), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ss.data(), e->d_seqs, ss.size() * sizeof(SeqState), hipMemcpyDeviceToHost));
+        bool live = false;
+        for (int b = 0; b < e->B; ++b) live |= ss[b].active != 0;
+        if (live && !ls.done)
+            return fail(MTTS_ESTATE, "output_scores cannot change while a run is open (it is read when a run begins)");
+        e->run_open = false;
+    }
+    e->scores_next = on;
+    return MTTS_OK;
+}
+
+// host_lp float [capacity_steps][rows][8]: row space and step range of mtts_read_generated
+int32_t mtts_read_scores(MttsEngine* e, float* host_lp, int32_t capacity_steps, int32_t* n_steps) {
+    if (!e || !e->began || !host_lp) return fail(MTTS_ESTATE, "nothing generated");
+    if (!e->scores_on) return fail(MTTS_ESTATE, "the run was started with output_scores off (mtts_set_output_scores)");
+    HIPCHK(hipSetDevice(e->device));
+    TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
+    const int steps = e->h_ls->step;
+    if (steps > capacity_steps) return fail(MTTS_EINVAL, "output buffer holds %d steps, need %d", capacity_steps, steps);
+    std::vector<float> tmp((size_t)std::max(steps, 1) * 8);
+    for (int b = 0; b < e->B; ++b) {
+        if (steps) HIPCHK(hipMemcpy(tmp.data(), e->d_lp + (size_t)b * e->gen_cap * 8, (size_t)steps * 8 * 4, hipMemcpyDeviceToHost));
+        for (int s = 0; s < steps; ++s) memcpy(host_lp + ((size_t)s * e->B + b) * 8, tmp.data() + (size_t)s * 8, 8 * sizeof(float));
+    }
+    if (n_steps) *n_steps = steps;
+    return MTTS_OK;
 }
 
 int32_t mtts_read_logits_f32(MttsEngine* e, float* l0, float* l17, void* stream) {
@@ -1349,6 +1426,7 @@ int32_t mtts_generate(MttsEngine* e, const int64_t* ids, const uint8_t* mask, in
     }
     if (decisions) TRY(read_rows(e, e->d_declog, decisions, steps, &ns));
     *out_len = total;
+    e->run_open = false;               // (a forced replay may stop before every row has finished)
     return MTTS_OK;
 }
 
@@ -1379,6 +1457,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     if (B < 1 || B > e->cfg.max_batch) return fail(MTTS_EINVAL, "batch %d exceeds max_batch %d", B, e->cfg.max_batch);
     if (gen_cap < 8) return fail(MTTS_EINVAL, "gen_cap too small");
     TRY(ensure_gen_storage(e, gen_cap));
+    TRY(start_scores(e, st));
     e->B = B; e->steps_issued = 0; e->has_forced = false; e->continuous = true;
     e->max_steps = 1 << 30;
     e->n_real.assign(B, 0);
@@ -1403,6 +1482,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     HIPCHK(hipMemsetAsync(e->sscr.overflow, 0, (size_t)e->cfg.max_batch * 4, st));
     HIPCHK(hipStreamSynchronize(st));
     e->began = true;
+    e->run_open = true;
     return MTTS_OK;
 }
 
@@ -1623,6 +1703,20 @@ int32_t mtts_slot_read(MttsEngine* e, int32_t slot, int64_t* host_rows, int32_t 
     return MTTS_OK;
 }
 
+// log-probabilities of one slot's generated rows: host_rows float [steps][8]
+int32_t mtts_slot_read_scores(MttsEngine* e, int32_t slot, float* host_rows, int32_t capacity_steps, int32_t* n_steps) {
+    if (!e || !e->began || !host_rows || slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "bad argument");
+    if (!e->scores_on) return fail(MTTS_ESTATE, "the run was started with output_scores off (mtts_set_output_scores)");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());
+    SeqState cur;
+    HIPCHK(hipMemcpy(&cur, e->d_seqs + slot, sizeof(cur), hipMemcpyDeviceToHost));
+    if (cur.step > capacity_steps) return fail(MTTS_EINVAL, "buffer holds %d steps, need %d", capacity_steps, cur.step);
+    if (cur.step) HIPCHK(hipMemcpy(host_rows, e->d_lp + (size_t)slot * e->gen_cap * 8, (size_t)cur.step * 8 * 4, hipMemcpyDeviceToHost));
+    if (n_steps) *n_steps = cur.step;
+    return MTTS_OK;
+}
+
 // Frames first..first+n-1 of every sequence as codec codes int64 [8][B][n] on the device (delay pattern undone,
 // channel-0 offset removed): lets the codec decode windows while the decode loop is still running.  The caller
 // orders `stream` after the steps that produced frame first+n+6 (event / same stream).
@@ -1706,8 +1800,8 @@ int32_t mtts_k_rmsnorm(const void* x, const void* w, void* y, int32_t rows, int3
     return MTTS_OK;
 }
 
-int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
-                      int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, void* stream) {
+static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                    int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp, void* stream) {
     if (!logits || !cfg || !dev_tokens || rows < 1 || vocab < 1 || channel < 0 || channel > 7) return fail(MTTS_EINVAL, "sample: bad argument");
     hipStream_t st = S(stream);
     MttsSamplerCfg h[8];
@@ -1722,9 +1816,11 @@ int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const voi
     HIPCHK(hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice));
     SampleScratch sc;
     struct ScratchGuard { SampleScratch* s; ~ScratchGuard() { free_scratch(*s); } } sg{&sc};
-    sc = SampleScratch{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    sc = SampleScratch{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     TRY(alloc_scratch(sc, rows, vocab));
-    launch_sample_single(logits, rows, vocab, (const uint32_t*)bitmap, (vocab + 31) / 32, d, mask_id, seed, step, channel, dec, err, sc, full_cap_for(vocab), st);
+    if (dev_logp) TRY(alloc_lp_scratch(sc, rows));
+    launch_sample_single(logits, rows, vocab, (const uint32_t*)bitmap, (vocab + 31) / 32, d, mask_id, seed, step, channel, dec, err, sc,
+                         full_cap_for(vocab), dev_logp ? 1 : 0, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     std::vector<int32_t> hd((size_t)rows * 8);
@@ -1734,8 +1830,26 @@ int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const voi
     std::vector<int32_t> outv(rows);
     for (int r = 0; r < rows; ++r) outv[r] = hd[(size_t)r * 8 + channel];
     HIPCHK(hipMemcpy(dev_tokens, outv.data(), rows * 4, hipMemcpyHostToDevice));
+    if (dev_logp) {
+        std::vector<float> hl((size_t)rows * 8), outl(rows);
+        HIPCHK(hipMemcpy(hl.data(), sc.lp, hl.size() * 4, hipMemcpyDeviceToHost));
+        for (int r = 0; r < rows; ++r) outl[r] = hl[(size_t)r * 8 + channel];
+        HIPCHK(hipMemcpy(dev_logp, outl.data(), rows * 4, hipMemcpyHostToDevice));
+    }
     if (herr) return fail(MTTS_EINVAL, "sample: more than 4096 candidate tokens");
     return MTTS_OK;
+}
+
+int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                      int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, void* stream) {
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, stream);
+}
+
+int32_t mtts_k_sample_scores(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                             int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
+                             void* stream) {
+    if (!dev_logp) return fail(MTTS_EINVAL, "sample: null dev_logp");
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, stream);
 }
 
 // ---- per-kernel entry points for attention and RoPE / cache write (unit tests) ----------------------------------------

@@ -106,6 +106,9 @@ struct SampleScratch {
     int32_t* full_idx;     // [rows][full_cap]   full-vocabulary path: key of every token
     uint32_t* nuc_cnt;     // [rows][2048] level-0 histogram (count) left by the collect kernel for the full-vocabulary kernel
     unsigned long long* nuc_mass;   // [rows][2048] ... and mass (exp(s - max) * 2^45, exact integer sums)
+    // the next two exist only once output_scores was asked for (null otherwise; only the LP kernels touch them)
+    float* slice_sum;      // [rows][SAMP_NS] output_scores, greedy channel 0: sum of exp(s - slice_val) over the slice (its max IS slice_val)
+    float* lp;             // [rows][8] output_scores: log-probability of decisions[row][c], read by update_kernel
 };
 
 struct SampleCtx {         // resolved per (row, channel)
@@ -171,6 +174,30 @@ __device__ __forceinline__ void block_argmax(float& bv, int& bi, float* shf, int
     __syncthreads();
 }
 
+// block-wide exclusive prefix sum of one double per thread (NT threads); returns (exclusive, total).
+// Sums run in fp64: a nucleus over the whole 152 k vocabulary has terms of 1e-5 of the total, and the draw must
+// land on the same token as the oracle's fp64 cumulative sum.
+template <int NT>
+__device__ __forceinline__ double block_excl_scan(double v, double* sh, double& total) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    double inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        double t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();
+    if (lane == 63) sh[wid] = inc;
+    __syncthreads();
+    double base = 0.0, tot = 0.0;
+    for (int w = 0; w < NT / 64; ++w) { if (w < wid) base += sh[w]; tot += sh[w]; }
+    total = tot;
+    __syncthreads();
+    return base + inc - v;
+}
+
+// LP (output_scores): a greedy row's slices also leave sum exp(s - slice max), combined by sample_final_kernel.
+template <bool LP>
 __global__ __launch_bounds__(SAMP_T) void sample_scan_kernel(
     const uint16_t* __restrict__ logits0, int V0, const uint32_t* __restrict__ bitmaps, int bm_words,
     const MttsSamplerCfg* __restrict__ cfgs, const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs,
@@ -179,6 +206,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_scan_kernel(
     __shared__ uint32_t hist[2048];
     __shared__ float shf[SAMP_T / 64];
     __shared__ int shi[SAMP_T / 64];
+    __shared__ double shd[SAMP_T / 64];
     const int b = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
@@ -198,6 +226,18 @@ __global__ __launch_bounds__(SAMP_T) void sample_scan_kernel(
     }
     block_argmax(bv, bi, shf, shi);
     if (tid == 0) { sc.slice_val[b * SAMP_NS + slice] = bv; sc.slice_idx[b * SAMP_NS + slice] = bi; }
+    if (LP && !cfg.do_sample) {
+        // second pass over the slice (L2 resident): at most 19 fp32 terms per thread, then fp64 in a fixed order
+        float loc = 0.f;
+        if (bv > -INFINITY)
+            for (int i = i0 + tid; i < i1; i += SAMP_T) {
+                const float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp);
+                if (s > -INFINITY) loc += expf(s - bv);
+            }
+        double tot;
+        (void)block_excl_scan<SAMP_T>((double)loc, shd, tot);
+        if (tid == 0) sc.slice_sum[b * SAMP_NS + slice] = (float)tot;
+    }
     if (want_hist)
         for (int i = tid; i < 2048; i += SAMP_T)
             if (hist[i]) atomicAdd(&sc.hist[(size_t)b * 2048 + i], hist[i]);
@@ -321,34 +361,13 @@ __global__ __launch_bounds__(SAMP_T) void sample_collect_kernel(
     }
 }
 
-// block-wide exclusive prefix sum of one double per thread (NT threads); returns (exclusive, total).
-// Sums run in fp64: a nucleus over the whole 152 k vocabulary has terms of 1e-5 of the total, and the draw must
-// land on the same token as the oracle's fp64 cumulative sum.
-template <int NT>
-__device__ __forceinline__ double block_excl_scan(double v, double* sh, double& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    double inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        double t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) sh[wid] = inc;
-    __syncthreads();
-    double base = 0.0, tot = 0.0;
-    for (int w = 0; w < NT / 64; ++w) { if (w < wid) base += sh[w]; tot += sh[w]; }
-    total = tot;
-    __syncthreads();
-    return base + inc - v;
-}
-
 // Everything after the candidates are known: sort, HF top-k / top-p cuts, Philox draw.
 // val/idx: n candidate (score, id) pairs (LDS for the fast path, global memory for the full-vocabulary path),
-// capacity >= next_pow2(n).  NT threads.  Returns the chosen token in every thread.
+// capacity >= next_pow2(n).  NT threads.  Returns the chosen token in every thread; lp (may be null): thread 0's
+// receives log(softmax over the kept set)[pick].
 template <int NT>
 __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, int n, const MttsSamplerCfg& cfg, float smax,
-                             uint32_t step, uint32_t b, uint32_t c, uint64_t seed, double* shd, int* sh_i) {
+                             uint32_t step, uint32_t b, uint32_t c, uint64_t seed, double* shd, int* sh_i, float* lp) {
     const int tid = threadIdx.x;
     // bitonic sort of P = next_pow2(n) slots by (score asc, id asc); padding sorts last
     int P = 1;
@@ -423,9 +442,12 @@ __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, i
     __syncthreads();
     int r = sh_i[1];
     if (r >= nk) r = nk - 1;                    // u*tot rounding: fall back to the last kept token
+    // output_scores: log-probability of the pick under the distribution it was drawn from (the kept set, total `tot`)
+    if (lp && tid == 0) *lp = (float)((double)(cval[n - 1 - r] - smax) - log(tot));
     return cidx[n - 1 - r];
 }
 
+template <bool LP>
 __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
     const uint16_t* __restrict__ logits0, const uint16_t* __restrict__ logits17, int V0, int Vs, int Vs_pad,
     const uint32_t* __restrict__ bitmaps, int bm_words, const MttsSamplerCfg* __restrict__ cfgs,
@@ -501,15 +523,46 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
     }
     if (!cfg.do_sample) {
         if (tid == 0) decisions[out_slot] = amax;
+        if (LP) {
+            // greedy: lp = log_softmax over every finite processed score at the argmax = -log(sum exp(s - smax)).
+            // -inf scores add nothing; an all -inf row (cannot occur: the argmax is finite) gives NaN, no trap.
+            double tot = 0.0;
+            if (big) {
+                if (tid == 0)                    // the row's 32 (slice max, slice sum) pairs, in slice order
+                    for (int j = 0; j < SAMP_NS; ++j) {
+                        const float m = sc.slice_val[b * SAMP_NS + j];
+                        if (m > -INFINITY) tot += (double)sc.slice_sum[b * SAMP_NS + j] * (double)expf(m - smax);
+                    }
+            } else {
+                float loc = 0.f;
+                if (smax > -INFINITY)
+                    for (int i = tid; i < x.V; i += SAMP_T) {
+                        const float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp);
+                        if (s > -INFINITY) loc += expf(s - smax);
+                    }
+                (void)block_excl_scan<SAMP_T>((double)loc, shd, tot);
+            }
+            if (tid == 0) sc.lp[out_slot] = tot > 0.0 ? (float)(-log(tot)) : __uint_as_float(0x7fc00000u);
+        }
         return;
     }
     if (n > SAMP_CAND || n == 0) {               // too many candidates: hand the row to the full-vocabulary kernel
-        if (tid == 0) { decisions[out_slot] = amax; if (n > SAMP_CAND && sc.overflow[b] == 0) sc.overflow[b] = 1; }
+        if (tid == 0) {
+            decisions[out_slot] = amax;
+            if (n > SAMP_CAND && sc.overflow[b] == 0) sc.overflow[b] = 1;
+            // channel 0 with too many candidates: the full-vocabulary kernel overwrites this.  n == 0 (every score -inf:
+            // cannot occur, the argmax is finite) on ANY channel: the NaN is final, nothing follows for channels 1-7
+            if (LP) sc.lp[out_slot] = __uint_as_float(0x7fc00000u);
+        }
         return;
     }
+    float lpv = 0.f;
     const int pick = finish_sample<SAMP_T>(cval, cidx, n, cfg, smax, (uint32_t)x.step, x.row_id, (uint32_t)x.c,
-                                           single_vocab > 0 ? seed : x.seed, shd, sh_i);
-    if (tid == 0) decisions[out_slot] = pick;
+                                           single_vocab > 0 ? seed : x.seed, shd, sh_i, LP ? &lpv : nullptr);
+    if (tid == 0) {
+        decisions[out_slot] = pick;
+        if (LP) sc.lp[out_slot] = lpv;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -674,8 +727,8 @@ __device__ void nuc_drop_prefix(NucShared& S, int binA, unsigned int dc, u64 dm,
 __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
     const uint16_t* __restrict__ logits0, int V0, const uint32_t* __restrict__ bitmaps, int bm_words,
     const MttsSamplerCfg* __restrict__ cfgs, const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs,
-    uint64_t seed, int32_t* __restrict__ decisions, SampleScratch sc, int full_cap, int single_vocab, int single_mask, int single_step,
-    int single_channel) {
+    uint64_t seed, int32_t* __restrict__ decisions, SampleScratch sc, int full_cap, int emit_lp, int single_vocab, int single_mask,
+    int single_step, int single_channel) {
     __shared__ NucShared S;
     __shared__ float shf[SAMP_FT / 64];
     __shared__ int shi[SAMP_FT / 64];
@@ -774,7 +827,15 @@ __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
             pick = nuc_select_id(S, keys, bins, V, z, smax, binA, kd, false, j - 1);
         }
     }
-    if (tid == 0) { decisions[b * 8 + x.c] = pick; sc.overflow[b] = 0; }
+    if (tid == 0) {
+        decisions[b * 8 + x.c] = pick;
+        sc.overflow[b] = 0;
+        // output_scores: the pick's own score over the exact integer mass of the kept set (the pick's quantised mass would
+        // carry only a few significant bits for an unlikely token)
+        if (emit_lp)
+            sc.lp[b * 8 + x.c] = n > 0 ? (float)((double)(unfkey(keys[pick]) - smax) - log((double)tot / NUC_SCALE))
+                                       : __uint_as_float(0x7fc00000u);
+    }
 }
 
 // One block; thread b handles sequence slot b.  Restates modeling_asteroid.py:139-169 with a per-dialogue clock.
@@ -783,7 +844,8 @@ __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __
                               const int32_t* __restrict__ forced, const int32_t* __restrict__ tf_tail,
                               int32_t* __restrict__ gen, int32_t* __restrict__ cur_tokens,
                               SeqState* __restrict__ seqs, RowMeta* __restrict__ meta, uint32_t* __restrict__ bitmaps,
-                              int bm_words, LoopState* __restrict__ ls, int eos, int spad, int sp_lo, int sp_hi) {
+                              int bm_words, LoopState* __restrict__ ls, int eos, int spad, int sp_lo, int sp_hi,
+                              const float* __restrict__ lp_in, float* __restrict__ lp_out) {
     __shared__ int any_unfinished;
     if (ls->done) return;
     const int b = threadIdx.x, B = ls->B;
@@ -842,6 +904,17 @@ __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __
 #pragma unroll
                 for (int c = 1; c < 8; ++c) tok[c] = spad;
             }
+            // output_scores (lp_out [slot][gen_cap][8], laid out like gen): the sampler's log-probability where the appended
+            // token is the model's decision, NaN where teacher forcing, the EOS flush or finished-row padding replaced it.
+            // The rule is the one applied to tok[] above; the replay hook (forced) has no part in it.
+            if (lp_out) {
+                const bool flush = s.nas > 0 && s.nas < 7;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    const bool used = s.unfinished && !(step < 7 && c >= step + 1) && !(flush && (c == 0 || s.nas < 8 - c));
+                    lp_out[slot + c] = used ? lp_in[b * 8 + c] : __uint_as_float(0x7fc00000u);
+                }
+            }
             if (dec_log && !as_draw) {
 #pragma unroll
                 for (int c = 0; c < 8; ++c) dec_log[slot + c] = tok[c];
@@ -889,46 +962,48 @@ __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __
 }
 
 static SampleScratch g_dummy_scratch;
+// emit_lp (output_scores): the LP instantiations of the scan / final kernels; off, the step runs the plain ones.
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps, int bm_words,
                    const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed, int32_t* decisions,
-                   int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap, hipStream_t st) {
+                   int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap, int emit_lp, hipStream_t st) {
     const int big0 = V0 > SAMP_CAND ? 1 : 0;
     if (big0) {
-        hipLaunchKernelGGL(sample_scan_kernel, dim3(SAMP_NS, B), dim3(SAMP_T), 0, st, (const uint16_t*)logits0, V0,
-                           bitmaps, bm_words, cfgs, ls, seqs, sc, 0, 0, 0, 0);
+        hipLaunchKernelGGL(emit_lp ? sample_scan_kernel<true> : sample_scan_kernel<false>, dim3(SAMP_NS, B), dim3(SAMP_T), 0, st,
+                           (const uint16_t*)logits0, V0, bitmaps, bm_words, cfgs, ls, seqs, sc, 0, 0, 0, 0);
         if (ch0_sampled)
             hipLaunchKernelGGL(sample_collect_kernel, dim3(SAMP_NS, B), dim3(SAMP_T), 0, st, (const uint16_t*)logits0, V0,
                                bitmaps, bm_words, cfgs, ls, seqs, sc, full_cap, 0, 0, 0, 0);
     }
-    hipLaunchKernelGGL(sample_final_kernel, dim3(8, B), dim3(SAMP_T), 0, st, (const uint16_t*)logits0,
-                       (const uint16_t*)logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, err, sc,
-                       big0, 0, 0, 0, 0);
+    hipLaunchKernelGGL(emit_lp ? sample_final_kernel<true> : sample_final_kernel<false>, dim3(8, B), dim3(SAMP_T), 0, st,
+                       (const uint16_t*)logits0, (const uint16_t*)logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed,
+                       decisions, err, sc, big0, 0, 0, 0, 0);
     if (big0 && ch0_sampled)
         hipLaunchKernelGGL(sample_full_kernel, dim3(B), dim3(SAMP_FT), 0, st, (const uint16_t*)logits0, V0, bitmaps,
-                           bm_words, cfgs, ls, seqs, seed, decisions, sc, full_cap, 0, 0, 0, 0);
+                           bm_words, cfgs, ls, seqs, seed, decisions, sc, full_cap, emit_lp, 0, 0, 0, 0);
 }
 void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
                           const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
-                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, hipStream_t st) {
+                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp, hipStream_t st) {
     if (vocab > SAMP_CAND) {
-        hipLaunchKernelGGL(sample_scan_kernel, dim3(SAMP_NS, rows), dim3(SAMP_T), 0, st, (const uint16_t*)logits, vocab,
-                           bitmap, bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, sc, vocab, mask_id, step, channel);
+        hipLaunchKernelGGL(emit_lp ? sample_scan_kernel<true> : sample_scan_kernel<false>, dim3(SAMP_NS, rows), dim3(SAMP_T), 0, st,
+                           (const uint16_t*)logits, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr,
+                           (const SeqState*)nullptr, sc, vocab, mask_id, step, channel);
         hipLaunchKernelGGL(sample_collect_kernel, dim3(SAMP_NS, rows), dim3(SAMP_T), 0, st, (const uint16_t*)logits, vocab,
                            bitmap, bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, sc, full_cap, vocab, mask_id, step, channel);
     }
-    hipLaunchKernelGGL(sample_final_kernel, dim3(1, rows), dim3(SAMP_T), 0, st, (const uint16_t*)logits,
-                       (const uint16_t*)nullptr, vocab, vocab, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr,
-                       (const SeqState*)nullptr, seed, decisions, err, sc, 1, vocab, mask_id, step, channel);
+    hipLaunchKernelGGL(emit_lp ? sample_final_kernel<true> : sample_final_kernel<false>, dim3(1, rows), dim3(SAMP_T), 0, st,
+                       (const uint16_t*)logits, (const uint16_t*)nullptr, vocab, vocab, vocab, bitmap, bm_words, cfgs8,
+                       (const LoopState*)nullptr, (const SeqState*)nullptr, seed, decisions, err, sc, 1, vocab, mask_id, step, channel);
     if (vocab > SAMP_CAND)
         hipLaunchKernelGGL(sample_full_kernel, dim3(rows), dim3(SAMP_FT), 0, st, (const uint16_t*)logits, vocab, bitmap,
-                           bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, seed, decisions, sc, full_cap, vocab,
-                           mask_id, step, channel);
+                           bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, seed, decisions, sc, full_cap, emit_lp,
+                           vocab, mask_id, step, channel);
 }
 void launch_update(const int32_t* decisions, int32_t* dec_log, const int32_t* forced, const int32_t* tf_tail,
                    int32_t* gen, int32_t* cur_tokens, SeqState* seqs, RowMeta* meta, uint32_t* bitmaps, int bm_words,
-                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, hipStream_t st) {
+                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out, hipStream_t st) {
     hipLaunchKernelGGL(update_kernel, dim3(1), dim3(MTTS_RCAP), 0, st, decisions, dec_log, forced, tf_tail, gen,
-                       cur_tokens, seqs, meta, bitmaps, bm_words, ls, eos, spad, sp_lo, sp_hi);
+                       cur_tokens, seqs, meta, bitmaps, bm_words, ls, eos, spad, sp_lo, sp_hi, lp_in, lp_out);
 }
 
 // Un-shift the delay pattern on the device (reference generation_utils.py:416-425):

@@ -102,6 +102,23 @@ def _load_safetensors_dir(path):
     return sd
 
 
+class GenerateOutput:
+    """What generate(return_dict_in_generate=True) returns (HF GenerateDecoderOnlyOutput, modeling_asteroid.py:171-195
+    of the reference), reduced to what the engine keeps: `sequences` and, with output_scores=True,
+    `transition_scores` float32 [B*n, G, 8] = compute_transition_scores(sequences, scores, normalize_logits=True)
+    per channel (NaN where the token is not a model decision) and `sequences_scores` [B*n] = their nansum.  The full
+    per-step score rows are not materialised: `scores` is None."""
+
+    def __init__(self, sequences, transition_scores=None):
+        self.sequences = sequences
+        self.scores = None
+        self.transition_scores = transition_scores
+        self.sequences_scores = None if transition_scores is None else torch.nansum(transition_scores, dim=(1, 2))
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+
 class AsteroidTTSInstruct:
     MAX_ENGINE_BATCH = 128          # rows one engine pass carries (4 activation tiles share each weight stream)
 
@@ -171,10 +188,19 @@ class AsteroidTTSInstruct:
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,
-                 num_return_sequences=None, **_):
+                 num_return_sequences=None, return_dict_in_generate=False, output_scores=False, **kw):
         """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
         num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
-        repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages."""
+        repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages.
+        return_dict_in_generate=True -> GenerateOutput (.sequences = that tensor); with output_scores=True it carries
+        the per-token log-probabilities from the device sampler (modeling_asteroid.py:69-80,171-195 of the reference
+        return full score rows; see GenerateOutput)."""
+        if return_dict_in_generate:
+            bad = [k for k in ("output_logits", "output_attentions", "output_hidden_states") if kw.get(k)]
+            if bad:
+                raise ValueError(f"{', '.join(bad)} with return_dict_in_generate: the MI355X engine keeps no logits, attentions "
+                                 "or hidden states; only output_scores (per-token log-probabilities) is available")
+        want_lp = bool(return_dict_in_generate and output_scores)
         gc = self.generation_config
         B, T, C = input_ids.shape
         if C != self.channels:
@@ -207,10 +233,14 @@ class AsteroidTTSInstruct:
         if R <= self.MAX_ENGINE_BATCH:
             # one static batch, the reference's semantics: finished rows emit (eos, 1024 x 7) until the batch ends
             out = eng.generate(ids, msk, int(max_length), layers=layers, do_samples=do_samples, seed=seed,
-                               row_ids=[r * n + j for r in rows for j in range(n)], takes=n)
+                               row_ids=[r * n + j for r in rows for j in range(n)], takes=n, output_scores=want_lp)
         else:
-            out = self._generate_scheduled(eng, ids, msk, int(max_length), layers, do_samples, seed, rows, n)
-        return torch.from_numpy(out).to(input_ids.device)
+            out = self._generate_scheduled(eng, ids, msk, int(max_length), layers, do_samples, seed, rows, n, want_lp)
+        out, lp = out if want_lp else (out, None)
+        seq = torch.from_numpy(out).to(input_ids.device)
+        if not return_dict_in_generate:
+            return seq
+        return GenerateOutput(seq, None if lp is None else torch.from_numpy(lp).to(input_ids.device))
 
     def _next_seed(self, seed):
         """Philox key of this call.  Explicit `seed=` / `generation_config.seed` / `model.sample_seed` win; otherwise it
@@ -224,7 +254,7 @@ class AsteroidTTSInstruct:
         self._calls += 1
         return int(seed)
 
-    def _generate_scheduled(self, eng, ids, msk, max_length, layers, do_samples, seed, rows, takes=1):
+    def _generate_scheduled(self, eng, ids, msk, max_length, layers, do_samples, seed, rows, takes=1, output_scores=False):
         """More rows than one pass carries: the continuous batcher serves them through MAX_ENGINE_BATCH slots (a
         finished dialogue's slot and KV pages go to the next one).  Row i draws from the Philox stream
         (seed; step, rows[i], channel) -- the stream row i of one static batch would use, so the same seed and prompts
@@ -239,7 +269,8 @@ class AsteroidTTSInstruct:
         new = max_length - T
         cb = ContinuousBatcher(eng, slots=self.MAX_ENGINE_BATCH, gen_cap=max_length - base + 8, layers=layers,   # max_new + 7 flush steps
                                do_samples=do_samples)
-        res = cb.run(prompts, new, seeds=[seed] * B, row_ids=rows, takes=takes)     # row k = take k % takes of prompt k // takes
+        res = cb.run(prompts, new, seeds=[seed] * B, row_ids=rows, takes=takes, output_scores=output_scores)     # row k = take k % takes of prompt k // takes
+        res, sc = res if output_scores else (res, None)
         G = max(r.shape[0] - (T - pads[k // takes] - 7) for k, r in enumerate(res))
         full = np.full((B * takes, base + G, C), self.config.speech_pad_token, dtype=np.int64)
         full[:, :, 0] = self.config.eos_token_id            # finished-row padding (modeling_asteroid.py:155-158)
@@ -248,4 +279,9 @@ class AsteroidTTSInstruct:
             full[k, :base] = ids[b, :base]
             gen = r[T - pads[b] - 7:]
             full[k, base:base + gen.shape[0]] = gen
-        return full
+        if not output_scores:
+            return full
+        lp = np.full((B * takes, G, C), np.nan, dtype=np.float32)      # NaN: padding after a dialogue has left
+        for k, v in enumerate(sc):
+            lp[k, :v.shape[0]] = v
+        return full, lp

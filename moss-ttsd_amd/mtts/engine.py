@@ -121,14 +121,25 @@ class Engine:
         capi.check(self.lib.mtts_set_takes(self._h, takes))
         return takes
 
+    def set_output_scores(self, on):
+        """Sticky engine switch, read when the next run begins (begin / generate / sched_open): per-token
+        log-probabilities (include/mtts.h: mtts_set_output_scores).  MttsError(ESTATE) when it would change while rows of
+        a run are still unfinished -- also a run that was abandoned mid-flight (begin + a few steps): end that one with
+        sched_open(slots, gen_cap, output_scores=<its setting>) first.  begin / generate / sched_open call this with their
+        own `output_scores` argument, so the same holds for them."""
+        capi.check(self.lib.mtts_set_output_scores(self._h, 1 if on else 0))
+
     def generate(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, forced=None,
-                 forced_as_draw=False, row_ids=None, takes=1):
+                 forced_as_draw=False, row_ids=None, takes=1, output_scores=False):
         """forced (verification hook): int64 [B,G,8] full sequences of a reference run.  -> (ids, decisions [steps,B,8]).
         forced_as_draw: the forced row replaces each step's raw draw before the state machine (replay of a SAMPLED
         run); decisions are then the raw draws.  forced_as_draw="all": also for rows that max_length has cut off (the
         reference keeps evaluating them; scripted tests of chained resurrections).
         takes: sampled takes per prompt (HF num_return_sequences): B*takes rows, row b*takes+j is take j of prompt b,
-        equal to the run of the repeat-interleaved batch; row_ids then has B*takes entries."""
+        equal to the run of the repeat-interleaved batch; row_ids then has B*takes entries.
+        output_scores: the return value gains a last element lp, float32 [B*takes, G, 8] aligned with ids[:, T-7:]:
+        log_softmax(processed scores)[the sampler's decision], NaN where the appended token is not a model decision
+        (teacher forcing, EOS flush, finished-row padding)."""
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
         R = B * int(takes)
@@ -139,6 +150,7 @@ class Engine:
         out = np.zeros((R, cap, 8), dtype=np.int64)
         out_len = C.c_int32(0)
         scfg = sampler_cfgs(layers, do_samples)
+        self.set_output_scores(output_scores)
         self._set_row_ids(row_ids, R)       # Philox row id of each row (default: its position in this batch)
         self._set_takes(takes)
         fptr, flen, dptr, dec = None, 0, None, None
@@ -151,15 +163,19 @@ class Engine:
         capi.check(self.lib.mtts_generate(self._h, ids.ctypes.data, m.ctypes.data, B, T, int(max_length), scfg,
                                           C.c_uint64(seed), out.ctypes.data, cap, C.byref(out_len), fptr, flen, dptr, None))
         res = out[:, :out_len.value].copy()
-        if forced is not None:
-            return res, dec[:out_len.value - (T - 7)].copy()
-        return res
+        ret = (res,) if forced is None else (res, dec[:out_len.value - (T - 7)].copy())
+        if output_scores:
+            ret += (np.ascontiguousarray(self.read_scores(out_len.value - (T - 7)).transpose(1, 0, 2)),)
+        return ret if len(ret) > 1 else ret[0]
 
-    def begin(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, row_ids=None, takes=1):
-        """Prefill; takes as in generate() (the run then has B*takes rows)."""
+    def begin(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, row_ids=None, takes=1,
+              output_scores=False):
+        """Prefill; takes as in generate() (the run then has B*takes rows); output_scores: keep log-probabilities
+        for read_scores()."""
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
         self._B, self._T = B * int(takes), T
+        self.set_output_scores(output_scores)
         self._set_row_ids(row_ids, B * int(takes))
         self._set_takes(takes)
         capi.check(self.lib.mtts_begin(self._h, ids.ctypes.data, m.ctypes.data, B, T, int(max_length),
@@ -181,6 +197,13 @@ class Engine:
         capi.check(self.lib.mtts_read_generated(self._h, buf.ctypes.data, capacity_steps, C.byref(n)))
         return buf[:n.value]
 
+    def read_scores(self, capacity_steps):
+        """-> float32 [steps, rows, 8] log-probabilities of the run's generated rows (row space of read_generated)."""
+        buf = np.zeros((max(int(capacity_steps), 1), self._B, 8), dtype=np.float32)
+        n = C.c_int32(0)
+        capi.check(self.lib.mtts_read_scores(self._h, buf.ctypes.data, buf.shape[0], C.byref(n)))
+        return buf[:n.value]
+
     def read_logits(self):
         V0, Vs = self.cfg["vocab_size"], self.cfg["speech_vocab_size"]
         if self.dtype != "bf16":
@@ -195,8 +218,9 @@ class Engine:
         return f(l0), f(l17)
 
     # ---- continuous batching ---------------------------------------------------------
-    def sched_open(self, slots, gen_cap, layers=None, do_samples=None):
+    def sched_open(self, slots, gen_cap, layers=None, do_samples=None, output_scores=False):
         self._B = int(slots)
+        self.set_output_scores(output_scores)
         capi.check(self.lib.mtts_sched_open(self._h, int(slots), int(gen_cap), sampler_cfgs(layers, do_samples), None))
 
     def submit(self, slot, ids, max_length, seed=0, row_id=0):
@@ -222,6 +246,13 @@ class Engine:
         buf = np.zeros((int(capacity), 8), dtype=np.int64)
         n = C.c_int32(0)
         capi.check(self.lib.mtts_slot_read(self._h, int(slot), buf.ctypes.data, int(capacity), C.byref(n)))
+        return buf[:n.value].copy()
+
+    def slot_read_scores(self, slot, capacity):
+        """-> float32 [steps, 8] log-probabilities of the slot's generated rows (like slot_read)."""
+        buf = np.zeros((max(int(capacity), 1), 8), dtype=np.float32)
+        n = C.c_int32(0)
+        capi.check(self.lib.mtts_slot_read_scores(self._h, int(slot), buf.ctypes.data, buf.shape[0], C.byref(n)))
         return buf[:n.value].copy()
 
     def evict(self, slot):

@@ -35,9 +35,10 @@ class ContinuousBatcher:
         self.steps_per_poll = int(steps_per_poll)
         self.evictions = 0
         self.forks = 0                                                # takes started by Engine.fork (no prefill of their own)
+        self._layers, self._do_samples, self._scores = layers, do_samples, False
         engine.sched_open(self.slots, self.gen_cap, layers=layers, do_samples=do_samples)
 
-    def run(self, prompts, max_new_tokens, seeds=None, base_seed=0, row_ids=None, takes=1):
+    def run(self, prompts, max_new_tokens, seeds=None, base_seed=0, row_ids=None, takes=1, output_scores=False):
         """prompts: list of int64 [T_i,8] delay-shifted prompts (no padding); max_new_tokens: int or list
         (HF semantics: max_length = T_i + max_new).  seeds: one Philox key per dialogue (default base_seed + i, so
         that concurrent dialogues draw from different streams).  Returns a list of int64 [T_i-7+G_i, 8] in
@@ -45,10 +46,17 @@ class ContinuousBatcher:
         dialogues' positions in a batch they draw what that static batch's rows draw.
         takes: sampled takes per prompt; take j of prompt i draws with seeds[i] and row id row_ids[i] * takes + j (the
         row of the repeat-interleaved batch), and the result list holds len(prompts) * takes entries, take j of prompt
-        i at i * takes + j."""
+        i at i * takes + j.
+        output_scores: returns (results, scores), scores[k] float32 [G_k, 8] = the log-probabilities of job k's generated
+        rows (Engine.generate: lp).  They are a function of (prompt, seed, row id) like the tokens: an evicted and re-run
+        dialogue, a forked take and a queued take all reproduce them."""
         takes = int(takes)
         if takes < 1:
             raise ValueError(f"takes must be >= 1 (got {takes})")
+        if bool(output_scores) != self._scores:                       # the switch is read when the scheduler opens
+            self._scores = bool(output_scores)
+            self.eng.sched_open(self.slots, self.gen_cap, layers=self._layers, do_samples=self._do_samples,
+                                output_scores=self._scores)
         n = len(prompts)
         mnt = [max_new_tokens] * n if np.isscalar(max_new_tokens) else list(max_new_tokens)
         seeds = list(seeds) if seeds is not None else [int(base_seed) + i for i in range(n)]
@@ -62,6 +70,7 @@ class ContinuousBatcher:
         forks = set(range(0, n * takes, takes)) if takes > 1 else set()
         n *= takes
         results = [None] * n
+        scores = [None] * n
         owner = [-1] * self.slots
         queue = list(range(n)) if takes == 1 else list(range(0, n, takes))
         steps = 0
@@ -113,12 +122,14 @@ class ContinuousBatcher:
                 if owner[s] >= 0 and not st[s, 0]:                    # left the batch: collect
                     i = owner[s]
                     rows = self.eng.slot_read(s, self.gen_cap)
+                    if self._scores:
+                        scores[i] = self.eng.slot_read_scores(s, self.gen_cap)
                     ids = np.asarray(prompts[i], dtype=np.int64)
                     results[i] = np.concatenate([ids[:ids.shape[0] - 7], rows], axis=0)
                     owner[s] = -1
                     hold = False
         self.engine_steps = steps
-        return results
+        return (results, scores) if self._scores else results
 
     def _fork_takes(self, s, i, takes, T, owner, queue, seeds, row_ids):
         """Take 0 of a prompt (job i) has just been submitted to slot s: fork takes 1.. into free slots while a page for
