@@ -236,6 +236,14 @@ int32_t mtts_k_gemm_bench(int32_t N, int32_t K, int32_t epi, int32_t ksplit, int
  * tiled prefill kernel. */
 int32_t mtts_k_gemm_bf16(const void* dev_w, const void* dev_x, void* dev_y,
                          int32_t M, int32_t N, int32_t K, int32_t ksplit, void* stream);
+/* number of GEMM launches of this process that took a depth-specialised kernel (gemm_depth_kernel / gemm_gateup48_kernel)
+ * instead of gemm_skinny_kernel; under graph replay a launch counts once, when it is captured (tests: did the dispatch fire) */
+int64_t mtts_debug_gemm_depth_launches(void);
+/* The decode path's gate/up GEMM with its SwiGLU epilogue: W[N,K] holds gate and up rows interleaved (row 2i = gate i,
+ * row 2i+1 = up i), Y[M,N/2] = bf16(bf16(silu(bf16(gate))) * bf16(up)), row-major.  M <= 128, N % 32 == 0, no split-K.
+ * Like mtts_k_gemm_bf16 and mtts_k_gemm_bench it reads MTTS_GEMM_DEPTH on every call (0: gemm_skinny_kernel only). */
+int32_t mtts_k_gemm_swiglu_bf16(const void* dev_w, const void* dev_x, void* dev_y,
+                                int32_t M, int32_t N, int32_t K, void* stream);
 /* RMSNorm (Qwen3RMSNorm, modeling_qwen3.py:59-64): x,w bf16 -> y bf16, rows x n. */
 int32_t mtts_k_rmsnorm(const void* dev_x, const void* dev_w, void* dev_y,
                        int32_t rows, int32_t n, float eps, void* stream);

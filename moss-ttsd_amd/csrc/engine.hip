@@ -20,7 +20,7 @@
 #include "common.h"
 
 // ---- kernels' launchers (other translation units) ---------------------------
-struct GemmPlan { int waves, ksplit, kt_per_split, kt_per_wave; };
+struct GemmPlan { int waves, ksplit, kt_per_split, kt_per_wave, depth; };
 enum { EPI_PARTIAL = 0, EPI_BF16 = 1, EPI_SILU = 2 };
 GemmPlan mtts_plan_gemm(int Npad, int K, int want_ksplit);
 GemmPlan mtts_plan_gemm_forced(int Npad, int K, int ksplit, int waves);
@@ -105,6 +105,12 @@ static inline int linger_bound(int B) { return 6 * B + 8; }
 
 // ---- errors -------------------------------------------------------------------
 static thread_local char g_err[512] = "";
+// MTTS_GEMM_DEPTH=0: every decode GEMM runs gemm_skinny_kernel, as before the depth-specialised kernels (gemm.hip);
+// the engine reads it at creation, the per-kernel hooks per call
+static int gemm_depth_env() {
+    const char* g = getenv("MTTS_GEMM_DEPTH");
+    return (g && atoi(g) == 0) ? 0 : 1;
+}
 static int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -148,6 +154,7 @@ struct MttsEngine {
     float* partial2 = nullptr;          // small-batch path: o_proj / down_proj slabs (the qkv slabs stay in `partial`)
     void *x2 = nullptr, *act_rm = nullptr;   // small-batch path: second residual buffer (ping-pong), row-major SwiGLU output
     int small_rows = SMALL_RP;          // decode batches up to this many dialogues take the small-batch path (0 = off)
+    int gemm_depth = 1;                 // depth-specialised decode GEMMs (gemm.hip; MTTS_GEMM_DEPTH=0: off)
     void *x = nullptr, *xn = nullptr, *attn_p = nullptr, *act_p = nullptr, *qbuf = nullptr, *hlast = nullptr, *xh = nullptr;
     void *logits0 = nullptr, *logits17 = nullptr, *join_logits0 = nullptr, *join_logits17 = nullptr;
     void* scores = nullptr;
@@ -450,6 +457,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     if (const char* g = getenv("MTTS_KV_PACK_MIN")) e->pack_min_work = atoi(g);
     if (const char* g = getenv("MTTS_PREFILL_MFMA_PAGES")) e->pf_mfma_pages = atoi(g);
     if (const char* g = getenv("MTTS_SMALL_ROWS")) e->small_rows = std::min(std::max(atoi(g), 0), SMALL_RP);
+    e->gemm_depth = gemm_depth_env();
     e->H = c->hidden_size; e->I = c->intermediate_size; e->L = c->num_hidden_layers;
     e->nq = c->num_attention_heads; e->nkv = c->num_key_value_heads;
     e->V0 = c->vocab_size; e->Vs = c->speech_vocab_size;
@@ -490,6 +498,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     e->p_d = mtts_plan_gemm(round_up(H, 32), I, 0);
     e->p_h0 = mtts_plan_gemm(e->V0_pad, H, 1);
     e->p_h17 = mtts_plan_gemm(7 * e->Vs_pad, H, 1);
+    for (GemmPlan* p : {&e->p_qkv, &e->p_o, &e->p_gu, &e->p_d, &e->p_h0, &e->p_h17}) p->depth = e->gemm_depth;
     // activations hold a whole prefill pass (MTTS_PFCAP rows); split-K slabs: up to 8 of [MTTS_PFCAP][Npad] fp32
     size_t pmax = (size_t)8 * std::max(e->qkv_rows, round_up(H, 32));
     if (!e->f32) {
@@ -1775,6 +1784,7 @@ int32_t mtts_k_gemm_bf16(const void* w, const void* x, void* y, int32_t M, int32
     void *wp = nullptr, *xp = nullptr;
     float* part = nullptr;
     GemmPlan p = mtts_plan_gemm(Npad, K, ksplit);
+    p.depth = gemm_depth_env();
     HookBufs hb;
     TRY(hb.get((uint16_t**)&wp, (size_t)Npad * K));
     // M <= 128: skinny kernel (decode); above: tiled kernel (prefill), ksplit as given or its own choice
@@ -1788,6 +1798,29 @@ int32_t mtts_k_gemm_bf16(const void* w, const void* x, void* y, int32_t M, int32
     if (tiled) launch_gemm_tile(EPI_PARTIAL, M, ks, wp, xp, K, Npad, Npad, part, nullptr, st);
     else launch_gemm(EPI_PARTIAL, tiles, p, wp, xp, K, Npad, Npad, part, nullptr, st);
     launch_reduce_partial_bf16(part, y, ks, Npad, N, M, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+long long mtts_gemm_depth_launches();
+int64_t mtts_debug_gemm_depth_launches(void) { return (int64_t)mtts_gemm_depth_launches(); }
+void launch_unpack_rows(const void* packed, void* out, int R, int K, hipStream_t st);
+int32_t mtts_k_gemm_swiglu_bf16(const void* w, const void* x, void* y, int32_t M, int32_t N, int32_t K, void* stream) {
+    if (!w || !x || !y || M < 1 || M > MTTS_RCAP || K % 16 || N < 32 || N % 32) return fail(MTTS_EINVAL, "gemm_swiglu: need 1<=M<=128, K%%16==0, N%%32==0");
+    hipStream_t st = S(stream);
+    void *wp = nullptr, *xp = nullptr, *op = nullptr;
+    GemmPlan p = mtts_plan_gemm(N, K, 1);          // as the engine plans gate/up: no split-K
+    p.depth = gemm_depth_env();
+    HookBufs hb;
+    const int tiles = (M + 31) / 32, tp = tiles == 3 ? 4 : tiles;
+    TRY(hb.get((uint16_t**)&wp, (size_t)N * K));
+    TRY(hb.get((uint16_t**)&xp, (size_t)tp * 32 * K));
+    TRY(hb.get((uint16_t**)&op, (size_t)tp * 32 * (N / 2)));
+    launch_pack_weight(w, wp, N, K, N, 1, 0, st);
+    launch_pack_rows(x, xp, M, K, tp, st);
+    launch_gemm(EPI_SILU, tiles, p, wp, xp, K, N, N, nullptr, (uint16_t*)op, st);
+    launch_unpack_rows(op, y, M, N / 2, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     return MTTS_OK;
@@ -2081,6 +2114,7 @@ extern "C" int32_t mtts_k_gemm_bench(int32_t N, int32_t K, int32_t epi, int32_t 
     if (tile_rows > MTTS_PFCAP) return fail(MTTS_EINVAL, "gemm_bench: at most MTTS_PFCAP rows");
     GemmPlan p = (ksplit > 0 && waves > 0) ? mtts_plan_gemm_forced(N, K, ksplit, waves) : mtts_plan_gemm(N, K, tile_rows ? std::max(ksplit, 1) : ksplit);
     if (tile_rows) p.ksplit = std::max(ksplit, 1);
+    p.depth = gemm_depth_env();
     std::vector<uint16_t*> w(copies, nullptr);
     for (auto& q : w) { TRY(dalloc(&q, (size_t)N * K, false)); HIPCHK(hipMemset(q, 0x3c, (size_t)N * K * 2)); }
     uint16_t *x = nullptr, *out = nullptr;

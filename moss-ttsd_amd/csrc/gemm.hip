@@ -107,6 +107,138 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Depth-specialised skinny GEMMs (one 32-row activation tile).  gemm_skinny_kernel's k-loop keeps 3-4 KiB of weights
+// per wave in flight and its remainder loop pays one HBM round trip per k-tile; the decode shapes that launch one
+// 512-thread block per CU have the registers to request ALL of a wave's k-tiles before the first product.  The wave's
+// k-tile count is a template argument and the body is straight-line: X fragments first (the short trip: loads return
+// in order, behind the weights they would arrive last), then the weight tiles, then the MFMA chain over k ascending,
+// which the compiler's counted waits let start as tile i lands.  Same wave -> k-tile assignment, same order of
+// products into one accumulator, same LDS reduction in wave order, same epilogues as gemm_skinny_kernel: same bits.
+// ---------------------------------------------------------------------------------------------------
+template <int EPI>
+__device__ __forceinline__ void skinny_store(const float (&v)[4], int row, int n0, int ks, float* __restrict__ partial,
+                                             uint16_t* __restrict__ out, int Npad, int n_valid) {
+    if (EPI == EPI_PARTIAL) {
+        *(float4*)(partial + ((size_t)ks * MTTS_PFCAP + row) * Npad + n0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if (EPI == EPI_BF16) {
+        uint16_t* o = out + (size_t)row * Npad + n0;
+        if (n0 + 3 < n_valid) *(u32x2_t*)o = u32x2_t{pack2(v[0], v[1]), pack2(v[2], v[3])};
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (n0 + j < n_valid) o[j] = f2bf(v[j]);
+        }
+    } else {                                                   // SwiGLU, rounding points and layout of gemm_skinny_kernel
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float g = rbf(v[2 * j]), u = rbf(v[2 * j + 1]);
+            float a = rbf(g / (1.0f + expf(-g)));
+            out[xpack_off(row, (n0 >> 1) + j, Npad >> 1)] = f2bf(a * u);
+        }
+    }
+}
+
+// grid = (N/32, ksplit); block = WAVES*64; requires KT == ksplit * WAVES * KTW (no wave has a short or empty range).
+template <int WAVES, int KTW, int EPI>
+__global__ __launch_bounds__(WAVES * 64) void gemm_depth_kernel(
+    const u32x4_t* __restrict__ Wp, const u32x4_t* __restrict__ Xp, int KT, float* __restrict__ partial,
+    uint16_t* __restrict__ out, int Npad, int n_valid) {
+    __shared__ float red[WAVES][16][64];
+    const int nt = blockIdx.x, ks = blockIdx.y;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int kt0 = (ks * WAVES + wave) * KTW;
+    const u32x4_t* wp = Wp + ((size_t)nt * KT + kt0) * 64 + lane;
+    const u32x4_t* xp = Xp + (size_t)kt0 * 64 + lane;
+    u32x4_t a[KTW], b[KTW];
+#pragma unroll
+    for (int u = 0; u < KTW; ++u) b[u] = xp[(size_t)u * 64];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < KTW; ++u) {
+        a[u] = __builtin_nontemporal_load(wp + (size_t)u * 64);
+        __builtin_amdgcn_sched_barrier(0);                     // requests in the order of use: product u waits for tile u only
+    }
+    f32x16_t acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int u = 0; u < KTW; ++u)
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a[u], *(bf16x8_t*)&b[u], acc, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
+    __syncthreads();
+    for (int q = wave; q < 4; q += WAVES) {                    // q: register quad 4q..4q+3
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float s = red[0][4 * q + j][lane];
+#pragma unroll
+            for (int w = 1; w < WAVES; ++w) s += red[w][4 * q + j][lane];
+            v[j] = s;
+        }
+        skinny_store<EPI>(v, lane & 31, nt * 32 + 8 * q + 4 * (lane >> 5), ks, partial, out, Npad, n_valid);
+    }
+}
+
+// gate/up (SwiGLU epilogue, no split-K) on N/48 blocks instead of N/32: 12288 columns are 384 tiles for 256 CUs, a
+// round and a half.  A column's value does not depend on the block that computes it, so block b = 2p + o takes the 48
+// columns [48 b, 48 b + 48): the whole weight tile 3p + 2o and one half of tile 3p + 1 (o = 0: its columns 0-15,
+// o = 1: 16-31), which it shares with its neighbour.  The half tile goes through the same 32x32x16 MFMA: the lanes
+// that hold its 16 weight rows load them (two 256-byte segments of the tile's KiB); the other lanes repeat the address
+// of lane ^ 16 (same cache lines, no branch in the load stream), which makes their accumulator rows copies that the
+// epilogue drops together with the neighbour's two register quads.  gate/up pairs are adjacent columns and never
+// straddle the 16-column boundary.  One block per CU, so every wave requests its whole K range at once: KTW X
+// fragments, then KTW (whole tile, half tile) pairs.  Requires KT == WAVES * KTW and Npad % 96 == 0.
+template <int WAVES, int KTW>
+__global__ __launch_bounds__(WAVES * 64) void gemm_gateup48_kernel(
+    const u32x4_t* __restrict__ Wp, const u32x4_t* __restrict__ Xp, int KT, uint16_t* __restrict__ out, int Npad) {
+    __shared__ float red[WAVES][24][64];
+    const int p = blockIdx.x >> 1, o = blockIdx.x & 1;
+    const int tf = 3 * p + 2 * o, th = 3 * p + 1;              // whole tile, shared tile
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int kt0 = wave * KTW;
+    const int hl = (((lane >> 4) & 1) == o) ? lane : (lane ^ 16);
+    const u32x4_t* wp = Wp + ((size_t)tf * KT + kt0) * 64 + lane;
+    const u32x4_t* hp = Wp + ((size_t)th * KT + kt0) * 64 + hl;
+    const u32x4_t* xp = Xp + (size_t)kt0 * 64 + lane;
+    u32x4_t a[KTW], h[KTW], b[KTW];
+#pragma unroll
+    for (int u = 0; u < KTW; ++u) b[u] = xp[(size_t)u * 64];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < KTW; ++u) {
+        a[u] = __builtin_nontemporal_load(wp + (size_t)u * 64);
+        h[u] = __builtin_nontemporal_load(hp + (size_t)u * 64);
+        __builtin_amdgcn_sched_barrier(0);                     // requests in the order of use
+    }
+    f32x16_t acc, acch;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = acch[i] = 0.f;
+#pragma unroll
+    for (int u = 0; u < KTW; ++u) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a[u], *(bf16x8_t*)&b[u], acc, 0, 0, 0);
+        acch = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&h[u], *(bf16x8_t*)&b[u], acch, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) red[wave][16 + r][lane] = o ? acch[8 + r] : acch[r];   // quads 2o, 2o + 1 are ours
+    __syncthreads();
+    for (int q6 = wave; q6 < 6; q6 += WAVES) {                 // quads 0..3: whole tile; 4, 5: our half of the shared tile
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float s = red[0][4 * q6 + j][lane];
+#pragma unroll
+            for (int w = 1; w < WAVES; ++w) s += red[w][4 * q6 + j][lane];
+            v[j] = s;
+        }
+        const int nt = q6 < 4 ? tf : th, q = q6 < 4 ? q6 : 2 * o + (q6 - 4);
+        skinny_store<EPI_SILU>(v, lane & 31, nt * 32 + 8 * q + 4 * (lane >> 5), 0, nullptr, out, Npad, Npad);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Small-batch decode GEMM (1..SMALL_RP rows): the same weight stream and MFMA tile as gemm_skinny_kernel, but
 //   * the B operand (activations) is built by a PROLOGUE into LDS, compact [k/8][SMALL_RP rows][8 bf16]:
 //       PRO_NORM     residual + split-K slabs of the previous Linear -> x', RMSNorm(x')*w   (replaces resid_norm_kernel)
@@ -471,6 +603,7 @@ __global__ void reduce_partial_bf16_kernel(const float* __restrict__ partial, ui
 
 struct GemmPlan {
     int waves, ksplit, kt_per_split, kt_per_wave;
+    int depth;      // 1: launch_gemm may take a depth-specialised kernel where the shape has one (0: MTTS_GEMM_DEPTH=0)
 };
 
 // Choose the decomposition so that the grid is >= ~256 blocks where the shape allows
@@ -490,6 +623,7 @@ static GemmPlan plan_gemm(int Npad, int K, int want_ksplit) {
     // (very wide GEMMs -- head 0 -- used to run faster with 4 waves; with 8-byte logit stores 8 waves win: 115 vs 126 us)
     p.waves = w;
     p.kt_per_wave = (p.kt_per_split + w - 1) / w;
+    p.depth = 1;
     return p;
 }
 
@@ -521,9 +655,45 @@ static void launch_gemm_mb(int mb, const GemmPlan& p, const void* Wp, const void
     else launch_gemm_epi<EPI, 4>(p, Wp, Xp, K, Npad, n_valid, partial, out, st);     // 3 tiles run as 4 (zero tile)
 }
 
+// The depth-specialised kernels take the decode shapes they were built for: one activation tile, 8 waves, an exact
+// split (every wave owns exactly KTW k-tiles).  Returns false for every other call: the caller runs gemm_skinny_kernel.
+static long long g_depth_launches = 0;      // launches that took a depth-specialised kernel (test hook: mtts_debug_gemm_depth_launches)
+long long mtts_gemm_depth_launches() { return g_depth_launches; }
+static bool launch_gemm_depth(int epi, int mb, const GemmPlan& p, const void* Wp, const void* Xp, int K, int Npad,
+                              int n_valid, float* partial, uint16_t* out, hipStream_t st) {
+    const int KT = K / 16;
+    if (!p.depth || mb > 1 || p.waves != 8 || K % 16 || KT != p.ksplit * 8 * p.kt_per_wave || p.kt_per_split != 8 * p.kt_per_wave)
+        return false;
+    if (epi == EPI_PARTIAL) {
+        dim3 grid(Npad / 32, p.ksplit);
+#define MTTS_DEPTH_CASE(KTW)                                                                                        \
+    case KTW:                                                                                                       \
+        hipLaunchKernelGGL((gemm_depth_kernel<8, KTW, EPI_PARTIAL>), grid, dim3(512), 0, st, (const u32x4_t*)Wp,    \
+                           (const u32x4_t*)Xp, KT, partial, out, Npad, n_valid);                                    \
+        ++g_depth_launches;                                                                                         \
+        return true;
+        // o_proj (4 k-tiles per wave) and down_proj (12).  8 (qkv: one unrolled pass of gemm_skinny_kernel already) was
+        // built and timed: 5.32 against 5.47 us, inside the spread of either leg, so it is not instantiated.
+        switch (p.kt_per_wave) {
+            MTTS_DEPTH_CASE(4)
+            MTTS_DEPTH_CASE(12)
+        }
+#undef MTTS_DEPTH_CASE
+        return false;
+    }
+    if (epi == EPI_SILU && p.ksplit == 1 && p.kt_per_wave == 16 && Npad % 96 == 0 && n_valid == Npad) {
+        hipLaunchKernelGGL((gemm_gateup48_kernel<8, 16>), dim3(Npad / 48), dim3(512), 0, st, (const u32x4_t*)Wp,
+                           (const u32x4_t*)Xp, KT, out, Npad);
+        ++g_depth_launches;
+        return true;
+    }
+    return false;
+}
+
 // mb = number of 32-row activation tiles (1..4) that share the weight stream
 void launch_gemm(int epi, int mb, const GemmPlan& p, const void* Wp, const void* Xp, int K, int Npad, int n_valid,
                  float* partial, uint16_t* out, hipStream_t st) {
+    if (launch_gemm_depth(epi, mb, p, Wp, Xp, K, Npad, n_valid, partial, out, st)) return;
     if (epi == EPI_PARTIAL) launch_gemm_mb<EPI_PARTIAL>(mb, p, Wp, Xp, K, Npad, n_valid, partial, out, st);
     else if (epi == EPI_BF16) launch_gemm_mb<EPI_BF16>(mb, p, Wp, Xp, K, Npad, n_valid, partial, out, st);
     else launch_gemm_mb<EPI_SILU>(mb, p, Wp, Xp, K, Npad, n_valid, partial, out, st);
@@ -589,6 +759,7 @@ GemmPlan mtts_plan_gemm_forced(int Npad, int K, int ksplit, int waves) {
     p.kt_per_split = (KT + ksplit - 1) / ksplit;
     p.waves = waves;
     p.kt_per_wave = (p.kt_per_split + waves - 1) / waves;
+    p.depth = 1;
     return p;
 }
 
