@@ -16,7 +16,7 @@
 // softmax statistics, a page's scores, the fused epilogue's operands, a sealed page's dictionary) is requested before
 // what is large; and nothing on the way may wait for "all loads" -- which the compiler's wait counts do after a JOIN of
 // code paths with different numbers of loads in flight: hence one straight-line body per page form.
-#include "common.h"
+#include "launch.h"
 #include <cstdlib>
 // (tuning aid, tools/ab_build.sh: waves per SIMD the sealed-page kernels are compiled for; 0 = the compiler's choice --
 //  5 was measured and lost, profiles/r03_kv_pack_ab.txt item 4)
@@ -1066,21 +1066,21 @@ template <int G>
 static void launch_attn_g(const void* qbuf, void* kcache, void* vcache, const int32_t* page_table,
                           const RowMeta* meta, void* scores, float* stats, float* opart, void* out_packed, int R,
                           int pages_bound, int max_pages, int total_pages, int nchunks_max, int nq, int nkv, float scale,
-                          const QkvFuse* fuse, int phase, hipStream_t st, const KvPack* pack) {
-    if (phase == 11) {   // prefill tiles (32 consecutive positions of one dialogue per tile)
+                          const QkvFuse* fuse, AttnPhase phase, hipStream_t st, const KvPack* pack) {
+    if (phase == ATTN_PF_SCORES) {   // prefill tiles (32 consecutive positions of one dialogue per tile)
         dim3 ga((pages_bound + 3) / 4, nkv, R / MTTS_MAXR);
         hipLaunchKernelGGL((attn_prefill_scores_kernel<G>), ga, dim3(256), 0, st, (const uint16_t*)qbuf, (const u32x4_t*)kcache,
                            page_table, meta, (uint16_t*)scores, stats, max_pages, total_pages, nq, nkv, scale);
         return;
     }
     const int nchunks_pf = (max_pages + ATT_PF - 1) / ATT_PF;      // prefill rows: chunks of ATT_PF pages
-    if (phase == 12) {
+    if (phase == ATTN_PF_PV) {
         dim3 gb((pages_bound + 4 * ATT_PF - 1) / (4 * ATT_PF), nkv, R / MTTS_MAXR);
         hipLaunchKernelGGL((attn_prefill_pv_kernel<G>), gb, dim3(256), 0, st, (const uint16_t*)scores, (const float*)stats,
                            (const uint32_t*)vcache, page_table, meta, opart, max_pages, total_pages, nchunks_pf, nq, nkv);
         return;
     }
-    if (phase == 13) {
+    if (phase == ATTN_PF_COMBINE) {
         hipLaunchKernelGGL(attn_combine_kernel, dim3(R, (nq + 3) / 4), dim3(512), 0, st, (const float*)opart, meta,
                            (uint16_t*)out_packed, nchunks_pf, nq, ATT_PF);
         return;
@@ -1099,12 +1099,12 @@ static void launch_attn_g(const void* qbuf, void* kcache, void* vcache, const in
         if (pv_stats_first()) MTTS_PV2(FU, PK, true); \
         else MTTS_PV2(FU, PK, false);          \
     } while (0)
-    if (phase == 0 || phase == 1) {
+    if (phase == ATTN_ALL || phase == ATTN_SCORES) {
         dim3 ga((pages_bound + 3) / 4, nkv, R);
         if (fuse) { if (kpk) MTTS_SC(true, true); else MTTS_SC(true, false); }
         else { if (kpk) MTTS_SC(false, true); else MTTS_SC(false, false); }
     }
-    if (phase == 0 || phase == 2) {
+    if (phase == ATTN_ALL || phase == ATTN_PV) {
         dim3 gb((pages_bound + ATT_PB - 1) / ATT_PB, nkv, R);
         if (fuse) { if (vpk) MTTS_PV(true, true); else MTTS_PV(true, false); }
         else { if (vpk) MTTS_PV(false, true); else MTTS_PV(false, false); }
@@ -1112,17 +1112,17 @@ static void launch_attn_g(const void* qbuf, void* kcache, void* vcache, const in
 #undef MTTS_SC
 #undef MTTS_PV
 #undef MTTS_PV2
-    if (phase == 0 || phase == 3)
+    if (phase == ATTN_ALL || phase == ATTN_COMBINE)
         hipLaunchKernelGGL(attn_combine_kernel, dim3(R, (nq + 3) / 4), dim3(512), 0, st, (const float*)opart, meta,
                            (uint16_t*)out_packed, nchunks_max, nq, ATT_PB);
 }
 
-// phase 1/2/3 = scores / P.V / combine for decode-style rows (one dialogue per row), 11/12/13 = the same for prefill
-// tiles.  `fuse` (decode rows only) moves the q/k/v epilogue into phases 1 and 2: no qkv_post launch before them.
+// One phase per call (AttnPhase, launch.h).  `fuse` (decode rows only) moves the q/k/v epilogue into ATTN_SCORES and
+// ATTN_PV: no qkv_post launch before them.
 int launch_attn(const void* qbuf, void* kcache, void* vcache, const int32_t* page_table,
                 const RowMeta* meta, void* scores, float* stats, float* opart, void* out_packed, int R,
                 int pages_bound, int max_pages, int total_pages, int nchunks_max, int nq, int nkv, float scale,
-                const QkvFuse* fuse, int phase, hipStream_t st, const KvPack* pack) {
+                const QkvFuse* fuse, AttnPhase phase, hipStream_t st, const KvPack* pack) {
     int G = nq / nkv;
 #define MTTS_ATT(GG)                                                                                              \
     launch_attn_g<GG>(qbuf, kcache, vcache, page_table, meta, scores, stats, opart, out_packed, R, pages_bound,   \

@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "../../include/mtts.h"
-#include "common.h"
+#include "launch.h"
 
 // ------------------------------------------------------------------------------------
 // fp32 GEMM: C[M,N] = epi(A[M,K] * W^T), W is [N][K] (B_KN=false) or [K][N] (B_KN=true).
@@ -1050,9 +1050,6 @@ struct MttsCodec {
     long fused_pw_rows = -1;
     std::map<const float*, uint16_t*> wplanes_perm;   // W2 planes with the K order the fused kernel's second GEMM expects
 };
-void launch_split_pack_w2perm(hipStream_t st, const float* w2, uint16_t* hi, uint16_t* lo);
-void launch_vocos_pw_fused(hipStream_t st, const uint16_t* xn_planes, long x_plane_elems, const uint16_t* w1_planes, const float* b1,
-                           const uint16_t* w2perm_planes, long w_plane_elems, const float* b2, const float* gamma, float* h, int M);
 
 extern "C" int32_t mtts_codec_create(const MttsCodecConfig* c, int32_t device, MttsCodec** out) {
     if (!c || !out) return cfail(MTTS_EINVAL, "null argument");

@@ -18,7 +18,7 @@
 // j = 32 jt + 8 q + 4 h + r (register 4 q + r).  W2 is packed with its K index PERMUTED so that k-step 2 jt + ks, lane half h,
 // element e means j = 32 jt + 16 ks + 8 (e >> 2) + 4 h + (e & 3): then registers 8 ks .. 8 ks + 7 of the tile, after GELU and
 // split, ARE the lane's B-operand fragment of that k-step.
-#include "common.h"
+#include "launch.h"
 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 

@@ -1,0 +1,252 @@
+// What engine.hip (engine object, C ABI of the product path) and hooks.hip (per-kernel test / bench entry points)
+// share: the engine's definition, error reporting, and the owner of device memory.  Only these two files include it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "launch.h"
+
+// ---- errors -------------------------------------------------------------------
+#define MTTS_LOCAL __attribute__((visibility("hidden")))
+extern MTTS_LOCAL thread_local char g_err[512];          // engine.hip; mtts_last_error() of the calling thread
+MTTS_LOCAL int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+#define HIPCHK(x)                                                                          \
+    do {                                                                                   \
+        hipError_t _e = (x);                                                               \
+        if (_e != hipSuccess) return fail(MTTS_EHIP, "%s: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
+    } while (0)
+#define TRY(x)             \
+    do {                   \
+        int _r = (x);      \
+        if (_r) return _r; \
+    } while (0)
+
+static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+static inline hipStream_t S(void* s) { return (hipStream_t)s; }
+// MTTS_GEMM_DEPTH=0: every decode GEMM runs gemm_skinny_kernel, as before the depth-specialised kernels (gemm.hip);
+// the engine reads it at creation, the per-kernel hooks per call
+static inline int gemm_depth_env() {
+    const char* g = getenv("MTTS_GEMM_DEPTH");
+    return (g && atoi(g) == 0) ? 0 : 1;
+}
+
+template <typename T>
+static int dalloc(T** p, size_t n, bool zero = true) {
+    HIPCHK(hipMalloc((void**)p, n * sizeof(T)));
+    if (zero) HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
+    return 0;
+}
+
+// Owner of device and pinned host memory (the engine's, or a test hook's): what it handed out is freed when it dies,
+// or earlier by release().  The first free that does not succeed is kept, so that a double or stale free is reported
+// (mtts_engine_destroy) instead of passing silently.
+struct DevBufs {
+    struct Buf { void* p; bool pinned; };
+    std::vector<Buf> bufs;
+    std::string free_error;
+    DevBufs() = default;
+    DevBufs(const DevBufs&) = delete;
+    DevBufs& operator=(const DevBufs&) = delete;
+    ~DevBufs() { free_all(); }
+    template <typename T>
+    int get(T** out, size_t n, bool zero = true) {
+        TRY(dalloc(out, n, zero));
+        bufs.push_back({(void*)*out, false});
+        return 0;
+    }
+    template <typename T>
+    int get_pinned(T** out, size_t n) {             // zeroed
+        HIPCHK(hipHostMalloc((void**)out, n * sizeof(T)));
+        bufs.push_back({(void*)*out, true});
+        memset((void*)*out, 0, n * sizeof(T));
+        return 0;
+    }
+    // free now (a buffer that is being reallocated); null is fine, a pointer this owner does not hold is an error
+    template <typename T>
+    void release(T*& p) {
+        if (!p) return;
+        auto it = std::find_if(bufs.begin(), bufs.end(), [&](const Buf& b) { return b.p == (void*)p; });
+        if (it == bufs.end()) note(hipErrorInvalidValue, (void*)p);
+        else { free_one(*it); bufs.erase(it); }
+        p = nullptr;
+    }
+    void free_all() {
+        for (const Buf& b : bufs) free_one(b);
+        bufs.clear();
+    }
+private:
+    void free_one(const Buf& b) {
+        const hipError_t r = b.pinned ? hipHostFree(b.p) : hipFree(b.p);
+        if (r != hipSuccess) note(r, b.p);
+    }
+    void note(hipError_t r, void* p) {
+        if (!free_error.empty()) return;
+        char msg[160];
+        snprintf(msg, sizeof(msg), "freeing %p: %s", p, hipGetErrorString(r));
+        free_error = msg;
+    }
+};
+
+// ---- sampler scratch (sampler.hip: SampleScratch) --------------------------------------------------------------
+static inline int full_cap_for(int vocab) { int p = 1; while (p < vocab) p <<= 1; return vocab > SAMP_CAND ? p : 0; }
+static inline int alloc_scratch(DevBufs& m, SampleScratch& sc, int rows, int vocab) {
+    const int fc = full_cap_for(vocab);
+    TRY(m.get(&sc.overflow, (size_t)rows));
+    if (fc) {            // full-vocabulary path (sampling without top_k): per token a key and a level-0 bin, per row the level-0 histogram
+        TRY(m.get(&sc.full_val, (size_t)rows * fc, false));
+        TRY(m.get(&sc.full_idx, (size_t)rows * fc, false));
+        TRY(m.get(&sc.nuc_cnt, (size_t)rows * 2048));
+        TRY(m.get(&sc.nuc_mass, (size_t)rows * 2048));
+    }
+    TRY(m.get(&sc.hist, (size_t)rows * 2048));
+    TRY(m.get(&sc.slice_val, (size_t)rows * SAMP_NS));
+    TRY(m.get(&sc.slice_idx, (size_t)rows * SAMP_NS));
+    TRY(m.get(&sc.cand_val, (size_t)rows * SAMP_CAND));
+    TRY(m.get(&sc.cand_idx, (size_t)rows * SAMP_CAND));
+    TRY(m.get(&sc.cand_n, (size_t)rows));
+    return 0;
+}
+// output_scores scratch: only when asked for
+static inline int alloc_lp_scratch(DevBufs& m, SampleScratch& sc, int rows) {
+    if (sc.lp) return 0;
+    TRY(m.get(&sc.slice_sum, (size_t)rows * SAMP_NS));
+    TRY(m.get(&sc.lp, (size_t)rows * 8));
+    return 0;
+}
+
+// ---- the engine ------------------------------------------------------------------------------------------------
+struct Layer {
+    void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr;     // packed
+    void *ln_in = nullptr, *ln_post = nullptr, *qn = nullptr, *kn = nullptr; // bf16 vectors
+    int bound = 0;
+};
+
+enum { PROF_SCORES = 0, PROF_PV = 1, PROF_GEMM = 2, PROF_STEP = 3, PROF_N = 4 };
+
+struct MttsEngine {
+    DevBufs mem;                        // owns every device / pinned pointer below
+    MttsConfig cfg;
+    int device = 0;
+    int H, I, L, nq, nkv, V0, Vs, Vs_pad, V0_pad, qkv_rows;
+    std::vector<Layer> layers;
+    void* emb[8] = {nullptr};          // row-major tables (gather)
+    void* head0 = nullptr;             // packed [V0_pad][H]
+    void* heads17 = nullptr;           // packed [7*Vs_pad][H]
+    void* final_norm = nullptr;
+    uint16_t *rope_cos = nullptr, *rope_sin = nullptr;
+    int rope_rows = 0;
+    int emb_bound = 0, norm_bound = 0;
+    const uint16_t** d_tables = nullptr;
+    // plans
+    GemmPlan p_qkv, p_o, p_gu, p_d, p_h0, p_h17;
+    // workspaces
+    float* partial = nullptr;
+    float* partial2 = nullptr;          // small-batch path: o_proj / down_proj slabs (the qkv slabs stay in `partial`)
+    void *x2 = nullptr, *act_rm = nullptr;   // small-batch path: second residual buffer (ping-pong), row-major SwiGLU output
+    int small_rows = SMALL_RP;          // decode batches up to this many dialogues take the small-batch path (0 = off)
+    int gemm_depth = 1;                 // depth-specialised decode GEMMs (gemm.hip; MTTS_GEMM_DEPTH=0: off)
+    void *x = nullptr, *xn = nullptr, *attn_p = nullptr, *act_p = nullptr, *qbuf = nullptr, *hlast = nullptr, *xh = nullptr;
+    void *logits0 = nullptr, *logits17 = nullptr, *join_logits0 = nullptr, *join_logits17 = nullptr;
+    void* scores = nullptr;
+    float *stats = nullptr, *opart = nullptr;
+    // kv
+    void *kcache = nullptr, *vcache = nullptr;
+    size_t layer_stride = 0;           // elements per layer in each cache
+    int total_pages = 0, max_pages = 0, nchunks_max = 0;
+    int32_t* d_page_table = nullptr;
+    std::vector<int32_t> h_page_table;  // [slot][max_pages]: pages a slot owns, in position order
+    // KV page pool: pages are handed out on demand as a dialogue's length crosses a page boundary and come back
+    // when it finishes (free list = stack; initial order ascending, or shuffled by MTTS_PAGE_SHUFFLE for the tests)
+    std::vector<int32_t> free_pages;
+    std::vector<int32_t> n_pages;       // pages each slot owns
+    std::vector<int32_t> page_owners;   // slots whose table holds the page (> 1: a prompt page shared by takes, pool_share)
+    std::vector<char> slot_live;        // host's view: the slot holds a dialogue that may still step
+    PageEdits pending_edits;            // table entries not yet on the device
+    int forced_draw = 0;
+    std::vector<int32_t> next_row_ids;  // Philox row ids of the next mtts_begin (mtts_set_row_ids); empty = 0..B-1
+    int next_takes = 1;                 // takes per prompt of the next mtts_begin / mtts_generate (mtts_set_takes)
+    int takes = 1;                      // of the current static run: row b*takes+j is take j of prompt b
+    // ---- MTTS_DTYPE_F32 engine (f32path.hip): plain fp32 copies of everything, no packed layouts ----
+    bool f32 = false;
+    int h16 = 0;                        // MTTS_DTYPE_F16: the fp32 engine with fp16 rounding points (f32path.hip: r16)
+    struct LayerF32 { float *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr, *ln_in = nullptr, *ln_post = nullptr, *qn = nullptr, *kn = nullptr; };
+    std::vector<LayerF32> lf;
+    float* embf[8] = {nullptr};
+    const float** d_tables_f = nullptr;
+    float *final_norm_f = nullptr, *rope_cos_f = nullptr, *rope_sin_f = nullptr;
+    float *kcache_f = nullptr, *vcache_f = nullptr;
+    float *xf = nullptr, *xnf = nullptr, *qkvf = nullptr, *qbuf_f = nullptr, *attnf = nullptr, *yf = nullptr, *guf = nullptr,
+          *actf = nullptr, *hlast_f = nullptr, *scores_f = nullptr;
+    // generation state
+    SeqState* d_seqs = nullptr;
+    RowMeta* d_meta = nullptr;          // decode rows
+    LoopState* d_ls = nullptr;
+    LoopState* h_ls = nullptr;          // pinned mirror
+    SeqState* h_seqs = nullptr;         // pinned mirror of d_seqs (mtts_sync_state)
+    int32_t *d_decisions = nullptr, *d_cur = nullptr, *d_gen = nullptr, *d_declog = nullptr, *d_forced = nullptr,
+            *d_tf = nullptr;
+    uint32_t* d_bitmaps = nullptr;
+    int bm_words = 0;
+    MttsSamplerCfg* d_scfg = nullptr;
+    SampleScratch sscr;
+    int ch0_sampled = 0;
+    // output_scores: per-token log-probabilities [slot][gen_cap][8] fp32, laid out like d_gen; allocated on first use
+    float* d_lp = nullptr;
+    int lp_cap = 0;                     // gen_cap the buffer was allocated for
+    int scores_next = 0;                // mtts_set_output_scores: read by the next mtts_begin / mtts_generate / mtts_sched_open
+    int scores_on = 0;                  // of the current run
+    bool run_open = false;              // a run has begun and has not been seen to end (mtts_set_output_scores)
+    int32_t* d_pf_tokens = nullptr;     // prefill staging
+    RowMeta* d_pf_meta = nullptr;
+    size_t pf_cap_rows = 0;
+    int gen_cap = 0;
+    // current run
+    int B = 0, T = 0, base_length = 0, max_length = 0, max_steps = 0, steps_issued = 0;
+    bool continuous = false;
+    std::vector<int> join_step;         // engine step at which each slot's dialogue joined
+    std::vector<int> n_real;
+    int max_real = 0;
+    uint64_t seed = 0;
+    bool began = false, has_forced = false;
+    // decode-step graphs: one captured step per (rows, KV page bound, ...) key, replayed by mtts_step
+    struct StepGraph { int B, pages, forced, ch0, scores; hipGraphExec_t exec; };
+    std::vector<StepGraph> graphs;
+    hipStream_t cap_stream = nullptr;
+    bool use_graphs = true;
+    // sealed KV pages (attn.hip: kv_seal): every COMPLETE page also kept in a lossless 13-bit form the decode attention
+    // reads instead of the bf16 page (MTTS_KV_PACK=0: off, no second pool)
+    int kv_pack = 1;
+    void *kpack = nullptr, *vpack = nullptr;
+    size_t pk_layer_stride = 0;         // bytes per layer of a sealed pool
+    // read policy: a page that did not seal costs a wasted sealed read + the bf16 read (29 units instead of 16), so a
+    // layer whose K (or V) pages stop sealing (more than 1 in 8 since mtts_begin) goes back to bf16 reads; the sealer
+    // counts per layer {K sealed, K not, V sealed, V not}, mtts_sync_state looks at the counts (MTTS_KV_PACK=2: no policy)
+    unsigned long long *d_seal_cnt = nullptr, *h_seal_cnt = nullptr;
+    std::vector<char> pack_k_on, pack_v_on;
+    int pack_min_work = 512;            // sealed reads from this many rows x KV pages up (MTTS_KV_PACK_MIN)
+    int fuse_qkv_max = 2560;            // decode: q/k/v epilogue inside the attention kernels while rows x KV pages <= this (round 3: 1024 -> 2560 = 32 rows x 80 pages, once its loads go out before the page's: wins at 32 x 64, loses at 64 x 64)
+    int pf_mfma_pages = 0;              // prefill attention: tile-sharing MFMA kernels from this many KV pages up (0 = always; a dialogue's numerics must not depend on its batch)
+    // profiling
+    bool prof = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[PROF_N];
+    int64_t prof_bytes[PROF_N] = {0, 0, 0, 0};
+};
+
+// this layer's sealed pools, each null where the read policy (or MTTS_KV_PACK=0) says bf16 pages
+static inline KvPack layer_pack(MttsEngine* e, int n, int pages_bound) {
+    KvPack pk{nullptr, nullptr};
+    // few rows x pages: the passes are latency-bound and the unpack sits on the critical path (B=1 at 2 k: +4 %; break-even
+    // at 8 rows x 64 pages, -6 % at 16 x 64: profiles/r03_kv_pack_ab.txt)
+    if (e->B * pages_bound < e->pack_min_work) return pk;
+    if (e->kpack && e->pack_k_on[n]) pk.k = (uint8_t*)e->kpack + e->pk_layer_stride * n;
+    if (e->vpack && e->pack_v_on[n]) pk.v = (uint8_t*)e->vpack + e->pk_layer_stride * n;
+    return pk;
+}

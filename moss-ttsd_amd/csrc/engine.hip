@@ -6,95 +6,8 @@
 //   AsteroidTTSModel._prepare_multi_modal_inputs    modeling_asteroid.py:235-250
 //   CustomMixin._sample                             modeling_asteroid.py:83-169
 // and, third-party, transformers Qwen3Model.forward (models/qwen3/modeling_qwen3.py).
-#include <hip/hip_runtime.h>
+#include "engine.h"
 
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/mtts.h"
-#include "common.h"
-
-// ---- kernels' launchers (other translation units) ---------------------------
-struct GemmPlan { int waves, ksplit, kt_per_split, kt_per_wave, depth; };
-enum { EPI_PARTIAL = 0, EPI_BF16 = 1, EPI_SILU = 2 };
-GemmPlan mtts_plan_gemm(int Npad, int K, int want_ksplit);
-GemmPlan mtts_plan_gemm_forced(int Npad, int K, int ksplit, int waves);
-void launch_gemm(int epi, int mb, const GemmPlan& p, const void* Wp, const void* Xp, int K, int Npad, int n_valid,
-                 float* partial, uint16_t* out, hipStream_t st);
-int mtts_tile_ksplit(int Npad, int K, int R);
-void launch_gemm_tile(int epi, int R, int ksplit, const void* Wp, const void* Xp, int K, int Npad, int n_valid,
-                      float* partial, uint16_t* out, hipStream_t st);
-int mtts_small_lds_bytes(const GemmPlan& p, int K, int pro);
-enum { EPI_SILU_RM = 3 };
-void launch_gemv_small(int epi, int pro, const GemmPlan& p, const void* Wp, int K, int Npad, int n_valid, float* partial,
-                       uint16_t* out, const SmallPro& pr, hipStream_t st);
-void launch_pack_weight(const void* src, void* dst, int rows, int cols, int rows_pad, int row_mul, int row_off, hipStream_t st);
-void launch_pack_rows(const void* src, void* dst, int R, int K, int tiles, hipStream_t st);
-void launch_reduce_partial_bf16(const float* partial, void* out, int ksplit, int Npad, int n_valid, int R, hipStream_t st);
-void launch_embed_norm(const int32_t* tokens, const RowMeta* meta, const uint16_t* const* tables, const void* norm_w,
-                       void* x, void* xn_packed, int R, int H, float eps, hipStream_t st);
-void launch_resid_norm(const float* partial, int ksplit, int Npad, void* x, const void* norm_w, void* xn_packed,
-                       void* hlast, const RowMeta* meta, int R, int H, float eps, hipStream_t st);
-void launch_qkv_post(const float* partial, int ksplit, int Npad, const RowMeta* meta, const void* qnw, const void* knw,
-                     const void* cosb, const void* sinb, void* qbuf, void* kcache, void* vcache,
-                     const int32_t* page_table, int max_pages, int total_pages, int R, int nq, int nkv, float eps,
-                     hipStream_t st);
-void launch_rmsnorm_rows(const void* x, const void* w, void* y, int rows, int n, float eps, hipStream_t st);
-void launch_fill_random_bf16(void* p, size_t n, uint32_t seed, hipStream_t st);
-int launch_attn(const void* qbuf, void* kcache, void* vcache, const int32_t* page_table,
-                const RowMeta* meta, void* scores, float* stats, float* opart, void* out_packed, int R,
-                int pages_bound, int max_pages, int total_pages, int nchunks_max, int nq, int nkv, float scale,
-                const QkvFuse* fuse, int phase, hipStream_t st, const KvPack* pack = nullptr);
-void launch_kv_seal_rows(const void* kcache, const void* vcache, void* kpack, void* vpack, const int32_t* page_table,
-                         const RowMeta* meta, int R, int max_pages, int total_pages, int nkv, int L, unsigned long long* cnt, hipStream_t st);
-void launch_kv_seal_all(const void* kcache, const void* vcache, void* kpack, void* vpack, int total_pages, int nkv, int L,
-                        unsigned long long* cnt, hipStream_t st);
-void launch_kv_seal_pages(const void* raw, void* pk, int npages, int as_k, hipStream_t st);
-void launch_kv_pack_count(const void* kpack, const void* vpack, const int32_t* page_table, const int32_t* complete, int B, int max_pages,
-                          int total_pages, int nkv, int L, unsigned long long* out, hipStream_t st);
-struct SeqState { int32_t nas, unfinished, kv_len, step, base_length, max_length, row_id, active; uint64_t seed; };
-struct LoopState { int32_t step, done, continuous, B, error, gen_cap, forced_draw, logits_f32; };
-struct SampleScratch { uint32_t* hist; float* slice_val; int32_t* slice_idx; float* cand_val; int32_t* cand_idx; uint32_t* cand_n; int32_t* overflow; float* full_val; int32_t* full_idx; uint32_t* nuc_cnt; unsigned long long* nuc_mass; float* slice_sum; float* lp; };
-#define SAMP_CAND 4096
-#define SAMP_NS 32
-void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps,
-                   int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed,
-                   int32_t* decisions, int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap,
-                   int emit_lp, hipStream_t st);
-void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
-                          const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
-                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp, hipStream_t st);
-static int alloc_scratch(SampleScratch& sc, int rows, int vocab);
-static int full_cap_for(int vocab) { int p = 1; while (p < vocab) p <<= 1; return vocab > SAMP_CAND ? p : 0; }
-static void free_scratch(SampleScratch& sc);
-void launch_update(const int32_t* decisions, int32_t* dec_log, const int32_t* forced, const int32_t* tf_tail,
-                   int32_t* gen, int32_t* cur_tokens, SeqState* seqs, RowMeta* meta, uint32_t* bitmaps, int bm_words,
-                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out, hipStream_t st);
-
-void launch_export_codes(const int32_t* gen, int64_t* codes, int B, int first, int n, int speech_offset, int clamp_hi,
-                         int cap, hipStream_t st);
-void launch_f32_embed_norm(const int32_t* tokens, const RowMeta* meta, const float* const* tables, const float* norm_w, float* x,
-                           float* xn, int R, int H, float eps, int h16, hipStream_t st);
-void launch_f32_resid_norm(const float* y, float* x, const float* norm_w, float* xn, float* hlast, const RowMeta* meta, int R,
-                           int H, float eps, int h16, hipStream_t st);
-void launch_f32_linear(const float* W, const float* X, float* Y, int R, int N, int K, long ldy, int h16, bool gemv, hipStream_t st);
-void launch_f32_qkv_post(const float* qkv, int ldq, const RowMeta* meta, const float* qnw, const float* knw, const float* cosb,
-                         const float* sinb, float* qbuf, float* kcache, float* vcache, const int32_t* page_table, int max_pages,
-                         int total_pages, int R, int nq, int nkv, float eps, int h16, hipStream_t st);
-void launch_f32_attn(const float* qbuf, const float* kcache, const float* vcache, const int32_t* page_table, const RowMeta* meta,
-                     float* scores, float* out, int R, int max_pages, int total_pages, int nq, int nkv, float scale, int Lmax,
-                     int h16, hipStream_t st);
-void launch_f32_swiglu(const float* gu, float* act, int R, int I, int h16, hipStream_t st);
-#define MTTS_PF32CAP 256       // rows of a prefill pass in the fp32 engine (bounds its fp32 score scratch)
-struct PageEdits { int32_t n; int32_t idx[31]; int32_t val[31]; };     // page-table entries handed over as launch arguments
-void launch_set_pages(int32_t* table, const PageEdits& ed, hipStream_t st);
-void launch_fork(void* kc, void* vc, size_t layer_bytes, size_t head_bytes, int blk_bytes, int L, int nkv, const ForkJob& job,
-                 hipStream_t st);
 #define FLUSH_STEPS 7          // a dialogue whose EOS falls within 7 steps of max_length still runs its delay-pattern flush (modeling_asteroid.py:165-168)
 #define LINGER_STEPS 14        // static batch: a row finished BY max_length can be resurrected for a flush while another row's flush is still running (sampler.hip: update_kernel), so a batch runs up to 6 + 8 steps past max_length after ONE resurrection
 // Resurrections chain: a resurrected row's own 7-step flush keeps the batch alive, and every step of it re-tests the other
@@ -103,194 +16,17 @@ void launch_fork(void* kc, void* vc, size_t layer_bytes, size_t head_bytes, int 
 // LINGER_STEPS at least; a chain that outruns the room is reported (MTTS_ESTATE), never truncated silently.
 static inline int linger_bound(int B) { return 6 * B + 8; }
 
-// ---- errors -------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-// MTTS_GEMM_DEPTH=0: every decode GEMM runs gemm_skinny_kernel, as before the depth-specialised kernels (gemm.hip);
-// the engine reads it at creation, the per-kernel hooks per call
-static int gemm_depth_env() {
-    const char* g = getenv("MTTS_GEMM_DEPTH");
-    return (g && atoi(g) == 0) ? 0 : 1;
-}
-static int fail(int code, const char* fmt, ...) {
+thread_local char g_err[512] = "";
+int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
 }
-#define HIPCHK(x)                                                                          \
-    do {                                                                                   \
-        hipError_t _e = (x);                                                               \
-        if (_e != hipSuccess) return fail(MTTS_EHIP, "%s: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-
-struct Layer {
-    void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr;     // packed
-    void *ln_in = nullptr, *ln_post = nullptr, *qn = nullptr, *kn = nullptr; // bf16 vectors
-    int bound = 0;
-};
-
-enum { PROF_SCORES = 0, PROF_PV = 1, PROF_GEMM = 2, PROF_STEP = 3, PROF_N = 4 };
-
-struct MttsEngine {
-    MttsConfig cfg;
-    int device = 0;
-    int H, I, L, nq, nkv, V0, Vs, Vs_pad, V0_pad, qkv_rows;
-    std::vector<Layer> layers;
-    void* emb[8] = {nullptr};          // row-major tables (gather)
-    void* head0 = nullptr;             // packed [V0_pad][H]
-    void* heads17 = nullptr;           // packed [7*Vs_pad][H]
-    void* final_norm = nullptr;
-    void *rope_cos = nullptr, *rope_sin = nullptr;
-    int rope_rows = 0;
-    int emb_bound = 0, norm_bound = 0;
-    const uint16_t** d_tables = nullptr;
-    // plans
-    GemmPlan p_qkv, p_o, p_gu, p_d, p_h0, p_h17;
-    // workspaces
-    float* partial = nullptr;
-    float* partial2 = nullptr;          // small-batch path: o_proj / down_proj slabs (the qkv slabs stay in `partial`)
-    void *x2 = nullptr, *act_rm = nullptr;   // small-batch path: second residual buffer (ping-pong), row-major SwiGLU output
-    int small_rows = SMALL_RP;          // decode batches up to this many dialogues take the small-batch path (0 = off)
-    int gemm_depth = 1;                 // depth-specialised decode GEMMs (gemm.hip; MTTS_GEMM_DEPTH=0: off)
-    void *x = nullptr, *xn = nullptr, *attn_p = nullptr, *act_p = nullptr, *qbuf = nullptr, *hlast = nullptr, *xh = nullptr;
-    void *logits0 = nullptr, *logits17 = nullptr, *join_logits0 = nullptr, *join_logits17 = nullptr;
-    void* scores = nullptr;
-    float *stats = nullptr, *opart = nullptr;
-    // kv
-    void *kcache = nullptr, *vcache = nullptr;
-    size_t layer_stride = 0;           // elements per layer in each cache
-    int total_pages = 0, max_pages = 0, nchunks_max = 0;
-    int32_t* d_page_table = nullptr;
-    std::vector<int32_t> h_page_table;  // [slot][max_pages]: pages a slot owns, in position order
-    // KV page pool: pages are handed out on demand as a dialogue's length crosses a page boundary and come back
-    // when it finishes (free list = stack; initial order ascending, or shuffled by MTTS_PAGE_SHUFFLE for the tests)
-    std::vector<int32_t> free_pages;
-    std::vector<int32_t> n_pages;       // pages each slot owns
-    std::vector<int32_t> page_owners;   // slots whose table holds the page (> 1: a prompt page shared by takes, pool_share)
-    std::vector<char> slot_live;        // host's view: the slot holds a dialogue that may still step
-    PageEdits pending_edits;            // table entries not yet on the device
-    int forced_draw = 0;
-    std::vector<int32_t> next_row_ids;  // Philox row ids of the next mtts_begin (mtts_set_row_ids); empty = 0..B-1
-    int next_takes = 1;                 // takes per prompt of the next mtts_begin / mtts_generate (mtts_set_takes)
-    int takes = 1;                      // of the current static run: row b*takes+j is take j of prompt b
-    // ---- MTTS_DTYPE_F32 engine (f32path.hip): plain fp32 copies of everything, no packed layouts ----
-    bool f32 = false;
-    int h16 = 0;                        // MTTS_DTYPE_F16: the fp32 engine with fp16 rounding points (f32path.hip: r16)
-    struct LayerF32 { float *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr, *ln_in = nullptr, *ln_post = nullptr, *qn = nullptr, *kn = nullptr; };
-    std::vector<LayerF32> lf;
-    float* embf[8] = {nullptr};
-    const float** d_tables_f = nullptr;
-    float *final_norm_f = nullptr, *rope_cos_f = nullptr, *rope_sin_f = nullptr;
-    float *kcache_f = nullptr, *vcache_f = nullptr;
-    float *xf = nullptr, *xnf = nullptr, *qkvf = nullptr, *qbuf_f = nullptr, *attnf = nullptr, *yf = nullptr, *guf = nullptr,
-          *actf = nullptr, *hlast_f = nullptr, *scores_f = nullptr;
-    // generation state
-    SeqState* d_seqs = nullptr;
-    RowMeta* d_meta = nullptr;          // decode rows
-    LoopState* d_ls = nullptr;
-    LoopState* h_ls = nullptr;          // pinned mirror
-    SeqState* h_seqs = nullptr;         // pinned mirror of d_seqs (mtts_sync_state)
-    int32_t *d_decisions = nullptr, *d_cur = nullptr, *d_gen = nullptr, *d_declog = nullptr, *d_forced = nullptr,
-            *d_tf = nullptr;
-    uint32_t* d_bitmaps = nullptr;
-    int bm_words = 0;
-    MttsSamplerCfg* d_scfg = nullptr;
-    SampleScratch sscr = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int ch0_sampled = 0;
-    // output_scores: per-token log-probabilities [slot][gen_cap][8] fp32, laid out like d_gen; allocated on first use
-    float* d_lp = nullptr;
-    int lp_cap = 0;                     // gen_cap the buffer was allocated for
-    int scores_next = 0;                // mtts_set_output_scores: read by the next mtts_begin / mtts_generate / mtts_sched_open
-    int scores_on = 0;                  // of the current run
-    bool run_open = false;              // a run has begun and has not been seen to end (mtts_set_output_scores)
-    int32_t* d_pf_tokens = nullptr;     // prefill staging
-    RowMeta* d_pf_meta = nullptr;
-    size_t pf_cap_rows = 0;
-    int gen_cap = 0;
-    // current run
-    int B = 0, T = 0, base_length = 0, max_length = 0, max_steps = 0, steps_issued = 0;
-    bool continuous = false;
-    std::vector<int> join_step;         // engine step at which each slot's dialogue joined
-    std::vector<int> n_real;
-    int max_real = 0;
-    uint64_t seed = 0;
-    bool began = false, has_forced = false;
-    // decode-step graphs: one captured step per (rows, KV page bound, ...) key, replayed by mtts_step
-    struct StepGraph { int B, pages, forced, ch0, scores; hipGraphExec_t exec; };
-    std::vector<StepGraph> graphs;
-    hipStream_t cap_stream = nullptr;
-    bool use_graphs = true;
-    // sealed KV pages (attn.hip: kv_seal): every COMPLETE page also kept in a lossless 13-bit form the decode attention
-    // reads instead of the bf16 page (MTTS_KV_PACK=0: off, no second pool)
-    int kv_pack = 1;
-    void *kpack = nullptr, *vpack = nullptr;
-    size_t pk_layer_stride = 0;         // bytes per layer of a sealed pool
-    // read policy: a page that did not seal costs a wasted sealed read + the bf16 read (29 units instead of 16), so a
-    // layer whose K (or V) pages stop sealing (more than 1 in 8 since mtts_begin) goes back to bf16 reads; the sealer
-    // counts per layer {K sealed, K not, V sealed, V not}, mtts_sync_state looks at the counts (MTTS_KV_PACK=2: no policy)
-    unsigned long long *d_seal_cnt = nullptr, *h_seal_cnt = nullptr;
-    std::vector<char> pack_k_on, pack_v_on;
-    int pack_min_work = 512;            // sealed reads from this many rows x KV pages up (MTTS_KV_PACK_MIN)
-    int fuse_qkv_max = 2560;            // decode: q/k/v epilogue inside the attention kernels while rows x KV pages <= this (round 3: 1024 -> 2560 = 32 rows x 80 pages, once its loads go out before the page's: wins at 32 x 64, loses at 64 x 64)
-    int pf_mfma_pages = 0;              // prefill attention: tile-sharing MFMA kernels from this many KV pages up (0 = always; a dialogue's numerics must not depend on its batch)
-    // profiling
-    bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[PROF_N];
-    int64_t prof_bytes[PROF_N] = {0, 0, 0, 0};
-};
-
-static hipStream_t S(void* s) { return (hipStream_t)s; }
 
 const char* mtts_last_error(void) { return g_err; }
 int32_t mtts_version(void) { return 202; }
-
-template <typename T>
-static int dalloc(T** p, size_t n, bool zero = true) {
-    HIPCHK(hipMalloc((void**)p, n * sizeof(T)));
-    if (zero) HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
-    return 0;
-}
-#define TRY(x)             \
-    do {                   \
-        int _r = (x);      \
-        if (_r) return _r; \
-    } while (0)
-
-static int alloc_scratch(SampleScratch& sc, int rows, int vocab) {
-    const int fc = full_cap_for(vocab);
-    sc.full_val = nullptr; sc.full_idx = nullptr; sc.nuc_cnt = nullptr; sc.nuc_mass = nullptr;
-    TRY(dalloc(&sc.overflow, (size_t)rows));
-    if (fc) {            // full-vocabulary path (sampling without top_k): per token a key and a level-0 bin, per row the level-0 histogram
-        TRY(dalloc(&sc.full_val, (size_t)rows * fc, false));
-        TRY(dalloc(&sc.full_idx, (size_t)rows * fc, false));
-        TRY(dalloc(&sc.nuc_cnt, (size_t)rows * 2048));
-        TRY(dalloc(&sc.nuc_mass, (size_t)rows * 2048));
-    }
-    TRY(dalloc(&sc.hist, (size_t)rows * 2048));
-    TRY(dalloc(&sc.slice_val, (size_t)rows * SAMP_NS));
-    TRY(dalloc(&sc.slice_idx, (size_t)rows * SAMP_NS));
-    TRY(dalloc(&sc.cand_val, (size_t)rows * SAMP_CAND));
-    TRY(dalloc(&sc.cand_idx, (size_t)rows * SAMP_CAND));
-    TRY(dalloc(&sc.cand_n, (size_t)rows));
-    sc.slice_sum = nullptr; sc.lp = nullptr;          // output_scores scratch: alloc_lp_scratch, only when asked for
-    return 0;
-}
-static int alloc_lp_scratch(SampleScratch& sc, int rows) {
-    if (sc.lp) return 0;
-    TRY(dalloc(&sc.slice_sum, (size_t)rows * SAMP_NS));
-    TRY(dalloc(&sc.lp, (size_t)rows * 8));
-    return 0;
-}
-static void free_scratch(SampleScratch& sc) {
-    hipFree(sc.hist); hipFree(sc.slice_val); hipFree(sc.slice_idx); hipFree(sc.cand_val); hipFree(sc.cand_idx); hipFree(sc.cand_n);
-    hipFree(sc.overflow);
-    if (sc.slice_sum) hipFree(sc.slice_sum);
-    if (sc.lp) hipFree(sc.lp);
-    if (sc.full_val) { hipFree(sc.full_val); hipFree(sc.full_idx); hipFree(sc.nuc_cnt); hipFree(sc.nuc_mass); }
-}
 
 // ---- KV page pool -----------------------------------------------------------------------------------------------
 // Free list = stack whose top is the lowest page number (a fresh engine hands pages out in ascending order).
@@ -379,24 +115,24 @@ static int create_f32(MttsEngine* e) {
     const size_t H = e->H, I = e->I, D = MTTS_HD;
     e->lf.resize(e->L);
     for (auto& l : e->lf) {
-        TRY(dalloc(&l.wqkv, (size_t)e->qkv_rows * H, false));
-        TRY(dalloc(&l.wo, H * e->nq * D, false));
-        TRY(dalloc(&l.wgu, 2 * I * H, false));
-        TRY(dalloc(&l.wd, H * I, false));
-        TRY(dalloc(&l.ln_in, H)); TRY(dalloc(&l.ln_post, H)); TRY(dalloc(&l.qn, D)); TRY(dalloc(&l.kn, D));
+        TRY(e->mem.get(&l.wqkv, (size_t)e->qkv_rows * H, false));
+        TRY(e->mem.get(&l.wo, H * e->nq * D, false));
+        TRY(e->mem.get(&l.wgu, 2 * I * H, false));
+        TRY(e->mem.get(&l.wd, H * I, false));
+        TRY(e->mem.get(&l.ln_in, H)); TRY(e->mem.get(&l.ln_post, H)); TRY(e->mem.get(&l.qn, D)); TRY(e->mem.get(&l.kn, D));
     }
-    TRY(dalloc(&e->embf[0], (size_t)e->V0 * H, false));
-    for (int ch = 1; ch < 8; ++ch) TRY(dalloc(&e->embf[ch], (size_t)e->Vs * H, false));
-    TRY(dalloc(&e->final_norm_f, H));
-    TRY(dalloc(&e->d_tables_f, 8));
+    TRY(e->mem.get(&e->embf[0], (size_t)e->V0 * H, false));
+    for (int ch = 1; ch < 8; ++ch) TRY(e->mem.get(&e->embf[ch], (size_t)e->Vs * H, false));
+    TRY(e->mem.get(&e->final_norm_f, H));
+    TRY(e->mem.get(&e->d_tables_f, 8));
     HIPCHK(hipMemcpy((void*)e->d_tables_f, e->embf, 8 * sizeof(void*), hipMemcpyHostToDevice));
     const size_t P = MTTS_PF32CAP;
-    TRY(dalloc(&e->xf, P * H)); TRY(dalloc(&e->xnf, P * H)); TRY(dalloc(&e->yf, P * H));
-    TRY(dalloc(&e->qkvf, P * e->qkv_rows)); TRY(dalloc(&e->qbuf_f, P * e->nq * D)); TRY(dalloc(&e->attnf, P * e->nq * D));
-    TRY(dalloc(&e->guf, P * 2 * I)); TRY(dalloc(&e->actf, P * I));
-    TRY(dalloc(&e->hlast_f, (size_t)MTTS_RCAP * H));
-    TRY(dalloc((float**)&e->logits0, (size_t)MTTS_RCAP * e->V0_pad));
-    TRY(dalloc((float**)&e->logits17, (size_t)MTTS_RCAP * 7 * e->Vs_pad));
+    TRY(e->mem.get(&e->xf, P * H)); TRY(e->mem.get(&e->xnf, P * H)); TRY(e->mem.get(&e->yf, P * H));
+    TRY(e->mem.get(&e->qkvf, P * e->qkv_rows)); TRY(e->mem.get(&e->qbuf_f, P * e->nq * D)); TRY(e->mem.get(&e->attnf, P * e->nq * D));
+    TRY(e->mem.get(&e->guf, P * 2 * I)); TRY(e->mem.get(&e->actf, P * I));
+    TRY(e->mem.get(&e->hlast_f, (size_t)MTTS_RCAP * H));
+    TRY(e->mem.get((float**)&e->logits0, (size_t)MTTS_RCAP * e->V0_pad));
+    TRY(e->mem.get((float**)&e->logits17, (size_t)MTTS_RCAP * 7 * e->Vs_pad));
     return 0;
 }
 
@@ -435,6 +171,11 @@ static int forward_rows_f32(MttsEngine* e, const int32_t* d_tokens, const RowMet
     return MTTS_OK;
 }
 
+static void drop_graphs(MttsEngine* e) {
+    for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
+    e->graphs.clear();
+}
+
 int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out) {
     if (!c || !out) return fail(MTTS_EINVAL, "null argument");
     if (c->head_dim != MTTS_HD) return fail(MTTS_EINVAL, "head_dim must be 128 (got %d)", c->head_dim);
@@ -447,8 +188,21 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     if (c->max_batch < 1 || c->max_batch > MTTS_RCAP) return fail(MTTS_EINVAL, "max_batch must be 1..128");
     if (c->vocab_size <= 152694 || c->speech_vocab_size <= 1024)
         return fail(MTTS_EINVAL, "vocab too small for the reference's hard-coded mask ids 152694 / 1024");
+    if (c->dtype != MTTS_DTYPE_BF16 && c->dtype != MTTS_DTYPE_F32 && c->dtype != MTTS_DTYPE_F16)
+        return fail(MTTS_EINVAL, "dtype %d not built (bf16 = 0, fp32 = 1, fp16 = 2)", c->dtype);
+    if (c->kv_pool_pages < 0) return fail(MTTS_EINVAL, "kv_pool_pages must be >= 0");
     HIPCHK(hipSetDevice(device));
-    MttsEngine* e = new MttsEngine();
+    // a failure from here on destroys the half-built engine; the message stays that of the failure
+    struct Destroy {
+        void operator()(MttsEngine* p) const {
+            const std::string keep = g_err;
+            mtts_engine_destroy(p);
+            snprintf(g_err, sizeof(g_err), "%s", keep.c_str());
+        }
+    };
+    std::unique_ptr<MttsEngine, Destroy> holder(new MttsEngine());
+    MttsEngine* e = holder.get();
+    DevBufs& m = e->mem;
     e->cfg = *c;
     e->device = device;
     if (const char* g = getenv("MTTS_GRAPHS")) e->use_graphs = atoi(g) != 0;
@@ -465,31 +219,28 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     e->qkv_rows = (e->nq + 2 * e->nkv) * MTTS_HD;
     e->layers.resize(e->L);
     const int H = e->H, I = e->I;
-    if (c->dtype != MTTS_DTYPE_BF16 && c->dtype != MTTS_DTYPE_F32 && c->dtype != MTTS_DTYPE_F16)
-        return fail(MTTS_EINVAL, "dtype %d not built (bf16 = 0, fp32 = 1, fp16 = 2)", c->dtype);
     e->f32 = c->dtype != MTTS_DTYPE_BF16;
     e->h16 = c->dtype == MTTS_DTYPE_F16;
     if (e->f32) TRY(create_f32(e));
     // packed weights (zeroed: padding rows must be zero)
-    if (!e->f32)
-    for (auto& l : e->layers) {
-        TRY(dalloc((uint16_t**)&l.wqkv, (size_t)e->qkv_rows * H));
-        TRY(dalloc((uint16_t**)&l.wo, (size_t)H * e->nq * MTTS_HD));
-        TRY(dalloc((uint16_t**)&l.wgu, (size_t)2 * I * H));
-        TRY(dalloc((uint16_t**)&l.wd, (size_t)round_up(H, 32) * I));
-        TRY(dalloc((uint16_t**)&l.ln_in, (size_t)H));
-        TRY(dalloc((uint16_t**)&l.ln_post, (size_t)H));
-        TRY(dalloc((uint16_t**)&l.qn, (size_t)MTTS_HD));
-        TRY(dalloc((uint16_t**)&l.kn, (size_t)MTTS_HD));
-    }
     if (!e->f32) {
-    TRY(dalloc((uint16_t**)&e->emb[0], (size_t)e->V0 * H, false));
-    for (int ch = 1; ch < 8; ++ch) TRY(dalloc((uint16_t**)&e->emb[ch], (size_t)e->Vs * H, false));
-    TRY(dalloc((uint16_t**)&e->head0, (size_t)e->V0_pad * H));
-    TRY(dalloc((uint16_t**)&e->heads17, (size_t)7 * e->Vs_pad * H));
-    TRY(dalloc((uint16_t**)&e->final_norm, (size_t)H));
-    TRY(dalloc(&e->d_tables, 8));
-    HIPCHK(hipMemcpy((void*)e->d_tables, e->emb, 8 * sizeof(void*), hipMemcpyHostToDevice));
+        for (auto& l : e->layers) {
+            TRY(m.get((uint16_t**)&l.wqkv, (size_t)e->qkv_rows * H));
+            TRY(m.get((uint16_t**)&l.wo, (size_t)H * e->nq * MTTS_HD));
+            TRY(m.get((uint16_t**)&l.wgu, (size_t)2 * I * H));
+            TRY(m.get((uint16_t**)&l.wd, (size_t)round_up(H, 32) * I));
+            TRY(m.get((uint16_t**)&l.ln_in, (size_t)H));
+            TRY(m.get((uint16_t**)&l.ln_post, (size_t)H));
+            TRY(m.get((uint16_t**)&l.qn, (size_t)MTTS_HD));
+            TRY(m.get((uint16_t**)&l.kn, (size_t)MTTS_HD));
+        }
+        TRY(m.get((uint16_t**)&e->emb[0], (size_t)e->V0 * H, false));
+        for (int ch = 1; ch < 8; ++ch) TRY(m.get((uint16_t**)&e->emb[ch], (size_t)e->Vs * H, false));
+        TRY(m.get((uint16_t**)&e->head0, (size_t)e->V0_pad * H));
+        TRY(m.get((uint16_t**)&e->heads17, (size_t)7 * e->Vs_pad * H));
+        TRY(m.get((uint16_t**)&e->final_norm, (size_t)H));
+        TRY(m.get(&e->d_tables, 8));
+        HIPCHK(hipMemcpy((void*)e->d_tables, e->emb, 8 * sizeof(void*), hipMemcpyHostToDevice));
     }
     // plans
     e->p_qkv = mtts_plan_gemm(e->qkv_rows, H, 0);
@@ -502,35 +253,34 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     // activations hold a whole prefill pass (MTTS_PFCAP rows); split-K slabs: up to 8 of [MTTS_PFCAP][Npad] fp32
     size_t pmax = (size_t)8 * std::max(e->qkv_rows, round_up(H, 32));
     if (!e->f32) {
-    TRY(dalloc(&e->partial, pmax * MTTS_PFCAP));
-    TRY(dalloc(&e->partial2, (size_t)8 * round_up(H, 32) * MTTS_PFCAP));
-    TRY(dalloc((uint16_t**)&e->x2, (size_t)MTTS_MAXR * H));
-    TRY(dalloc((uint16_t**)&e->act_rm, (size_t)MTTS_MAXR * I));
-    TRY(dalloc((uint16_t**)&e->x, (size_t)MTTS_PFCAP * H));
-    TRY(dalloc((uint16_t**)&e->xn, (size_t)MTTS_PFCAP * H));
-    TRY(dalloc((uint16_t**)&e->xh, (size_t)MTTS_RCAP * H));
-    TRY(dalloc((uint16_t**)&e->hlast, (size_t)MTTS_RCAP * H));
-    TRY(dalloc((uint16_t**)&e->attn_p, (size_t)MTTS_PFCAP * e->nq * MTTS_HD));
-    TRY(dalloc((uint16_t**)&e->act_p, (size_t)MTTS_PFCAP * I));
-    TRY(dalloc((uint16_t**)&e->qbuf, (size_t)MTTS_PFCAP * e->nq * MTTS_HD));
-    TRY(dalloc((uint16_t**)&e->logits0, (size_t)MTTS_RCAP * e->V0_pad));        // channel-0 rows padded to 32 tokens
-    TRY(dalloc((uint16_t**)&e->logits17, (size_t)MTTS_RCAP * 7 * e->Vs_pad));
-    TRY(dalloc((uint16_t**)&e->join_logits0, (size_t)MTTS_MAXR * e->V0_pad));
-    TRY(dalloc((uint16_t**)&e->join_logits17, (size_t)MTTS_MAXR * 7 * e->Vs_pad));
+        TRY(m.get(&e->partial, pmax * MTTS_PFCAP));
+        TRY(m.get(&e->partial2, (size_t)8 * round_up(H, 32) * MTTS_PFCAP));
+        TRY(m.get((uint16_t**)&e->x2, (size_t)MTTS_MAXR * H));
+        TRY(m.get((uint16_t**)&e->act_rm, (size_t)MTTS_MAXR * I));
+        TRY(m.get((uint16_t**)&e->x, (size_t)MTTS_PFCAP * H));
+        TRY(m.get((uint16_t**)&e->xn, (size_t)MTTS_PFCAP * H));
+        TRY(m.get((uint16_t**)&e->xh, (size_t)MTTS_RCAP * H));
+        TRY(m.get((uint16_t**)&e->hlast, (size_t)MTTS_RCAP * H));
+        TRY(m.get((uint16_t**)&e->attn_p, (size_t)MTTS_PFCAP * e->nq * MTTS_HD));
+        TRY(m.get((uint16_t**)&e->act_p, (size_t)MTTS_PFCAP * I));
+        TRY(m.get((uint16_t**)&e->qbuf, (size_t)MTTS_PFCAP * e->nq * MTTS_HD));
+        TRY(m.get((uint16_t**)&e->logits0, (size_t)MTTS_RCAP * e->V0_pad));        // channel-0 rows padded to 32 tokens
+        TRY(m.get((uint16_t**)&e->logits17, (size_t)MTTS_RCAP * 7 * e->Vs_pad));
+        TRY(m.get((uint16_t**)&e->join_logits0, (size_t)MTTS_MAXR * e->V0_pad));
+        TRY(m.get((uint16_t**)&e->join_logits17, (size_t)MTTS_MAXR * 7 * e->Vs_pad));
     }
     // KV pool
     e->max_pages = (c->max_seq_len + MTTS_PAGE - 1) / MTTS_PAGE + 1;
     e->total_pages = c->kv_pool_pages > 0 ? c->kv_pool_pages : e->max_pages * c->max_batch;
-    if (c->kv_pool_pages < 0) return fail(MTTS_EINVAL, "kv_pool_pages must be >= 0");
     e->nchunks_max = (e->max_pages + ATT_PB - 1) / ATT_PB;
     e->layer_stride = (size_t)e->total_pages * e->nkv * MTTS_PAGE * MTTS_HD;
     if (e->f32) {
-        TRY(dalloc(&e->kcache_f, e->layer_stride * e->L));
-        TRY(dalloc(&e->vcache_f, e->layer_stride * e->L));
-        TRY(dalloc(&e->scores_f, (size_t)MTTS_PF32CAP * e->nq * e->max_pages * MTTS_PAGE, false));
+        TRY(m.get(&e->kcache_f, e->layer_stride * e->L));
+        TRY(m.get(&e->vcache_f, e->layer_stride * e->L));
+        TRY(m.get(&e->scores_f, (size_t)MTTS_PF32CAP * e->nq * e->max_pages * MTTS_PAGE, false));
     } else {
-        TRY(dalloc((uint16_t**)&e->kcache, e->layer_stride * e->L));
-        TRY(dalloc((uint16_t**)&e->vcache, e->layer_stride * e->L));
+        TRY(m.get((uint16_t**)&e->kcache, e->layer_stride * e->L));
+        TRY(m.get((uint16_t**)&e->vcache, e->layer_stride * e->L));
         if (e->kv_pack) {
             // the second pool is an optimisation: when the card cannot hold it beside everything else (a very large
             // kv_pool_pages), the engine runs on bf16 pages alone instead of failing
@@ -543,128 +293,118 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
             }
         }
         if (e->kv_pack) {
-            TRY(dalloc((uint8_t**)&e->kpack, e->pk_layer_stride * e->L));
-            TRY(dalloc((uint8_t**)&e->vpack, e->pk_layer_stride * e->L));
-            TRY(dalloc(&e->d_seal_cnt, (size_t)e->L * 4));
-            HIPCHK(hipHostMalloc((void**)&e->h_seal_cnt, (size_t)e->L * 4 * sizeof(unsigned long long)));
-            memset(e->h_seal_cnt, 0, (size_t)e->L * 4 * sizeof(unsigned long long));
+            TRY(m.get((uint8_t**)&e->kpack, e->pk_layer_stride * e->L));
+            TRY(m.get((uint8_t**)&e->vpack, e->pk_layer_stride * e->L));
+            TRY(m.get(&e->d_seal_cnt, (size_t)e->L * 4));
+            TRY(m.get_pinned(&e->h_seal_cnt, (size_t)e->L * 4));
             e->pack_k_on.assign(e->L, 1);
             e->pack_v_on.assign(e->L, 1);
         }
     }
-    TRY(dalloc(&e->d_page_table, (size_t)c->max_batch * e->max_pages));
+    TRY(m.get(&e->d_page_table, (size_t)c->max_batch * e->max_pages));
     e->h_page_table.assign((size_t)c->max_batch * e->max_pages, 0);
     e->n_pages.assign(c->max_batch, 0);
     e->slot_live.assign(c->max_batch, 0);
     e->pending_edits.n = 0;
     pool_reset(e);
     if (!e->f32) {
-    TRY(dalloc((uint16_t**)&e->scores, (size_t)MTTS_PFCAP * e->nq * e->max_pages * MTTS_PAGE));
-    TRY(dalloc(&e->stats, (size_t)MTTS_PFCAP * e->nq * e->max_pages * 2));
-    TRY(dalloc(&e->opart, (size_t)MTTS_PFCAP * e->nq * ((e->max_pages + ATT_PF - 1) / ATT_PF) * MTTS_HD));   // prefill chunking is the finer one
+        TRY(m.get((uint16_t**)&e->scores, (size_t)MTTS_PFCAP * e->nq * e->max_pages * MTTS_PAGE));
+        TRY(m.get(&e->stats, (size_t)MTTS_PFCAP * e->nq * e->max_pages * 2));
+        TRY(m.get(&e->opart, (size_t)MTTS_PFCAP * e->nq * ((e->max_pages + ATT_PF - 1) / ATT_PF) * MTTS_HD));   // prefill chunking is the finer one
     }
     // state
-    TRY(dalloc(&e->d_seqs, MTTS_RCAP));
-    TRY(dalloc(&e->d_meta, MTTS_RCAP));
-    TRY(dalloc(&e->d_ls, 1));
-    HIPCHK(hipHostMalloc((void**)&e->h_ls, sizeof(LoopState)));
-    memset(e->h_ls, 0, sizeof(LoopState));
-    HIPCHK(hipHostMalloc((void**)&e->h_seqs, MTTS_RCAP * sizeof(SeqState)));
-    TRY(dalloc(&e->d_decisions, MTTS_RCAP * 8));
-    TRY(dalloc(&e->d_cur, MTTS_RCAP * 8));
-    TRY(dalloc(&e->d_tf, MTTS_RCAP * 7 * 8));
+    TRY(m.get(&e->d_seqs, MTTS_RCAP));
+    TRY(m.get(&e->d_meta, MTTS_RCAP));
+    TRY(m.get(&e->d_ls, 1));
+    TRY(m.get_pinned(&e->h_ls, 1));
+    TRY(m.get_pinned(&e->h_seqs, MTTS_RCAP));
+    TRY(m.get(&e->d_decisions, MTTS_RCAP * 8));
+    TRY(m.get(&e->d_cur, MTTS_RCAP * 8));
+    TRY(m.get(&e->d_tf, MTTS_RCAP * 7 * 8));
     e->bm_words = (e->V0 + 31) / 32;
-    TRY(dalloc(&e->d_bitmaps, (size_t)MTTS_RCAP * 8 * e->bm_words));
-    TRY(dalloc(&e->d_scfg, 8));
-    TRY(alloc_scratch(e->sscr, c->max_batch, e->V0));
-    *out = e;
+    TRY(m.get(&e->d_bitmaps, (size_t)MTTS_RCAP * 8 * e->bm_words));
+    TRY(m.get(&e->d_scfg, 8));
+    TRY(alloc_scratch(m, e->sscr, c->max_batch, e->V0));
+    *out = holder.release();
     return MTTS_OK;
-}
-
-static void drop_graphs(MttsEngine* e) {
-    for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
-    e->graphs.clear();
 }
 
 int32_t mtts_engine_destroy(MttsEngine* e) {
     if (!e) return MTTS_OK;
     hipSetDevice(e->device);
     hipDeviceSynchronize();
-    for (auto& l : e->layers) {
-        hipFree(l.wqkv); hipFree(l.wo); hipFree(l.wgu); hipFree(l.wd);
-        hipFree(l.ln_in); hipFree(l.ln_post); hipFree(l.qn); hipFree(l.kn);
-    }
-    for (int c = 0; c < 8; ++c) hipFree(e->emb[c]);
-    for (auto& l : e->lf) { hipFree(l.wqkv); hipFree(l.wo); hipFree(l.wgu); hipFree(l.wd); hipFree(l.ln_in); hipFree(l.ln_post); hipFree(l.qn); hipFree(l.kn); }
-    for (int c = 0; c < 8; ++c) hipFree(e->embf[c]);
-    {
-        void* fp[] = {(void*)e->d_tables_f, e->final_norm_f, e->rope_cos_f, e->rope_sin_f, e->kcache_f, e->vcache_f, e->xf, e->xnf, e->qkvf,
-                      e->qbuf_f, e->attnf, e->yf, e->guf, e->actf, e->hlast_f, e->scores_f};
-        for (void* q : fp) if (q) hipFree(q);
-    }
-    void* ptrs[] = {e->partial2, e->x2, e->act_rm, e->head0, e->heads17, e->final_norm, e->rope_cos, e->rope_sin, (void*)e->d_tables, e->partial, e->x,
-                    e->xn, e->xh, e->hlast, e->attn_p, e->act_p, e->qbuf, e->logits0, e->logits17, e->join_logits0, e->join_logits17, e->scores, e->stats,
-                    e->opart, e->kcache, e->vcache, e->kpack, e->vpack, e->d_page_table, e->d_seqs, e->d_meta, e->d_ls, e->d_decisions,
-                    e->d_cur, e->d_gen, e->d_declog, e->d_forced, e->d_tf, e->d_bitmaps, e->d_scfg, e->d_pf_tokens,
-                    e->d_pf_meta, e->d_lp};
-    for (void* p : ptrs) if (p) hipFree(p);
-    if (e->h_ls) hipHostFree(e->h_ls);
-    if (e->h_seqs) hipHostFree(e->h_seqs);
-    if (e->h_seal_cnt) hipHostFree(e->h_seal_cnt);
-    if (e->d_seal_cnt) hipFree(e->d_seal_cnt);
-    free_scratch(e->sscr);
     drop_graphs(e);
     if (e->cap_stream) hipStreamDestroy(e->cap_stream);
     for (int w = 0; w < PROF_N; ++w) for (auto& pr : e->ev[w]) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
+    e->mem.free_all();
+    const std::string err = e->mem.free_error;
     delete e;
-    return MTTS_OK;
+    return err.empty() ? MTTS_OK : fail(MTTS_EHIP, "mtts_engine_destroy: %s", err.c_str());
 }
 
-static bool ends_with(const std::string& s, const char* suf) {
-    size_t n = strlen(suf);
-    return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
-}
+// ---- weight binding ---------------------------------------------------------------------------------------------
+// Where a state-dict tensor goes.  The bf16 engine keeps vectors and embedding tables as plain copies and matrices in
+// MFMA-fragment order (launch_pack_weight); the fp32 engine keeps plain row-major copies (q|k|v rows one after another,
+// gate rows then up rows).
+struct WeightSlot {
+    int64_t rows = 0, cols = 0;      // expected shape; cols == 1: a vector, given as [n], [n,1] or [1,n]
+    void* copy_to = nullptr;         // bf16: plain copy (vectors, embedding tables)
+    void* pack_to = nullptr;         // bf16: packed matrix [rows_pad][cols], source row r at row_mul * r + row_off
+    int rows_pad = 0, row_mul = 1, row_off = 0;
+    float* f32_to = nullptr;         // fp32: plain copy, starting at row f32_row
+    int64_t f32_row = 0;
+    int* bound = nullptr;            // mask that records the binding; null: a name that is accepted and ignored
+    int bit = 0;
+};
 
-// fp32 engine: plain row-major copies (q|k|v rows one after another, gate rows then up rows)
-static int bind_weight_f32(MttsEngine* e, const char* name_c, const float* src, int64_t rows, int64_t cols, hipStream_t st) {
-    std::string name(name_c);
-    const int64_t H = e->H, I = e->I, D = MTTS_HD;
-    auto put = [&](float* dst, int64_t r, int64_t c) -> int {
-        const bool vec = (c == 1) && ((rows == r && cols == 1) || (rows == 1 && cols == r));
-        if (!vec && !(rows == r && cols == c)) return fail(MTTS_EINVAL, "%s: expected [%lld,%lld] got [%lld,%lld]", name_c, (long long)r, (long long)c, (long long)rows, (long long)cols);
-        HIPCHK(hipMemcpyAsync(dst, src, (size_t)r * c * 4, hipMemcpyDeviceToDevice, st));
-        return 0;
-    };
+static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
+    const std::string name(name_c);
+    const int64_t H = e->H, I = e->I, D = MTTS_HD, Hp = round_up(e->H, 32), QD = e->nq * D, KD = e->nkv * D;
     int ch = -1;
-    if (sscanf(name_c, "model.embedding_list.%d.weight", &ch) == 1) {
+    if (sscanf(name_c, "model.embedding_list.%d.weight", &ch) == 1 && name.size() > 7 && name.compare(name.size() - 7, 7, ".weight") == 0) {
         if (ch < 0 || ch > 7) return fail(MTTS_EINVAL, "bad channel in %s", name_c);
-        TRY(put(e->embf[ch], ch == 0 ? e->V0 : e->Vs, H));
-        e->emb_bound |= 1 << ch;
+        w.rows = ch == 0 ? e->V0 : e->Vs; w.cols = H;
+        w.copy_to = e->emb[ch]; w.f32_to = e->embf[ch];
+        // the head is tied to the embedding (modeling_asteroid.py:315-317)
+        w.pack_to = ch == 0 ? e->head0 : e->heads17;
+        w.rows_pad = ch == 0 ? e->V0_pad : 7 * e->Vs_pad;
+        w.row_off = ch == 0 ? 0 : (ch - 1) * e->Vs_pad;
+        w.bound = &e->emb_bound; w.bit = 1 << ch;
         return MTTS_OK;
     }
-    if (name == "model.language_model.norm.weight") { TRY(put(e->final_norm_f, H, 1)); e->norm_bound = 1; return MTTS_OK; }
-    if (name.find("lm_heads.") == 0 || name == "model.language_model.embed_tokens.weight") return MTTS_OK;
+    if (name == "model.language_model.norm.weight") {
+        w.rows = H; w.cols = 1; w.copy_to = e->final_norm; w.f32_to = e->final_norm_f; w.bound = &e->norm_bound; w.bit = 1;
+        return MTTS_OK;
+    }
+    if (name.find("lm_heads.") == 0 || name == "model.language_model.embed_tokens.weight") return MTTS_OK;  // tied / unused
     int n = -1;
     char rest[128];
-    if (sscanf(name_c, "model.language_model.layers.%d.%127s", &n, rest) == 2) {
-        if (n < 0 || n >= e->L) return fail(MTTS_EINVAL, "layer index out of range in %s", name_c);
-        auto& l = e->lf[n];
-        Layer& lb = e->layers[n];
-        std::string r(rest);
-        if (r == "input_layernorm.weight") { TRY(put(l.ln_in, H, 1)); lb.bound |= 1; }
-        else if (r == "post_attention_layernorm.weight") { TRY(put(l.ln_post, H, 1)); lb.bound |= 2; }
-        else if (r == "self_attn.q_norm.weight") { TRY(put(l.qn, D, 1)); lb.bound |= 4; }
-        else if (r == "self_attn.k_norm.weight") { TRY(put(l.kn, D, 1)); lb.bound |= 8; }
-        else if (r == "self_attn.q_proj.weight") { TRY(put(l.wqkv, e->nq * D, H)); lb.bound |= 16; }
-        else if (r == "self_attn.k_proj.weight") { TRY(put(l.wqkv + (size_t)e->nq * D * H, e->nkv * D, H)); lb.bound |= 32; }
-        else if (r == "self_attn.v_proj.weight") { TRY(put(l.wqkv + (size_t)(e->nq + e->nkv) * D * H, e->nkv * D, H)); lb.bound |= 64; }
-        else if (r == "self_attn.o_proj.weight") { TRY(put(l.wo, H, e->nq * D)); lb.bound |= 128; }
-        else if (r == "mlp.gate_proj.weight") { TRY(put(l.wgu, I, H)); lb.bound |= 256; }
-        else if (r == "mlp.up_proj.weight") { TRY(put(l.wgu + (size_t)I * H, I, H)); lb.bound |= 512; }
-        else if (r == "mlp.down_proj.weight") { TRY(put(l.wd, H, I)); lb.bound |= 1024; }
-        else return fail(MTTS_EINVAL, "unknown tensor %s", name_c);
-        return MTTS_OK;
-    }
+    if (sscanf(name_c, "model.language_model.layers.%d.%127s", &n, rest) != 2) return fail(MTTS_EINVAL, "unknown tensor %s", name_c);
+    if (n < 0 || n >= e->L) return fail(MTTS_EINVAL, "layer index out of range in %s", name_c);
+    Layer& l = e->layers[n];
+    const MttsEngine::LayerF32 f = e->f32 ? e->lf[n] : MttsEngine::LayerF32{};
+    const struct { const char* name; int64_t rows, cols; void* bf; float* f32; int rows_pad, row_mul, row_off; int64_t f32_row; } t[] = {
+        {"input_layernorm.weight", H, 1, l.ln_in, f.ln_in, 0, 1, 0, 0},
+        {"post_attention_layernorm.weight", H, 1, l.ln_post, f.ln_post, 0, 1, 0, 0},
+        {"self_attn.q_norm.weight", D, 1, l.qn, f.qn, 0, 1, 0, 0},
+        {"self_attn.k_norm.weight", D, 1, l.kn, f.kn, 0, 1, 0, 0},
+        {"self_attn.q_proj.weight", QD, H, l.wqkv, f.wqkv, e->qkv_rows, 1, 0, 0},
+        {"self_attn.k_proj.weight", KD, H, l.wqkv, f.wqkv, e->qkv_rows, 1, (int)QD, QD},
+        {"self_attn.v_proj.weight", KD, H, l.wqkv, f.wqkv, e->qkv_rows, 1, (int)(QD + KD), QD + KD},
+        {"self_attn.o_proj.weight", H, QD, l.wo, f.wo, (int)Hp, 1, 0, 0},
+        {"mlp.gate_proj.weight", I, H, l.wgu, f.wgu, (int)(2 * I), 2, 0, 0},
+        {"mlp.up_proj.weight", I, H, l.wgu, f.wgu, (int)(2 * I), 2, 1, I},
+        {"mlp.down_proj.weight", H, I, l.wd, f.wd, (int)Hp, 1, 0, 0},
+    };
+    for (int i = 0; i < 11; ++i)
+        if (!strcmp(rest, t[i].name)) {
+            w.rows = t[i].rows; w.cols = t[i].cols;
+            (t[i].cols == 1 ? w.copy_to : w.pack_to) = t[i].bf;
+            w.rows_pad = t[i].rows_pad; w.row_mul = t[i].row_mul; w.row_off = t[i].row_off;
+            w.f32_to = t[i].f32; w.f32_row = t[i].f32_row;
+            w.bound = &l.bound; w.bit = 1 << i;       // a complete layer has all 11 bits: 2047 (mtts_weights_ready)
+            return MTTS_OK;
+        }
     return fail(MTTS_EINVAL, "unknown tensor %s", name_c);
 }
 
@@ -673,87 +413,42 @@ int32_t mtts_bind_weight(MttsEngine* e, const char* name_c, const void* src, int
     HIPCHK(hipSetDevice(e->device));
     drop_graphs(e);
     hipStream_t st = S(stream);
-    if (e->f32) return bind_weight_f32(e, name_c, (const float*)src, rows, cols, st);
-    std::string name(name_c);
-    const int H = e->H, I = e->I, D = MTTS_HD;
-    auto expect = [&](int64_t r, int64_t c) { return rows == r && cols == c; };
-    auto copyvec = [&](void* dst, int64_t n) -> int {
-        if (!(rows == n && cols == 1) && !(rows == 1 && cols == n)) return fail(MTTS_EINVAL, "%s: expected vector of %lld", name_c, (long long)n);
-        HIPCHK(hipMemcpyAsync(dst, src, n * 2, hipMemcpyDeviceToDevice, st));
-        return 0;
-    };
-    int ch = -1;
-    if (sscanf(name_c, "model.embedding_list.%d.weight", &ch) == 1 && ends_with(name, ".weight") && name.find("embedding_list") != std::string::npos) {
-        if (ch < 0 || ch > 7) return fail(MTTS_EINVAL, "bad channel in %s", name_c);
-        int64_t V = ch == 0 ? e->V0 : e->Vs;
-        if (!expect(V, H)) return fail(MTTS_EINVAL, "%s: expected [%lld,%d] got [%lld,%lld]", name_c, (long long)V, H, (long long)rows, (long long)cols);
-        HIPCHK(hipMemcpyAsync(e->emb[ch], src, (size_t)V * H * 2, hipMemcpyDeviceToDevice, st));
-        // the head is tied to the embedding (modeling_asteroid.py:315-317)
-        if (ch == 0) launch_pack_weight(src, e->head0, V, H, e->V0_pad, 1, 0, st);
-        else launch_pack_weight(src, e->heads17, V, H, 7 * e->Vs_pad, 1, (ch - 1) * e->Vs_pad, st);
-        e->emb_bound |= 1 << ch;
-        return MTTS_OK;
-    }
-    if (name == "model.language_model.norm.weight") { TRY(copyvec(e->final_norm, H)); e->norm_bound = 1; return MTTS_OK; }
-    if (name.find("lm_heads.") == 0 || name == "model.language_model.embed_tokens.weight") return MTTS_OK;  // tied / unused
-    int n = -1;
-    char rest[128];
-    if (sscanf(name_c, "model.language_model.layers.%d.%127s", &n, rest) == 2) {
-        if (n < 0 || n >= e->L) return fail(MTTS_EINVAL, "layer index out of range in %s", name_c);
-        Layer& l = e->layers[n];
-        std::string r(rest);
-        if (r == "input_layernorm.weight") { TRY(copyvec(l.ln_in, H)); l.bound |= 1; }
-        else if (r == "post_attention_layernorm.weight") { TRY(copyvec(l.ln_post, H)); l.bound |= 2; }
-        else if (r == "self_attn.q_norm.weight") { TRY(copyvec(l.qn, D)); l.bound |= 4; }
-        else if (r == "self_attn.k_norm.weight") { TRY(copyvec(l.kn, D)); l.bound |= 8; }
-        else if (r == "self_attn.q_proj.weight") {
-            if (!expect(e->nq * D, H)) return fail(MTTS_EINVAL, "%s: bad shape", name_c);
-            launch_pack_weight(src, l.wqkv, rows, H, e->qkv_rows, 1, 0, st); l.bound |= 16;
-        } else if (r == "self_attn.k_proj.weight") {
-            if (!expect(e->nkv * D, H)) return fail(MTTS_EINVAL, "%s: bad shape", name_c);
-            launch_pack_weight(src, l.wqkv, rows, H, e->qkv_rows, 1, e->nq * D, st); l.bound |= 32;
-        } else if (r == "self_attn.v_proj.weight") {
-            if (!expect(e->nkv * D, H)) return fail(MTTS_EINVAL, "%s: bad shape", name_c);
-            launch_pack_weight(src, l.wqkv, rows, H, e->qkv_rows, 1, (e->nq + e->nkv) * D, st); l.bound |= 64;
-        } else if (r == "self_attn.o_proj.weight") {
-            if (!expect(H, e->nq * D)) return fail(MTTS_EINVAL, "%s: bad shape", name_c);
-            launch_pack_weight(src, l.wo, rows, e->nq * D, round_up(H, 32), 1, 0, st); l.bound |= 128;
-        } else if (r == "mlp.gate_proj.weight") {
-            if (!expect(I, H)) return fail(MTTS_EINVAL, "%s: bad shape", name_c);
-            launch_pack_weight(src, l.wgu, rows, H, 2 * I, 2, 0, st); l.bound |= 256;
-        } else if (r == "mlp.up_proj.weight") {
-            if (!expect(I, H)) return fail(MTTS_EINVAL, "%s: bad shape", name_c);
-            launch_pack_weight(src, l.wgu, rows, H, 2 * I, 2, 1, st); l.bound |= 512;
-        } else if (r == "mlp.down_proj.weight") {
-            if (!expect(H, I)) return fail(MTTS_EINVAL, "%s: bad shape", name_c);
-            launch_pack_weight(src, l.wd, rows, I, round_up(H, 32), 1, 0, st); l.bound |= 1024;
-        } else return fail(MTTS_EINVAL, "unknown tensor %s", name_c);
+    WeightSlot w;
+    TRY(resolve_weight(e, name_c, w));
+    if (!w.bound) return MTTS_OK;
+    const bool shape_ok = w.cols == 1 ? (rows == w.rows && cols == 1) || (rows == 1 && cols == w.rows) : rows == w.rows && cols == w.cols;
+    if (!shape_ok)
+        return fail(MTTS_EINVAL, "%s: expected [%lld,%lld] got [%lld,%lld]", name_c, (long long)w.rows, (long long)w.cols, (long long)rows, (long long)cols);
+    const size_t n = (size_t)w.rows * w.cols;
+    if (e->f32) {
+        HIPCHK(hipMemcpyAsync(w.f32_to + w.f32_row * w.cols, src, n * 4, hipMemcpyDeviceToDevice, st));
+    } else {
+        if (w.copy_to) HIPCHK(hipMemcpyAsync(w.copy_to, src, n * 2, hipMemcpyDeviceToDevice, st));
+        if (w.pack_to) launch_pack_weight(src, w.pack_to, (int)w.rows, (int)w.cols, w.rows_pad, w.row_mul, w.row_off, st);
         HIPCHK(hipGetLastError());
-        return MTTS_OK;
     }
-    return fail(MTTS_EINVAL, "unknown tensor %s", name_c);
+    *w.bound |= w.bit;
+    return MTTS_OK;
 }
 
+template <typename T>
+static int bind_rope_tables(MttsEngine* e, T*& c, T*& s, const void* cosb, const void* sinb, int rows, hipStream_t st) {
+    e->mem.release(c);
+    e->mem.release(s);
+    TRY(e->mem.get(&c, (size_t)rows * 64, false));
+    TRY(e->mem.get(&s, (size_t)rows * 64, false));
+    HIPCHK(hipMemcpyAsync(c, cosb, (size_t)rows * 64 * sizeof(T), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(s, sinb, (size_t)rows * 64 * sizeof(T), hipMemcpyDeviceToDevice, st));
+    e->rope_rows = rows;
+    return MTTS_OK;
+}
 int32_t mtts_bind_rope(MttsEngine* e, const void* cosb, const void* sinb, int32_t rows, void* stream) {
     if (!e || !cosb || !sinb || rows < 1) return fail(MTTS_EINVAL, "bad rope table");
     HIPCHK(hipSetDevice(e->device));
     drop_graphs(e);
-    if (e->f32) {           // fp32 tables [rows][64], as Qwen3RotaryEmbedding leaves them before the cast to the model dtype
-        if (e->rope_cos_f) { hipFree(e->rope_cos_f); hipFree(e->rope_sin_f); }
-        TRY(dalloc(&e->rope_cos_f, (size_t)rows * 64, false));
-        TRY(dalloc(&e->rope_sin_f, (size_t)rows * 64, false));
-        HIPCHK(hipMemcpyAsync(e->rope_cos_f, cosb, (size_t)rows * 256, hipMemcpyDeviceToDevice, S(stream)));
-        HIPCHK(hipMemcpyAsync(e->rope_sin_f, sinb, (size_t)rows * 256, hipMemcpyDeviceToDevice, S(stream)));
-        e->rope_rows = rows;
-        return MTTS_OK;
-    }
-    if (e->rope_cos) { hipFree(e->rope_cos); hipFree(e->rope_sin); }
-    TRY(dalloc((uint16_t**)&e->rope_cos, (size_t)rows * 64, false));
-    TRY(dalloc((uint16_t**)&e->rope_sin, (size_t)rows * 64, false));
-    HIPCHK(hipMemcpyAsync(e->rope_cos, cosb, (size_t)rows * 128, hipMemcpyDeviceToDevice, S(stream)));
-    HIPCHK(hipMemcpyAsync(e->rope_sin, sinb, (size_t)rows * 128, hipMemcpyDeviceToDevice, S(stream)));
-    e->rope_rows = rows;
-    return MTTS_OK;
+    // fp32 engine: fp32 tables [rows][64], as Qwen3RotaryEmbedding leaves them before the cast to the model dtype
+    if (e->f32) return bind_rope_tables(e, e->rope_cos_f, e->rope_sin_f, cosb, sinb, rows, S(stream));
+    return bind_rope_tables(e, e->rope_cos, e->rope_sin, cosb, sinb, rows, S(stream));
 }
 
 int32_t mtts_weights_ready(MttsEngine* e) {
@@ -795,15 +490,36 @@ static int pack_policy_reset(MttsEngine* e, hipStream_t st) {
     if (changed) drop_graphs(e);
     return 0;
 }
-// this layer's sealed pools, each null where the read policy (or MTTS_KV_PACK=0) says bf16 pages
-static KvPack layer_pack(MttsEngine* e, int n, int pages_bound) {
-    KvPack pk{nullptr, nullptr};
-    // few rows x pages: the passes are latency-bound and the unpack sits on the critical path (B=1 at 2 k: +4 %; break-even
-    // at 8 rows x 64 pages, -6 % at 16 x 64: profiles/r03_kv_pack_ab.txt)
-    if (e->B * pages_bound < e->pack_min_work) return pk;
-    if (e->kpack && e->pack_k_on[n]) pk.k = (uint8_t*)e->kpack + e->pk_layer_stride * n;
-    if (e->vpack && e->pack_v_on[n]) pk.v = (uint8_t*)e->vpack + e->pk_layer_stride * n;
-    return pk;
+// The attention section of layer n, after its qkv GEMM left `ks_qkv` slabs in `partial`: the q/k/v epilogue (a launch of
+// its own, or `fused` into the attention kernels: decode rows only), then `nphases` attention launches: scores, P.V and
+// (3) the combine that forward_small leaves to its o_proj prologue.  `prefill`: the tile-sharing kernels; `sealed`: rows
+// may read complete pages in their sealed form (decode rows; a prefill pass may complete a page itself).
+static int attend_layer(MttsEngine* e, int n, const RowMeta* d_meta, int R, int pages_bound, int ks_qkv, int nphases, bool prefill,
+                        bool fused, bool sealed, hipStream_t st, int64_t kv_tokens_hint) {
+    static const AttnPhase decode_ph[3] = {ATTN_SCORES, ATTN_PV, ATTN_COMBINE}, prefill_ph[3] = {ATTN_PF_SCORES, ATTN_PF_PV, ATTN_PF_COMBINE};
+    Layer& l = e->layers[n];
+    const float eps = e->cfg.rms_norm_eps, scale = 1.0f / sqrtf((float)MTTS_HD);
+    uint16_t* kc = (uint16_t*)e->kcache + e->layer_stride * n;
+    uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * n;
+    const QkvFuse fz{e->partial, ks_qkv, e->qkv_rows, (const uint16_t*)l.qn, (const uint16_t*)l.kn, e->rope_cos, e->rope_sin, eps};
+    const KvPack pk = layer_pack(e, n, pages_bound);
+    if (!fused)
+        launch_qkv_post(e->partial, ks_qkv, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos, e->rope_sin, e->qbuf,
+                        kc, vc, e->d_page_table, e->max_pages, e->total_pages, R, e->nq, e->nkv, eps, st);
+    for (int i = 0; i < nphases; ++i) {
+        hipEvent_t ev = nullptr;
+        if (i < 2) prof_begin(e, i == 0 ? PROF_SCORES : PROF_PV, st, &ev);
+        if (launch_attn(e->qbuf, kc, vc, e->d_page_table, d_meta, e->scores, e->stats, e->opart, e->attn_p, R,
+                        pages_bound, e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale,
+                        fused ? &fz : nullptr, (prefill ? prefill_ph : decode_ph)[i], st, (sealed && (pk.k || pk.v)) ? &pk : nullptr))
+            return fail(MTTS_EINVAL, "attention group size not built");
+        if (i < 2) prof_end(e, st, ev);
+    }
+    if (e->prof) {   // algorithmic bytes: one K (or V) row of 128 bf16 per kv head per cached token
+        e->prof_bytes[PROF_SCORES] += kv_tokens_hint * e->nkv * MTTS_HD * 2;
+        e->prof_bytes[PROF_PV] += kv_tokens_hint * e->nkv * MTTS_HD * 2;
+    }
+    return 0;
 }
 static bool small_path_fits(MttsEngine* e) {
     const int H = e->H;
@@ -815,38 +531,17 @@ static bool small_path_fits(MttsEngine* e) {
 static int forward_small(MttsEngine* e, const RowMeta* d_meta, int pages_bound, hipStream_t st, int64_t kv_tokens_hint) {
     const int H = e->H, I = e->I, nq = e->nq, nkv = e->nkv, Hp = round_up(H, 32), R = MTTS_MAXR;
     const float eps = e->cfg.rms_norm_eps;
-    const float scale = 1.0f / sqrtf((float)MTTS_HD);
     uint16_t* xa = (uint16_t*)e->x;                    // embed_norm has left the embedding sum here
     uint16_t* xb = (uint16_t*)e->x2;
     SmallPro base{};
     base.rows = e->B; base.eps = eps; base.slab_npad = Hp;
     for (int n = 0; n < e->L; ++n) {
         Layer& l = e->layers[n];
-        uint16_t* kc = (uint16_t*)e->kcache + e->layer_stride * n;
-        uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * n;
         SmallPro pq = base;                            // input norm (+ the previous layer's down_proj slabs)
         pq.x_in = xa; pq.x_out = xb; pq.slabs = e->partial2; pq.ksplit = n ? e->p_d.ksplit : 0; pq.norm_w = (const uint16_t*)l.ln_in;
         launch_gemv_small(EPI_PARTIAL, PRO_NORM, e->p_qkv, l.wqkv, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, pq, st);
-        const bool fused = e->B * pages_bound <= e->fuse_qkv_max;
-        const QkvFuse fz{e->partial, e->p_qkv.ksplit, e->qkv_rows, (const uint16_t*)l.qn, (const uint16_t*)l.kn,
-                         (const uint16_t*)e->rope_cos, (const uint16_t*)e->rope_sin, eps};
-        const KvPack pk = layer_pack(e, n, pages_bound);
-        if (!fused)
-            launch_qkv_post(e->partial, e->p_qkv.ksplit, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos, e->rope_sin, e->qbuf,
-                            kc, vc, e->d_page_table, e->max_pages, e->total_pages, R, nq, nkv, eps, st);
-        for (int phase = 1; phase <= 2; ++phase) {
-            hipEvent_t ev = nullptr;
-            prof_begin(e, phase == 1 ? PROF_SCORES : PROF_PV, st, &ev);
-            if (launch_attn(e->qbuf, kc, vc, e->d_page_table, d_meta, e->scores, e->stats, e->opart, e->attn_p, R,
-                            pages_bound, e->max_pages, e->total_pages, e->nchunks_max, nq, nkv, scale,
-                            fused ? &fz : nullptr, phase, st, (pk.k || pk.v) ? &pk : nullptr))
-                return fail(MTTS_EINVAL, "attention group size not built");
-            prof_end(e, st, ev);
-        }
-        if (e->prof) {
-            e->prof_bytes[PROF_SCORES] += kv_tokens_hint * nkv * MTTS_HD * 2;
-            e->prof_bytes[PROF_PV] += kv_tokens_hint * nkv * MTTS_HD * 2;
-        }
+        TRY(attend_layer(e, n, d_meta, R, pages_bound, e->p_qkv.ksplit, 2, false, e->B * pages_bound <= e->fuse_qkv_max, true, st,
+                         kv_tokens_hint));
         SmallPro po = base;                            // o_proj: the chunk partials of P.V are summed in its prologue
         po.opart = e->opart; po.meta = d_meta; po.nchunks_max = e->nchunks_max; po.nq = nq; po.pages_per_chunk = ATT_PB;
         launch_gemv_small(EPI_PARTIAL, PRO_COMBINE, e->p_o, l.wo, nq * MTTS_HD, Hp, Hp, e->partial2, nullptr, po, st);
@@ -875,7 +570,6 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
                         int heads, hipStream_t st, int64_t kv_tokens_hint) {
     const int H = e->H, I = e->I, nq = e->nq, nkv = e->nkv;
     const float eps = e->cfg.rms_norm_eps;
-    const float scale = 1.0f / sqrtf((float)MTTS_HD);
     const int Hp = round_up(H, 32);
     const int mb = (R + 31) / 32;                    // activation row tiles sharing each weight stream
     // prefill passes always take the tiled GEMM with a split-K that depends on the shape only (chosen for a
@@ -887,8 +581,6 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
     if (heads == 1 && e->B <= e->small_rows && small_path_fits(e)) return forward_small(e, d_meta, pages_bound, st, kv_tokens_hint);
     for (int n = 0; n < e->L; ++n) {
         Layer& l = e->layers[n];
-        uint16_t* kc = (uint16_t*)e->kcache + e->layer_stride * n;
-        uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * n;
         const int ks_qkv = tiled ? mtts_tile_ksplit(e->qkv_rows, H, 1024) : e->p_qkv.ksplit;
         const int ks_o = tiled ? mtts_tile_ksplit(Hp, nq * MTTS_HD, 1024) : e->p_o.ksplit;
         const int ks_d = tiled ? mtts_tile_ksplit(Hp, I, 1024) : e->p_d.ksplit;
@@ -898,31 +590,10 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
         // need every K/V row of the pass in the cache before any of its attention runs, so they keep the launch
         // (fused where it pays: every attention block repeats the q epilogue, which costs more than the saved launch
         // once rows x pages is large -- break-even between 32 x 64 and 64 x 64 rows x pages since round 3; the results are bit-identical)
-        const bool fused = heads == 1 && e->B * pages_bound <= e->fuse_qkv_max;
-        const QkvFuse fz{e->partial, ks_qkv, e->qkv_rows, (const uint16_t*)l.qn, (const uint16_t*)l.kn,
-                         (const uint16_t*)e->rope_cos, (const uint16_t*)e->rope_sin, eps};
-        if (!fused)
-            launch_qkv_post(e->partial, ks_qkv, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos, e->rope_sin, e->qbuf,
-                            kc, vc, e->d_page_table, e->max_pages, e->total_pages, R, nq, nkv, eps, st);
-        // decode rows are one dialogue each (phases 1,2); prefill tiles are 32 consecutive positions of one
-        // dialogue and share their K/V pages (phases 11,12,13: chunks of ATT_PF pages)
-        const int ph0 = (heads != 1 && pages_bound >= e->pf_mfma_pages) ? 10 : 0;
-        // decode rows read complete pages in their sealed form; prefill rows (a page may be completed by the pass
-        // itself) read the bf16 pages
-        const KvPack pk = layer_pack(e, n, pages_bound);
-        for (int phase = 1; phase <= 3; ++phase) {
-            hipEvent_t ev = nullptr;
-            if (phase < 3) prof_begin(e, phase == 1 ? PROF_SCORES : PROF_PV, st, &ev);
-            if (launch_attn(e->qbuf, kc, vc, e->d_page_table, d_meta, e->scores, e->stats, e->opart, e->attn_p, R,
-                            pages_bound, e->max_pages, e->total_pages, e->nchunks_max, nq, nkv, scale,
-                            fused ? &fz : nullptr, ph0 + phase, st, (heads == 1 && (pk.k || pk.v)) ? &pk : nullptr))
-                return fail(MTTS_EINVAL, "attention group size not built");
-            if (phase < 3) prof_end(e, st, ev);
-        }
-        if (e->prof) {   // algorithmic bytes: one K (or V) row of 128 bf16 per kv head per cached token
-            e->prof_bytes[PROF_SCORES] += kv_tokens_hint * nkv * MTTS_HD * 2;
-            e->prof_bytes[PROF_PV] += kv_tokens_hint * nkv * MTTS_HD * 2;
-        }
+        // decode rows are one dialogue each and read complete pages in their sealed form; prefill tiles are 32 consecutive
+        // positions of one dialogue, share their K/V pages (chunks of ATT_PF pages) and read the bf16 pages
+        TRY(attend_layer(e, n, d_meta, R, pages_bound, ks_qkv, 3, heads != 1 && pages_bound >= e->pf_mfma_pages,
+                         heads == 1 && e->B * pages_bound <= e->fuse_qkv_max, heads == 1, st, kv_tokens_hint));
         if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
         else launch_gemm(EPI_PARTIAL, mb, e->p_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
         launch_resid_norm(e->partial, ks_o, Hp, e->x, l.ln_post, e->xn, nullptr, d_meta, R, H, eps, st);
@@ -954,16 +625,27 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
     return MTTS_OK;
 }
 
+// prefill of the first `Mpad` staged rows in passes of up to MTTS_PFCAP (a multiple of MTTS_RCAP each); K/V of a pass are
+// written before its attention runs.  `last_heads`: the heads argument of the last pass.
+static int prefill_staged(MttsEngine* e, size_t Mpad, int pages_bound, int last_heads, hipStream_t st) {
+    const size_t pfcap = e->f32 ? MTTS_PF32CAP : MTTS_PFCAP;
+    for (size_t off = 0; off < Mpad; off += pfcap) {
+        const int rows = (int)std::min<size_t>(pfcap, Mpad - off);
+        TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, off + rows >= Mpad ? last_heads : 0, st, 0));
+    }
+    return 0;
+}
+
 // generated-token storage [slot][gen_cap][8] (+ decision log and forced rows of the same shape)
 static int ensure_gen_storage(MttsEngine* e, int steps) {
     if (steps <= e->gen_cap) return 0;
-    if (e->d_gen) { hipFree(e->d_gen); hipFree(e->d_declog); hipFree(e->d_forced); }
+    e->mem.release(e->d_gen); e->mem.release(e->d_declog); e->mem.release(e->d_forced);
     drop_graphs(e);                      // captured steps hold the old pointers
     e->gen_cap = steps;
     const size_t n = (size_t)e->cfg.max_batch * steps * 8;
-    TRY(dalloc(&e->d_gen, n));
-    TRY(dalloc(&e->d_declog, n));
-    TRY(dalloc(&e->d_forced, n, false));
+    TRY(e->mem.get(&e->d_gen, n));
+    TRY(e->mem.get(&e->d_declog, n));
+    TRY(e->mem.get(&e->d_forced, n, false));
     return 0;
 }
 
@@ -974,16 +656,49 @@ static int start_scores(MttsEngine* e, hipStream_t st) {
     if (!e->scores_on) return 0;
     if (!e->sscr.lp) {
         drop_graphs(e);                  // (captured steps hold the scratch pointers by value)
-        TRY(alloc_lp_scratch(e->sscr, e->cfg.max_batch));
+        TRY(alloc_lp_scratch(e->mem, e->sscr, e->cfg.max_batch));
     }
     const size_t n = (size_t)e->cfg.max_batch * e->gen_cap * 8;
     if (!e->d_lp || e->lp_cap != e->gen_cap) {
-        if (e->d_lp) { hipFree(e->d_lp); e->d_lp = nullptr; }
+        e->mem.release(e->d_lp);
         drop_graphs(e);                  // captured steps hold the old pointer
-        TRY(dalloc(&e->d_lp, n, false));
+        TRY(e->mem.get(&e->d_lp, n, false));
         e->lp_cap = e->gen_cap;
     }
     HIPCHK(hipMemsetAsync(e->d_lp, 0xff, n * sizeof(float), st));
+    return 0;
+}
+
+// prefill staging: room for `rows` flattened prompt rows
+static int grow_prefill_staging(MttsEngine* e, size_t rows) {
+    if (rows <= e->pf_cap_rows) return 0;
+    e->mem.release(e->d_pf_tokens); e->mem.release(e->d_pf_meta);
+    e->pf_cap_rows = 0;
+    TRY(e->mem.get(&e->d_pf_tokens, rows * 8, false));
+    TRY(e->mem.get(&e->d_pf_meta, rows, false));
+    e->pf_cap_rows = rows;
+    return 0;
+}
+
+// A new run starts from `seqs` (MTTS_RCAP slots; the idle ones as IDLE_SEQ) with every decode row idle, the loop state at
+// step 0, the run's sampler settings and clean sampler scratch.  Returns with `st` drained.
+static const SeqState IDLE_SEQ{-1, 0, 0, 0, 0, 0, 0, 0, 0};
+static int reset_run_state(MttsEngine* e, const std::vector<SeqState>& seqs, bool continuous, const MttsSamplerCfg* sampler, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(e->d_seqs, seqs.data(), seqs.size() * sizeof(SeqState), hipMemcpyHostToDevice, st));
+    if (continuous) e->forced_draw = 0;
+    LoopState ls{0, 0, continuous ? 1 : 0, e->B, 0, e->gen_cap, e->forced_draw, e->f32 ? 1 : 0};
+    e->continuous = continuous;
+    e->join_step.assign(MTTS_RCAP, 0);
+    HIPCHK(hipMemcpyAsync(e->d_ls, &ls, sizeof(ls), hipMemcpyHostToDevice, st));
+    *e->h_ls = ls;
+    std::vector<RowMeta> dm(MTTS_RCAP, RowMeta{-1, 0, 0, 0});
+    HIPCHK(hipMemcpyAsync(e->d_meta, dm.data(), dm.size() * sizeof(RowMeta), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->d_scfg, sampler, 8 * sizeof(MttsSamplerCfg), hipMemcpyHostToDevice, st));
+    e->ch0_sampled = sampler[0].do_sample ? 1 : 0;
+    HIPCHK(hipMemsetAsync(e->sscr.hist, 0, (size_t)e->cfg.max_batch * 2048 * 4, st));
+    HIPCHK(hipMemsetAsync(e->sscr.cand_n, 0, (size_t)e->cfg.max_batch * 4, st));
+    HIPCHK(hipMemsetAsync(e->sscr.overflow, 0, (size_t)e->cfg.max_batch * 4, st));
+    HIPCHK(hipStreamSynchronize(st));   // the host arrays (the callers' too) may go out of scope
     return 0;
 }
 
@@ -1101,12 +816,7 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
             }
             metas[r] = RowMeta{b * takes, i, i == e->n_real[b * takes] - 1 ? 1 : 0, 0};
         }
-    if (Mpad > e->pf_cap_rows) {
-        if (e->d_pf_tokens) { hipFree(e->d_pf_tokens); hipFree(e->d_pf_meta); }
-        TRY(dalloc(&e->d_pf_tokens, Mpad * 8, false));
-        TRY(dalloc(&e->d_pf_meta, Mpad, false));
-        e->pf_cap_rows = Mpad;
-    }
+    TRY(grow_prefill_staging(e, Mpad));
     HIPCHK(hipMemcpyAsync(e->d_pf_tokens, toks.data(), Mpad * 8 * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(e->d_pf_meta, metas.data(), Mpad * sizeof(RowMeta), hipMemcpyHostToDevice, st));
     // history bitmaps (HF repetition penalty sees the whole channel incl. pads: modeling_asteroid.py:129)
@@ -1129,35 +839,15 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
                     tf[((size_t)rw * 7 + s) * 8 + c] = (int32_t)tk;
                 }
         HIPCHK(hipMemcpyAsync(e->d_tf, tf.data(), tf.size() * 4, hipMemcpyHostToDevice, st));
-        std::vector<SeqState> ss(MTTS_RCAP, SeqState{-1, 0, 0, 0, 0, 0, 0, 0, 0});
+        std::vector<SeqState> ss(MTTS_RCAP, IDLE_SEQ);
         if (!e->next_row_ids.empty() && (int)e->next_row_ids.size() != R)
             return fail(MTTS_EINVAL, "mtts_set_row_ids gave %d ids, the batch has %d rows", (int)e->next_row_ids.size(), R);
         for (int b = 0; b < R; ++b)
             ss[b] = SeqState{-1, 1, e->n_real[b], 0, base, max_length, e->next_row_ids.empty() ? b : e->next_row_ids[b], 1, seed};
         e->next_row_ids.clear();
-        HIPCHK(hipMemcpyAsync(e->d_seqs, ss.data(), ss.size() * sizeof(SeqState), hipMemcpyHostToDevice, st));
-        LoopState ls{0, 0, 0, R, 0, e->gen_cap, e->forced_draw, e->f32 ? 1 : 0};
-        e->continuous = false;
-        e->join_step.assign(MTTS_RCAP, 0);
-        HIPCHK(hipMemcpyAsync(e->d_ls, &ls, sizeof(ls), hipMemcpyHostToDevice, st));
-        *e->h_ls = ls;
-        std::vector<RowMeta> dm(MTTS_RCAP, RowMeta{-1, 0, 0, 0});
-        HIPCHK(hipMemcpyAsync(e->d_meta, dm.data(), dm.size() * sizeof(RowMeta), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(e->d_scfg, sampler, 8 * sizeof(MttsSamplerCfg), hipMemcpyHostToDevice, st));
-        e->ch0_sampled = sampler[0].do_sample ? 1 : 0;
-        HIPCHK(hipMemsetAsync(e->sscr.hist, 0, (size_t)e->cfg.max_batch * 2048 * 4, st));
-        HIPCHK(hipMemsetAsync(e->sscr.cand_n, 0, (size_t)e->cfg.max_batch * 4, st));
-        HIPCHK(hipMemsetAsync(e->sscr.overflow, 0, (size_t)e->cfg.max_batch * 4, st));
-        HIPCHK(hipStreamSynchronize(st));   // host vectors above go out of scope
+        TRY(reset_run_state(e, ss, false, sampler, st));   // drains st: the host vectors above go out of scope
     }
-    // prefill: chunks of 32 flattened tokens; K/V of a chunk are written before its attention runs
-    const int pages_bound = (e->max_real + MTTS_PAGE - 1) / MTTS_PAGE;
-    const size_t pfcap = e->f32 ? MTTS_PF32CAP : MTTS_PFCAP;
-    for (size_t off = 0; off < Mpad; off += pfcap) {
-        const int rows = (int)std::min<size_t>(pfcap, Mpad - off);     // multiple of MTTS_RCAP
-        const bool lastc = off + rows >= Mpad;
-        TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, lastc ? 2 : 0, st, 0));
-    }
+    TRY(prefill_staged(e, Mpad, (e->max_real + MTTS_PAGE - 1) / MTTS_PAGE, 2, st));
     // takes: the partially filled last prompt page of each source row into its takes' private pages, and the source
     // row's logits into theirs (bitmaps, teacher-forcing tails and states were uploaded for every row above)
     if (fork.nr) TRY(launch_fork_job(e, fork, false, st));
@@ -1293,16 +983,51 @@ int32_t mtts_sync_state(MttsEngine* e, int32_t* steps_done, int32_t* all_finishe
     return MTTS_OK;
 }
 
-static int read_rows(MttsEngine* e, const int32_t* d_src, int64_t* host, int capacity_steps, int* n_steps) {
-    int steps = e->h_ls->step;
-    if (steps > capacity_steps) return fail(MTTS_EINVAL, "output buffer holds %d steps, need %d", capacity_steps, steps);
-    std::vector<int32_t> tmp((size_t)std::max(steps, 1) * 8);
-    for (int b = 0; b < e->B; ++b) {
-        if (steps) HIPCHK(hipMemcpy(tmp.data(), d_src + (size_t)b * e->gen_cap * 8, (size_t)steps * 8 * 4, hipMemcpyDeviceToHost));
+// `nslots` slots from `slot0` of a device array [slot][gen_cap][8] -> host [step][slot - slot0][8]
+template <typename Src, typename Dst>
+static int read_slots(MttsEngine* e, const Src* d_src, int slot0, int nslots, int steps, Dst* host) {
+    std::vector<Src> tmp((size_t)std::max(steps, 1) * 8);
+    for (int b = 0; b < nslots; ++b) {
+        if (steps) HIPCHK(hipMemcpy(tmp.data(), d_src + (size_t)(slot0 + b) * e->gen_cap * 8, (size_t)steps * 8 * sizeof(Src), hipMemcpyDeviceToHost));
         for (int s = 0; s < steps; ++s)
-            for (int c = 0; c < 8; ++c) host[((size_t)s * e->B + b) * 8 + c] = tmp[(size_t)s * 8 + c];
+            for (int c = 0; c < 8; ++c) host[((size_t)s * nslots + b) * 8 + c] = tmp[(size_t)s * 8 + c];
     }
+    return MTTS_OK;
+}
+// every row of the run, all steps so far
+template <typename Src, typename Dst>
+static int read_rows(MttsEngine* e, const Src* d_src, Dst* host, int capacity_steps, int* n_steps) {
+    const int steps = e->h_ls->step;
+    if (steps > capacity_steps) return fail(MTTS_EINVAL, "output buffer holds %d steps, need %d", capacity_steps, steps);
+    TRY(read_slots(e, d_src, 0, e->B, steps, host));
     if (n_steps) *n_steps = steps;
+    return MTTS_OK;
+}
+// one slot of a scheduler run, the steps its dialogue has run
+template <typename Src, typename Dst>
+static int slot_read(MttsEngine* e, const Src* d_src, int slot, Dst* host_rows, int capacity_steps, int* n_steps) {
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());
+    SeqState cur;
+    HIPCHK(hipMemcpy(&cur, e->d_seqs + slot, sizeof(cur), hipMemcpyDeviceToHost));
+    if (cur.step > capacity_steps) return fail(MTTS_EINVAL, "buffer holds %d steps, need %d", capacity_steps, cur.step);
+    TRY(read_slots(e, d_src, slot, 1, cur.step, host_rows));
+    if (n_steps) *n_steps = cur.step;
+    return MTTS_OK;
+}
+// last forward's logits (T = the engine's logits element): channel 0 [B][V0], channels 1..7 [7][B][Vs]
+template <typename T>
+static int read_logits(MttsEngine* e, T* l0, T* l17, void* stream) {
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(S(stream)));
+    if (l0) HIPCHK(hipMemcpy2D(l0, (size_t)e->V0 * sizeof(T), e->logits0, (size_t)e->V0_pad * sizeof(T), (size_t)e->V0 * sizeof(T), e->B, hipMemcpyDeviceToHost));
+    if (l17) {
+        std::vector<T> tmp((size_t)MTTS_RCAP * 7 * e->Vs_pad);
+        HIPCHK(hipMemcpy(tmp.data(), e->logits17, tmp.size() * sizeof(T), hipMemcpyDeviceToHost));
+        for (int c = 0; c < 7; ++c)
+            for (int b = 0; b < e->B; ++b)
+                memcpy(l17 + ((size_t)c * e->B + b) * e->Vs, tmp.data() + ((size_t)b * 7 + c) * e->Vs_pad, (size_t)e->Vs * sizeof(T));
+    }
     return MTTS_OK;
 }
 
@@ -1340,47 +1065,19 @@ int32_t mtts_read_scores(MttsEngine* e, float* host_lp, int32_t capacity_steps, 
     if (!e->scores_on) return fail(MTTS_ESTATE, "the run was started with output_scores off (mtts_set_output_scores)");
     HIPCHK(hipSetDevice(e->device));
     TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
-    const int steps = e->h_ls->step;
-    if (steps > capacity_steps) return fail(MTTS_EINVAL, "output buffer holds %d steps, need %d", capacity_steps, steps);
-    std::vector<float> tmp((size_t)std::max(steps, 1) * 8);
-    for (int b = 0; b < e->B; ++b) {
-        if (steps) HIPCHK(hipMemcpy(tmp.data(), e->d_lp + (size_t)b * e->gen_cap * 8, (size_t)steps * 8 * 4, hipMemcpyDeviceToHost));
-        for (int s = 0; s < steps; ++s) memcpy(host_lp + ((size_t)s * e->B + b) * 8, tmp.data() + (size_t)s * 8, 8 * sizeof(float));
-    }
-    if (n_steps) *n_steps = steps;
-    return MTTS_OK;
+    return read_rows(e, e->d_lp, host_lp, capacity_steps, n_steps);
 }
 
 int32_t mtts_read_logits_f32(MttsEngine* e, float* l0, float* l17, void* stream) {
     if (!e || !e->began) return fail(MTTS_ESTATE, "mtts_begin has not run");
     if (!e->f32) return fail(MTTS_ESTATE, "bf16 engine: use mtts_read_logits");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(S(stream)));
-    if (l0) HIPCHK(hipMemcpy2D(l0, (size_t)e->V0 * 4, e->logits0, (size_t)e->V0_pad * 4, (size_t)e->V0 * 4, e->B, hipMemcpyDeviceToHost));
-    if (l17) {
-        std::vector<float> tmp((size_t)MTTS_RCAP * 7 * e->Vs_pad);
-        HIPCHK(hipMemcpy(tmp.data(), e->logits17, tmp.size() * 4, hipMemcpyDeviceToHost));
-        for (int c = 0; c < 7; ++c)
-            for (int b = 0; b < e->B; ++b)
-                memcpy(l17 + ((size_t)c * e->B + b) * e->Vs, tmp.data() + ((size_t)b * 7 + c) * e->Vs_pad, (size_t)e->Vs * 4);
-    }
-    return MTTS_OK;
+    return read_logits(e, l0, l17, stream);
 }
 
 int32_t mtts_read_logits(MttsEngine* e, uint16_t* l0, uint16_t* l17, void* stream) {
     if (!e || !e->began) return fail(MTTS_ESTATE, "mtts_begin has not run");
     if (e->f32) return fail(MTTS_ESTATE, "fp32 engine: use mtts_read_logits_f32");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(S(stream)));
-    if (l0) HIPCHK(hipMemcpy2D(l0, (size_t)e->V0 * 2, e->logits0, (size_t)e->V0_pad * 2, (size_t)e->V0 * 2, e->B, hipMemcpyDeviceToHost));
-    if (l17) {
-        std::vector<uint16_t> tmp((size_t)MTTS_RCAP * 7 * e->Vs_pad);
-        HIPCHK(hipMemcpy(tmp.data(), e->logits17, tmp.size() * 2, hipMemcpyDeviceToHost));
-        for (int c = 0; c < 7; ++c)
-            for (int b = 0; b < e->B; ++b)
-                memcpy(l17 + ((size_t)c * e->B + b) * e->Vs, tmp.data() + ((size_t)b * 7 + c) * e->Vs_pad, (size_t)e->Vs * 2);
-    }
-    return MTTS_OK;
+    return read_logits(e, l0, l17, stream);
 }
 
 int32_t mtts_generate(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32_t B, int32_t T, int32_t max_length,
@@ -1470,26 +1167,12 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     e->B = B; e->steps_issued = 0; e->has_forced = false; e->continuous = true;
     e->max_steps = 1 << 30;
     e->n_real.assign(B, 0);
-    e->join_step.assign(MTTS_RCAP, 0);
     e->max_real = 0;
     HIPCHK(hipStreamSynchronize(st));
     for (int b = 0; b < e->cfg.max_batch; ++b) { pool_release(e, b); e->slot_live[b] = 0; }
     e->pending_edits.n = 0;
     TRY(pack_policy_reset(e, st));
-    std::vector<SeqState> ss(MTTS_RCAP, SeqState{-1, 0, 0, 0, 0, 0, 0, 0, 0});
-    HIPCHK(hipMemcpyAsync(e->d_seqs, ss.data(), ss.size() * sizeof(SeqState), hipMemcpyHostToDevice, st));
-    LoopState ls{0, 0, 1, B, 0, e->gen_cap, 0, e->f32 ? 1 : 0};
-    e->forced_draw = 0;
-    HIPCHK(hipMemcpyAsync(e->d_ls, &ls, sizeof(ls), hipMemcpyHostToDevice, st));
-    *e->h_ls = ls;
-    std::vector<RowMeta> dm(MTTS_RCAP, RowMeta{-1, 0, 0, 0});
-    HIPCHK(hipMemcpyAsync(e->d_meta, dm.data(), dm.size() * sizeof(RowMeta), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->d_scfg, sampler, 8 * sizeof(MttsSamplerCfg), hipMemcpyHostToDevice, st));
-    e->ch0_sampled = sampler[0].do_sample ? 1 : 0;
-    HIPCHK(hipMemsetAsync(e->sscr.hist, 0, (size_t)e->cfg.max_batch * 2048 * 4, st));
-    HIPCHK(hipMemsetAsync(e->sscr.cand_n, 0, (size_t)e->cfg.max_batch * 4, st));
-    HIPCHK(hipMemsetAsync(e->sscr.overflow, 0, (size_t)e->cfg.max_batch * 4, st));
-    HIPCHK(hipStreamSynchronize(st));
+    TRY(reset_run_state(e, std::vector<SeqState>(MTTS_RCAP, IDLE_SEQ), true, sampler, st));
     e->began = true;
     e->run_open = true;
     return MTTS_OK;
@@ -1548,21 +1231,12 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
             else tf[(i - n) * 8 + c] = (int32_t)t;
         }
     for (int i = 0; i < n; ++i) metas[i] = RowMeta{slot, i, i == n - 1 ? 1 : 0, 0};
-    if (Mpad > e->pf_cap_rows) {
-        if (e->d_pf_tokens) { hipFree(e->d_pf_tokens); hipFree(e->d_pf_meta); }
-        TRY(dalloc(&e->d_pf_tokens, Mpad * 8, false));
-        TRY(dalloc(&e->d_pf_meta, Mpad, false));
-        e->pf_cap_rows = Mpad;
-    }
+    TRY(grow_prefill_staging(e, Mpad));
     HIPCHK(hipMemcpy(e->d_pf_tokens, toks.data(), Mpad * 8 * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_pf_meta, metas.data(), Mpad * sizeof(RowMeta), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_bitmaps + (size_t)slot * 8 * e->bm_words, bm.data(), bm.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_tf + (size_t)slot * 7 * 8, tf.data(), tf.size() * 4, hipMemcpyHostToDevice));
-    const int pages_bound = (n + MTTS_PAGE - 1) / MTTS_PAGE;
-    const size_t pfcap = e->f32 ? MTTS_PF32CAP : MTTS_PFCAP;
-    for (size_t off = 0; off < Mpad; off += pfcap)
-        TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, (int)std::min<size_t>(pfcap, Mpad - off),
-                         pages_bound, 0, st, 0));
+    TRY(prefill_staged(e, Mpad, (n + MTTS_PAGE - 1) / MTTS_PAGE, 0, st));
     // logits of the dialogue's last prompt token only: heads on a one-row activation tile, copied into its slot
     // (the other slots' logits belong to dialogues that are mid-flight)
     if (e->f32) {            // fp32 engine: the GEMV writes the slot's logits rows directly
@@ -1700,30 +1374,14 @@ int32_t mtts_set_forced_mode(MttsEngine* e, int32_t as_draw) {
 // generated rows of one slot: host_rows int64 [steps][8]
 int32_t mtts_slot_read(MttsEngine* e, int32_t slot, int64_t* host_rows, int32_t capacity_steps, int32_t* n_steps) {
     if (!e || !e->began || !host_rows || slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "bad argument");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipDeviceSynchronize());
-    SeqState cur;
-    HIPCHK(hipMemcpy(&cur, e->d_seqs + slot, sizeof(cur), hipMemcpyDeviceToHost));
-    if (cur.step > capacity_steps) return fail(MTTS_EINVAL, "buffer holds %d steps, need %d", capacity_steps, cur.step);
-    std::vector<int32_t> tmp((size_t)std::max(cur.step, 1) * 8);
-    if (cur.step) HIPCHK(hipMemcpy(tmp.data(), e->d_gen + (size_t)slot * e->gen_cap * 8, (size_t)cur.step * 8 * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < cur.step * 8; ++i) host_rows[i] = tmp[i];
-    if (n_steps) *n_steps = cur.step;
-    return MTTS_OK;
+    return slot_read(e, e->d_gen, slot, host_rows, capacity_steps, n_steps);
 }
 
 // log-probabilities of one slot's generated rows: host_rows float [steps][8]
 int32_t mtts_slot_read_scores(MttsEngine* e, int32_t slot, float* host_rows, int32_t capacity_steps, int32_t* n_steps) {
     if (!e || !e->began || !host_rows || slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "bad argument");
     if (!e->scores_on) return fail(MTTS_ESTATE, "the run was started with output_scores off (mtts_set_output_scores)");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipDeviceSynchronize());
-    SeqState cur;
-    HIPCHK(hipMemcpy(&cur, e->d_seqs + slot, sizeof(cur), hipMemcpyDeviceToHost));
-    if (cur.step > capacity_steps) return fail(MTTS_EINVAL, "buffer holds %d steps, need %d", capacity_steps, cur.step);
-    if (cur.step) HIPCHK(hipMemcpy(host_rows, e->d_lp + (size_t)slot * e->gen_cap * 8, (size_t)cur.step * 8 * 4, hipMemcpyDeviceToHost));
-    if (n_steps) *n_steps = cur.step;
-    return MTTS_OK;
+    return slot_read(e, e->d_lp, slot, host_rows, capacity_steps, n_steps);
 }
 
 // Frames first..first+n-1 of every sequence as codec codes int64 [8][B][n] on the device (delay pattern undone,
@@ -1765,381 +1423,3 @@ int32_t mtts_profile_read(MttsEngine* e, int32_t which, double* total_ms, int64_
     return MTTS_OK;
 }
 
-// ---- per-kernel entry points --------------------------------------------------------
-// device buffers of a test hook: freed on every return path
-struct HookBufs {
-    std::vector<void*> p;
-    ~HookBufs() { for (void* q : p) if (q) hipFree(q); }
-    template <typename T>
-    int get(T** out, size_t n, bool zero = true) {
-        int rc = dalloc(out, n, zero);
-        if (!rc) p.push_back((void*)*out);
-        return rc;
-    }
-};
-int32_t mtts_k_gemm_bf16(const void* w, const void* x, void* y, int32_t M, int32_t N, int32_t K, int32_t ksplit, void* stream) {
-    if (!w || !x || !y || M < 1 || M > MTTS_PFCAP || K % 16 || N < 1) return fail(MTTS_EINVAL, "gemm: need 1<=M<=MTTS_PFCAP, K%%16==0");
-    hipStream_t st = S(stream);
-    int Npad = round_up(N, 32);
-    void *wp = nullptr, *xp = nullptr;
-    float* part = nullptr;
-    GemmPlan p = mtts_plan_gemm(Npad, K, ksplit);
-    p.depth = gemm_depth_env();
-    HookBufs hb;
-    TRY(hb.get((uint16_t**)&wp, (size_t)Npad * K));
-    // M <= 128: skinny kernel (decode); above: tiled kernel (prefill), ksplit as given or its own choice
-    const bool tiled = M > MTTS_RCAP;
-    const int ks = tiled ? (ksplit > 0 ? ksplit : mtts_tile_ksplit(Npad, K, M)) : p.ksplit;
-    TRY(hb.get((uint16_t**)&xp, (size_t)MTTS_PFCAP * K));
-    TRY(hb.get(&part, (size_t)ks * MTTS_PFCAP * Npad));
-    launch_pack_weight(w, wp, N, K, Npad, 1, 0, st);
-    const int tiles = (M + 31) / 32;
-    launch_pack_rows(x, xp, M, K, tiles == 3 ? 4 : tiles, st);
-    if (tiled) launch_gemm_tile(EPI_PARTIAL, M, ks, wp, xp, K, Npad, Npad, part, nullptr, st);
-    else launch_gemm(EPI_PARTIAL, tiles, p, wp, xp, K, Npad, Npad, part, nullptr, st);
-    launch_reduce_partial_bf16(part, y, ks, Npad, N, M, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return MTTS_OK;
-}
-
-long long mtts_gemm_depth_launches();
-int64_t mtts_debug_gemm_depth_launches(void) { return (int64_t)mtts_gemm_depth_launches(); }
-void launch_unpack_rows(const void* packed, void* out, int R, int K, hipStream_t st);
-int32_t mtts_k_gemm_swiglu_bf16(const void* w, const void* x, void* y, int32_t M, int32_t N, int32_t K, void* stream) {
-    if (!w || !x || !y || M < 1 || M > MTTS_RCAP || K % 16 || N < 32 || N % 32) return fail(MTTS_EINVAL, "gemm_swiglu: need 1<=M<=128, K%%16==0, N%%32==0");
-    hipStream_t st = S(stream);
-    void *wp = nullptr, *xp = nullptr, *op = nullptr;
-    GemmPlan p = mtts_plan_gemm(N, K, 1);          // as the engine plans gate/up: no split-K
-    p.depth = gemm_depth_env();
-    HookBufs hb;
-    const int tiles = (M + 31) / 32, tp = tiles == 3 ? 4 : tiles;
-    TRY(hb.get((uint16_t**)&wp, (size_t)N * K));
-    TRY(hb.get((uint16_t**)&xp, (size_t)tp * 32 * K));
-    TRY(hb.get((uint16_t**)&op, (size_t)tp * 32 * (N / 2)));
-    launch_pack_weight(w, wp, N, K, N, 1, 0, st);
-    launch_pack_rows(x, xp, M, K, tp, st);
-    launch_gemm(EPI_SILU, tiles, p, wp, xp, K, N, N, nullptr, (uint16_t*)op, st);
-    launch_unpack_rows(op, y, M, N / 2, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return MTTS_OK;
-}
-
-int32_t mtts_k_rmsnorm(const void* x, const void* w, void* y, int32_t rows, int32_t n, float eps, void* stream) {
-    if (!x || !w || !y || rows < 1 || n < 1) return fail(MTTS_EINVAL, "rmsnorm: bad argument");
-    launch_rmsnorm_rows(x, w, y, rows, n, eps, S(stream));
-    HIPCHK(hipGetLastError());
-    return MTTS_OK;
-}
-
-static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
-                    int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp, void* stream) {
-    if (!logits || !cfg || !dev_tokens || rows < 1 || vocab < 1 || channel < 0 || channel > 7) return fail(MTTS_EINVAL, "sample: bad argument");
-    hipStream_t st = S(stream);
-    MttsSamplerCfg h[8];
-    for (int i = 0; i < 8; ++i) h[i] = *cfg;
-    MttsSamplerCfg* d = nullptr;
-    int32_t *err = nullptr, *dec = nullptr;
-    if (rows > MTTS_RCAP) return fail(MTTS_EINVAL, "sample: at most 128 rows");
-    HookBufs hb;
-    TRY(hb.get(&d, 8));
-    TRY(hb.get(&err, 1));
-    TRY(hb.get(&dec, (size_t)rows * 8));
-    HIPCHK(hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice));
-    SampleScratch sc;
-    struct ScratchGuard { SampleScratch* s; ~ScratchGuard() { free_scratch(*s); } } sg{&sc};
-    sc = SampleScratch{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    TRY(alloc_scratch(sc, rows, vocab));
-    if (dev_logp) TRY(alloc_lp_scratch(sc, rows));
-    launch_sample_single(logits, rows, vocab, (const uint32_t*)bitmap, (vocab + 31) / 32, d, mask_id, seed, step, channel, dec, err, sc,
-                         full_cap_for(vocab), dev_logp ? 1 : 0, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<int32_t> hd((size_t)rows * 8);
-    int32_t herr = 0;
-    HIPCHK(hipMemcpy(hd.data(), dec, hd.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&herr, err, 4, hipMemcpyDeviceToHost));
-    std::vector<int32_t> outv(rows);
-    for (int r = 0; r < rows; ++r) outv[r] = hd[(size_t)r * 8 + channel];
-    HIPCHK(hipMemcpy(dev_tokens, outv.data(), rows * 4, hipMemcpyHostToDevice));
-    if (dev_logp) {
-        std::vector<float> hl((size_t)rows * 8), outl(rows);
-        HIPCHK(hipMemcpy(hl.data(), sc.lp, hl.size() * 4, hipMemcpyDeviceToHost));
-        for (int r = 0; r < rows; ++r) outl[r] = hl[(size_t)r * 8 + channel];
-        HIPCHK(hipMemcpy(dev_logp, outl.data(), rows * 4, hipMemcpyHostToDevice));
-    }
-    if (herr) return fail(MTTS_EINVAL, "sample: more than 4096 candidate tokens");
-    return MTTS_OK;
-}
-
-int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
-                      int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, void* stream) {
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, stream);
-}
-
-int32_t mtts_k_sample_scores(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
-                             int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
-                             void* stream) {
-    if (!dev_logp) return fail(MTTS_EINVAL, "sample: null dev_logp");
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, stream);
-}
-
-// ---- per-kernel entry points for attention and RoPE / cache write (unit tests) ----------------------------------------
-void launch_pack_kv_pages(const void* K, const void* V, void* kcache, void* vcache, const int32_t* page_table, const int32_t* lens,
-                          int S, int Lmax, int nkv, int max_pages, int total_pages, hipStream_t st);
-void launch_bf16_to_f32(const void* a, float* b, size_t n, hipStream_t st);
-void launch_unpack_rows(const void* packed, void* out, int R, int K, hipStream_t st);
-
-// q/k/v epilogue of one token per row (qkv_post_kernel): dev_qkv bf16 [R][(nq+2*nkv)*128] = the three Linears' outputs,
-// host_pos int32 [R] positions, dev_qnorm / dev_knorm bf16 [128], dev_cos / dev_sin bf16 [rope_rows][64].
-// Outputs bf16: dev_q [R][nq][128] (normed + rotated), dev_k [R][nkv][128] (normed + rotated, read back from the K page it was
-// written to), dev_v [R][nkv][128] (read back from the V page).  Every row is its own sequence (page table = one page each).
-int32_t mtts_k_rope_kvwrite(const void* dev_qkv, const int32_t* host_pos, const void* dev_qnorm, const void* dev_knorm,
-                            const void* dev_cos, const void* dev_sin, int32_t R, int32_t nq, int32_t nkv, float eps,
-                            void* dev_q, void* dev_k, void* dev_v, void* stream) {
-    if (!dev_qkv || !host_pos || !dev_q || !dev_k || !dev_v || R < 1 || R > MTTS_RCAP || nq < 1 || nkv < 1) return fail(MTTS_EINVAL, "rope_kvwrite: bad argument");
-    hipStream_t st = S(stream);
-    const int N = (nq + 2 * nkv) * MTTS_HD;
-    int maxpos = 0;
-    for (int r = 0; r < R; ++r) { if (host_pos[r] < 0) return fail(MTTS_EINVAL, "negative position"); maxpos = std::max(maxpos, host_pos[r]); }
-    const int max_pages = maxpos / MTTS_PAGE + 1, total_pages = R * max_pages;
-    float* slab = nullptr; RowMeta* meta = nullptr; int32_t* pt = nullptr; uint16_t *kc = nullptr, *vc = nullptr;
-    HookBufs hb;
-    TRY(hb.get(&slab, (size_t)MTTS_PFCAP * N));
-    TRY(hb.get(&meta, R)); TRY(hb.get(&pt, (size_t)R * max_pages));
-    TRY(hb.get(&kc, (size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD)); TRY(hb.get(&vc, (size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD));
-    std::vector<RowMeta> hm(R);
-    std::vector<int32_t> hpt((size_t)R * max_pages);
-    for (int r = 0; r < R; ++r) { hm[r] = RowMeta{r, host_pos[r], 1, 0}; for (int p = 0; p < max_pages; ++p) hpt[(size_t)r * max_pages + p] = r * max_pages + p; }
-    HIPCHK(hipMemcpy(meta, hm.data(), R * sizeof(RowMeta), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pt, hpt.data(), hpt.size() * 4, hipMemcpyHostToDevice));
-    launch_bf16_to_f32(dev_qkv, slab, (size_t)R * N, st);
-    launch_qkv_post(slab, 1, N, meta, dev_qnorm, dev_knorm, dev_cos, dev_sin, dev_q, kc, vc, pt, max_pages, total_pages, R, nq, nkv, eps, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    // read the written K / V rows back out of their pages
-    std::vector<uint16_t> hk((size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD), hv(hk.size()), ok((size_t)R * nkv * MTTS_HD), ov(ok.size());
-    HIPCHK(hipMemcpy(hk.data(), kc, hk.size() * 2, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hv.data(), vc, hv.size() * 2, hipMemcpyDeviceToHost));
-    for (int r = 0; r < R; ++r)
-        for (int h = 0; h < nkv; ++h)
-            for (int d = 0; d < MTTS_HD; ++d) {
-                const int page = r * max_pages + host_pos[r] / MTTS_PAGE, t = host_pos[r] % MTTS_PAGE;
-                const size_t base = ((size_t)h * total_pages + page) * (MTTS_PAGE * MTTS_HD);
-                ok[((size_t)r * nkv + h) * MTTS_HD + d] = hk[base + (((d >> 3) * 64) + t) * 8 + (d & 7)];
-                ov[((size_t)r * nkv + h) * MTTS_HD + d] = hv[base + ((size_t)(t >> 1) * MTTS_HD + d) * 2 + (t & 1)];
-            }
-    HIPCHK(hipMemcpy(dev_k, ok.data(), ok.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dev_v, ov.data(), ov.size() * 2, hipMemcpyHostToDevice));
-    return MTTS_OK;
-}
-
-// Decode attention of one query token per row over a paged cache (attn_scores / attn_pv / attn_combine, the launches of
-// a decode step): dev_q bf16 [R][nq][128]; dev_k / dev_v bf16 [R][Lmax][nkv][128] row-major (row r uses its first
-// host_lens[r] tokens; its query sits at position host_lens[r]-1); host_page_table int32 [R][pages] with
-// pages = ceil(Lmax/64): any permutation of 0..R*pages-1 (NULL = consecutive).  dev_out bf16 [R][nq*128].
-int32_t mtts_k_paged_attn_decode(const void* dev_q, const void* dev_k, const void* dev_v, const int32_t* host_lens,
-                                 const int32_t* host_page_table, int32_t R, int32_t Lmax, int32_t nq, int32_t nkv,
-                                 void* dev_out, void* stream) {
-    if (!dev_q || !dev_k || !dev_v || !host_lens || !dev_out || R < 1 || R > MTTS_MAXR || Lmax < 1 || nq < 1 || nkv < 1 || nq % nkv)
-        return fail(MTTS_EINVAL, "paged_attn_decode: bad argument (1..32 rows)");
-    hipStream_t st = S(stream);
-    const int max_pages = (Lmax + MTTS_PAGE - 1) / MTTS_PAGE, total_pages = R * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
-    std::vector<int32_t> hpt((size_t)R * max_pages);
-    std::vector<char> seen(total_pages, 0);
-    for (size_t i = 0; i < hpt.size(); ++i) {
-        hpt[i] = host_page_table ? host_page_table[i] : (int32_t)i;
-        if (hpt[i] < 0 || hpt[i] >= total_pages || seen[hpt[i]]) return fail(MTTS_EINVAL, "page table must be a permutation of 0..%d", total_pages - 1);
-        seen[hpt[i]] = 1;
-    }
-    std::vector<RowMeta> hm(MTTS_MAXR, RowMeta{-1, 0, 0, 0});
-    int pages_bound = 1;
-    for (int r = 0; r < R; ++r) {
-        if (host_lens[r] < 1 || host_lens[r] > Lmax) return fail(MTTS_EINVAL, "row %d: length %d outside 1..%d", r, host_lens[r], Lmax);
-        hm[r] = RowMeta{r, host_lens[r] - 1, 1, 0};
-        pages_bound = std::max(pages_bound, (host_lens[r] + MTTS_PAGE - 1) / MTTS_PAGE);
-    }
-    RowMeta* meta = nullptr; int32_t *pt = nullptr, *lens = nullptr; uint16_t *kc = nullptr, *vc = nullptr, *scores = nullptr, *outp = nullptr;
-    float *stats = nullptr, *opart = nullptr;
-    const size_t cache_n = (size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD;
-    HookBufs hb;
-    TRY(hb.get(&meta, MTTS_MAXR)); TRY(hb.get(&pt, hpt.size())); TRY(hb.get(&lens, R));
-    TRY(hb.get(&kc, cache_n)); TRY(hb.get(&vc, cache_n));
-    TRY(hb.get(&scores, (size_t)MTTS_MAXR * nq * max_pages * MTTS_PAGE));
-    TRY(hb.get(&stats, (size_t)MTTS_MAXR * nq * max_pages * 2));
-    TRY(hb.get(&opart, (size_t)MTTS_MAXR * nq * nch * MTTS_HD));
-    TRY(hb.get(&outp, (size_t)MTTS_MAXR * nq * MTTS_HD));
-    HIPCHK(hipMemcpy(meta, hm.data(), hm.size() * sizeof(RowMeta), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pt, hpt.data(), hpt.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(lens, host_lens, R * 4, hipMemcpyHostToDevice));
-    launch_pack_kv_pages(dev_k, dev_v, kc, vc, pt, lens, R, Lmax, nkv, max_pages, total_pages, st);
-    // like the engine: complete pages are read in their sealed form unless MTTS_KV_PACK=0
-    KvPack pk{nullptr, nullptr};
-    const char* g = getenv("MTTS_KV_PACK");
-    if (!g || atoi(g) != 0) {
-        uint8_t *kp = nullptr, *vp = nullptr;
-        const size_t pk_n = (size_t)total_pages * nkv * MTTS_PKU * 64 * 16;
-        TRY(hb.get(&kp, pk_n)); TRY(hb.get(&vp, pk_n));
-        launch_kv_seal_all(kc, vc, kp, vp, total_pages, nkv, 1, nullptr, st);
-        pk = KvPack{kp, vp};
-    }
-    const float scale = 1.0f / sqrtf((float)MTTS_HD);
-    if (launch_attn(dev_q, kc, vc, pt, meta, scores, stats, opart, outp, MTTS_MAXR, pages_bound, max_pages, total_pages, nch, nq, nkv,
-                    scale, nullptr, 0, st, pk.k ? &pk : nullptr))
-        return fail(MTTS_EINVAL, "attention group size not built (1, 2, 4)");
-    launch_unpack_rows(outp, dev_out, R, nq * MTTS_HD, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return MTTS_OK;
-}
-
-// Test hook for the sealed page format (attn.hip: seal_lane): `npages` bf16 pages of 16 KiB -> sealed pages of 13 KiB.
-extern "C" int32_t mtts_k_kv_seal(const void* dev_pages, int32_t npages, void* dev_sealed, int32_t as_k, void* stream) {
-    if (!dev_pages || !dev_sealed || npages < 1) return fail(MTTS_EINVAL, "kv_seal: bad argument");
-    launch_kv_seal_pages(dev_pages, dev_sealed, npages, as_k, S(stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(S(stream)));
-    return MTTS_OK;
-}
-
-// Debug hook: out6 = {complete K pages of the live sequences (x kv heads x layers), of which not sealed (a lane did not
-// fit: read as bf16), the same two numbers for V, layers whose K / V reads currently use the sealed pages}.
-// MTTS_ESTATE when the engine runs without sealed pages.
-extern "C" int32_t mtts_debug_kv_pack_stats(MttsEngine* e, int64_t* out6) {
-    if (!e || !out6) return fail(MTTS_EINVAL, "null argument");
-    if (!e->kpack) return fail(MTTS_ESTATE, "the engine keeps no sealed pages (fp32 / fp16 engine, or MTTS_KV_PACK=0)");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<SeqState> ss(MTTS_RCAP);
-    HIPCHK(hipMemcpy(ss.data(), e->d_seqs, ss.size() * sizeof(SeqState), hipMemcpyDeviceToHost));
-    std::vector<int32_t> complete(e->B, 0);
-    for (int b = 0; b < e->B; ++b)
-        if (e->slot_live[b]) complete[b] = std::min(ss[b].kv_len >> 6, e->n_pages[b]);
-    HookBufs hb;
-    int32_t* dc = nullptr; unsigned long long* dout = nullptr;
-    TRY(hb.get(&dc, e->B)); TRY(hb.get(&dout, 4));
-    HIPCHK(hipMemcpy(dc, complete.data(), e->B * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dout, 0, 32));
-    launch_kv_pack_count(e->kpack, e->vpack, e->d_page_table, dc, e->B, e->max_pages, e->total_pages, e->nkv, e->L, dout, nullptr);
-    HIPCHK(hipGetLastError());
-    unsigned long long h[4];
-    HIPCHK(hipMemcpy(h, dout, 32, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 4; ++i) out6[i] = (int64_t)h[i];
-    out6[4] = out6[5] = 0;
-    for (int n = 0; n < e->L; ++n) { out6[4] += e->pack_k_on[n]; out6[5] += e->pack_v_on[n]; }
-    return MTTS_OK;
-}
-
-// Measurement hook (bench/profiling only): pretend every live sequence already holds `kv_len` tokens.
-// The cache content is whatever the pages hold; used to reach a long context without replaying it
-// when collecting PMC counters.
-extern "C" int32_t mtts_debug_set_kv_len(MttsEngine* e, int32_t kv_len) {
-    if (!e || !e->began) return fail(MTTS_ESTATE, "mtts_begin has not run");
-    if (e->f32) return fail(MTTS_EINVAL, "measurement hook of the bf16 engine");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipDeviceSynchronize());
-    const int cap = std::min(e->max_pages * MTTS_PAGE, e->rope_rows);          // positions the pages and the RoPE table hold
-    const int limit = cap - MTTS_PAGE;
-    if (kv_len < 1 || kv_len > limit) return fail(MTTS_EINVAL, "kv_len %d outside 1..%d", kv_len, limit);
-    e->max_steps = std::min(e->max_steps, e->steps_issued + cap - kv_len);   // stay inside the pages and the RoPE table
-    std::vector<SeqState> ss(MTTS_RCAP);
-    HIPCHK(hipMemcpy(ss.data(), e->d_seqs, ss.size() * sizeof(SeqState), hipMemcpyDeviceToHost));
-    for (int b = 0; b < e->B; ++b) { ss[b].kv_len = kv_len; e->n_real[b] = kv_len - e->steps_issued; }
-    e->max_real = kv_len - e->steps_issued;
-    HIPCHK(hipMemcpy(e->d_seqs, ss.data(), ss.size() * sizeof(SeqState), hipMemcpyHostToDevice));
-    launch_fill_random_bf16(e->kcache, e->layer_stride * e->L, 0x1234u, nullptr);
-    launch_fill_random_bf16(e->vcache, e->layer_stride * e->L, 0x9876u, nullptr);
-    if (e->kpack) launch_kv_seal_all(e->kcache, e->vcache, e->kpack, e->vpack, e->total_pages, e->nkv, e->L, nullptr, nullptr);
-    HIPCHK(hipDeviceSynchronize());
-    return MTTS_OK;
-}
-
-// Measurement hook: `iters` back-to-back launches of one attention pass (phase 1 = scores, 2 = PV) at the
-// engine's CURRENT decode state, cycling over the layers' caches; average duration from two HIP events on the
-// launch stream.  (Events around a single launch also time the launch gap, which rocprof's kernel duration
-// does not; a train of launches does not have that bias.)
-extern "C" int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* avg_ms, int64_t* bytes_per_launch) {
-    if (!e || !e->began || (phase != 1 && phase != 2) || iters < 1 || !avg_ms) return fail(MTTS_EINVAL, "attn_bench: bad argument");
-    if (e->f32) return fail(MTTS_EINVAL, "measurement hook of the bf16 engine");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipDeviceSynchronize());
-    const float scale = 1.0f / sqrtf((float)MTTS_HD);
-    const int R = round_up(e->B, 32);
-    const int len_bound = e->max_real + e->steps_issued + 1;
-    const int pages_bound = (len_bound + MTTS_PAGE - 1) / MTTS_PAGE;
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    auto run = [&](int n) {
-        for (int i = 0; i < n; ++i) {
-            const int layer = i % e->L;
-            uint16_t* kc = (uint16_t*)e->kcache + e->layer_stride * layer;
-            uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * layer;
-            // the product's decode launch: q/k/v epilogue fused (the slabs are whatever the last step left there)
-            const QkvFuse fz{e->partial, e->p_qkv.ksplit, e->qkv_rows, (const uint16_t*)e->layers[layer].qn,
-                             (const uint16_t*)e->layers[layer].kn, (const uint16_t*)e->rope_cos, (const uint16_t*)e->rope_sin,
-                             e->cfg.rms_norm_eps};
-            const KvPack pk = layer_pack(e, layer, pages_bound);
-            launch_attn(e->qbuf, kc, vc, e->d_page_table, e->d_meta, e->scores, e->stats, e->opart, e->attn_p, R, pages_bound,
-                        e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale, e->B * pages_bound <= e->fuse_qkv_max ? &fz : nullptr, phase, nullptr,
-                        (pk.k || pk.v) ? &pk : nullptr);
-        }
-    };
-    run(e->L);                               // warm-up
-    hipEventRecord(e0, nullptr);
-    run(iters);
-    hipEventRecord(e1, nullptr);
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = ms / iters;
-    if (bytes_per_launch) {
-        std::vector<RowMeta> m(MTTS_RCAP);
-        HIPCHK(hipMemcpy(m.data(), e->d_meta, m.size() * sizeof(RowMeta), hipMemcpyDeviceToHost));
-        int64_t tok = 0;
-        for (int b = 0; b < R; ++b) if (m[b].seq >= 0) tok += m[b].pos + 1;
-        *bytes_per_launch = tok * e->nkv * MTTS_HD * 2;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    return MTTS_OK;
-}
-
-// Tuning hook (not part of the product path): average time of one skinny-GEMM launch over `copies`
-// distinct weight buffers (so that no launch finds its weights in L2 / Infinity Cache).
-extern "C" int32_t mtts_k_gemm_bench(int32_t N, int32_t K, int32_t epi, int32_t ksplit, int32_t waves, int32_t copies,
-                                     int32_t iters, float* avg_us) {
-    if (N % 32 || K % 16 || copies < 1 || iters < 1 || !avg_us) return fail(MTTS_EINVAL, "gemm_bench: bad argument");
-    // waves < 0: the tiled prefill kernel on -waves rows (<= MTTS_PFCAP), split-K as given
-    const int tile_rows = waves < 0 ? -waves : 0;
-    if (tile_rows > MTTS_PFCAP) return fail(MTTS_EINVAL, "gemm_bench: at most MTTS_PFCAP rows");
-    GemmPlan p = (ksplit > 0 && waves > 0) ? mtts_plan_gemm_forced(N, K, ksplit, waves) : mtts_plan_gemm(N, K, tile_rows ? std::max(ksplit, 1) : ksplit);
-    if (tile_rows) p.ksplit = std::max(ksplit, 1);
-    p.depth = gemm_depth_env();
-    std::vector<uint16_t*> w(copies, nullptr);
-    for (auto& q : w) { TRY(dalloc(&q, (size_t)N * K, false)); HIPCHK(hipMemset(q, 0x3c, (size_t)N * K * 2)); }
-    uint16_t *x = nullptr, *out = nullptr;
-    float* part = nullptr;
-    TRY(dalloc(&x, (size_t)MTTS_PFCAP * K, false));
-    HIPCHK(hipMemset(x, 0x3c, (size_t)MTTS_PFCAP * K * 2));
-    TRY(dalloc(&out, (size_t)MTTS_PFCAP * N));
-    TRY(dalloc(&part, (size_t)p.ksplit * MTTS_PFCAP * N));
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    auto go = [&](int i) {
-        if (tile_rows) launch_gemm_tile(epi, tile_rows, p.ksplit, w[i % copies], x, K, N, N, part, out, nullptr);
-        else launch_gemm(epi, 1, p, w[i % copies], x, K, N, N, part, out, nullptr);
-    };
-    for (int i = 0; i < copies; ++i) go(i);
-    HIPCHK(hipDeviceSynchronize());
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters; ++i) go(i);
-    hipEventRecord(e1, nullptr);
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    hipEventElapsedTime(&ms, e0, e1);
-    *avg_us = ms * 1000.f / iters;
-    for (auto q : w) hipFree(q);
-    hipFree(x); hipFree(out); hipFree(part);
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    return MTTS_OK;
-}

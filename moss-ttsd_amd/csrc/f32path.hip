@@ -19,7 +19,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 
 __device__ __forceinline__ float r16(float v, int h16) { return h16 ? __half2float(__float2half_rn(v)) : v; }
 
@@ -225,7 +225,6 @@ void launch_f32_resid_norm(const float* y, float* x, const float* norm_w, float*
                            int H, float eps, int h16, hipStream_t st) {
     hipLaunchKernelGGL(f32_resid_norm_kernel, dim3(R), dim3(256), 0, st, y, x, norm_w, xn, hlast, meta, H, eps, h16);
 }
-void mtts_gemm_f32_exact(hipStream_t st, const float* A, const float* W, float* C, int M, int N, int K, long ldc);   // codec.hip
 // Decode rows (one dialogue each; `gemv`) go through the GEMV kernel 8 rows per launch whatever the batch size, prefill
 // passes through the exact-f32 MFMA GEMM whatever their row count: which kernel -- hence which fp32 summation order -- a
 // dialogue's numbers come from must not depend on how many other dialogues share its batch.

@@ -10,9 +10,8 @@
 // owns one 32-row N-tile; its waves split the K range and reduce through LDS.
 // With v_mfma_f32_32x32x16_bf16, A = W tile (32 n x 16 k), B = X^T (16 k x 32
 // rows): D[n][row], lane holds column `row = lane&31` and 16 n values.
-#include "common.h"
+#include "launch.h"
 
-enum { EPI_PARTIAL = 0, EPI_BF16 = 1, EPI_SILU = 2 };
 
 // grid = (N/32, ksplit); block = WAVES*64.  MB = row tiles (of 32) that share the weight stream.
 // kt_per_split: k-tiles (of 16) per blockIdx.y; kt_per_wave: per wave inside that.
@@ -250,7 +249,6 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_gateup48_kernel(
 // the small path gives the same bits as the general path (tested).  MFMA lanes whose row is >= SMALL_RP feed zeros.
 // grid = (N/32, ksplit), block = WAVES*64 (WAVES 4 or 8: the norm prologue works in groups of 256 threads).
 // ---------------------------------------------------------------------------------------------------
-enum { EPI_SILU_RM = 3 };      // SwiGLU, row-major bf16 [rows][N/2] output
 
 template <int WAVES, int EPI, int PRO>
 __global__ __launch_bounds__(WAVES * 64, 4) void gemv_small_kernel(
@@ -600,11 +598,6 @@ __global__ void reduce_partial_bf16_kernel(const float* __restrict__ partial, ui
     for (int k = 0; k < ksplit; ++k) s += partial[((size_t)k * MTTS_PFCAP + r) * Npad + n];
     out[idx] = f2bf(s);
 }
-
-struct GemmPlan {
-    int waves, ksplit, kt_per_split, kt_per_wave;
-    int depth;      // 1: launch_gemm may take a depth-specialised kernel where the shape has one (0: MTTS_GEMM_DEPTH=0)
-};
 
 // Choose the decomposition so that the grid is >= ~256 blocks where the shape allows
 // and every wave gets >= 4 k-tiles.

@@ -1,0 +1,361 @@
+// Per-kernel entry points of libmtts.so for the unit tests, and the measurement / debug hooks of bench.py and the tools
+// (mtts_k_*, mtts_debug_*: include/mtts.h).  None of them is on the product path.  A hook's device buffers live in a
+// DevBufs of its own: freed on every return path.
+#include "engine.h"
+
+int32_t mtts_k_gemm_bf16(const void* w, const void* x, void* y, int32_t M, int32_t N, int32_t K, int32_t ksplit, void* stream) {
+    if (!w || !x || !y || M < 1 || M > MTTS_PFCAP || K % 16 || N < 1) return fail(MTTS_EINVAL, "gemm: need 1<=M<=MTTS_PFCAP, K%%16==0");
+    hipStream_t st = S(stream);
+    int Npad = round_up(N, 32);
+    void *wp = nullptr, *xp = nullptr;
+    float* part = nullptr;
+    GemmPlan p = mtts_plan_gemm(Npad, K, ksplit);
+    p.depth = gemm_depth_env();
+    DevBufs hb;
+    TRY(hb.get((uint16_t**)&wp, (size_t)Npad * K));
+    // M <= 128: skinny kernel (decode); above: tiled kernel (prefill), ksplit as given or its own choice
+    const bool tiled = M > MTTS_RCAP;
+    const int ks = tiled ? (ksplit > 0 ? ksplit : mtts_tile_ksplit(Npad, K, M)) : p.ksplit;
+    TRY(hb.get((uint16_t**)&xp, (size_t)MTTS_PFCAP * K));
+    TRY(hb.get(&part, (size_t)ks * MTTS_PFCAP * Npad));
+    launch_pack_weight(w, wp, N, K, Npad, 1, 0, st);
+    const int tiles = (M + 31) / 32;
+    launch_pack_rows(x, xp, M, K, tiles == 3 ? 4 : tiles, st);
+    if (tiled) launch_gemm_tile(EPI_PARTIAL, M, ks, wp, xp, K, Npad, Npad, part, nullptr, st);
+    else launch_gemm(EPI_PARTIAL, tiles, p, wp, xp, K, Npad, Npad, part, nullptr, st);
+    launch_reduce_partial_bf16(part, y, ks, Npad, N, M, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+int64_t mtts_debug_gemm_depth_launches(void) { return (int64_t)mtts_gemm_depth_launches(); }
+int32_t mtts_k_gemm_swiglu_bf16(const void* w, const void* x, void* y, int32_t M, int32_t N, int32_t K, void* stream) {
+    if (!w || !x || !y || M < 1 || M > MTTS_RCAP || K % 16 || N < 32 || N % 32) return fail(MTTS_EINVAL, "gemm_swiglu: need 1<=M<=128, K%%16==0, N%%32==0");
+    hipStream_t st = S(stream);
+    void *wp = nullptr, *xp = nullptr, *op = nullptr;
+    GemmPlan p = mtts_plan_gemm(N, K, 1);          // as the engine plans gate/up: no split-K
+    p.depth = gemm_depth_env();
+    DevBufs hb;
+    const int tiles = (M + 31) / 32, tp = tiles == 3 ? 4 : tiles;
+    TRY(hb.get((uint16_t**)&wp, (size_t)N * K));
+    TRY(hb.get((uint16_t**)&xp, (size_t)tp * 32 * K));
+    TRY(hb.get((uint16_t**)&op, (size_t)tp * 32 * (N / 2)));
+    launch_pack_weight(w, wp, N, K, N, 1, 0, st);
+    launch_pack_rows(x, xp, M, K, tp, st);
+    launch_gemm(EPI_SILU, tiles, p, wp, xp, K, N, N, nullptr, (uint16_t*)op, st);
+    launch_unpack_rows(op, y, M, N / 2, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+int32_t mtts_k_rmsnorm(const void* x, const void* w, void* y, int32_t rows, int32_t n, float eps, void* stream) {
+    if (!x || !w || !y || rows < 1 || n < 1) return fail(MTTS_EINVAL, "rmsnorm: bad argument");
+    launch_rmsnorm_rows(x, w, y, rows, n, eps, S(stream));
+    HIPCHK(hipGetLastError());
+    return MTTS_OK;
+}
+
+static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                    int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp, void* stream) {
+    if (!logits || !cfg || !dev_tokens || rows < 1 || vocab < 1 || channel < 0 || channel > 7) return fail(MTTS_EINVAL, "sample: bad argument");
+    hipStream_t st = S(stream);
+    MttsSamplerCfg h[8];
+    for (int i = 0; i < 8; ++i) h[i] = *cfg;
+    MttsSamplerCfg* d = nullptr;
+    int32_t *err = nullptr, *dec = nullptr;
+    if (rows > MTTS_RCAP) return fail(MTTS_EINVAL, "sample: at most 128 rows");
+    DevBufs hb;
+    TRY(hb.get(&d, 8));
+    TRY(hb.get(&err, 1));
+    TRY(hb.get(&dec, (size_t)rows * 8));
+    HIPCHK(hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice));
+    SampleScratch sc;
+    TRY(alloc_scratch(hb, sc, rows, vocab));
+    if (dev_logp) TRY(alloc_lp_scratch(hb, sc, rows));
+    launch_sample_single(logits, rows, vocab, (const uint32_t*)bitmap, (vocab + 31) / 32, d, mask_id, seed, step, channel, dec, err, sc,
+                         full_cap_for(vocab), dev_logp ? 1 : 0, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int32_t> hd((size_t)rows * 8);
+    int32_t herr = 0;
+    HIPCHK(hipMemcpy(hd.data(), dec, hd.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&herr, err, 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> outv(rows);
+    for (int r = 0; r < rows; ++r) outv[r] = hd[(size_t)r * 8 + channel];
+    HIPCHK(hipMemcpy(dev_tokens, outv.data(), rows * 4, hipMemcpyHostToDevice));
+    if (dev_logp) {
+        std::vector<float> hl((size_t)rows * 8), outl(rows);
+        HIPCHK(hipMemcpy(hl.data(), sc.lp, hl.size() * 4, hipMemcpyDeviceToHost));
+        for (int r = 0; r < rows; ++r) outl[r] = hl[(size_t)r * 8 + channel];
+        HIPCHK(hipMemcpy(dev_logp, outl.data(), rows * 4, hipMemcpyHostToDevice));
+    }
+    if (herr) return fail(MTTS_EINVAL, "sample: more than 4096 candidate tokens");
+    return MTTS_OK;
+}
+
+int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                      int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, void* stream) {
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, stream);
+}
+
+int32_t mtts_k_sample_scores(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                             int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
+                             void* stream) {
+    if (!dev_logp) return fail(MTTS_EINVAL, "sample: null dev_logp");
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, stream);
+}
+
+// ---- per-kernel entry points for attention and RoPE / cache write (unit tests) ----------------------------------------
+
+// q/k/v epilogue of one token per row (qkv_post_kernel): dev_qkv bf16 [R][(nq+2*nkv)*128] = the three Linears' outputs,
+// host_pos int32 [R] positions, dev_qnorm / dev_knorm bf16 [128], dev_cos / dev_sin bf16 [rope_rows][64].
+// Outputs bf16: dev_q [R][nq][128] (normed + rotated), dev_k [R][nkv][128] (normed + rotated, read back from the K page it was
+// written to), dev_v [R][nkv][128] (read back from the V page).  Every row is its own sequence (page table = one page each).
+int32_t mtts_k_rope_kvwrite(const void* dev_qkv, const int32_t* host_pos, const void* dev_qnorm, const void* dev_knorm,
+                            const void* dev_cos, const void* dev_sin, int32_t R, int32_t nq, int32_t nkv, float eps,
+                            void* dev_q, void* dev_k, void* dev_v, void* stream) {
+    if (!dev_qkv || !host_pos || !dev_q || !dev_k || !dev_v || R < 1 || R > MTTS_RCAP || nq < 1 || nkv < 1) return fail(MTTS_EINVAL, "rope_kvwrite: bad argument");
+    hipStream_t st = S(stream);
+    const int N = (nq + 2 * nkv) * MTTS_HD;
+    int maxpos = 0;
+    for (int r = 0; r < R; ++r) { if (host_pos[r] < 0) return fail(MTTS_EINVAL, "negative position"); maxpos = std::max(maxpos, host_pos[r]); }
+    const int max_pages = maxpos / MTTS_PAGE + 1, total_pages = R * max_pages;
+    float* slab = nullptr; RowMeta* meta = nullptr; int32_t* pt = nullptr; uint16_t *kc = nullptr, *vc = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&slab, (size_t)MTTS_PFCAP * N));
+    TRY(hb.get(&meta, R)); TRY(hb.get(&pt, (size_t)R * max_pages));
+    TRY(hb.get(&kc, (size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD)); TRY(hb.get(&vc, (size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD));
+    std::vector<RowMeta> hm(R);
+    std::vector<int32_t> hpt((size_t)R * max_pages);
+    for (int r = 0; r < R; ++r) { hm[r] = RowMeta{r, host_pos[r], 1, 0}; for (int p = 0; p < max_pages; ++p) hpt[(size_t)r * max_pages + p] = r * max_pages + p; }
+    HIPCHK(hipMemcpy(meta, hm.data(), R * sizeof(RowMeta), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(pt, hpt.data(), hpt.size() * 4, hipMemcpyHostToDevice));
+    launch_bf16_to_f32(dev_qkv, slab, (size_t)R * N, st);
+    launch_qkv_post(slab, 1, N, meta, dev_qnorm, dev_knorm, dev_cos, dev_sin, dev_q, kc, vc, pt, max_pages, total_pages, R, nq, nkv, eps, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    // read the written K / V rows back out of their pages
+    std::vector<uint16_t> hk((size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD), hv(hk.size()), ok((size_t)R * nkv * MTTS_HD), ov(ok.size());
+    HIPCHK(hipMemcpy(hk.data(), kc, hk.size() * 2, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hv.data(), vc, hv.size() * 2, hipMemcpyDeviceToHost));
+    for (int r = 0; r < R; ++r)
+        for (int h = 0; h < nkv; ++h)
+            for (int d = 0; d < MTTS_HD; ++d) {
+                const int page = r * max_pages + host_pos[r] / MTTS_PAGE, t = host_pos[r] % MTTS_PAGE;
+                const size_t base = ((size_t)h * total_pages + page) * (MTTS_PAGE * MTTS_HD);
+                ok[((size_t)r * nkv + h) * MTTS_HD + d] = hk[base + (((d >> 3) * 64) + t) * 8 + (d & 7)];
+                ov[((size_t)r * nkv + h) * MTTS_HD + d] = hv[base + ((size_t)(t >> 1) * MTTS_HD + d) * 2 + (t & 1)];
+            }
+    HIPCHK(hipMemcpy(dev_k, ok.data(), ok.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dev_v, ov.data(), ov.size() * 2, hipMemcpyHostToDevice));
+    return MTTS_OK;
+}
+
+// Decode attention of one query token per row over a paged cache (attn_scores / attn_pv / attn_combine, the launches of
+// a decode step): dev_q bf16 [R][nq][128]; dev_k / dev_v bf16 [R][Lmax][nkv][128] row-major (row r uses its first
+// host_lens[r] tokens; its query sits at position host_lens[r]-1); host_page_table int32 [R][pages] with
+// pages = ceil(Lmax/64): any permutation of 0..R*pages-1 (NULL = consecutive).  dev_out bf16 [R][nq*128].
+int32_t mtts_k_paged_attn_decode(const void* dev_q, const void* dev_k, const void* dev_v, const int32_t* host_lens,
+                                 const int32_t* host_page_table, int32_t R, int32_t Lmax, int32_t nq, int32_t nkv,
+                                 void* dev_out, void* stream) {
+    if (!dev_q || !dev_k || !dev_v || !host_lens || !dev_out || R < 1 || R > MTTS_MAXR || Lmax < 1 || nq < 1 || nkv < 1 || nq % nkv)
+        return fail(MTTS_EINVAL, "paged_attn_decode: bad argument (1..32 rows)");
+    hipStream_t st = S(stream);
+    const int max_pages = (Lmax + MTTS_PAGE - 1) / MTTS_PAGE, total_pages = R * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
+    std::vector<int32_t> hpt((size_t)R * max_pages);
+    std::vector<char> seen(total_pages, 0);
+    for (size_t i = 0; i < hpt.size(); ++i) {
+        hpt[i] = host_page_table ? host_page_table[i] : (int32_t)i;
+        if (hpt[i] < 0 || hpt[i] >= total_pages || seen[hpt[i]]) return fail(MTTS_EINVAL, "page table must be a permutation of 0..%d", total_pages - 1);
+        seen[hpt[i]] = 1;
+    }
+    std::vector<RowMeta> hm(MTTS_MAXR, RowMeta{-1, 0, 0, 0});
+    int pages_bound = 1;
+    for (int r = 0; r < R; ++r) {
+        if (host_lens[r] < 1 || host_lens[r] > Lmax) return fail(MTTS_EINVAL, "row %d: length %d outside 1..%d", r, host_lens[r], Lmax);
+        hm[r] = RowMeta{r, host_lens[r] - 1, 1, 0};
+        pages_bound = std::max(pages_bound, (host_lens[r] + MTTS_PAGE - 1) / MTTS_PAGE);
+    }
+    RowMeta* meta = nullptr; int32_t *pt = nullptr, *lens = nullptr; uint16_t *kc = nullptr, *vc = nullptr, *scores = nullptr, *outp = nullptr;
+    float *stats = nullptr, *opart = nullptr;
+    const size_t cache_n = (size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD;
+    DevBufs hb;
+    TRY(hb.get(&meta, MTTS_MAXR)); TRY(hb.get(&pt, hpt.size())); TRY(hb.get(&lens, R));
+    TRY(hb.get(&kc, cache_n)); TRY(hb.get(&vc, cache_n));
+    TRY(hb.get(&scores, (size_t)MTTS_MAXR * nq * max_pages * MTTS_PAGE));
+    TRY(hb.get(&stats, (size_t)MTTS_MAXR * nq * max_pages * 2));
+    TRY(hb.get(&opart, (size_t)MTTS_MAXR * nq * nch * MTTS_HD));
+    TRY(hb.get(&outp, (size_t)MTTS_MAXR * nq * MTTS_HD));
+    HIPCHK(hipMemcpy(meta, hm.data(), hm.size() * sizeof(RowMeta), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(pt, hpt.data(), hpt.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(lens, host_lens, R * 4, hipMemcpyHostToDevice));
+    launch_pack_kv_pages(dev_k, dev_v, kc, vc, pt, lens, R, Lmax, nkv, max_pages, total_pages, st);
+    // like the engine: complete pages are read in their sealed form unless MTTS_KV_PACK=0
+    KvPack pk{nullptr, nullptr};
+    const char* g = getenv("MTTS_KV_PACK");
+    if (!g || atoi(g) != 0) {
+        uint8_t *kp = nullptr, *vp = nullptr;
+        const size_t pk_n = (size_t)total_pages * nkv * MTTS_PKU * 64 * 16;
+        TRY(hb.get(&kp, pk_n)); TRY(hb.get(&vp, pk_n));
+        launch_kv_seal_all(kc, vc, kp, vp, total_pages, nkv, 1, nullptr, st);
+        pk = KvPack{kp, vp};
+    }
+    const float scale = 1.0f / sqrtf((float)MTTS_HD);
+    if (launch_attn(dev_q, kc, vc, pt, meta, scores, stats, opart, outp, MTTS_MAXR, pages_bound, max_pages, total_pages, nch, nq, nkv,
+                    scale, nullptr, ATTN_ALL, st, pk.k ? &pk : nullptr))
+        return fail(MTTS_EINVAL, "attention group size not built (1, 2, 4)");
+    launch_unpack_rows(outp, dev_out, R, nq * MTTS_HD, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+// Test hook for the sealed page format (attn.hip: seal_lane): `npages` bf16 pages of 16 KiB -> sealed pages of 13 KiB.
+int32_t mtts_k_kv_seal(const void* dev_pages, int32_t npages, void* dev_sealed, int32_t as_k, void* stream) {
+    if (!dev_pages || !dev_sealed || npages < 1) return fail(MTTS_EINVAL, "kv_seal: bad argument");
+    launch_kv_seal_pages(dev_pages, dev_sealed, npages, as_k, S(stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(S(stream)));
+    return MTTS_OK;
+}
+
+// Debug hook: out6 = {complete K pages of the live sequences (x kv heads x layers), of which not sealed (a lane did not
+// fit: read as bf16), the same two numbers for V, layers whose K / V reads currently use the sealed pages}.
+// MTTS_ESTATE when the engine runs without sealed pages.
+int32_t mtts_debug_kv_pack_stats(MttsEngine* e, int64_t* out6) {
+    if (!e || !out6) return fail(MTTS_EINVAL, "null argument");
+    if (!e->kpack) return fail(MTTS_ESTATE, "the engine keeps no sealed pages (fp32 / fp16 engine, or MTTS_KV_PACK=0)");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<SeqState> ss(MTTS_RCAP);
+    HIPCHK(hipMemcpy(ss.data(), e->d_seqs, ss.size() * sizeof(SeqState), hipMemcpyDeviceToHost));
+    std::vector<int32_t> complete(e->B, 0);
+    for (int b = 0; b < e->B; ++b)
+        if (e->slot_live[b]) complete[b] = std::min(ss[b].kv_len >> 6, e->n_pages[b]);
+    DevBufs hb;
+    int32_t* dc = nullptr; unsigned long long* dout = nullptr;
+    TRY(hb.get(&dc, e->B)); TRY(hb.get(&dout, 4));
+    HIPCHK(hipMemcpy(dc, complete.data(), e->B * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dout, 0, 32));
+    launch_kv_pack_count(e->kpack, e->vpack, e->d_page_table, dc, e->B, e->max_pages, e->total_pages, e->nkv, e->L, dout, nullptr);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[4];
+    HIPCHK(hipMemcpy(h, dout, 32, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) out6[i] = (int64_t)h[i];
+    out6[4] = out6[5] = 0;
+    for (int n = 0; n < e->L; ++n) { out6[4] += e->pack_k_on[n]; out6[5] += e->pack_v_on[n]; }
+    return MTTS_OK;
+}
+
+// Measurement hook (bench/profiling only): pretend every live sequence already holds `kv_len` tokens.
+// The cache content is whatever the pages hold; used to reach a long context without replaying it
+// when collecting PMC counters.
+int32_t mtts_debug_set_kv_len(MttsEngine* e, int32_t kv_len) {
+    if (!e || !e->began) return fail(MTTS_ESTATE, "mtts_begin has not run");
+    if (e->f32) return fail(MTTS_EINVAL, "measurement hook of the bf16 engine");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());
+    const int cap = std::min(e->max_pages * MTTS_PAGE, e->rope_rows);          // positions the pages and the RoPE table hold
+    const int limit = cap - MTTS_PAGE;
+    if (kv_len < 1 || kv_len > limit) return fail(MTTS_EINVAL, "kv_len %d outside 1..%d", kv_len, limit);
+    e->max_steps = std::min(e->max_steps, e->steps_issued + cap - kv_len);   // stay inside the pages and the RoPE table
+    std::vector<SeqState> ss(MTTS_RCAP);
+    HIPCHK(hipMemcpy(ss.data(), e->d_seqs, ss.size() * sizeof(SeqState), hipMemcpyDeviceToHost));
+    for (int b = 0; b < e->B; ++b) { ss[b].kv_len = kv_len; e->n_real[b] = kv_len - e->steps_issued; }
+    e->max_real = kv_len - e->steps_issued;
+    HIPCHK(hipMemcpy(e->d_seqs, ss.data(), ss.size() * sizeof(SeqState), hipMemcpyHostToDevice));
+    launch_fill_random_bf16(e->kcache, e->layer_stride * e->L, 0x1234u, nullptr);
+    launch_fill_random_bf16(e->vcache, e->layer_stride * e->L, 0x9876u, nullptr);
+    if (e->kpack) launch_kv_seal_all(e->kcache, e->vcache, e->kpack, e->vpack, e->total_pages, e->nkv, e->L, nullptr, nullptr);
+    HIPCHK(hipDeviceSynchronize());
+    return MTTS_OK;
+}
+
+// Measurement hook: `iters` back-to-back launches of one attention pass (phase 1 = scores, 2 = PV) at the
+// engine's CURRENT decode state, cycling over the layers' caches; average duration from two HIP events on the
+// launch stream.  (Events around a single launch also time the launch gap, which rocprof's kernel duration
+// does not; a train of launches does not have that bias.)
+int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* avg_ms, int64_t* bytes_per_launch) {
+    if (!e || !e->began || (phase != ATTN_SCORES && phase != ATTN_PV) || iters < 1 || !avg_ms) return fail(MTTS_EINVAL, "attn_bench: bad argument");
+    if (e->f32) return fail(MTTS_EINVAL, "measurement hook of the bf16 engine");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());
+    const float scale = 1.0f / sqrtf((float)MTTS_HD);
+    const int R = round_up(e->B, 32);
+    const int len_bound = e->max_real + e->steps_issued + 1;
+    const int pages_bound = (len_bound + MTTS_PAGE - 1) / MTTS_PAGE;
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    auto run = [&](int n) {
+        for (int i = 0; i < n; ++i) {
+            const int layer = i % e->L;
+            uint16_t* kc = (uint16_t*)e->kcache + e->layer_stride * layer;
+            uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * layer;
+            // the product's decode launch: q/k/v epilogue fused (the slabs are whatever the last step left there)
+            const QkvFuse fz{e->partial, e->p_qkv.ksplit, e->qkv_rows, (const uint16_t*)e->layers[layer].qn,
+                             (const uint16_t*)e->layers[layer].kn, e->rope_cos, e->rope_sin, e->cfg.rms_norm_eps};
+            const KvPack pk = layer_pack(e, layer, pages_bound);
+            launch_attn(e->qbuf, kc, vc, e->d_page_table, e->d_meta, e->scores, e->stats, e->opart, e->attn_p, R, pages_bound,
+                        e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale, e->B * pages_bound <= e->fuse_qkv_max ? &fz : nullptr, (AttnPhase)phase, nullptr,
+                        (pk.k || pk.v) ? &pk : nullptr);
+        }
+    };
+    run(e->L);                               // warm-up
+    hipEventRecord(e0, nullptr);
+    run(iters);
+    hipEventRecord(e1, nullptr);
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    *avg_ms = ms / iters;
+    if (bytes_per_launch) {
+        std::vector<RowMeta> m(MTTS_RCAP);
+        HIPCHK(hipMemcpy(m.data(), e->d_meta, m.size() * sizeof(RowMeta), hipMemcpyDeviceToHost));
+        int64_t tok = 0;
+        for (int b = 0; b < R; ++b) if (m[b].seq >= 0) tok += m[b].pos + 1;
+        *bytes_per_launch = tok * e->nkv * MTTS_HD * 2;
+    }
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    return MTTS_OK;
+}
+
+// Tuning hook (not part of the product path): average time of one skinny-GEMM launch over `copies`
+// distinct weight buffers (so that no launch finds its weights in L2 / Infinity Cache).
+int32_t mtts_k_gemm_bench(int32_t N, int32_t K, int32_t epi, int32_t ksplit, int32_t waves, int32_t copies,
+                                     int32_t iters, float* avg_us) {
+    if (N % 32 || K % 16 || copies < 1 || iters < 1 || !avg_us) return fail(MTTS_EINVAL, "gemm_bench: bad argument");
+    // waves < 0: the tiled prefill kernel on -waves rows (<= MTTS_PFCAP), split-K as given
+    const int tile_rows = waves < 0 ? -waves : 0;
+    if (tile_rows > MTTS_PFCAP) return fail(MTTS_EINVAL, "gemm_bench: at most MTTS_PFCAP rows");
+    GemmPlan p = (ksplit > 0 && waves > 0) ? mtts_plan_gemm_forced(N, K, ksplit, waves) : mtts_plan_gemm(N, K, tile_rows ? std::max(ksplit, 1) : ksplit);
+    if (tile_rows) p.ksplit = std::max(ksplit, 1);
+    p.depth = gemm_depth_env();
+    DevBufs hb;
+    std::vector<uint16_t*> w(copies, nullptr);
+    for (auto& q : w) { TRY(hb.get(&q, (size_t)N * K, false)); HIPCHK(hipMemset(q, 0x3c, (size_t)N * K * 2)); }
+    uint16_t *x = nullptr, *out = nullptr;
+    float* part = nullptr;
+    TRY(hb.get(&x, (size_t)MTTS_PFCAP * K, false));
+    HIPCHK(hipMemset(x, 0x3c, (size_t)MTTS_PFCAP * K * 2));
+    TRY(hb.get(&out, (size_t)MTTS_PFCAP * N));
+    TRY(hb.get(&part, (size_t)p.ksplit * MTTS_PFCAP * N));
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    auto go = [&](int i) {
+        if (tile_rows) launch_gemm_tile(epi, tile_rows, p.ksplit, w[i % copies], x, K, N, N, part, out, nullptr);
+        else launch_gemm(epi, 1, p, w[i % copies], x, K, N, N, part, out, nullptr);
+    };
+    for (int i = 0; i < copies; ++i) go(i);
+    HIPCHK(hipDeviceSynchronize());
+    hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) go(i);
+    hipEventRecord(e1, nullptr);
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    *avg_us = ms * 1000.f / iters;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    return MTTS_OK;
+}

@@ -1,0 +1,151 @@
+// Host-side interface of the kernel files: the structs that cross between host and device code, and the one prototype
+// of every launcher that one .hip defines and another calls.  Included by the defining file as well as by its callers,
+// so a prototype or a layout cannot drift.  (common.h holds the device helpers and the structs kernels take as arguments.)
+#pragma once
+#include <type_traits>
+
+#include "../../include/mtts.h"
+#include "common.h"
+
+// ---- gemm.hip -------------------------------------------------------------------------------------------------------
+enum { EPI_PARTIAL = 0, EPI_BF16 = 1, EPI_SILU = 2,
+       EPI_SILU_RM = 3 };      // SwiGLU, row-major bf16 [rows][N/2] output (gemv_small_kernel only)
+struct GemmPlan {
+    int waves, ksplit, kt_per_split, kt_per_wave;
+    int depth;      // 1: launch_gemm may take a depth-specialised kernel where the shape has one (0: MTTS_GEMM_DEPTH=0)
+};
+GemmPlan mtts_plan_gemm(int Npad, int K, int want_ksplit);
+GemmPlan mtts_plan_gemm_forced(int Npad, int K, int ksplit, int waves);
+void launch_gemm(int epi, int mb, const GemmPlan& p, const void* Wp, const void* Xp, int K, int Npad, int n_valid,
+                 float* partial, uint16_t* out, hipStream_t st);
+int mtts_tile_ksplit(int Npad, int K, int R);
+void launch_gemm_tile(int epi, int R, int ksplit, const void* Wp, const void* Xp, int K, int Npad, int n_valid,
+                      float* partial, uint16_t* out, hipStream_t st);
+int mtts_small_lds_bytes(const GemmPlan& p, int K, int pro);
+void launch_gemv_small(int epi, int pro, const GemmPlan& p, const void* Wp, int K, int Npad, int n_valid, float* partial,
+                       uint16_t* out, const SmallPro& pr, hipStream_t st);
+long long mtts_gemm_depth_launches();
+void launch_pack_weight(const void* src, void* dst, int rows, int cols, int rows_pad, int row_mul, int row_off, hipStream_t st);
+void launch_pack_rows(const void* src, void* dst, int R, int K, int tiles, hipStream_t st);
+void launch_reduce_partial_bf16(const float* partial, void* out, int ksplit, int Npad, int n_valid, int R, hipStream_t st);
+
+// ---- layer.hip ------------------------------------------------------------------------------------------------------
+struct PageEdits { int32_t n; int32_t idx[31]; int32_t val[31]; };     // page-table entries handed over as launch arguments
+static_assert(sizeof(PageEdits) == 252, "PageEdits is a kernel argument: one 32-bit count + 31 (index, value) pairs");
+void launch_embed_norm(const int32_t* tokens, const RowMeta* meta, const uint16_t* const* tables, const void* norm_w,
+                       void* x, void* xn_packed, int R, int H, float eps, hipStream_t st);
+void launch_resid_norm(const float* partial, int ksplit, int Npad, void* x, const void* norm_w, void* xn_packed,
+                       void* hlast, const RowMeta* meta, int R, int H, float eps, hipStream_t st);
+void launch_qkv_post(const float* partial, int ksplit, int Npad, const RowMeta* meta, const void* qnw, const void* knw,
+                     const void* cosb, const void* sinb, void* qbuf, void* kcache, void* vcache,
+                     const int32_t* page_table, int max_pages, int total_pages, int R, int nq, int nkv, float eps,
+                     hipStream_t st);
+void launch_rmsnorm_rows(const void* x, const void* w, void* y, int rows, int n, float eps, hipStream_t st);
+void launch_fill_random_bf16(void* p, size_t n, uint32_t seed, hipStream_t st);
+void launch_set_pages(int32_t* table, const PageEdits& ed, hipStream_t st);
+void launch_fork(void* kc, void* vc, size_t layer_bytes, size_t head_bytes, int blk_bytes, int L, int nkv, const ForkJob& job,
+                 hipStream_t st);
+void launch_pack_kv_pages(const void* K, const void* V, void* kcache, void* vcache, const int32_t* page_table, const int32_t* lens,
+                          int S, int Lmax, int nkv, int max_pages, int total_pages, hipStream_t st);
+void launch_bf16_to_f32(const void* a, float* b, size_t n, hipStream_t st);
+void launch_unpack_rows(const void* packed, void* out, int R, int K, hipStream_t st);
+
+// ---- attn.hip -------------------------------------------------------------------------------------------------------
+// One launch_attn call = one phase: scores / P.V / combine for decode-style rows (one dialogue per row), the same three
+// for prefill tiles (32 consecutive positions of one dialogue), or ATTN_ALL = the three decode phases in one call.
+// (mtts_k_attn_bench takes the number across the ABI: the values stay.)
+enum AttnPhase { ATTN_ALL = 0, ATTN_SCORES = 1, ATTN_PV = 2, ATTN_COMBINE = 3,
+                 ATTN_PF_SCORES = 11, ATTN_PF_PV = 12, ATTN_PF_COMBINE = 13 };
+int launch_attn(const void* qbuf, void* kcache, void* vcache, const int32_t* page_table,
+                const RowMeta* meta, void* scores, float* stats, float* opart, void* out_packed, int R,
+                int pages_bound, int max_pages, int total_pages, int nchunks_max, int nq, int nkv, float scale,
+                const QkvFuse* fuse, AttnPhase phase, hipStream_t st, const KvPack* pack = nullptr);
+void launch_kv_seal_rows(const void* kcache, const void* vcache, void* kpack, void* vpack, const int32_t* page_table,
+                         const RowMeta* meta, int R, int max_pages, int total_pages, int nkv, int L, unsigned long long* cnt, hipStream_t st);
+void launch_kv_seal_all(const void* kcache, const void* vcache, void* kpack, void* vpack, int total_pages, int nkv, int L,
+                        unsigned long long* cnt, hipStream_t st);
+void launch_kv_seal_pages(const void* raw, void* pk, int npages, int as_k, hipStream_t st);
+void launch_kv_pack_count(const void* kpack, const void* vpack, const int32_t* page_table, const int32_t* complete, int B, int max_pages,
+                          int total_pages, int nkv, int L, unsigned long long* out, hipStream_t st);
+
+// ---- sampler.hip ----------------------------------------------------------------------------------------------------
+struct SeqState {           // one per sequence slot, device resident.  Every dialogue carries its own clock so
+                            // that slots can be refilled while others are mid-flight (continuous batching).
+    int32_t nas;            // needs_additional_steps
+    int32_t unfinished;
+    int32_t kv_len;         // real tokens already in the KV cache
+    int32_t step;           // decode steps this dialogue has run (= rows it generated)
+    int32_t base_length;    // T-7 (padded slots) of its prompt
+    int32_t max_length;     // HF max_length in padded slots
+    int32_t row_id;         // Philox counter word 1 (batch row index in mtts_generate, 0 for scheduled dialogues)
+    int32_t active;         // slot holds a dialogue that still steps
+    uint64_t seed;          // Philox key
+};
+
+struct LoopState {          // one per engine, device resident
+    int32_t step;           // decode steps executed so far by the engine
+    int32_t done;           // no active row is unfinished
+    int32_t continuous;     // 1: a finished row leaves the batch at once (scheduler); 0: it keeps emitting the
+                            //    reference's finished-row padding until the whole batch is done (mtts_generate)
+    int32_t B;
+    int32_t error;          // sticky device-side error
+    int32_t gen_cap;        // rows of generated-token storage per slot
+    int32_t forced_draw;    // forced replay: 1 (2: cut-off rows too) = the forced row replaces the step's raw draw BEFORE the state machine
+                            //    (replay of a sampled reference run); 0 = it replaces the state machine's output
+    int32_t logits_f32;     // the logits buffers hold fp32 (MTTS_DTYPE_F32 engine) instead of bf16
+};
+// both are memcpy'd between host and device
+static_assert(sizeof(SeqState) == 40 && std::is_trivially_copyable<SeqState>::value, "SeqState layout");
+static_assert(sizeof(LoopState) == 32 && std::is_trivially_copyable<LoopState>::value, "LoopState layout");
+
+#define SAMP_CAND 4096
+#define SAMP_NS 32
+struct SampleScratch {
+    uint32_t* hist = nullptr;        // [32][2048]
+    float* slice_val = nullptr;      // [32][SAMP_NS]
+    int32_t* slice_idx = nullptr;    // [32][SAMP_NS]
+    float* cand_val = nullptr;       // [32][SAMP_CAND]
+    int32_t* cand_idx = nullptr;     // [32][SAMP_CAND]
+    uint32_t* cand_n = nullptr;      // [rows]
+    int32_t* overflow = nullptr;     // [rows] set by the final kernel when a row needs the full-vocabulary path
+    float* full_val = nullptr;       // [rows][full_cap]   full-vocabulary path: level-0 bin (uint16) of every token
+    int32_t* full_idx = nullptr;     // [rows][full_cap]   full-vocabulary path: key of every token
+    uint32_t* nuc_cnt = nullptr;     // [rows][2048] level-0 histogram (count) left by the collect kernel for the full-vocabulary kernel
+    unsigned long long* nuc_mass = nullptr;   // [rows][2048] ... and mass (exp(s - max) * 2^45, exact integer sums)
+    // the next two exist only once output_scores was asked for (null otherwise; only the LP kernels touch them)
+    float* slice_sum = nullptr;      // [rows][SAMP_NS] output_scores, greedy channel 0: sum of exp(s - slice_val) over the slice (its max IS slice_val)
+    float* lp = nullptr;             // [rows][8] output_scores: log-probability of decisions[row][c], read by update_kernel
+};
+void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps,
+                   int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed,
+                   int32_t* decisions, int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap,
+                   int emit_lp, hipStream_t st);
+void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
+                          const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
+                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp, hipStream_t st);
+void launch_update(const int32_t* decisions, int32_t* dec_log, const int32_t* forced, const int32_t* tf_tail,
+                   int32_t* gen, int32_t* cur_tokens, SeqState* seqs, RowMeta* meta, uint32_t* bitmaps, int bm_words,
+                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out, hipStream_t st);
+void launch_export_codes(const int32_t* gen, int64_t* codes, int B, int first, int n, int speech_offset, int clamp_hi,
+                         int cap, hipStream_t st);
+
+// ---- f32path.hip ----------------------------------------------------------------------------------------------------
+#define MTTS_PF32CAP 256       // rows of a prefill pass in the fp32 engine (bounds its fp32 score scratch)
+void launch_f32_embed_norm(const int32_t* tokens, const RowMeta* meta, const float* const* tables, const float* norm_w, float* x,
+                           float* xn, int R, int H, float eps, int h16, hipStream_t st);
+void launch_f32_resid_norm(const float* y, float* x, const float* norm_w, float* xn, float* hlast, const RowMeta* meta, int R,
+                           int H, float eps, int h16, hipStream_t st);
+void launch_f32_linear(const float* W, const float* X, float* Y, int R, int N, int K, long ldy, int h16, bool gemv, hipStream_t st);
+void launch_f32_qkv_post(const float* qkv, int ldq, const RowMeta* meta, const float* qnw, const float* knw, const float* cosb,
+                         const float* sinb, float* qbuf, float* kcache, float* vcache, const int32_t* page_table, int max_pages,
+                         int total_pages, int R, int nq, int nkv, float eps, int h16, hipStream_t st);
+void launch_f32_attn(const float* qbuf, const float* kcache, const float* vcache, const int32_t* page_table, const RowMeta* meta,
+                     float* scores, float* out, int R, int max_pages, int total_pages, int nq, int nkv, float scale, int Lmax,
+                     int h16, hipStream_t st);
+void launch_f32_swiglu(const float* gu, float* act, int R, int I, int h16, hipStream_t st);
+
+// ---- codec.hip / codec_fused.hip ------------------------------------------------------------------------------------
+void mtts_gemm_f32_exact(hipStream_t st, const float* A, const float* W, float* C, int M, int N, int K, long ldc);
+void launch_split_pack_w2perm(hipStream_t st, const float* w2, uint16_t* hi, uint16_t* lo);
+void launch_vocos_pw_fused(hipStream_t st, const uint16_t* xn_planes, long x_plane_elems, const uint16_t* w1_planes, const float* b1,
+                           const uint16_t* w2perm_planes, long w_plane_elems, const float* b2, const float* gamma, float* h, int M);

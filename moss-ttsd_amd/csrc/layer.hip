@@ -1,7 +1,7 @@
 // Elementwise / normalisation kernels of one decoder layer, each fused with the
 // split-K reduction of the GEMM in front of it.  All rounding points follow the
 // reference's CPU bf16 execution (oracle/asteroid_oracle.py lists them).
-#include "common.h"
+#include "launch.h"
 
 // block-wide sum over 256 threads
 __device__ __forceinline__ float block_sum_256(float v, float* sh) {
@@ -290,7 +290,6 @@ void launch_fill_random_bf16(void* p, size_t n, uint32_t seed, hipStream_t st) {
 }
 
 // Page-table edits handed over as launch arguments (engine.hip: pool_flush).
-struct PageEdits { int32_t n; int32_t idx[31]; int32_t val[31]; };
 __global__ void set_pages_kernel(int32_t* __restrict__ table, PageEdits ed) {
     if ((int)threadIdx.x < ed.n) table[ed.idx[threadIdx.x]] = ed.val[threadIdx.x];
 }

@@ -12,35 +12,7 @@
 // are walked in descending score and the first whose running sum of
 // exp(score - max) exceeds u * total is taken.  oracle/asteroid_oracle.py
 // (sample_from_scores) states the same rule.
-#include "common.h"
-#include "../../include/mtts.h"
-
-
-struct SeqState {           // one per sequence slot, device resident.  Every dialogue carries its own clock so
-                            // that slots can be refilled while others are mid-flight (continuous batching).
-    int32_t nas;            // needs_additional_steps
-    int32_t unfinished;
-    int32_t kv_len;         // real tokens already in the KV cache
-    int32_t step;           // decode steps this dialogue has run (= rows it generated)
-    int32_t base_length;    // T-7 (padded slots) of its prompt
-    int32_t max_length;     // HF max_length in padded slots
-    int32_t row_id;         // Philox counter word 1 (batch row index in mtts_generate, 0 for scheduled dialogues)
-    int32_t active;         // slot holds a dialogue that still steps
-    uint64_t seed;          // Philox key
-};
-
-struct LoopState {          // one per engine, device resident
-    int32_t step;           // decode steps executed so far by the engine
-    int32_t done;           // no active row is unfinished
-    int32_t continuous;     // 1: a finished row leaves the batch at once (scheduler); 0: it keeps emitting the
-                            //    reference's finished-row padding until the whole batch is done (mtts_generate)
-    int32_t B;
-    int32_t error;          // sticky device-side error
-    int32_t gen_cap;        // rows of generated-token storage per slot
-    int32_t forced_draw;    // forced replay: 1 (2: cut-off rows too) = the forced row replaces the step's raw draw BEFORE the state machine
-                            //    (replay of a sampled reference run); 0 = it replaces the state machine's output
-    int32_t logits_f32;     // the logits buffers hold fp32 (MTTS_DTYPE_F32 engine) instead of bf16
-};
+#include "launch.h"
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t* out) {
@@ -91,25 +63,6 @@ __device__ __forceinline__ float proc_score(LogitsPtr logits, int i, int mask_id
 // first whose running sum of exp(score - max) exceeds u * total wins.
 // ---------------------------------------------------------------------------
 #define SAMP_T 256
-#define SAMP_CAND 4096
-#define SAMP_NS 32
-
-struct SampleScratch {
-    uint32_t* hist;        // [32][2048]
-    float* slice_val;      // [32][SAMP_NS]
-    int32_t* slice_idx;    // [32][SAMP_NS]
-    float* cand_val;       // [32][SAMP_CAND]
-    int32_t* cand_idx;     // [32][SAMP_CAND]
-    uint32_t* cand_n;      // [rows]
-    int32_t* overflow;     // [rows] set by the final kernel when a row needs the full-vocabulary path
-    float* full_val;       // [rows][full_cap]   full-vocabulary path: level-0 bin (uint16) of every token
-    int32_t* full_idx;     // [rows][full_cap]   full-vocabulary path: key of every token
-    uint32_t* nuc_cnt;     // [rows][2048] level-0 histogram (count) left by the collect kernel for the full-vocabulary kernel
-    unsigned long long* nuc_mass;   // [rows][2048] ... and mass (exp(s - max) * 2^45, exact integer sums)
-    // the next two exist only once output_scores was asked for (null otherwise; only the LP kernels touch them)
-    float* slice_sum;      // [rows][SAMP_NS] output_scores, greedy channel 0: sum of exp(s - slice_val) over the slice (its max IS slice_val)
-    float* lp;             // [rows][8] output_scores: log-probability of decisions[row][c], read by update_kernel
-};
 
 struct SampleCtx {         // resolved per (row, channel)
     LogitsPtr lg;

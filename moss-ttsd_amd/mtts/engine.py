@@ -73,9 +73,12 @@ class Engine:
         torch.cuda.synchronize(self.device)
 
     def close(self):
+        """-> mtts_engine_destroy's code: MTTS_OK, or MTTS_EHIP when freeing one of the engine's buffers failed."""
+        rc = 0
         if self._h:
-            self.lib.mtts_engine_destroy(self._h)
+            rc = self.lib.mtts_engine_destroy(self._h)
             self._h = C.c_void_p()
+        return rc
 
     def __del__(self):
         try:
