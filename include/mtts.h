@@ -223,7 +223,8 @@ int32_t mtts_debug_set_kv_len(MttsEngine* e, int32_t kv_len);   /* also fills th
  * reads when more than 1 in 8 of its pages did not seal)}.  MTTS_ESTATE when the engine keeps none (fp32 / fp16 engines,
  * MTTS_KV_PACK=0). */
 int32_t mtts_debug_kv_pack_stats(MttsEngine* e, int64_t* out6);
-/* train of `iters` launches of one decode attention pass (1 scores, 2 P.V) at the current state; when the product would
+/* train of `iters` launches of one decode attention pass (1 scores, 2 P.V, 3 combine, 0 = the three in a row, 4 = the
+ * whole-row kernel that does all three in one launch) at the current state; when the product would
  * run the fused q/k/v epilogue at this size the train does too and overwrites the current position's K/V rows:
  * call it only when no further step follows */
 int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* avg_ms, int64_t* bytes_per_launch);
@@ -239,6 +240,19 @@ int32_t mtts_k_gemm_bf16(const void* dev_w, const void* dev_x, void* dev_y,
 /* number of GEMM launches of this process that took a depth-specialised kernel (gemm_depth_kernel / gemm_gateup48_kernel)
  * instead of gemm_skinny_kernel; under graph replay a launch counts once, when it is captured (tests: did the dispatch fire) */
 int64_t mtts_debug_gemm_depth_launches(void);
+/* number of whole-row decode attention launches (attn_row_kernel) of this process; counted like the above */
+int64_t mtts_debug_attn_row_launches(void);
+/* Test hook: the attention section of one decode layer (fused q/k/v epilogue, scores, P.V, sum of the chunk partials) on
+ * given qkv slabs, path 0 = the two-pass kernels + combine, 1 = the whole-row kernel.  dev_slabs fp32 [ksplit][R][(nq +
+ * 2 nkv) * 128]; dev_k / dev_v bf16 [R][Lmax][nkv][128] = the tokens already cached (row r: host_lens[r] - 1 of them;
+ * host_lens[r] = its length with the new token, 0 = idle row); dev_cos / dev_sin bf16 [Lmax][64]; sealed != 0: complete
+ * pages are read in their sealed form.  Out: dev_out bf16 [32][nq*128] (X-fragment layout), the bf16 pools after the
+ * launch dev_kcache / dev_vcache [nkv][R*pages][64*128] and (sealed, may be NULL) the sealed pools [nkv][R*pages][13*64*16 B]. */
+int32_t mtts_k_attn_section(const float* dev_slabs, int32_t ksplit, const void* dev_qnw, const void* dev_knw, const void* dev_cos,
+                            const void* dev_sin, float eps, const void* dev_k, const void* dev_v, const int32_t* host_lens,
+                            const int32_t* host_page_table, int32_t R, int32_t Lmax, int32_t nq, int32_t nkv, int32_t sealed,
+                            int32_t path, void* dev_out, void* dev_kcache, void* dev_vcache, void* dev_kpack, void* dev_vpack,
+                            void* stream);
 /* The decode path's gate/up GEMM with its SwiGLU epilogue: W[N,K] holds gate and up rows interleaved (row 2i = gate i,
  * row 2i+1 = up i), Y[M,N/2] = bf16(bf16(silu(bf16(gate))) * bf16(up)), row-major.  M <= 128, N % 32 == 0, no split-K.
  * Like mtts_k_gemm_bf16 and mtts_k_gemm_bench it reads MTTS_GEMM_DEPTH on every call (0: gemm_skinny_kernel only). */

@@ -17,6 +17,8 @@
 // what is large; and nothing on the way may wait for "all loads" -- which the compiler's wait counts do after a JOIN of
 // code paths with different numbers of loads in flight: hence one straight-line body per page form.
 #include "launch.h"
+#include <algorithm>
+#include <atomic>
 #include <cstdlib>
 // (tuning aid, tools/ab_build.sh: waves per SIMD the sealed-page kernels are compiled for; 0 = the compiler's choice --
 //  5 was measured and lost, profiles/r03_kv_pack_ab.txt item 4)
@@ -853,6 +855,360 @@ __global__ __launch_bounds__(512) void attn_combine_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Whole-row decode attention: ONE launch per layer, one block per (row, kv head), for batches wide enough that
+// rows x kv heads fills the machine.  The block does what attn_scores (fused epilogue) + attn_pv + attn_combine do for
+// its row, operation for operation -- same rounding points, same page forms and fallbacks, same summation orders, hence
+// the same bits -- but the bf16 scores, the per-page (max, sumexp) pairs and the chunk partials live in LDS instead of
+// HBM, the q/k/v epilogue runs once per block, and nothing waits on another block.
+//   K phase     waves take the row's pages round-robin: attn_scores_kernel's page body; scores and pairs -> LDS
+//   statistics  every wave reduces the pairs by attn_pv_kernel's own sequence (lane p = page p, strided beyond 64)
+//   V phase     work item i = pages 2i, 2i+1 = attn_pv_kernel's (chunk i / 4, wave i % 4), dealt round-robin; one
+//               accumulator set across both pages, add_xor32, the item's G x 128 fp32 vector -> LDS
+//   epilogue    per chunk ((r0 + r1) + r2) + r3, chunks added in ascending order from 0.f, f2bf at xpack_off
+// Dynamic LDS (attn_row_lds_bytes): q, the new K / V rows, the per-wave rescaled q and probability pairs, then per page
+// of the launch's bound G x (8 B of pairs + 128 B of scores) and per chunk 4 x G x 512 B of item vectors.
+// ---------------------------------------------------------------------------------------------------
+#ifndef ROW_WAVES
+#define ROW_WAVES 12          // waves per whole-row block: 3 per SIMD, at most 168 registers each (the sealed-page bodies take
+                              // 138-152; 16 waves would have to fit 128, spill, and lose: profiles/attn_row_ab.json; 8 is no faster)
+#endif
+static_assert(ROW_WAVES >= 6 && ROW_WAVES <= 16, "one wave per q head + the K row + the V row; at most 1024 threads");
+static std::atomic<long long> g_row_launches{0};
+long long mtts_attn_row_launches() { return g_row_launches.load(); }
+int attn_row_lds_bytes(int G, bool pk, int pages_bound) {
+    const int nch = (pages_bound + ATT_PB - 1) / ATT_PB;
+    return G * 256 + 512 + (pk ? ROW_WAVES * G * 256 : 0) + ROW_WAVES * G * 128 + G * pages_bound * (8 + 128) + PV_WAVES * nch * G * 512;
+}
+
+template <int G, bool PK>
+__global__ __launch_bounds__(ROW_WAVES * 64) void attn_row_kernel(
+    u32x4_t* __restrict__ kcache, u32x4_t* __restrict__ vcache, const int32_t* __restrict__ page_table,
+    const RowMeta* __restrict__ meta, uint16_t* __restrict__ out_packed, int npb, int max_pages, int total_pages, int nq,
+    int nkv, float scale, QkvFuse f, const u32x4_t* __restrict__ kpack, const u32x4_t* __restrict__ vpack) {
+    constexpr int W = ROW_WAVES;
+    extern __shared__ __attribute__((aligned(16))) uint8_t row_lds[];
+    uint32_t* qs = (uint32_t*)row_lds;                                       // [G][64] bf16 pairs, as stored
+    uint16_t* knew = (uint16_t*)(row_lds + G * 256);                         // [128]
+    uint16_t* vnew = knew + MTTS_HD;                                         // [128]
+    uint32_t* qw = (uint32_t*)(row_lds + G * 256 + 512);                     // [W][G][64] q times a sealed page's powers of two
+    uint16_t* pbuf = (uint16_t*)((uint8_t*)qw + (PK ? W * G * 256 : 0));     // [W][G][64] probabilities of a wave's page
+    float2* st = (float2*)((uint8_t*)pbuf + W * G * 128);                    // [G][npb] per-page (max, sumexp)
+    uint16_t* sc = (uint16_t*)(st + G * npb);                                // [G][npb * 64] bf16 scores
+    float* items = (float*)(sc + (size_t)G * npb * MTTS_PAGE);               // [PV_WAVES * chunks][G][128]
+    const int r = blockIdx.y, kvh = blockIdx.x;
+    const RowMeta m = meta[r];
+    if (m.seq < 0) {                                  // an idle row: attn_combine_kernel's empty sum
+        for (int i = threadIdx.x; i < G * MTTS_HD; i += W * 64) out_packed[xpack_off(r, kvh * G * MTTS_HD + i, nq * MTTS_HD)] = f2bf(0.f);
+        return;
+    }
+    const int len = m.pos + 1;
+    const int npages = min((len + MTTS_PAGE - 1) / MTTS_PAGE, npb);
+    const int nch = (npages + ATT_PB - 1) / ATT_PB;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int own_pg = m.pos >> 6;                    // page that receives this step's token
+    const int sub = lane >> 5, dl = lane & 31;
+    const int32_t* ptab = page_table + (size_t)m.seq * max_pages;
+
+    // ---- q/k/v epilogue, once per block: wave g < G = q head g, wave G = the new K row, wave G + 1 = the new V row.
+    //      These waves finish it before they request a page (the slabs' 16 registers are free again by then); the other
+    //      waves have the row's first pages in flight meanwhile, so pages go round-robin over `vw`, which puts the
+    //      epilogue waves last.
+    const bool epi = wave < G + 2;
+    const int vw = epi ? wave + W - (G + 2) : wave - (G + 2);
+    if (epi) {
+        const int col = (wave < G ? kvh * G + wave : wave == G ? nq + kvh : nq + nkv + kvh) * MTTS_HD;
+        FuseVec pfv{0.f, 0.f, 0.f, 0.f};
+        if (wave <= G) pfv = fuse_load_vec(f, wave == G ? f.knorm_w : f.qnorm_w, m.pos, lane);
+        float a, b;
+        if (f.ksplit <= 8) {
+            float pta[8], ptb[8];
+            fuse_reduce_request(f, r, col, lane, pta, ptb);
+            fuse_reduce_sum(f, pta, ptb, a, b);
+        } else fuse_reduce(f, r, col, lane, a, b);
+        const int opage = ptab[own_pg], tok = m.pos & 63;
+        if (wave <= G) {
+            float o1, o2;
+            fuse_norm_rope(f, pfv, a, b, o1, o2);
+            if (wave < G) {
+                ((uint16_t*)(qs + wave * 64))[lane] = f2bf(o1);
+                ((uint16_t*)(qs + wave * 64))[lane + 64] = f2bf(o2);
+            } else {
+                knew[lane] = f2bf(o1);
+                knew[lane + 64] = f2bf(o2);
+                uint16_t* base = (uint16_t*)kcache + ((size_t)kvh * total_pages + opage) * (MTTS_PAGE * MTTS_HD);
+                base[(((lane >> 3) * 64) + tok) * 8 + (lane & 7)] = f2bf(o1);       // element (tok, d) at ((d/8)*64 + tok)*8 + d%8
+                base[((((lane + 64) >> 3) * 64) + tok) * 8 + (lane & 7)] = f2bf(o2);
+            }
+        } else {
+            vnew[lane] = f2bf(a);
+            vnew[lane + 64] = f2bf(b);
+            uint16_t* dst = (uint16_t*)vcache + ((size_t)kvh * total_pages + opage) * (MTTS_PAGE * MTTS_HD) + (size_t)(tok >> 1) * (MTTS_HD * 2) + (tok & 1);
+            dst[2 * lane] = f2bf(a);                      // element (tok, d) at ((tok>>1)*128 + d)*2 + (tok&1)
+            dst[2 * (lane + 64)] = f2bf(b);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    auto stage = [&]() { __syncthreads(); };          // (waits for LDS only: a page's loads keep flying across it)
+
+    // ---- K phase: attn_scores_kernel's page body; `first`: the wave's first page, requested before the block's q is complete
+    auto finish = [&](int pg, const float* acc) {
+        const int tok = pg * MTTS_PAGE + lane;
+        const bool valid = tok < len;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            float s = rbf(rbf(acc[g]) * scale);
+            if (valid) sc[(size_t)g * npb * MTTS_PAGE + tok] = f2bf(s);
+            float mx = wave_max(valid ? s : -INFINITY);
+            float e = valid ? expf(s - mx) : 0.f;
+            float sm = wave_sum(e);
+            if (lane == 0) st[g * npb + pg] = float2{mx, sm};
+        }
+    };
+    auto raw_dots = [&](int pg, u32x4_t (&kv)[16]) {
+        if (pg == own_pg && lane == (m.pos & 63)) {   // this lane's token is the new one: take its K from LDS
+#pragma unroll
+            for (int j = 0; j < 16; ++j) kv[j] = *(const u32x4_t*)&knew[8 * j];
+        }
+        float acc[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const u32x4_t q = *(const u32x4_t*)&qs[g * 64 + 4 * j];
+                acc[g] = dot2bf(kv[j].x, q.x, acc[g]);
+                acc[g] = dot2bf(kv[j].y, q.y, acc[g]);
+                acc[g] = dot2bf(kv[j].z, q.z, acc[g]);
+                acc[g] = dot2bf(kv[j].w, q.w, acc[g]);
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) asm volatile("" : "+v"(acc[g]));
+            if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+        finish(pg, acc);
+    };
+    auto k_page = [&](int pg, bool first) {
+        const int page = ptab[pg];
+        const u32x4_t* kp = kcache + ((size_t)kvh * total_pages + page) * (MTTS_PAGE * MTTS_HD / 8) + lane;
+        if (PK && pg < own_pg) {                      // (wave-uniform) a complete page: its sealed form
+            u32x4_t pk[MTTS_PKU];
+            const u32x4_t* pp = kpack + ((size_t)kvh * total_pages + page) * (MTTS_PKU * 64) + lane;
+#pragma unroll
+            for (int j = 0; j < MTTS_PKU; ++j) pk[pk_order(j)] = __builtin_nontemporal_load(pp + pk_order(j) * 64);
+            if (first) stage();
+            bool qok = true;                          // the page's K is k 2^-s per dim: this wave's q becomes q 2^s (exact, or flagged)
+            const uint32_t sh = pk[12].z;
+            uint32_t* qwv = qw + wave * G * 64;
+            __builtin_amdgcn_wave_barrier();          // (the previous page's reads of qwv are done: same wave, in order)
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const uint32_t qd = qs[g * 64 + lane];
+                uint32_t out = 0u;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    uint32_t b = (qd >> (16 * h)) & 0xffffu;
+                    const int sft = (int)(int8_t)((sh >> (8 * h)) & 0xffu);
+                    if ((b & 0x7fffu) && sft) {
+                        const int e = (int)((b >> 7) & 0xffu), e2 = e + sft;
+                        if (e == 0 || e == 255 || e2 < 1 || e2 > 254) qok = false;
+                        else b = (b + ((uint32_t)sft << 7)) & 0xffffu;
+                    }
+                    out |= b << (16 * h);
+                }
+                qwv[g * 64 + lane] = out;
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (__any(pk[12].w != 0u || !qok)) {      // a row of this page (or this q) did not fit: take the bf16 page
+                u32x4_t kv[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) kv[j] = __builtin_nontemporal_load(kp + j * 64);
+                raw_dots(pg, kv);
+                return;
+            }
+            float acc[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) acc[g] = 0.f;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                uint32_t w[4];
+                pk_unit(pk, j, w);
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const u32x4_t q = *(const u32x4_t*)&qwv[g * 64 + 4 * j];
+                    acc[g] = dot2bf(w[0], q.x, acc[g]);
+                    acc[g] = dot2bf(w[1], q.y, acc[g]);
+                    acc[g] = dot2bf(w[2], q.z, acc[g]);
+                    acc[g] = dot2bf(w[3], q.w, acc[g]);
+                }
+#pragma unroll
+                for (int g = 0; g < G; ++g) asm volatile("" : "+v"(acc[g]));
+                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+            }
+            finish(pg, acc);
+        } else {                                      // the page being filled (or an engine without sealed pages): bf16
+            u32x4_t kv[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) kv[j] = __builtin_nontemporal_load(kp + j * 64);
+            if (first) stage();
+            raw_dots(pg, kv);
+        }
+    };
+    if (vw < npages) k_page(vw, true);
+    else stage();
+#pragma unroll 1
+    for (int pg = vw + W; pg < npages; pg += W) k_page(pg, false);
+
+    // ---- V phase: attn_pv_kernel's page body.  The wave's first V page is requested before the statistics.
+    u32x4_t vv[16];
+    bool packed = false;
+    const u32x4_t* vp = nullptr;
+    auto load_page = [&](int pg) {                    // complete pages are sealed: 13 loads per lane instead of 16
+        const int page = ptab[pg];
+        vp = vcache + ((size_t)kvh * total_pages + page) * (MTTS_PAGE * MTTS_HD / 8) + lane;
+        packed = PK && pg < own_pg;
+        if (packed) {
+            const u32x4_t* pp = vpack + ((size_t)kvh * total_pages + page) * (MTTS_PKU * 64) + lane;
+#pragma unroll
+            for (int it = 0; it < MTTS_PKU; ++it) vv[pk_order(it)] = __builtin_nontemporal_load(pp + pk_order(it) * 64);
+        } else {
+#pragma unroll
+            for (int it = 0; it < 16; ++it) vv[it] = __builtin_nontemporal_load(vp + it * 64);
+        }
+    };
+    if (2 * wave < npages) load_page(2 * wave);
+    __syncthreads();                                  // every page's scores and pair are in LDS
+    // row-wide softmax statistics from the per-page (max, sumexp) pairs
+    float M[G], S[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const float2* sg = st + g * npb;
+        const float2 s0 = lane < npages ? sg[lane] : float2{-INFINITY, 0.f};
+        float mx = -INFINITY;
+        mx = fmaxf(mx, s0.x);
+        for (int p = lane + 64; p < npages; p += 64) mx = fmaxf(mx, sg[p].x);
+        mx = wave_max(mx);
+        float sm = 0.f;
+        if (lane < npages) sm += s0.y * expf(s0.x - mx);
+        for (int p = lane + 64; p < npages; p += 64) sm += sg[p].y * expf(sg[p].x - mx);
+        sm = wave_sum(sm);
+        M[g] = mx;
+        S[g] = sm;
+    }
+    uint16_t* pb = pbuf + wave * G * MTTS_PAGE;
+#pragma unroll 1
+    for (int item = wave; item < PV_WAVES * nch; item += W) {
+        float acc[G][4];
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[g][i] = 0.f;
+#pragma unroll 1
+        for (int pp = 0; pp < ATT_PB / PV_WAVES; ++pp) {
+            const int pg = item * (ATT_PB / PV_WAVES) + pp;
+            if (pg >= npages) break;
+            if (pp > 0 || item != wave) load_page(pg);
+            if (pg == own_pg) {
+                // the new row comes from LDS, wherever the cache write stands: patch the token's half of its pair
+                const int tp = (m.pos & 63) >> 1;             // token pair inside the page
+                if (sub == (tp & 1)) {
+                    const uint32_t w01 = ((const uint32_t*)vnew)[2 * dl], w23 = ((const uint32_t*)vnew)[2 * dl + 1];
+                    const uint32_t nv[4] = {w01 & 0xffffu, w01 >> 16, w23 & 0xffffu, w23 >> 16};   // d = 4*dl .. 4*dl+3
+                    const bool hi = m.pos & 1;
+#pragma unroll
+                    for (int it = 0; it < 16; ++it)
+                        if (it == (tp >> 1)) {
+                            vv[it].x = hi ? (vv[it].x & 0xffffu) | (nv[0] << 16) : (vv[it].x & 0xffff0000u) | nv[0];
+                            vv[it].y = hi ? (vv[it].y & 0xffffu) | (nv[1] << 16) : (vv[it].y & 0xffff0000u) | nv[1];
+                            vv[it].z = hi ? (vv[it].z & 0xffffu) | (nv[2] << 16) : (vv[it].z & 0xffff0000u) | nv[2];
+                            vv[it].w = hi ? (vv[it].w & 0xffffu) | (nv[3] << 16) : (vv[it].w & 0xffff0000u) | nv[3];
+                        }
+                }
+            }
+            uint16_t pun[G];                              // the probabilities as the reference rounds them
+            bool pok = true;
+            {
+                const int tok = pg * MTTS_PAGE + lane;
+                // a sealed V page holds token t's values divided by 2^s[t] (lane t keeps s[t]): its probability takes the 2^s[t]
+                const int sv = (PK && packed) ? (int)(vv[12].z & 0xffu) : 0;
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    float p = 0.f;
+                    if (tok < len) {
+                        float s = bf2f(sc[(size_t)g * npb * MTTS_PAGE + tok]);
+                        p = expf(s - M[g]) / S[g];
+                    }
+                    uint32_t pbits = f2bf(p);
+                    pun[g] = (uint16_t)pbits;
+                    if (sv && (pbits & 0x7fffu)) {
+                        if (((pbits >> 7) & 0xffu) == 0u) pok = false;    // a denormal probability cannot be rescaled exactly
+                        else pbits += (uint32_t)sv << 7;                  // p <= 1, s <= 127: the exponent field stays <= 254
+                    }
+                    pb[g * MTTS_PAGE + lane] = (uint16_t)pbits;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (PK && packed && __any(vv[12].w != 0u || !pok)) {  // a lane did not fit the sealed form (or a probability its scale): the bf16 page
+                packed = false;
+#pragma unroll
+                for (int it = 0; it < 16; ++it) vv[it] = __builtin_nontemporal_load(vp + it * 64);
+#pragma unroll
+                for (int g = 0; g < G; ++g) pb[g * MTTS_PAGE + lane] = pun[g];
+                __builtin_amdgcn_wave_barrier();
+            }
+            if (PK && packed) {
+#pragma unroll
+                for (int it = 0; it < 16; ++it) {
+                    uint32_t w[4];
+                    pk_unit(vv, it, w);
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        const uint32_t pp2 = ((const uint32_t*)(pb + g * MTTS_PAGE))[it * 2 + sub];
+                        acc[g][0] = dot2bf(w[0], pp2, acc[g][0]);
+                        acc[g][1] = dot2bf(w[1], pp2, acc[g][1]);
+                        acc[g][2] = dot2bf(w[2], pp2, acc[g][2]);
+                        acc[g][3] = dot2bf(w[3], pp2, acc[g][3]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int it = 0; it < 16; ++it) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        const uint32_t pp2 = ((const uint32_t*)(pb + g * MTTS_PAGE))[it * 2 + sub];
+                        acc[g][0] = dot2bf(vv[it].x, pp2, acc[g][0]);
+                        acc[g][1] = dot2bf(vv[it].y, pp2, acc[g][1]);
+                        acc[g][2] = dot2bf(vv[it].z, pp2, acc[g][2]);
+                        acc[g][3] = dot2bf(vv[it].w, pp2, acc[g][3]);
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float v = add_xor32(acc[g][i]);
+                if (sub == 0) items[((size_t)item * G + g) * MTTS_HD + dl * 4 + i] = v;
+            }
+    }
+    __syncthreads();
+    // ---- attn_pv_kernel's sum over its four waves, then attn_combine_kernel's sum over the chunks
+    for (int i = threadIdx.x; i < G * MTTS_HD; i += W * 64) {
+        float s = 0.f;
+        for (int c = 0; c < nch; ++c) {
+            const float* it4 = items + (size_t)PV_WAVES * c * G * MTTS_HD + i;
+            float v = it4[0];
+#pragma unroll
+            for (int w = 1; w < PV_WAVES; ++w) v += it4[(size_t)w * G * MTTS_HD];
+            s += v;
+        }
+        out_packed[xpack_off(r, kvh * G * MTTS_HD + i, nq * MTTS_HD)] = f2bf(s);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Prefill attention: the 32 rows of an activation tile are consecutive positions of ONE dialogue (the host
 // pads every dialogue's prompt to whole tiles), so a tile shares its K/V pages: one block streams a page once
 // for 32 query rows instead of once per row, with the products on the matrix cores.  Same rounding points,
@@ -1088,6 +1444,17 @@ static void launch_attn_g(const void* qbuf, void* kcache, void* vcache, const in
     const QkvFuse f = fuse ? *fuse : QkvFuse{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0.f};
     const u32x4_t* kpk = pack ? (const u32x4_t*)pack->k : nullptr;
     const u32x4_t* vpk = pack ? (const u32x4_t*)pack->v : nullptr;
+    if (phase == ATTN_ROW) {        // the three decode phases in one launch (the caller has checked attn_row_fits)
+        const size_t lds = (size_t)attn_row_lds_bytes(G, kpk != nullptr, pages_bound);
+        if (kpk)
+            hipLaunchKernelGGL((attn_row_kernel<G, true>), dim3(nkv, R), dim3(ROW_WAVES * 64), lds, st, (u32x4_t*)kcache, (u32x4_t*)vcache,
+                               page_table, meta, (uint16_t*)out_packed, pages_bound, max_pages, total_pages, nq, nkv, scale, f, kpk, vpk);
+        else
+            hipLaunchKernelGGL((attn_row_kernel<G, false>), dim3(nkv, R), dim3(ROW_WAVES * 64), lds, st, (u32x4_t*)kcache, (u32x4_t*)vcache,
+                               page_table, meta, (uint16_t*)out_packed, pages_bound, max_pages, total_pages, nq, nkv, scale, f, kpk, vpk);
+        g_row_launches.fetch_add(1);
+        return;
+    }
 #define MTTS_SC(FU, PK)                                                                                                  \
     hipLaunchKernelGGL((attn_scores_kernel<G, FU, PK>), ga, dim3(256), 0, st, (const uint16_t*)qbuf, (u32x4_t*)kcache, \
                        page_table, meta, (uint16_t*)scores, stats, max_pages, total_pages, nq, nkv, scale, f, kpk)
@@ -1117,13 +1484,51 @@ static void launch_attn_g(const void* qbuf, void* kcache, void* vcache, const in
                            (uint16_t*)out_packed, nchunks_max, nq, ATT_PB);
 }
 
-// One phase per call (AttnPhase, launch.h).  `fuse` (decode rows only) moves the q/k/v epilogue into ATTN_SCORES and
+// The whole-row kernel takes the fused epilogue, K and V pages in the same form (both sealed or both bf16) and a page
+// bound whose LDS fits what the device gives one block.
+static int g_row_lds_max = 0;             // dynamic LDS a block may ask for: set by attn_row_prepare (0: not prepared, nothing fits)
+bool attn_row_fits(int G, const QkvFuse* fuse, const KvPack* pack, int pages_bound) {
+    const bool pk = pack && pack->k;
+    if (!fuse || (G != 1 && G != 2 && G != 4) || pk != (pack && pack->v)) return false;
+    return attn_row_lds_bytes(G, pk, pages_bound) <= g_row_lds_max;
+}
+// Once per device, before the first launch (and outside any stream capture): the kernels may ask for as much dynamic LDS
+// as the device gives one block.  -1: the limit could not be raised (the two-pass kernels still work).
+int attn_row_prepare() {
+    // what the device reports: per block, per block on request, and per CU (a single block may take a CU's whole LDS
+    // here); the largest the runtime accepts for every instantiation is the limit
+    int dev = 0, cand[3] = {0, 0, 0};
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    const hipDeviceAttribute_t attrs[3] = {hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, hipDeviceAttributeSharedMemPerBlockOptin,
+                                           hipDeviceAttributeMaxSharedMemoryPerBlock};
+    for (int i = 0; i < 3; ++i)
+        if (hipDeviceGetAttribute(&cand[i], attrs[i], dev) != hipSuccess) { cand[i] = 0; (void)hipGetLastError(); }
+    std::sort(cand, cand + 3, [](int x, int y) { return x > y; });
+    for (int i = 0; i < 3; ++i) {
+        const int lim = cand[i];
+        if (lim <= 0 || (i && lim == cand[i - 1])) continue;
+        hipError_t e = hipSuccess;
+#define MTTS_ROWP(GG, PK) \
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_row_kernel<GG, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
+        MTTS_ROWP(1, false); MTTS_ROWP(1, true); MTTS_ROWP(2, false); MTTS_ROWP(2, true); MTTS_ROWP(4, false); MTTS_ROWP(4, true);
+#undef MTTS_ROWP
+        if (e == hipSuccess) { g_row_lds_max = lim; return 0; }
+        (void)hipGetLastError();
+    }
+    return -1;
+}
+int attn_row_lds_limit() { return g_row_lds_max; }
+
+// One phase per call (AttnPhase, launch.h).  Returns -1 for a group size that is not built, -2 for an ATTN_ROW launch
+// that attn_row_fits refuses.  `fuse` (decode rows only) moves the q/k/v epilogue into ATTN_SCORES and
 // ATTN_PV: no qkv_post launch before them.
 int launch_attn(const void* qbuf, void* kcache, void* vcache, const int32_t* page_table,
                 const RowMeta* meta, void* scores, float* stats, float* opart, void* out_packed, int R,
                 int pages_bound, int max_pages, int total_pages, int nchunks_max, int nq, int nkv, float scale,
                 const QkvFuse* fuse, AttnPhase phase, hipStream_t st, const KvPack* pack) {
     int G = nq / nkv;
+    if (G != 1 && G != 2 && G != 4) return -1;
+    if (phase == ATTN_ROW && !attn_row_fits(G, fuse, pack, pages_bound)) return -2;
 #define MTTS_ATT(GG)                                                                                              \
     launch_attn_g<GG>(qbuf, kcache, vcache, page_table, meta, scores, stats, opart, out_packed, R, pages_bound,   \
                       max_pages, total_pages, nchunks_max, nq, nkv, scale, fuse, phase, st, pack)

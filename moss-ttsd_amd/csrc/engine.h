@@ -217,7 +217,7 @@ struct MttsEngine {
     uint64_t seed = 0;
     bool began = false, has_forced = false;
     // decode-step graphs: one captured step per (rows, KV page bound, ...) key, replayed by mtts_step
-    struct StepGraph { int B, pages, forced, ch0, scores; hipGraphExec_t exec; };
+    struct StepGraph { int B, pages, forced, ch0, scores, row; hipGraphExec_t exec; };
     std::vector<StepGraph> graphs;
     hipStream_t cap_stream = nullptr;
     bool use_graphs = true;
@@ -233,12 +233,28 @@ struct MttsEngine {
     std::vector<char> pack_k_on, pack_v_on;
     int pack_min_work = 512;            // sealed reads from this many rows x KV pages up (MTTS_KV_PACK_MIN)
     int fuse_qkv_max = 2560;            // decode: q/k/v epilogue inside the attention kernels while rows x KV pages <= this (round 3: 1024 -> 2560 = 32 rows x 80 pages, once its loads go out before the page's: wins at 32 x 64, loses at 64 x 64)
+    // whole-row decode attention (attn.hip: attn_row_kernel), MTTS_ATTN_ROW: 0 never, 1 by the shape (attn_row_auto), 2 whenever it fits
+    int attn_row = 1;
+    int n_cus = 0;                      // compute units of the device
     int pf_mfma_pages = 0;              // prefill attention: tile-sharing MFMA kernels from this many KV pages up (0 = always; a dialogue's numerics must not depend on its batch)
     // profiling
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[PROF_N];
     int64_t prof_bytes[PROF_N] = {0, 0, 0, 0};
 };
+
+// MTTS_ATTN_ROW=1: the shapes at which one block per (row, kv head) beats the two-pass kernels -- a function of the shape
+// only (both paths give the same bits, so it may depend on the batch): the blocks have to fill the machine.  No bound on
+// the context: at 32 rows it wins from 3 pages (most waves idle) to 8 k (profiles/attn_row_ab.json), and attn_row_fits
+// ends it where the LDS does
+static inline bool attn_row_auto(int rows, int nkv, int pages_bound, int n_cus) {
+    (void)pages_bound;
+    return n_cus > 0 && rows * nkv >= n_cus;
+}
+static inline bool attn_row_shape(const MttsEngine* e, int pages_bound) {
+    if (e->attn_row == 0 || e->f32) return false;
+    return e->attn_row == 2 || attn_row_auto(e->B, e->nkv, pages_bound, e->n_cus);
+}
 
 // this layer's sealed pools, each null where the read policy (or MTTS_KV_PACK=0) says bf16 pages
 static inline KvPack layer_pack(MttsEngine* e, int n, int pages_bound) {

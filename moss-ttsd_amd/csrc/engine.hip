@@ -210,6 +210,12 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     if (const char* g = getenv("MTTS_KV_PACK")) e->kv_pack = atoi(g);
     if (const char* g = getenv("MTTS_KV_PACK_MIN")) e->pack_min_work = atoi(g);
     if (const char* g = getenv("MTTS_PREFILL_MFMA_PAGES")) e->pf_mfma_pages = atoi(g);
+    if (const char* g = getenv("MTTS_ATTN_ROW")) e->attn_row = std::min(std::max(atoi(g), 0), 2);
+    HIPCHK(hipDeviceGetAttribute(&e->n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (e->attn_row && attn_row_prepare()) {       // auto goes on without the row kernel; asking for it outright is an error
+        if (e->attn_row == 2) return fail(MTTS_EINVAL, "attn_row_kernel: the dynamic LDS limit could not be raised");
+        e->attn_row = 0;
+    }
     if (const char* g = getenv("MTTS_SMALL_ROWS")) e->small_rows = std::min(std::max(atoi(g), 0), SMALL_RP);
     e->gemm_depth = gemm_depth_env();
     e->H = c->hidden_size; e->I = c->intermediate_size; e->L = c->num_hidden_layers;
@@ -503,6 +509,19 @@ static int attend_layer(MttsEngine* e, int n, const RowMeta* d_meta, int R, int 
     uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * n;
     const QkvFuse fz{e->partial, ks_qkv, e->qkv_rows, (const uint16_t*)l.qn, (const uint16_t*)l.kn, e->rope_cos, e->rope_sin, eps};
     const KvPack pk = layer_pack(e, n, pages_bound);
+    const KvPack* pkp = (sealed && (pk.k || pk.v)) ? &pk : nullptr;
+    // decode rows of a full-width batch: the whole section as one launch (the q/k/v epilogue is always inside), timed
+    // under the scores slot with the K + V bytes
+    if (!prefill && sealed && nphases == 3 && attn_row_shape(e, pages_bound) && attn_row_fits(e->nq / e->nkv, &fz, pkp, pages_bound)) {
+        hipEvent_t ev = nullptr;
+        prof_begin(e, PROF_SCORES, st, &ev);
+        if (const int rc = launch_attn(e->qbuf, kc, vc, e->d_page_table, d_meta, e->scores, e->stats, e->opart, e->attn_p, R, pages_bound,
+                                       e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale, &fz, ATTN_ROW, st, pkp))
+            return fail(MTTS_EINVAL, rc == -2 ? "the whole-row attention kernel does not take this launch" : "attention group size not built");
+        prof_end(e, st, ev);
+        if (e->prof) e->prof_bytes[PROF_SCORES] += 2 * kv_tokens_hint * e->nkv * MTTS_HD * 2;
+        return 0;
+    }
     if (!fused)
         launch_qkv_post(e->partial, ks_qkv, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos, e->rope_sin, e->qbuf,
                         kc, vc, e->d_page_table, e->max_pages, e->total_pages, R, e->nq, e->nkv, eps, st);
@@ -511,7 +530,7 @@ static int attend_layer(MttsEngine* e, int n, const RowMeta* d_meta, int R, int 
         if (i < 2) prof_begin(e, i == 0 ? PROF_SCORES : PROF_PV, st, &ev);
         if (launch_attn(e->qbuf, kc, vc, e->d_page_table, d_meta, e->scores, e->stats, e->opart, e->attn_p, R,
                         pages_bound, e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale,
-                        fused ? &fz : nullptr, (prefill ? prefill_ph : decode_ph)[i], st, (sealed && (pk.k || pk.v)) ? &pk : nullptr))
+                        fused ? &fz : nullptr, (prefill ? prefill_ph : decode_ph)[i], st, pkp))
             return fail(MTTS_EINVAL, "attention group size not built");
         if (i < 2) prof_end(e, st, ev);
     }
@@ -887,9 +906,9 @@ static int step_body(MttsEngine* e, int pages_bound, hipStream_t st, int64_t kvt
 }
 
 static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
-    const int forced = e->has_forced ? 1 : 0;
+    const int forced = e->has_forced ? 1 : 0, row = attn_row_shape(e, pages) ? 1 : 0;
     for (auto& g : e->graphs)
-        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled && g.scores == e->scores_on) {
+        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled && g.scores == e->scores_on && g.row == row) {
             *out = g.exec;
             return MTTS_OK;
         }
@@ -905,7 +924,7 @@ static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     HIPCHK(ie);
-    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, e->scores_on, exec});
+    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, e->scores_on, row, exec});
     *out = exec;
     return MTTS_OK;
 }

@@ -212,6 +212,88 @@ int32_t mtts_k_paged_attn_decode(const void* dev_q, const void* dev_k, const voi
     return MTTS_OK;
 }
 
+// Test hook: the attention section of one decode layer -- q/k/v epilogue, scores, P.V, sum of the chunk partials -- on
+// given qkv slabs, through either path: `path` 0 = attn_scores + attn_pv + attn_combine (fused epilogue), 1 = the
+// whole-row kernel (ATTN_ROW).  dev_slabs fp32 [ksplit][R][Npad], Npad = (nq + 2 nkv) * 128: the qkv GEMM's split-K
+// partials of the rows' new token; dev_k / dev_v bf16 [R][Lmax][nkv][128]: the tokens already cached (row r: its first
+// host_lens[r] - 1; host_lens[r] = its length WITH the new token, 0 = an idle row); dev_cos / dev_sin bf16 [Lmax][64];
+// host_page_table as in mtts_k_paged_attn_decode.  `sealed` != 0: every page is also sealed and complete pages are read
+// in that form.  Out: dev_out bf16 [32][nq*128] in the X-fragment layout (as the o_proj GEMM reads it), the bf16 pools
+// dev_kcache / dev_vcache [nkv][R * pages][64 * 128] after the launch (with the new K / V rows) and, when sealed and not
+// null, the sealed pools dev_kpack / dev_vpack [nkv][R * pages][13 * 64 * 16 B].
+int32_t mtts_k_attn_section(const float* dev_slabs, int32_t ksplit, const void* dev_qnw, const void* dev_knw, const void* dev_cos,
+                            const void* dev_sin, float eps, const void* dev_k, const void* dev_v, const int32_t* host_lens,
+                            const int32_t* host_page_table, int32_t R, int32_t Lmax, int32_t nq, int32_t nkv, int32_t sealed,
+                            int32_t path, void* dev_out, void* dev_kcache, void* dev_vcache, void* dev_kpack, void* dev_vpack,
+                            void* stream) {
+    if (!dev_slabs || !dev_qnw || !dev_knw || !dev_cos || !dev_sin || !dev_k || !dev_v || !host_lens || !dev_out || !dev_kcache ||
+        !dev_vcache || R < 1 || R > MTTS_MAXR || Lmax < 1 || nq < 1 || nkv < 1 || nq % nkv || ksplit < 1 || (path != 0 && path != 1))
+        return fail(MTTS_EINVAL, "attn_section: bad argument (1..32 rows, path 0 or 1)");
+    hipStream_t st = S(stream);
+    const int max_pages = (Lmax + MTTS_PAGE - 1) / MTTS_PAGE, total_pages = R * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
+    const int Npad = (nq + 2 * nkv) * MTTS_HD;
+    std::vector<int32_t> hpt((size_t)R * max_pages);
+    std::vector<char> seen(total_pages, 0);
+    for (size_t i = 0; i < hpt.size(); ++i) {
+        hpt[i] = host_page_table ? host_page_table[i] : (int32_t)i;
+        if (hpt[i] < 0 || hpt[i] >= total_pages || seen[hpt[i]]) return fail(MTTS_EINVAL, "page table must be a permutation of 0..%d", total_pages - 1);
+        seen[hpt[i]] = 1;
+    }
+    std::vector<RowMeta> hm(MTTS_MAXR, RowMeta{-1, 0, 0, 0});
+    std::vector<int32_t> cached(R, 0);
+    int pages_bound = 1;
+    for (int r = 0; r < R; ++r) {
+        if (host_lens[r] < 0 || host_lens[r] > Lmax) return fail(MTTS_EINVAL, "row %d: length %d outside 0..%d", r, host_lens[r], Lmax);
+        if (!host_lens[r]) continue;
+        hm[r] = RowMeta{r, host_lens[r] - 1, 1, 0};
+        cached[r] = host_lens[r] - 1;
+        pages_bound = std::max(pages_bound, (host_lens[r] + MTTS_PAGE - 1) / MTTS_PAGE);
+    }
+    pages_bound = std::min(round_up(pages_bound, ATT_PB), max_pages);      // as a captured decode step sizes its launches
+    RowMeta* meta = nullptr; int32_t *pt = nullptr, *lens = nullptr; uint16_t *kc = nullptr, *vc = nullptr, *scores = nullptr, *outp = nullptr;
+    float *stats = nullptr, *opart = nullptr, *slabs = nullptr;
+    uint8_t *kp = nullptr, *vp = nullptr;
+    const size_t cache_n = (size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD, pk_n = (size_t)total_pages * nkv * MTTS_PKU * 64 * 16;
+    DevBufs hb;
+    TRY(hb.get(&meta, MTTS_MAXR)); TRY(hb.get(&pt, hpt.size())); TRY(hb.get(&lens, R));
+    TRY(hb.get(&kc, cache_n)); TRY(hb.get(&vc, cache_n));
+    TRY(hb.get(&scores, (size_t)MTTS_MAXR * nq * max_pages * MTTS_PAGE));
+    TRY(hb.get(&stats, (size_t)MTTS_MAXR * nq * max_pages * 2));
+    TRY(hb.get(&opart, (size_t)MTTS_MAXR * nq * nch * MTTS_HD));
+    TRY(hb.get(&outp, (size_t)MTTS_MAXR * nq * MTTS_HD));
+    TRY(hb.get(&slabs, (size_t)ksplit * MTTS_PFCAP * Npad, false));        // (the kernels' slab stride is MTTS_PFCAP rows)
+    HIPCHK(hipMemcpyAsync(meta, hm.data(), hm.size() * sizeof(RowMeta), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pt, hpt.data(), hpt.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(lens, cached.data(), R * 4, hipMemcpyHostToDevice, st));
+    for (int k = 0; k < ksplit; ++k)
+        HIPCHK(hipMemcpyAsync(slabs + (size_t)k * MTTS_PFCAP * Npad, dev_slabs + (size_t)k * R * Npad, (size_t)R * Npad * 4, hipMemcpyDeviceToDevice, st));
+    launch_pack_kv_pages(dev_k, dev_v, kc, vc, pt, lens, R, Lmax, nkv, max_pages, total_pages, st);
+    KvPack pk{nullptr, nullptr};
+    if (sealed) {
+        TRY(hb.get(&kp, pk_n)); TRY(hb.get(&vp, pk_n));
+        launch_kv_seal_all(kc, vc, kp, vp, total_pages, nkv, 1, nullptr, st);
+        pk = KvPack{kp, vp};
+    }
+    const QkvFuse fz{slabs, ksplit, Npad, (const uint16_t*)dev_qnw, (const uint16_t*)dev_knw, (const uint16_t*)dev_cos, (const uint16_t*)dev_sin, eps};
+    const float scale = 1.0f / sqrtf((float)MTTS_HD);
+    if (path == 1) {
+        if (attn_row_prepare()) return fail(MTTS_EINVAL, "attn_row_kernel: the dynamic LDS limit could not be raised");
+        if (!attn_row_fits(nq / nkv, &fz, sealed ? &pk : nullptr, pages_bound)) return fail(MTTS_EINVAL, "attn_section: the whole-row kernel does not take this shape");
+    }
+    if (const int rc = launch_attn(nullptr, kc, vc, pt, meta, scores, stats, opart, outp, MTTS_MAXR, pages_bound, max_pages, total_pages, nch,
+                                   nq, nkv, scale, &fz, path == 1 ? ATTN_ROW : ATTN_ALL, st, sealed ? &pk : nullptr))
+        return fail(MTTS_EINVAL, rc == -2 ? "attn_section: the whole-row kernel does not take this shape" : "attention group size not built (1, 2, 4)");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dev_out, outp, (size_t)MTTS_MAXR * nq * MTTS_HD * 2, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(dev_kcache, kc, cache_n * 2, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(dev_vcache, vc, cache_n * 2, hipMemcpyDeviceToDevice, st));
+    if (sealed && dev_kpack) HIPCHK(hipMemcpyAsync(dev_kpack, kp, pk_n, hipMemcpyDeviceToDevice, st));
+    if (sealed && dev_vpack) HIPCHK(hipMemcpyAsync(dev_vpack, vp, pk_n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+int64_t mtts_debug_attn_row_launches(void) { return (int64_t)mtts_attn_row_launches(); }
+
 // Test hook for the sealed page format (attn.hip: seal_lane): `npages` bf16 pages of 16 KiB -> sealed pages of 13 KiB.
 int32_t mtts_k_kv_seal(const void* dev_pages, int32_t npages, void* dev_sealed, int32_t as_k, void* stream) {
     if (!dev_pages || !dev_sealed || npages < 1) return fail(MTTS_EINVAL, "kv_seal: bad argument");
@@ -273,12 +355,13 @@ int32_t mtts_debug_set_kv_len(MttsEngine* e, int32_t kv_len) {
     return MTTS_OK;
 }
 
-// Measurement hook: `iters` back-to-back launches of one attention pass (phase 1 = scores, 2 = PV) at the
+// Measurement hook: `iters` back-to-back launches of one attention pass (phase 1 = scores, 2 = PV, 3 = combine of the
+// two-pass kernels; 0 = those three in a row; 4 = the whole-row kernel, whatever MTTS_ATTN_ROW says) at the
 // engine's CURRENT decode state, cycling over the layers' caches; average duration from two HIP events on the
 // launch stream.  (Events around a single launch also time the launch gap, which rocprof's kernel duration
 // does not; a train of launches does not have that bias.)
 int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* avg_ms, int64_t* bytes_per_launch) {
-    if (!e || !e->began || (phase != ATTN_SCORES && phase != ATTN_PV) || iters < 1 || !avg_ms) return fail(MTTS_EINVAL, "attn_bench: bad argument");
+    if (!e || !e->began || phase < ATTN_ALL || phase > ATTN_ROW || iters < 1 || !avg_ms) return fail(MTTS_EINVAL, "attn_bench: bad argument");
     if (e->f32) return fail(MTTS_EINVAL, "measurement hook of the bf16 engine");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipDeviceSynchronize());
@@ -286,6 +369,15 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
     const int R = round_up(e->B, 32);
     const int len_bound = e->max_real + e->steps_issued + 1;
     const int pages_bound = (len_bound + MTTS_PAGE - 1) / MTTS_PAGE;
+    if (phase == ATTN_ROW) {
+        if (attn_row_prepare()) return fail(MTTS_EINVAL, "attn_row_kernel: the dynamic LDS limit could not be raised");
+        const QkvFuse f0{e->partial, e->p_qkv.ksplit, e->qkv_rows, nullptr, nullptr, nullptr, nullptr, 0.f};
+        for (int n = 0; n < e->L; ++n) {
+            const KvPack pk = layer_pack(e, n, pages_bound);
+            if (!attn_row_fits(e->nq / e->nkv, &f0, (pk.k || pk.v) ? &pk : nullptr, pages_bound))
+                return fail(MTTS_EINVAL, "attn_bench: the whole-row kernel does not take this shape");
+        }
+    }
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     auto run = [&](int n) {
@@ -298,7 +390,7 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
                              (const uint16_t*)e->layers[layer].kn, e->rope_cos, e->rope_sin, e->cfg.rms_norm_eps};
             const KvPack pk = layer_pack(e, layer, pages_bound);
             launch_attn(e->qbuf, kc, vc, e->d_page_table, e->d_meta, e->scores, e->stats, e->opart, e->attn_p, R, pages_bound,
-                        e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale, e->B * pages_bound <= e->fuse_qkv_max ? &fz : nullptr, (AttnPhase)phase, nullptr,
+                        e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale, (phase == ATTN_ROW || e->B * pages_bound <= e->fuse_qkv_max) ? &fz : nullptr, (AttnPhase)phase, nullptr,
                         (pk.k || pk.v) ? &pk : nullptr);
         }
     };
@@ -315,7 +407,8 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
         HIPCHK(hipMemcpy(m.data(), e->d_meta, m.size() * sizeof(RowMeta), hipMemcpyDeviceToHost));
         int64_t tok = 0;
         for (int b = 0; b < R; ++b) if (m[b].seq >= 0) tok += m[b].pos + 1;
-        *bytes_per_launch = tok * e->nkv * MTTS_HD * 2;
+        // K, V or both; the combine reads neither
+        *bytes_per_launch = phase == ATTN_COMBINE ? 0 : tok * e->nkv * MTTS_HD * 2 * ((phase == ATTN_ALL || phase == ATTN_ROW) ? 2 : 1);
     }
     hipEventDestroy(e0); hipEventDestroy(e1);
     return MTTS_OK;

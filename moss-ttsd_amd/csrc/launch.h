@@ -55,11 +55,16 @@ void launch_unpack_rows(const void* packed, void* out, int R, int K, hipStream_t
 // for prefill tiles (32 consecutive positions of one dialogue), or ATTN_ALL = the three decode phases in one call.
 // (mtts_k_attn_bench takes the number across the ABI: the values stay.)
 enum AttnPhase { ATTN_ALL = 0, ATTN_SCORES = 1, ATTN_PV = 2, ATTN_COMBINE = 3,
+                 ATTN_ROW = 4,       // the three decode phases as one launch, one block per (row, kv head): needs `fuse`
                  ATTN_PF_SCORES = 11, ATTN_PF_PV = 12, ATTN_PF_COMBINE = 13 };
 int launch_attn(const void* qbuf, void* kcache, void* vcache, const int32_t* page_table,
                 const RowMeta* meta, void* scores, float* stats, float* opart, void* out_packed, int R,
                 int pages_bound, int max_pages, int total_pages, int nchunks_max, int nq, int nkv, float scale,
                 const QkvFuse* fuse, AttnPhase phase, hipStream_t st, const KvPack* pack = nullptr);
+bool attn_row_fits(int G, const QkvFuse* fuse, const KvPack* pack, int pages_bound);   // ATTN_ROW can take this launch
+int attn_row_prepare();                  // once per device before the first ATTN_ROW launch (raises the kernels' LDS limit to the device's; -1: refused)
+int attn_row_lds_limit();                // bytes of dynamic LDS an ATTN_ROW block may take (0 before attn_row_prepare)
+long long mtts_attn_row_launches();      // ATTN_ROW launches issued by this process (captures count once)
 void launch_kv_seal_rows(const void* kcache, const void* vcache, void* kpack, void* vpack, const int32_t* page_table,
                          const RowMeta* meta, int R, int max_pages, int total_pages, int nkv, int L, unsigned long long* cnt, hipStream_t st);
 void launch_kv_seal_all(const void* kcache, const void* vcache, void* kpack, void* vpack, int total_pages, int nkv, int L,

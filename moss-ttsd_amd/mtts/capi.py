@@ -91,6 +91,9 @@ _SIGS = {
     "mtts_k_gemm_bf16": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p]),
     "mtts_debug_gemm_depth_launches": (C.c_int64, []),
+    "mtts_debug_attn_row_launches": (C.c_int64, []),
+    "mtts_k_attn_section": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 4 +
+                            [C.c_int32] * 6 + [C.c_void_p] * 6),
     "mtts_k_gemm_swiglu_bf16": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mtts_k_rmsnorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "mtts_k_rope_kvwrite": (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 4),
