@@ -154,6 +154,23 @@ int32_t mtts_read_generated(MttsEngine* e, int64_t* host_gen, int32_t capacity_s
 int32_t mtts_set_output_scores(MttsEngine* e, int32_t on);
 int32_t mtts_read_scores(MttsEngine* e, float* host_lp, int32_t capacity_steps, int32_t* n_steps);
 int32_t mtts_slot_read_scores(MttsEngine* e, int32_t slot, float* host_rows, int32_t capacity_steps, int32_t* n_steps);
+/* ---- teacher-forced scoring: the labels branch of AsteroidTTSInstruct.forward (modeling_asteroid.py:382-410: per channel
+ * lm_heads[i](hidden_states) and ForCausalLMLoss) reduced to one float per label; what inference engines call prompt
+ * log-probabilities.  host_input_ids int64 [B,T,8], host_attention_mask uint8 [B,T], host_labels int64 [B,T,8] (-100 =
+ * ignore), host_logp float [B,T,8] (out).  The HF shift applies: logp[b][t][c] = log_softmax(logits_c(h[b][t-1]))[labels[b][t][c]]
+ * for t >= 1, with logits_c in the model dtype upcast to fp32 (transformers ForCausalLMLoss); NaN at t = 0, at ignored
+ * labels and at padding (the convention of mtts_read_scores).  The caller reduces: loss_all[c] = -mean of the non-NaN
+ * logp[..., c].  Sequences are RIGHT-padded or unpadded (each mask row ones, then zeros, as causal-LM collators produce):
+ * real token i sits at position i, the reference's arange(T) positions when forward gets no position_ids.  The logits are
+ * never materialised (bf16 engine: fused head GEMM + log-sum-exp, csrc/score.hip); a value is run-to-run bit-identical
+ * and does not depend on what else shares the batch.  The KV pages the call takes are back in the pool when it returns
+ * and no state of a generation survives or is needed: mtts_begin afterwards behaves as if the call had not happened.
+ * Synchronous: `stream` is drained before it returns, on success and on failure, the device page table included.
+ * MTTS_EINVAL: a left-padded (or otherwise not ones-then-zeros) mask row, a label other than -100 at a
+ * masked position or outside [0, V_c), a token out of range, B > max_batch, T > max_seq_len; MTTS_ESTATE: a run is open
+ * (the rule of mtts_set_output_scores); MTTS_ENOMEM: the pool cannot hold the batch (reported before any launch). */
+int32_t mtts_score(MttsEngine* e, const int64_t* host_input_ids, const uint8_t* host_attention_mask,
+                   const int64_t* host_labels, int32_t B, int32_t T, float* host_logp, void* stream);
 /* last forward's logits: bf16 bits, channel 0 [B,vocab_size], channels 1..7 [7,B,speech_vocab_size] */
 int32_t mtts_read_logits(MttsEngine* e, uint16_t* host_logits0, uint16_t* host_logits17, void* stream);
 /* the same for an MTTS_DTYPE_F32 engine: fp32 logits */
@@ -212,6 +229,8 @@ int32_t mtts_debug_read_device_page_table(MttsEngine* e, int32_t* host_table, vo
 int32_t mtts_export_codes(MttsEngine* e, int32_t first, int32_t n, int64_t* dev_codes, void* stream);
 /* name of / time spent in the dominant decode kernel since the last reset, measured with hipEvents
  * on the launch stream (bench.py's roofline leg). */
+/* which: 0 attention scores, 1 P.V, 2 GEMM, 3 whole decode step, 4 the scoring kernels of mtts_score (head_ce_kernel +
+ * ce_finish_kernel, one entry per prefill pass). */
 int32_t mtts_profile_enable(MttsEngine* e, int32_t on);
 int32_t mtts_profile_read(MttsEngine* e, int32_t which, double* total_ms, int64_t* launches, int64_t* bytes);
 
@@ -288,6 +307,14 @@ int32_t mtts_k_paged_attn_decode(const void* dev_q, const void* dev_k, const voi
  * divided by 2^s[t], s[t] = (rounded mean of the non-zero exponent fields of token t's 128 values) - (the smallest such
  * mean of the page), rounded down to even, 0..126 (0 for an all-zero token); lane t keeps s[t] in the low byte of its spare; the same flags. */
 int32_t mtts_k_kv_seal(const void* dev_pages, int32_t npages, void* dev_sealed, int32_t as_k, void* stream);
+/* The scoring kernels on their own (mtts_score: lm_heads[i] + ForCausalLMLoss per token, modeling_asteroid.py:398-399):
+ * dev_w bf16 [N,K] row-major, dev_x bf16 [M,K], host_labels int32 [M * segments] (< 0 = ignore), dev_logp float
+ * [M * segments] = log_softmax over the first n_valid columns of bf16(X W^T) at the label, NaN where ignored.
+ * segments == 1: one head, n_valid <= N (rows n_valid..N-1 of W are padding the kernel must drop).  segments > 1: the
+ * speech-head layout, N = segments * n_valid, head s = rows [s * n_valid, (s + 1) * n_valid), each padded to a multiple
+ * of 32 rows in the packed matrix; labels and logp are [M][segments].  M <= 2048, K % 16 == 0. */
+int32_t mtts_k_head_ce(const void* dev_w, const void* dev_x, const int32_t* host_labels, int32_t M, int32_t N, int32_t K,
+                       int32_t n_valid, int32_t segments, float* dev_logp, void* stream);
 /* One sampler call on fp32-from-bf16 logits (HF processors + engine draw). */
 int32_t mtts_k_sample(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
                       const void* dev_history_bitmap, const MttsSamplerCfg* cfg,

@@ -98,6 +98,41 @@ __host__ __device__ __forceinline__ size_t xpack_off(int r, int k, int K) {
     return (size_t)(r >> 5) * 32 * K + (((size_t)(k >> 4) * 64) + (r & 31) + 32 * ((k >> 3) & 1)) * 8 + (k & 7);
 }
 
+// Main loop of the 128 x 128 tiled GEMMs (gemm.hip: gemm_tile_kernel; score.hip: head_ce_kernel): a wave's 2 x 2
+// accumulators acc[column tile][row tile] over k-tiles [0, n) of its two W tiles (w0, w1) and two X tiles (x0, x1), all
+// four pointers already at the wave's first k-tile and at the lane.  Fragments go straight from the packed layouts into
+// v_mfma_f32_32x32x16_bf16, eight k-tiles of loads in flight; each accumulator sums k in ascending order.  One copy, so
+// that a product computed by either kernel is the same number.
+__device__ __forceinline__ void tile_mainloop(f32x16_t (&acc)[2][2], const u32x4_t* __restrict__ w0, const u32x4_t* __restrict__ w1,
+                                              const u32x4_t* __restrict__ x0, const u32x4_t* __restrict__ x1, int n) {
+    constexpr int U = 8;
+    int i = 0;
+    for (; i + U <= n; i += U) {
+        u32x4_t a0[U], a1[U], b0[U], b1[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            a0[u] = w0[(size_t)(i + u) * 64];
+            a1[u] = w1[(size_t)(i + u) * 64];
+            b0[u] = x0[(size_t)(i + u) * 64];
+            b1[u] = x1[(size_t)(i + u) * 64];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a0[u], *(bf16x8_t*)&b0[u], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a0[u], *(bf16x8_t*)&b1[u], acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a1[u], *(bf16x8_t*)&b0[u], acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a1[u], *(bf16x8_t*)&b1[u], acc[1][1], 0, 0, 0);
+        }
+    }
+    for (; i < n; ++i) {
+        const u32x4_t a0 = w0[(size_t)i * 64], a1 = w1[(size_t)i * 64], b0 = x0[(size_t)i * 64], b1 = x1[(size_t)i * 64];
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a0, *(bf16x8_t*)&b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a0, *(bf16x8_t*)&b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a1, *(bf16x8_t*)&b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a1, *(bf16x8_t*)&b1, acc[1][1], 0, 0, 0);
+    }
+}
+
 // Decode rows: the q/k/v epilogue (split-K reduce, per-head RMSNorm, RoPE, cache write) runs inside the attention
 // kernels instead of a launch of its own; they need the qkv GEMM's slabs and the layer's small vectors.
 struct QkvFuse {

@@ -129,7 +129,9 @@ struct Layer {
     int bound = 0;
 };
 
-enum { PROF_SCORES = 0, PROF_PV = 1, PROF_GEMM = 2, PROF_STEP = 3, PROF_N = 4 };
+enum { PROF_SCORES = 0, PROF_PV = 1, PROF_GEMM = 2, PROF_STEP = 3,
+       PROF_CE = 4,          // mtts_score: head_ce_kernel + ce_finish_kernel of a pass (both launches of the 8 heads)
+       PROF_N = 5 };
 
 struct MttsEngine {
     DevBufs mem;                        // owns every device / pinned pointer below
@@ -204,6 +206,12 @@ struct MttsEngine {
     int scores_next = 0;                // mtts_set_output_scores: read by the next mtts_begin / mtts_generate / mtts_sched_open
     int scores_on = 0;                  // of the current run
     bool run_open = false;              // a run has begun and has not been seen to end (mtts_set_output_scores)
+    // teacher-forced scoring (mtts_score; score.hip): allocated by the first call
+    int32_t* d_sc_labels = nullptr;     // [staged rows][8]: the label of the row's NEXT position, -100 = none
+    float* d_sc_logp = nullptr;         // [staged rows][8]
+    size_t sc_cap_rows = 0;
+    float* sc_part = nullptr;           // bf16 engine: (m, s, l_label) per row of a pass and 128-column block, head 0 then heads 1..7
+    float* sc_logits = nullptr;         // fp32 / fp16 engines: fp32 logits of SCORE_F32_ROWS rows of one head
     int32_t* d_pf_tokens = nullptr;     // prefill staging
     RowMeta* d_pf_meta = nullptr;
     size_t pf_cap_rows = 0;
@@ -240,7 +248,7 @@ struct MttsEngine {
     // profiling
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[PROF_N];
-    int64_t prof_bytes[PROF_N] = {0, 0, 0, 0};
+    int64_t prof_bytes[PROF_N] = {0, 0, 0, 0, 0};
 };
 
 // MTTS_ATTN_ROW=1: the shapes at which one block per (row, kv head) beats the two-pass kernels -- a function of the shape

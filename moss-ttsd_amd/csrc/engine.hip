@@ -3,6 +3,7 @@
 //
 // Mirrors (file:line in /root/reference):
 //   AsteroidTTSInstruct.forward inference branch   modeling_asteroid.py:337-380,411-426
+//   AsteroidTTSInstruct.forward labels branch      modeling_asteroid.py:382-410 (mtts_score; kernels: score.hip)
 //   AsteroidTTSModel._prepare_multi_modal_inputs    modeling_asteroid.py:235-250
 //   CustomMixin._sample                             modeling_asteroid.py:83-169
 // and, third-party, transformers Qwen3Model.forward (models/qwen3/modeling_qwen3.py).
@@ -1057,23 +1058,30 @@ int32_t mtts_read_generated(MttsEngine* e, int64_t* host_gen, int32_t capacity_s
     return read_rows(e, e->d_gen, host_gen, capacity_steps, n_steps);
 }
 
+// A run counts as open until the device says it has ended: every row finished / every slot empty.  -> *open.
+static int run_still_open(MttsEngine* e, bool* open) {
+    *open = false;
+    if (!e->run_open) return MTTS_OK;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());
+    LoopState ls;
+    std::vector<SeqState> ss(MTTS_RCAP);
+    HIPCHK(hipMemcpy(&ls, e->d_ls, sizeof(ls), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ss.data(), e->d_seqs, ss.size() * sizeof(SeqState), hipMemcpyDeviceToHost));
+    bool live = false;
+    for (int b = 0; b < e->B; ++b) live |= ss[b].active != 0;
+    if (live && !ls.done) *open = true;
+    else e->run_open = false;
+    return MTTS_OK;
+}
+
 int32_t mtts_set_output_scores(MttsEngine* e, int32_t on) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     on = on ? 1 : 0;
     if (on == e->scores_next) return MTTS_OK;
-    if (e->run_open) {                   // the device knows whether the run has ended: every row finished / every slot empty
-        HIPCHK(hipSetDevice(e->device));
-        HIPCHK(hipDeviceSynchronize());
-        LoopState ls;
-        std::vector<SeqState> ss(MTTS_RCAP);
-        HIPCHK(hipMemcpy(&ls, e->d_ls, sizeof(ls), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ss.data(), e->d_seqs, ss.size() * sizeof(SeqState), hipMemcpyDeviceToHost));
-        bool live = false;
-        for (int b = 0; b < e->B; ++b) live |= ss[b].active != 0;
-        if (live && !ls.done)
-            return fail(MTTS_ESTATE, "output_scores cannot change while a run is open (it is read when a run begins)");
-        e->run_open = false;
-    }
+    bool open = false;
+    TRY(run_still_open(e, &open));
+    if (open) return fail(MTTS_ESTATE, "output_scores cannot change while a run is open (it is read when a run begins)");
     e->scores_next = on;
     return MTTS_OK;
 }
@@ -1085,6 +1093,175 @@ int32_t mtts_read_scores(MttsEngine* e, float* host_lp, int32_t capacity_steps, 
     HIPCHK(hipSetDevice(e->device));
     TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
     return read_rows(e, e->d_lp, host_lp, capacity_steps, n_steps);
+}
+
+// ---- teacher-forced scoring (the labels branch of AsteroidTTSInstruct.forward, modeling_asteroid.py:382-410) ---------
+#define SCORE_F32_ROWS 64      // fp32 / fp16 engines: rows whose logits of one head are materialised at a time (64 x 152 704 x 4 B = 37 MiB)
+
+// While a scoring pass runs, completed KV pages are not sealed: no decode follows that would read the sealed form, and
+// the seal counters steer the read policy of generation runs.
+struct NoSeal {
+    MttsEngine* e; void* k;
+    explicit NoSeal(MttsEngine* e_) : e(e_), k(e_->kpack) { e->kpack = nullptr; }
+    ~NoSeal() { e->kpack = k; }
+};
+
+// heads + log-softmax + label pick on the `rows` final-normed rows the pass has just left in xn (bf16: packed) / xnf
+static int score_pass(MttsEngine* e, const int32_t* labels, float* logp, int rows, hipStream_t st) {
+    const int H = e->H;
+    if (!e->f32) {
+        float* part17 = e->sc_part + head_ce_part_elems(MTTS_PFCAP, e->V0, 1);
+        hipEvent_t ev = nullptr;
+        prof_begin(e, PROF_CE, st, &ev);
+        launch_head_ce(e->head0, e->xn, rows, H, e->V0, 1, labels, 8, 0, e->sc_part, logp, 8, 0, st);
+        launch_head_ce(e->heads17, e->xn, rows, H, e->Vs, 7, labels, 8, 1, part17, logp, 8, 1, st);
+        prof_end(e, st, ev);
+        if (e->prof) e->prof_bytes[PROF_CE] += ((int64_t)e->V0_pad + 7 * e->Vs_pad) * H * 2;       // one read of the heads
+    } else {
+        for (int r0 = 0; r0 < rows; r0 += SCORE_F32_ROWS) {
+            const int n = std::min(SCORE_F32_ROWS, rows - r0);
+            for (int c = 0; c < 8; ++c) {
+                const int V = c == 0 ? e->V0 : e->Vs;
+                launch_f32_linear(e->embf[c], e->xnf + (size_t)r0 * H, e->sc_logits, n, V, H, e->V0_pad, e->h16, false, st);
+                launch_ce_rows_f32(e->sc_logits, e->V0_pad, n, V, labels + (size_t)r0 * 8, 8, c, logp + (size_t)r0 * 8, 8, c, st);
+            }
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return MTTS_OK;
+}
+
+int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const int64_t* labels, int32_t B, int32_t T,
+                   float* host_logp, void* stream) {
+    if (!e || !ids || !mask || !labels || !host_logp) return fail(MTTS_EINVAL, "null argument");
+    TRY(mtts_weights_ready(e));
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = S(stream);
+    if (B < 1 || B > e->cfg.max_batch) return fail(MTTS_EINVAL, "batch %d outside 1..max_batch %d", B, e->cfg.max_batch);
+    if (T < 1 || T > e->cfg.max_seq_len) return fail(MTTS_EINVAL, "T %d outside 1..max_seq_len %d", T, e->cfg.max_seq_len);
+    if (T > e->rope_rows) return fail(MTTS_EINVAL, "rope table has %d rows, need %d", e->rope_rows, T);
+    bool open = false;
+    TRY(run_still_open(e, &open));
+    if (open) return fail(MTTS_ESTATE, "mtts_score while a run is open: its rows still own KV pages and the activation buffers");
+    // masks: ones, then zeros (real token i sits at position i, the reference's arange(T) positions)
+    std::vector<int> len(B, 0);
+    int max_len = 0;
+    for (int b = 0; b < B; ++b) {
+        const uint8_t* m = mask + (size_t)b * T;
+        int n = 0;
+        while (n < T && m[n]) ++n;
+        for (int t = n; t < T; ++t)
+            if (m[t]) {
+                if (n == 0) return fail(MTTS_EINVAL, "attention_mask of row %d is left-padded: mtts_score takes right-padded or unpadded rows (ones, then zeros)", b);
+                return fail(MTTS_EINVAL, "attention_mask of row %d is not ones followed by zeros (right-padded or unpadded rows only)", b);
+            }
+        len[b] = n;
+        max_len = std::max(max_len, n);
+    }
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < T; ++t)
+            for (int c = 0; c < 8; ++c) {
+                const int64_t V = c == 0 ? e->V0 : e->Vs, lb = labels[((size_t)b * T + t) * 8 + c], tk = ids[((size_t)b * T + t) * 8 + c];
+                if (t >= len[b]) {
+                    if (lb != -100) return fail(MTTS_EINVAL, "label %lld at a masked position (row %d, position %d, channel %d)", (long long)lb, b, t, c);
+                    continue;
+                }
+                if (tk < 0 || tk >= V) return fail(MTTS_EINVAL, "token %lld out of range on channel %d", (long long)tk, c);
+                if (lb != -100 && (lb < 0 || lb >= V)) return fail(MTTS_EINVAL, "label %lld outside [0, %lld) on channel %d", (long long)lb, (long long)V, c);
+            }
+    // pages: the need is checked against the pool before anything is launched
+    size_t need = 0;
+    for (int b = 0; b < B; ++b) need += (size_t)(len[b] + MTTS_PAGE - 1) / MTTS_PAGE;
+    if (need > e->free_pages.size())
+        return fail(MTTS_ENOMEM, "scoring needs %zu KV pages, the pool has %zu free (%d pages of %d tokens)", need, e->free_pages.size(), e->total_pages, MTTS_PAGE);
+    // staged rows as in begin_run: every sequence starts on a 32-row tile boundary, filler rows are idle; the row of
+    // position t carries labels[t + 1] (the HF shift), the last position of a sequence and the fillers carry none
+    size_t Mtot = 0;
+    for (int b = 0; b < B; ++b) Mtot += (size_t)round_up(len[b], MTTS_MAXR);
+    const size_t Mpad = std::max<size_t>((Mtot + MTTS_RCAP - 1) / MTTS_RCAP * MTTS_RCAP, MTTS_RCAP);
+    std::vector<int32_t> toks(Mpad * 8, 0), labs(Mpad * 8, -100);
+    std::vector<RowMeta> metas(Mpad, RowMeta{-1, 0, 0, 0});
+    std::vector<size_t> row0(B, 0);
+    size_t r = 0;
+    for (int b = 0; b < B; r = (r + MTTS_MAXR - 1) / MTTS_MAXR * MTTS_MAXR, ++b) {
+        row0[b] = r;
+        for (int i = 0; i < len[b]; ++i, ++r) {
+            for (int c = 0; c < 8; ++c) {
+                toks[r * 8 + c] = (int32_t)ids[((size_t)b * T + i) * 8 + c];
+                if (i + 1 < len[b]) labs[r * 8 + c] = (int32_t)labels[((size_t)b * T + i + 1) * 8 + c];
+            }
+            metas[r] = RowMeta{b, i, 0, 0};
+        }
+    }
+    TRY(grow_prefill_staging(e, Mpad));
+    if (Mpad > e->sc_cap_rows) {
+        e->mem.release(e->d_sc_labels); e->mem.release(e->d_sc_logp);
+        e->sc_cap_rows = 0;
+        TRY(e->mem.get(&e->d_sc_labels, Mpad * 8, false));
+        TRY(e->mem.get(&e->d_sc_logp, Mpad * 8, false));
+        e->sc_cap_rows = Mpad;
+    }
+    if (!e->f32 && !e->sc_part)
+        TRY(e->mem.get(&e->sc_part, head_ce_part_elems(MTTS_PFCAP, e->V0, 1) + head_ce_part_elems(MTTS_PFCAP, e->Vs, 7), false));
+    if (e->f32 && !e->sc_logits) TRY(e->mem.get(&e->sc_logits, (size_t)SCORE_F32_ROWS * e->V0_pad, false));
+    // Sequence b borrows page-table row b.  The last run has ended, but a row may still list pages of it (they go back
+    // with the next mtts_begin): those entries are set aside and put back, and the borrowed pages return to the free
+    // list in the reverse of the order they were taken in, so the pool -- counts and page numbering -- is as before.
+    struct Borrow {
+        MttsEngine* e; int B; hipStream_t st;
+        std::vector<std::vector<int32_t>> kept;
+        Borrow(MttsEngine* e_, int B_, hipStream_t st_) : e(e_), B(B_), st(st_), kept(B_) {
+            for (int b = 0; b < B; ++b) {
+                kept[b].assign(e->h_page_table.begin() + (size_t)b * e->max_pages, e->h_page_table.begin() + (size_t)b * e->max_pages + e->n_pages[b]);
+                e->n_pages[b] = 0;
+            }
+        }
+        // Every return path: first wait for what was enqueued (launches that touch the borrowed pages, copies from the
+        // caller's host vectors), then give the pages back, restore the rows and wait for the device table to follow.
+        int end() {
+            if (done) return rc;
+            done = true;
+            auto note = [&](int r) { if (!rc) rc = r; };
+            if (hipStreamSynchronize(st) != hipSuccess) note(fail(MTTS_EHIP, "mtts_score: the stream failed while the pass ran"));
+            for (int b = B - 1; b >= 0; --b) pool_release(e, b);
+            for (int b = 0; b < B; ++b)
+                for (int32_t page : kept[b]) note(pool_append(e, b, page, st));
+            note(pool_flush(e, st));
+            if (hipStreamSynchronize(st) != hipSuccess) note(fail(MTTS_EHIP, "mtts_score: restoring the page table failed"));
+            return rc;
+        }
+        ~Borrow() {                    // (an error return: the error that caused it is the one reported)
+            const std::string keep = g_err;
+            end();
+            snprintf(g_err, sizeof(g_err), "%s", keep.c_str());
+        }
+        bool done = false; int rc = 0;
+    } borrow(e, B, st);
+    for (int b = 0; b < B; ++b) TRY(pool_grow(e, b, (len[b] + MTTS_PAGE - 1) / MTTS_PAGE, st));
+    TRY(pool_flush(e, st));
+    HIPCHK(hipMemcpyAsync(e->d_pf_tokens, toks.data(), Mpad * 8 * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->d_pf_meta, metas.data(), Mpad * sizeof(RowMeta), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->d_sc_labels, labs.data(), Mpad * 8 * 4, hipMemcpyHostToDevice, st));
+    {
+        NoSeal ns(e);
+        const size_t pfcap = e->f32 ? MTTS_PF32CAP : MTTS_PFCAP;
+        const int pages_bound = std::max(1, (max_len + MTTS_PAGE - 1) / MTTS_PAGE);
+        for (size_t off = 0; off < Mpad; off += pfcap) {
+            const int rows = (int)std::min<size_t>(pfcap, Mpad - off);
+            TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, 0, st, 0));
+            TRY(score_pass(e, e->d_sc_labels + off * 8, e->d_sc_logp + off * 8, rows, st));
+        }
+    }
+    std::vector<float> lp(Mpad * 8);
+    HIPCHK(hipMemcpyAsync(lp.data(), e->d_sc_logp, Mpad * 8 * sizeof(float), hipMemcpyDeviceToHost, st));
+    TRY(borrow.end());                 // drains st: the copy has landed, the pool and both page tables are as before
+    // logp[b][t] = what the row of position t - 1 computed; NaN at t = 0, at ignored labels and at padding
+    const float nanv = __builtin_nanf("");
+    for (size_t i = 0; i < (size_t)B * T * 8; ++i) host_logp[i] = nanv;
+    for (int b = 0; b < B; ++b)
+        for (int t = 1; t < len[b]; ++t)
+            memcpy(host_logp + ((size_t)b * T + t) * 8, lp.data() + (row0[b] + t - 1) * 8, 8 * sizeof(float));
+    return MTTS_OK;
 }
 
 int32_t mtts_read_logits_f32(MttsEngine* e, float* l0, float* l17, void* stream) {

@@ -489,33 +489,7 @@ __global__ __launch_bounds__(256) void gemm_tile_kernel(
     const u32x4_t* w1 = Wp + ((size_t)(n1 ? nt0 + 1 : nt0) * KT + kt0) * 64 + lane;
     const u32x4_t* x0 = Xp + (size_t)rt0 * xtile + (size_t)kt0 * 64 + lane;
     const u32x4_t* x1 = Xp + (size_t)(r1 ? rt0 + 1 : rt0) * xtile + (size_t)kt0 * 64 + lane;
-    constexpr int U = 8;
-    const int n = kt1 - kt0;
-    int i = 0;
-    for (; i + U <= n; i += U) {
-        u32x4_t a0[U], a1[U], b0[U], b1[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            a0[u] = w0[(size_t)(i + u) * 64];
-            a1[u] = w1[(size_t)(i + u) * 64];
-            b0[u] = x0[(size_t)(i + u) * 64];
-            b1[u] = x1[(size_t)(i + u) * 64];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a0[u], *(bf16x8_t*)&b0[u], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a0[u], *(bf16x8_t*)&b1[u], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a1[u], *(bf16x8_t*)&b0[u], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a1[u], *(bf16x8_t*)&b1[u], acc[1][1], 0, 0, 0);
-        }
-    }
-    for (; i < n; ++i) {
-        const u32x4_t a0 = w0[(size_t)i * 64], a1 = w1[(size_t)i * 64], b0 = x0[(size_t)i * 64], b1 = x1[(size_t)i * 64];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a0, *(bf16x8_t*)&b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a0, *(bf16x8_t*)&b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a1, *(bf16x8_t*)&b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(bf16x8_t*)&a1, *(bf16x8_t*)&b1, acc[1][1], 0, 0, 0);
-    }
+    tile_mainloop(acc, w0, w1, x0, x1, kt1 - kt0);
     // D[n][row]: lane holds column row = lane&31 and n = (i&3) + 8*(i>>2) + 4*(lane>>5)
 #pragma unroll
     for (int a = 0; a < 2; ++a) {

@@ -50,6 +50,39 @@ int32_t mtts_k_gemm_swiglu_bf16(const void* w, const void* x, void* y, int32_t M
     return MTTS_OK;
 }
 
+// The scoring kernels (score.hip) on a row-major head and activation: packed with the engine's pack launchers (heads of
+// n_valid rows at multiples of round_up(n_valid, 32), like heads17), then head_ce_kernel + ce_finish_kernel.
+int32_t mtts_k_head_ce(const void* w, const void* x, const int32_t* host_labels, int32_t M, int32_t N, int32_t K, int32_t n_valid,
+                       int32_t segments, float* dev_logp, void* stream) {
+    if (!w || !x || !host_labels || !dev_logp || M < 1 || M > MTTS_PFCAP || K < 16 || K % 16 || n_valid < 1 || segments < 1 ||
+        (segments == 1 ? n_valid > N : N != segments * n_valid))
+        return fail(MTTS_EINVAL, "head_ce: need 1<=M<=MTTS_PFCAP, K%%16==0, n_valid<=N (one head) or N==segments*n_valid");
+    for (int i = 0; i < M * segments; ++i)
+        if (host_labels[i] >= n_valid) return fail(MTTS_EINVAL, "head_ce: label %d outside [0, %d)", host_labels[i], n_valid);
+    hipStream_t st = S(stream);
+    const int seg_pad = round_up(segments == 1 ? N : n_valid, 32), Mpad = round_up(M, 32);
+    uint16_t *wp = nullptr, *xp = nullptr;
+    int32_t* lab = nullptr;
+    float* part = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&wp, (size_t)segments * seg_pad * K));
+    TRY(hb.get(&xp, (size_t)Mpad * K));
+    TRY(hb.get(&lab, (size_t)Mpad * segments, false));
+    TRY(hb.get(&part, head_ce_part_elems(M, n_valid, segments), false));
+    std::vector<int32_t> hl((size_t)Mpad * segments, -100);
+    std::copy(host_labels, host_labels + (size_t)M * segments, hl.begin());
+    HIPCHK(hipMemcpyAsync(lab, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st));
+    if (segments == 1) launch_pack_weight(w, wp, N, K, seg_pad, 1, 0, st);
+    else
+        for (int s = 0; s < segments; ++s)
+            launch_pack_weight((const uint16_t*)w + (size_t)s * n_valid * K, wp, n_valid, K, segments * seg_pad, 1, s * seg_pad, st);
+    launch_pack_rows(x, xp, M, K, Mpad / 32, st);
+    launch_head_ce(wp, xp, M, K, n_valid, segments, lab, segments, 0, part, dev_logp, segments, 0, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
 int32_t mtts_k_rmsnorm(const void* x, const void* w, void* y, int32_t rows, int32_t n, float eps, void* stream) {
     if (!x || !w || !y || rows < 1 || n < 1) return fail(MTTS_EINVAL, "rmsnorm: bad argument");
     launch_rmsnorm_rows(x, w, y, rows, n, eps, S(stream));

@@ -149,6 +149,21 @@ void launch_f32_attn(const float* qbuf, const float* kcache, const float* vcache
                      int h16, hipStream_t st);
 void launch_f32_swiglu(const float* gu, float* act, int R, int I, int h16, hipStream_t st);
 
+// ---- score.hip ------------------------------------------------------------------------------------------------------
+// Teacher-forced scoring (mtts_score).  A head of n_valid columns is cut into blocks of 128 columns (4 MFMA tiles): a
+// function of the vocabulary alone.  launch_head_ce: packed head weights (`segments` heads of round_up(n_valid, 32) rows
+// one after another) x packed activations of R rows -> logp[row * out_stride + out_off + seg] = log_softmax(bf16 logits
+// of head seg)[labels[row * lab_stride + lab_off + seg]], NaN where that label is < 0.  labels must hold round_up(R, 32)
+// rows, `part` head_ce_part_elems(R, n_valid, segments) floats.
+static inline int round_up32(int a) { return (a + 31) / 32 * 32; }
+static inline int head_ce_blocks(int n_valid) { return ((n_valid + 31) / 32 + 3) / 4; }
+size_t head_ce_part_elems(int rows, int n_valid, int segments);
+void launch_head_ce(const void* Wp, const void* Xp, int R, int K, int n_valid, int segments, const int32_t* labels, int lab_stride,
+                    int lab_off, float* part, float* logp, int out_stride, int out_off, hipStream_t st);
+// the same on R rows of materialised fp32 logits [R][ldy] of one head (fp32 / fp16 engines)
+void launch_ce_rows_f32(const float* logits, long ldy, int R, int n_valid, const int32_t* labels, int lab_stride, int lab_off,
+                        float* logp, int out_stride, int out_off, hipStream_t st);
+
 // ---- codec.hip / codec_fused.hip ------------------------------------------------------------------------------------
 void mtts_gemm_f32_exact(hipStream_t st, const float* A, const float* W, float* C, int M, int N, int K, long ldc);
 void launch_split_pack_w2perm(hipStream_t st, const float* w2, uint16_t* hi, uint16_t* lo);

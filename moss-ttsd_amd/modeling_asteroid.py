@@ -3,7 +3,7 @@
 Keeps the call surface `generation_utils` / `inference.py` use
 (reference modeling_asteroid.py: AsteroidTTSConfig :17-28, AsteroidTTSInstruct :288,
 `.from_pretrained`, `.eval()`, `.to(device)`, `.generate(input_ids, attention_mask)`,
-`.config`), and routes everything that computes to libmtts.so (hand-written HIP for
+`.config`; and the labels branch of `forward`, :382-410), and routes everything that computes to libmtts.so (hand-written HIP for
 gfx950) through mtts.engine.Engine.  There is no PyTorch forward here and no CPU path.
 """
 from __future__ import annotations
@@ -119,6 +119,21 @@ class GenerateOutput:
         return getattr(self, k)
 
 
+class AsteroidTTSOutputWithPast:
+    """The reference's output class (modeling_asteroid.py:30-37) as forward(labels=...) fills it with skip_logits: `loss`,
+    `loss_all`, and None for everything the engine does not keep.  One field more: `token_logprobs` float32 [B,T,8], the
+    log-probability of every label (NaN at t = 0, at ignored labels and at padding)."""
+
+    def __init__(self, loss=None, loss_all=None, token_logprobs=None):
+        self.loss = loss
+        self.loss_all = loss_all
+        self.logits = self.logits_all = self.past_key_values = self.hidden_states = self.attentions = None
+        self.token_logprobs = token_logprobs
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+
 class AsteroidTTSInstruct:
     MAX_ENGINE_BATCH = 128          # rows one engine pass carries (4 activation tiles share each weight stream)
 
@@ -136,6 +151,7 @@ class AsteroidTTSInstruct:
         self.sample_rows = None         # Philox row id of each row of the next generate() (a rank's share of a sharded
                                         # batch sets its rows' job-wide positions); None = 0..B-1
         self._calls = 0
+        self.weights = [1 for _ in range(self.channels)]      # per-channel loss weights (modeling_asteroid.py:297)
 
     # ---- loading -----------------------------------------------------------------
     @classmethod
@@ -185,6 +201,83 @@ class AsteroidTTSInstruct:
             self._engine.bind_state_dict(self._sd)
             self._engine_key = key
         return self._engine
+
+    # ---- teacher-forced loss (the labels branch of the reference's forward, modeling_asteroid.py:382-410) ----------
+    def set_weights(self, weights):
+        self.weights = weights
+
+    def _check_forward_args(self, input_ids, attention_mask, labels):
+        """-> numpy (ids int64 [B,T,8], mask uint8 [B,T], labels int64 [B,T,8]); ValueError before any engine exists."""
+        if labels is None:
+            raise ValueError("forward() without labels: the MI355X engine keeps no logits, so there is nothing to return; "
+                             "use generate() to decode, or pass labels for the per-channel losses")
+        if input_ids is None:
+            raise ValueError("forward() needs input_ids (inputs_embeds is not supported)")
+        as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        ids, lab = as_np(input_ids), as_np(labels)
+        if ids.ndim != 3:
+            raise ValueError(f"input_ids must be [batch, seq, channels], got shape {tuple(ids.shape)}")
+        B, T, C = ids.shape
+        if C != self.channels:
+            raise ValueError(f"Expected {self.channels} channels, got {C}")
+        if tuple(lab.shape) != tuple(ids.shape):
+            raise ValueError(f"labels must be shaped like input_ids {tuple(ids.shape)}, got {tuple(lab.shape)}")
+        msk = np.ones((B, T), dtype=np.uint8) if attention_mask is None else (as_np(attention_mask) > 0).astype(np.uint8)
+        if msk.shape != (B, T):
+            raise ValueError(f"attention_mask must be [batch, seq] = {(B, T)}, got {tuple(msk.shape)}")
+        ids, lab = ids.astype(np.int64), lab.astype(np.int64)
+        lens = msk.sum(1)
+        for b in range(B):
+            if not msk[b, :lens[b]].all():
+                kind = "left-padded" if not msk[b, 0] else "not ones followed by zeros"
+                raise ValueError(f"attention_mask of row {b} is {kind}: forward(labels=...) takes right-padded or unpadded "
+                                 "rows (the reference's positions are arange(T) for every row)")
+        if (lab[msk == 0] != -100).any():
+            raise ValueError("labels must be -100 wherever attention_mask is 0")
+        vocab = np.array([self.config.vocab_size] + [self.config.speech_vocab_size] * (C - 1))
+        if (((lab < 0) | (lab >= vocab)) & (lab != -100)).any():
+            raise ValueError("labels must be -100 or inside the channel's vocabulary")
+        return np.ascontiguousarray(ids), np.ascontiguousarray(msk), np.ascontiguousarray(lab)
+
+    @torch.no_grad()
+    def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, **kw):
+        """The training-branch forward of the reference, forward only: LongTensor [B,T,8] ids and labels (-100 = ignore),
+        mask [B,T] right-padded or unpadded -> AsteroidTTSOutputWithPast with `loss_all` (float32 [8]: the causal-LM loss of
+        each channel, mean over its labelled slots; NaN for a channel without one), `loss` (their mean under
+        `self.weights`) and `token_logprobs` [B,T,8]; return_dict=False -> (loss, loss_all, None).  The heads and the
+        log-softmax run fused on the device (csrc/score.hip); logits are never materialised, as with the reference's
+        skip_logits.  A batch beyond MAX_ENGINE_BATCH is scored in slices whose sums and counts are combined."""
+        # what would change the reference's result, or ask for what the engine does not keep, is refused, not dropped
+        bad = [k for k in ("position_ids", "inputs_embeds", "past_key_values", "cache_position") if kw.get(k) is not None]
+        bad += [k for k in ("output_attentions", "output_hidden_states", "use_cache") if kw.get(k)]
+        if kw.get("skip_logits") is False:
+            bad.append("skip_logits=False")
+        if bad:
+            raise ValueError(f"forward(labels=...) does not take {', '.join(bad)}: positions are arange(T) over right-padded rows, "
+                             "and the engine keeps no logits, cache, attentions or hidden states")
+        ids, msk, lab = self._check_forward_args(input_ids, attention_mask, labels)
+        B, T, C = ids.shape
+        eng = self._get_engine(min(B, self.MAX_ENGINE_BATCH), T)
+        lp = np.empty((B, T, C), dtype=np.float32)
+        sums, counts = np.zeros(C, dtype=np.float64), np.zeros(C, dtype=np.int64)
+        for b0 in range(0, B, self.MAX_ENGINE_BATCH):
+            sl = slice(b0, b0 + self.MAX_ENGINE_BATCH)
+            part = lp[sl] = eng.score(ids[sl], msk[sl], lab[sl])
+            ok = ~np.isnan(part)
+            sums += np.where(ok, part, 0).astype(np.float64).sum(axis=(0, 1))
+            counts += ok.sum(axis=(0, 1))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            loss_all = torch.from_numpy((-(sums / counts)).astype(np.float32)).to(self.device)   # 0 / 0: NaN, as cross_entropy's mean
+        total_weight = sum(self.weights)
+        loss = 0
+        for w, l in zip([w / total_weight for w in self.weights], loss_all):
+            loss = loss + w * l
+        if return_dict is not None and not return_dict:
+            return (loss, loss_all, None)
+        dev = input_ids.device if torch.is_tensor(input_ids) else self.device
+        return AsteroidTTSOutputWithPast(loss, loss_all, torch.from_numpy(lp).to(dev))
+
+    __call__ = forward
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,

@@ -171,6 +171,18 @@ class Engine:
             ret += (np.ascontiguousarray(self.read_scores(out_len.value - (T - 7)).transpose(1, 0, 2)),)
         return ret if len(ret) > 1 else ret[0]
 
+    def score(self, input_ids, attention_mask, labels):
+        """Teacher-forced scoring (include/mtts.h: mtts_score): int64 [B,T,8] ids and labels (-100 = ignore), mask [B,T]
+        right-padded or unpadded -> float32 [B,T,8], logp[b,t,c] = log_softmax(logits_c(h[b,t-1]))[labels[b,t,c]], NaN at
+        t = 0, at ignored labels and at padding.  No run may be open; the engine's KV pool is as before afterwards."""
+        ids, m = self._host_inputs(input_ids, attention_mask)
+        lab = np.ascontiguousarray(np.asarray(labels.cpu() if torch.is_tensor(labels) else labels), dtype=np.int64)
+        assert lab.shape == ids.shape
+        B, T, _ = ids.shape
+        out = np.empty((B, T, 8), dtype=np.float32)
+        capi.check(self.lib.mtts_score(self._h, ids.ctypes.data, m.ctypes.data, lab.ctypes.data, B, T, out.ctypes.data, None))
+        return out
+
     def begin(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, row_ids=None, takes=1,
               output_scores=False):
         """Prefill; takes as in generate() (the run then has B*takes rows); output_scores: keep log-probabilities
