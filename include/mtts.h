@@ -98,6 +98,19 @@ int32_t mtts_bind_weight(MttsEngine* e, const char* name, const void* dev_bf16,
                          int64_t rows, int64_t cols, void* stream);
 /* (an MTTS_DTYPE_F32 engine takes fp32 row-major tensors through the same calls: dev_bf16 / dev_cos_bf16 / dev_sin_bf16
  * then point to floats, and the engine keeps plain copies) */
+/* mtts_bind_weight with a LoRA adapter merged into the matrix (PEFT merge_and_unload, reference finetune/finetune.py:237,
+ * per matrix and on the device): behaves as mtts_bind_weight(name, merged), where for dev_base W [rows][cols] in the
+ * engine's weight format, dev_lora_a = lora_A.weight fp32 [r][cols] and dev_lora_b = lora_B.weight fp32 [rows][r]
+ *     acc = 0;  for j = 0 .. r-1 ascending: acc = acc + B[n][j] * A[j][k]      (fp32, one multiply and one add: no fma)
+ *     merged[n][k] = round_to_model_dtype(W[n][k] + acc * scaling)             (bf16 / fp16 RNE; none for fp32)
+ * scaling = lora_alpha / r, or lora_alpha / sqrt(r) with use_rslora, computed by the caller.  The merged matrix goes
+ * straight into the engine's layout (csrc/adapter.hip); no row-major merged copy exists.  `name` must be one of the seven
+ * projection weights of a layer (q/k/v/o_proj, gate/up/down_proj).  MTTS_EINVAL: any other name, a shape other than the
+ * weight's, r outside 1..256, a pointer that is not 16-byte aligned.  MTTS_ESTATE: a run is open (the rule of
+ * mtts_set_output_scores); the weights are then as they were.  Drops the captured step graphs, as mtts_bind_weight does.
+ * Stream-ordered: the three tensors may be freed once `stream` has passed the call. */
+int32_t mtts_bind_weight_lora(MttsEngine* e, const char* name, const void* dev_base, int64_t rows, int64_t cols,
+                              const float* dev_lora_a, const float* dev_lora_b, int32_t r, float scaling, void* stream);
 /* RoPE table cos|sin, bf16 [max_position][64] each, computed by the host the
  * way Qwen3RotaryEmbedding does (fp32 -> bf16). */
 int32_t mtts_bind_rope(MttsEngine* e, const void* dev_cos_bf16, const void* dev_sin_bf16,
@@ -315,6 +328,14 @@ int32_t mtts_k_kv_seal(const void* dev_pages, int32_t npages, void* dev_sealed, 
  * of 32 rows in the packed matrix; labels and logp are [M][segments].  M <= 2048, K % 16 == 0. */
 int32_t mtts_k_head_ce(const void* dev_w, const void* dev_x, const int32_t* host_labels, int32_t M, int32_t N, int32_t K,
                        int32_t n_valid, int32_t segments, float* dev_logp, void* stream);
+/* The adapter-merge kernels the engine runs (mtts_bind_weight_lora), into a caller-supplied buffer.  dtype 0: dev_base bf16
+ * [rows][cols] -> dev_out packed bf16 [rows_pad][cols] in fragment order, source row s on packed row s * row_mul + row_off;
+ * only the 16-byte groups of those rows are written (the rest of dev_out keeps what it held).  dtype 1 / 2: dev_base fp32
+ * [rows][cols] -> dev_out fp32 [rows][cols] row-major (2: rounded to fp16 values); the placement arguments are not used.
+ * cols % 16 == 0, 1 <= r <= 256, rows_pad % 32 == 0 and (rows - 1) * row_mul + row_off < rows_pad.  Synchronous. */
+int32_t mtts_k_lora_pack(const void* dev_base, int32_t rows, int32_t cols, const float* dev_lora_a, const float* dev_lora_b,
+                         int32_t r, float scaling, int32_t rows_pad, int32_t row_mul, int32_t row_off, int32_t dtype,
+                         void* dev_out, void* stream);
 /* One sampler call on fp32-from-bf16 logits (HF processors + engine draw). */
 int32_t mtts_k_sample(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
                       const void* dev_history_bitmap, const MttsSamplerCfg* cfg,

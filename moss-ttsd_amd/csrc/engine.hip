@@ -362,6 +362,7 @@ struct WeightSlot {
     int64_t f32_row = 0;
     int* bound = nullptr;            // mask that records the binding; null: a name that is accepted and ignored
     int bit = 0;
+    bool proj = false;               // one of a layer's seven projection matrices (what a LoRA adapter may target)
 };
 
 static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
@@ -410,6 +411,7 @@ static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
             w.rows_pad = t[i].rows_pad; w.row_mul = t[i].row_mul; w.row_off = t[i].row_off;
             w.f32_to = t[i].f32; w.f32_row = t[i].f32_row;
             w.bound = &l.bound; w.bit = 1 << i;       // a complete layer has all 11 bits: 2047 (mtts_weights_ready)
+            w.proj = t[i].cols != 1;
             return MTTS_OK;
         }
     return fail(MTTS_EINVAL, "unknown tensor %s", name_c);
@@ -434,6 +436,34 @@ int32_t mtts_bind_weight(MttsEngine* e, const char* name_c, const void* src, int
         if (w.pack_to) launch_pack_weight(src, w.pack_to, (int)w.rows, (int)w.cols, w.rows_pad, w.row_mul, w.row_off, st);
         HIPCHK(hipGetLastError());
     }
+    *w.bound |= w.bit;
+    return MTTS_OK;
+}
+
+// mtts_bind_weight with a LoRA adapter merged into the matrix on its way into the engine's layout (csrc/adapter.hip).
+static int run_still_open(MttsEngine* e, bool* open);
+int32_t mtts_bind_weight_lora(MttsEngine* e, const char* name_c, const void* base, int64_t rows, int64_t cols, const float* lora_a,
+                              const float* lora_b, int32_t r, float scaling, void* stream) {
+    if (!e || !name_c || !base || !lora_a || !lora_b) return fail(MTTS_EINVAL, "null argument");
+    if (r < 1 || r > 256) return fail(MTTS_EINVAL, "%s: adapter rank %d outside 1..256", name_c, r);
+    if (((uintptr_t)base | (uintptr_t)lora_a | (uintptr_t)lora_b) & 15) return fail(MTTS_EINVAL, "%s: tensors must be 16-byte aligned", name_c);
+    HIPCHK(hipSetDevice(e->device));
+    WeightSlot w;
+    TRY(resolve_weight(e, name_c, w));
+    if (!w.proj) return fail(MTTS_EINVAL, "%s is not a projection weight of a layer: an adapter cannot target it", name_c);
+    if (rows != w.rows || cols != w.cols)
+        return fail(MTTS_EINVAL, "%s: expected [%lld,%lld] got [%lld,%lld]", name_c, (long long)w.rows, (long long)w.cols, (long long)rows, (long long)cols);
+    bool open = false;
+    TRY(run_still_open(e, &open));
+    if (open) return fail(MTTS_ESTATE, "weights cannot change while a run is open (the rule of mtts_set_output_scores)");
+    drop_graphs(e);
+    hipStream_t st = S(stream);
+    if (e->f32)
+        launch_lora_rows_f32((const float*)base, lora_a, lora_b, r, scaling, w.f32_to + w.f32_row * w.cols, (int)w.rows, (int)w.cols,
+                             e->h16 ? 1 : 0, st);
+    else
+        launch_lora_pack(base, lora_a, lora_b, r, scaling, w.pack_to, (int)w.rows, (int)w.cols, w.row_mul, w.row_off, st);
+    HIPCHK(hipGetLastError());
     *w.bound |= w.bit;
     return MTTS_OK;
 }

@@ -83,6 +83,21 @@ int32_t mtts_k_head_ce(const void* w, const void* x, const int32_t* host_labels,
     return MTTS_OK;
 }
 
+int32_t mtts_k_lora_pack(const void* base, int32_t rows, int32_t cols, const float* lora_a, const float* lora_b, int32_t r, float scaling,
+                         int32_t rows_pad, int32_t row_mul, int32_t row_off, int32_t dtype, void* out, void* stream) {
+    if (!base || !lora_a || !lora_b || !out || rows < 1 || cols < 16 || cols % 16 || r < 1 || r > 256 || dtype < 0 || dtype > 2)
+        return fail(MTTS_EINVAL, "lora_pack: need rows >= 1, cols %% 16 == 0, 1 <= r <= 256, dtype 0..2");
+    if (((uintptr_t)base | (uintptr_t)lora_a | (uintptr_t)lora_b | (uintptr_t)out) & 15) return fail(MTTS_EINVAL, "lora_pack: pointers must be 16-byte aligned");
+    if (dtype == 0 && (rows_pad < 32 || rows_pad % 32 || row_mul < 1 || row_off < 0 || (int64_t)(rows - 1) * row_mul + row_off >= rows_pad))
+        return fail(MTTS_EINVAL, "lora_pack: rows_pad %% 32 == 0 and (rows - 1) * row_mul + row_off < rows_pad");
+    hipStream_t st = S(stream);
+    if (dtype == 0) launch_lora_pack(base, lora_a, lora_b, r, scaling, out, rows, cols, row_mul, row_off, st);
+    else launch_lora_rows_f32((const float*)base, lora_a, lora_b, r, scaling, (float*)out, rows, cols, dtype == 2, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
 int32_t mtts_k_rmsnorm(const void* x, const void* w, void* y, int32_t rows, int32_t n, float eps, void* stream) {
     if (!x || !w || !y || rows < 1 || n < 1) return fail(MTTS_EINVAL, "rmsnorm: bad argument");
     launch_rmsnorm_rows(x, w, y, rows, n, eps, S(stream));

@@ -164,6 +164,16 @@ void launch_head_ce(const void* Wp, const void* Xp, int R, int K, int n_valid, i
 void launch_ce_rows_f32(const float* logits, long ldy, int R, int n_valid, const int32_t* labels, int lab_stride, int lab_off,
                         float* logp, int out_stride, int out_off, hipStream_t st);
 
+// ---- adapter.hip ----------------------------------------------------------------------------------------------------
+// A LoRA adapter merged into a projection weight: merged = round(W + ((B A), r terms summed in ascending order) * scaling),
+// A fp32 [r][cols], B fp32 [rows][r], 1 <= r, cols % 16 == 0, every pointer 16-byte aligned.  launch_lora_pack: W bf16
+// row-major -> the packed buffer, with launch_pack_weight's placement (source row s on packed row s * row_mul + row_off,
+// only the groups of its source rows written).  launch_lora_rows_f32: W and dst fp32 row-major (h16: fp16 rounding).
+void launch_lora_pack(const void* base, const float* A, const float* B, int r, float scaling, void* dst, int rows, int cols,
+                      int row_mul, int row_off, hipStream_t st);
+void launch_lora_rows_f32(const float* base, const float* A, const float* B, int r, float scaling, float* dst, int rows, int cols,
+                          int h16, hipStream_t st);
+
 // ---- codec.hip / codec_fused.hip ------------------------------------------------------------------------------------
 void mtts_gemm_f32_exact(hipStream_t st, const float* A, const float* W, float* C, int M, int N, int K, long ldc);
 void launch_split_pack_w2perm(hipStream_t st, const float* w2, uint16_t* hi, uint16_t* lo);

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from mtts import synth
+from mtts import adapters, synth
 from mtts.engine import Engine
 
 _CFG_KEYS = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads",
@@ -151,6 +151,7 @@ class AsteroidTTSInstruct:
         self.sample_rows = None         # Philox row id of each row of the next generate() (a rank's share of a sharded
                                         # batch sets its rows' job-wide positions); None = 0..B-1
         self._calls = 0
+        self._adapter = None            # the active LoRA adapter: (tensors {weight name: (A, B)}, scaling); load_adapter()
         self.weights = [1 for _ in range(self.channels)]      # per-channel loss weights (modeling_asteroid.py:297)
 
     # ---- loading -----------------------------------------------------------------
@@ -161,6 +162,17 @@ class AsteroidTTSInstruct:
                                       f"torch_dtype={torch_dtype} is not one of them")
         if not os.path.isdir(model_path):
             raise FileNotFoundError(f"{model_path}: local checkpoint directory required (no network here)")
+        if adapters.is_adapter_dir(model_path):
+            # a PEFT checkpoint (adapter_config.json + adapter_model.*, no model of its own): the base it names, then the adapter
+            with open(os.path.join(model_path, "adapter_config.json")) as f:
+                base = json.load(f).get("base_model_name_or_path")
+            if not base or not os.path.isdir(base):
+                raise FileNotFoundError(f"{model_path} is an adapter checkpoint and its base_model_name_or_path = {base!r} is not a "
+                                        "local directory: load the base with from_pretrained(<local copy>) and call "
+                                        "load_adapter(<this directory>)")
+            m = cls.from_pretrained(base, torch_dtype=torch_dtype, attn_implementation=attn_implementation)
+            m.load_adapter(model_path)
+            return m
         cfg = AsteroidTTSConfig.from_pretrained(model_path)
         m = cls(cfg, _load_safetensors_dir(model_path), GenerationConfig.from_pretrained(model_path))
         m.dtype = {torch.float32: "fp32", torch.float16: "fp16"}.get(torch_dtype, "bf16")
@@ -178,6 +190,8 @@ class AsteroidTTSInstruct:
 
     def to(self, device):
         self.device = torch.device(device)
+        if self._adapter is not None:
+            self._adapter = ({k: tuple(t.to(self.device) for t in ab) for k, ab in self._adapter[0].items()}, self._adapter[1])
         return self
 
     def is_speech_token(self, tokens):
@@ -200,7 +214,60 @@ class AsteroidTTSInstruct:
                                   device=str(self.device), dtype=self.dtype)
             self._engine.bind_state_dict(self._sd)
             self._engine_key = key
+            if self._adapter is not None:
+                self._apply_adapter(self._engine, ())
         return self._engine
+
+    # ---- LoRA adapters (PEFT merge_and_unload on the resident engine: mtts/adapters.py, csrc/adapter.hip) ----------
+    def _apply_adapter(self, eng, previous):
+        """The active adapter's targets are bound merged; a weight in `previous` (names the engine holds merged with an
+        earlier adapter) that it does not target goes back to its base."""
+        tensors, scaling = self._adapter if self._adapter is not None else ({}, 0.0)
+        for name, (A, B) in tensors.items():
+            eng.bind_lora(name, self._sd[name], A, B, scaling, sync=False)
+        torch.cuda.synchronize(eng.device)
+        for name in previous:
+            if name not in tensors:
+                v = self._sd[name]
+                eng.bind(name, torch.from_numpy(v) if isinstance(v, np.ndarray) else v)
+
+    def load_adapter(self, path_or_tensors, scaling=None):
+        """Make a LoRA adapter the active one: a PEFT checkpoint directory (adapter_config.json + adapter_model.safetensors
+        | .bin; mtts.adapters.read_peft_dir lists what is refused), or {weight name: (lora_A [r, in], lora_B [out, r])}
+        with `scaling` (lora_alpha / r, or / sqrt(r) for rsLoRA).  One adapter is active at a time: loading replaces the
+        active one, and a weight the new adapter does not target goes back to its base.  On a resident engine this is one
+        merge-and-pack pass per targeted matrix; an engine built later gets the adapter after its weights."""
+        if isinstance(path_or_tensors, (str, os.PathLike)):
+            tensors, file_scaling, _ = adapters.read_peft_dir(os.fspath(path_or_tensors), self.config)
+            scaling = file_scaling if scaling is None else scaling
+        else:
+            if scaling is None:
+                raise ValueError("load_adapter(tensors) needs scaling (lora_alpha / r, or lora_alpha / sqrt(r) with rsLoRA)")
+            tensors = {k: tuple(torch.as_tensor(t).detach() for t in ab) for k, ab in dict(path_or_tensors).items()}
+            adapters.check_tensors(tensors, self.config)
+        # widened to fp32 once; kept where the model is, so that a swap on a resident engine uploads nothing
+        tensors = {k: tuple(torch.as_tensor(t).to(device=self.device, dtype=torch.float32).contiguous() for t in ab)
+                   for k, ab in tensors.items()}
+        missing = [k for k in tensors if k not in self._sd]
+        if missing:
+            raise ValueError(f"adapter targets {missing[0]!r}, which the base state dict does not hold")
+        old = self._adapter
+        self._adapter = (tensors, float(np.float32(scaling)))
+        if self._engine is not None:
+            try:
+                self._apply_adapter(self._engine, tuple(old[0]) if old is not None else ())
+            except Exception:
+                self._adapter = old         # (a run is open: the engine refused the first matrix and holds what it held)
+                raise
+        return self
+
+    def unload_adapter(self):
+        """Back to the base model: the projections the active adapter targets are rebound from the base state dict."""
+        previous = tuple(self._adapter[0]) if self._adapter is not None else ()
+        self._adapter = None
+        if self._engine is not None:
+            self._apply_adapter(self._engine, previous)
+        return self
 
     # ---- teacher-forced loss (the labels branch of the reference's forward, modeling_asteroid.py:382-410) ----------
     def set_weights(self, weights):

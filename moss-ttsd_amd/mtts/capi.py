@@ -51,6 +51,10 @@ _SIGS = {
     "mtts_engine_create": (C.c_int32, [C.POINTER(MttsConfig), C.c_int32, C.POINTER(C.c_void_p)]),
     "mtts_engine_destroy": (C.c_int32, [C.c_void_p]),
     "mtts_bind_weight": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "mtts_bind_weight_lora": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.c_float, C.c_void_p]),
+    "mtts_k_lora_pack": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mtts_bind_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mtts_weights_ready": (C.c_int32, [C.c_void_p]),
     "mtts_generate": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

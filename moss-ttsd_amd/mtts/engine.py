@@ -93,6 +93,22 @@ class Engine:
         capi.check(self.lib.mtts_bind_weight(self._h, name.encode(), t.data_ptr(), rows, cols, None))
         torch.cuda.synchronize(self.device)     # the engine has packed its own copy; `t` may go
 
+    def bind_lora(self, name: str, base, A, B, scaling, sync=True):
+        """bind(name, merged) with the LoRA merge done on the device on the way into the engine's layout (include/mtts.h:
+        mtts_bind_weight_lora): merged = round(base + ((B @ A), r terms in ascending order, fp32) * scaling).  base as
+        bind() takes it; A = lora_A.weight [r, in], B = lora_B.weight [out, r] (widened to fp32); scaling one fp32 value.
+        sync=False: the call is only enqueued (on the device's default stream, like the copies torch made for it); a caller
+        that binds many matrices synchronises once after the last."""
+        as_t = lambda v: torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+        t = as_t(base).to(device=self.device).to(self.model_dtype).to(self.tdtype).contiguous()
+        a, b = (as_t(v).to(device=self.device, dtype=torch.float32).contiguous() for v in (A, B))
+        if t.dim() != 2 or a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1] or tuple(t.shape) != (b.shape[0], a.shape[1]):
+            raise ValueError(f"{name}: base {tuple(t.shape)}, lora_A {tuple(a.shape)}, lora_B {tuple(b.shape)} are not [out, in], [r, in], [out, r]")
+        capi.check(self.lib.mtts_bind_weight_lora(self._h, name.encode(), t.data_ptr(), t.shape[0], t.shape[1], a.data_ptr(),
+                                                  b.data_ptr(), int(a.shape[0]), C.c_float(float(scaling)), None))
+        if sync:
+            torch.cuda.synchronize(self.device)     # the engine holds the merged matrix; the three tensors may go
+
     def bind_state_dict(self, sd):
         for k, v in sd.items():
             if k.startswith("lm_heads.") or k.endswith("embed_tokens.weight"):
