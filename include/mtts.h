@@ -290,9 +290,48 @@ int32_t mtts_k_attn_section(const float* dev_slabs, int32_t ksplit, const void* 
  * Like mtts_k_gemm_bf16 and mtts_k_gemm_bench it reads MTTS_GEMM_DEPTH on every call (0: gemm_skinny_kernel only). */
 int32_t mtts_k_gemm_swiglu_bf16(const void* dev_w, const void* dev_x, void* dev_y,
                                 int32_t M, int32_t N, int32_t K, void* stream);
-/* RMSNorm (Qwen3RMSNorm, modeling_qwen3.py:59-64): x,w bf16 -> y bf16, rows x n. */
+/* RMSNorm (Qwen3RMSNorm, modeling_qwen3.py:59-64): x,w bf16 -> y bf16, rows x n.  Runs rmsnorm_rows_kernel, a
+ * test-only entry point that the engine never launches; the kernels the engine runs are reached through
+ * mtts_k_embed_norm, mtts_k_resid_norm and mtts_k_gemv_small (tests/test_layer_kernels_gpu.py). */
 int32_t mtts_k_rmsnorm(const void* dev_x, const void* dev_w, void* dev_y,
                        int32_t rows, int32_t n, float eps, void* stream);
+/* ---- the layer kernels the engine launches, one launch each (tests/test_layer_kernels_gpu.py) ----
+ * epi / pro below are the launchers' numbers: epi 0 = fp32 split-K slabs (reduced to bf16 by the hook), 1 = bf16
+ * row-major with row stride round_up(N, 32), 2 = SwiGLU into the fragment layout, 3 = SwiGLU row-major (small kernel);
+ * pro 1 = residual + slabs + RMSNorm, 2 = sum of the P.V chunk partials, 3 = row-major activations.
+ *
+ * embed_norm_kernel on R rows: host_tokens int32 [R][8], host_seq int32 [R] (< 0 = idle row), host_tables = 8 device
+ * pointers to bf16 [host_vocab[c]][H], dev_norm_w bf16 [H].  Out: dev_x bf16 [R][H] (the residual stream) and dev_xn
+ * bf16 [R][H] (the normalised rows, unpacked from the fragment layout).  H % 16 == 0, H <= 8192, 1 <= R <= 2048. */
+int32_t mtts_k_embed_norm(const int32_t* host_tokens, const int32_t* host_seq, const void* const* host_tables,
+                          const int32_t* host_vocab, const void* dev_norm_w, int32_t R, int32_t H, float eps,
+                          void* dev_x, void* dev_xn, void* stream);
+/* resid_norm_kernel on R rows: dev_slabs fp32 [ksplit][R][Npad] (Npad = round_up(H, 32)), dev_x bf16 [R][H] updated in
+ * place, host_seq / host_last int32 [R] (seq < 0 = idle row, seq < nseq).  Out: dev_xn bf16 [R][H] row-major, and
+ * dev_hlast bf16 [nseq][H]: row seq[r] receives the xn row of every row r with last[r] != 0, the rest keeps what the
+ * caller put there. */
+int32_t mtts_k_resid_norm(const float* dev_slabs, int32_t ksplit, int32_t Npad, void* dev_x, const void* dev_norm_w,
+                          const int32_t* host_seq, const int32_t* host_last, int32_t R, int32_t H, int32_t nseq, float eps,
+                          void* dev_xn, void* dev_hlast, void* stream);
+/* One launch of gemv_small_kernel (decode of 1..4 dialogues) with (epi, pro) in the pairs the engine uses: (0,1) (0,2)
+ * (0,3) (3,1) (1,1).  dev_w bf16 [N][K] row-major; the plan is the engine's GEMM planner on round_up(N, 32), K and
+ * want_ksplit (which must be 1 unless epi == 0); MTTS_EINVAL when the prologue's LDS exceeds the budget the engine allows.
+ * pro 1: dev_x_in bf16 [rows][K], dev_slabs fp32 [slab_ksplit][rows][round_up(K, 32)] (slab_ksplit 0: none), dev_norm_w
+ *        bf16 [K]; dev_x_out bf16 [rows][K] receives x' (may be NULL; must not be dev_x_in).
+ * pro 2: K = nq * 128, dev_opart fp32 [rows][nq][nchunks_max][128], host_seq / host_pos int32 [rows] (seq < 0 = idle
+ *        row; a row sums its first ceil(ceil((pos + 1) / 64) / 8) chunks).
+ * pro 3: dev_xrows bf16 [rows][K].
+ * Out dev_y bf16: epi 0 [rows][N] (slabs reduced), epi 1 [rows][round_up(N, 32)] (columns < N written), epi 3
+ * [rows][N / 2] (N % 32 == 0).  With epi 1 / 3 and for dev_x_out the kernel writes the caller's buffers itself: whatever
+ * it must not write keeps its content.  out_plan (may be NULL) receives {waves per block, ksplit} of the launch. */
+int32_t mtts_k_gemv_small(int32_t epi, int32_t pro, const void* dev_w, int32_t rows, int32_t N, int32_t K, int32_t want_ksplit,
+                          const void* dev_x_in, const float* dev_slabs, int32_t slab_ksplit, const void* dev_norm_w, float eps,
+                          void* dev_x_out, const float* dev_opart, const int32_t* host_seq, const int32_t* host_pos, int32_t nq,
+                          int32_t nchunks_max, const void* dev_xrows, void* dev_y, int32_t* out_plan, void* stream);
+/* gemm_tile_kernel (every prefill pass) on 1 <= M <= 2048 rows, whatever M is: epi 0, Y[M,N] as mtts_k_gemm_bf16
+ * (ksplit 0 = the kernel's own choice), or epi 2, Y[M,N/2] as mtts_k_gemm_swiglu_bf16 (ksplit 0 or 1). */
+int32_t mtts_k_gemm_tile(int32_t epi, const void* dev_w, const void* dev_x, void* dev_y, int32_t M, int32_t N, int32_t K,
+                         int32_t ksplit, void* stream);
 /* q/k/v epilogue of one new token per row (per-head q/k RMSNorm, RoPE, K/V page write: transformers modeling_qwen3.py
  * :148-170,251-259): dev_qkv bf16 [R][(nq+2*nkv)*128] = the q|k|v Linear outputs, host_pos int32 [R], norm weights bf16
  * [128], RoPE tables bf16 [rows][64].  Out (bf16): dev_q [R][nq][128], dev_k / dev_v [R][nkv][128] as read back from the

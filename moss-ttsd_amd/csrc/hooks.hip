@@ -105,6 +105,161 @@ int32_t mtts_k_rmsnorm(const void* x, const void* w, void* y, int32_t rows, int3
     return MTTS_OK;
 }
 
+// ---- the layer kernels the engine launches, one launch each (tests/test_layer_kernels_gpu.py) -------------------------
+// Every launch goes through the launcher the engine calls (launch.h); a shape a kernel does not take is refused.
+
+// split-K slabs [ksplit][R][Npad] of a caller -> a buffer with the kernels' slab stride (MTTS_PFCAP rows)
+static int stage_slabs(DevBufs& hb, const float* dev_slabs, int ksplit, int R, int Npad, float** out, hipStream_t st) {
+    TRY(hb.get(out, (size_t)ksplit * MTTS_PFCAP * Npad, false));
+    for (int k = 0; k < ksplit; ++k)
+        HIPCHK(hipMemcpyAsync(*out + (size_t)k * MTTS_PFCAP * Npad, dev_slabs + (size_t)k * R * Npad, (size_t)R * Npad * 4, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int32_t mtts_k_embed_norm(const int32_t* host_tokens, const int32_t* host_seq, const void* const* host_tables,
+                          const int32_t* host_vocab, const void* dev_norm_w, int32_t R, int32_t H, float eps,
+                          void* dev_x, void* dev_xn, void* stream) {
+    if (!host_tokens || !host_seq || !host_tables || !host_vocab || !dev_norm_w || !dev_x || !dev_xn || R < 1 || R > MTTS_PFCAP ||
+        H < 16 || H % 16 || H > 8192)
+        return fail(MTTS_EINVAL, "embed_norm: need 1<=R<=MTTS_PFCAP, H%%16==0, H<=8192");
+    for (int c = 0; c < 8; ++c)
+        if (!host_tables[c] || host_vocab[c] < 1) return fail(MTTS_EINVAL, "embed_norm: table %d missing or empty", c);
+    for (int r = 0; r < R; ++r)
+        for (int c = 0; c < 8; ++c)
+            if (host_seq[r] >= 0 && (host_tokens[r * 8 + c] < 0 || host_tokens[r * 8 + c] >= host_vocab[c]))
+                return fail(MTTS_EINVAL, "embed_norm: row %d channel %d: token %d outside [0, %d)", r, c, host_tokens[r * 8 + c], host_vocab[c]);
+    hipStream_t st = S(stream);
+    int32_t* tok = nullptr; RowMeta* meta = nullptr; const uint16_t** tabs = nullptr; uint16_t* xnp = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&tok, (size_t)R * 8)); TRY(hb.get(&meta, R)); TRY(hb.get(&tabs, 8));
+    TRY(hb.get(&xnp, (size_t)round_up(R, 32) * H));
+    std::vector<RowMeta> hm(R);
+    for (int r = 0; r < R; ++r) hm[r] = RowMeta{host_seq[r] < 0 ? -1 : host_seq[r], 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(tok, host_tokens, (size_t)R * 8 * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(meta, hm.data(), R * sizeof(RowMeta), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(tabs, host_tables, 8 * sizeof(void*), hipMemcpyHostToDevice, st));
+    launch_embed_norm(tok, meta, tabs, dev_norm_w, dev_x, xnp, R, H, eps, st);
+    launch_unpack_rows(xnp, dev_xn, R, H, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+int32_t mtts_k_resid_norm(const float* dev_slabs, int32_t ksplit, int32_t Npad, void* dev_x, const void* dev_norm_w,
+                          const int32_t* host_seq, const int32_t* host_last, int32_t R, int32_t H, int32_t nseq, float eps,
+                          void* dev_xn, void* dev_hlast, void* stream) {
+    if (!dev_slabs || !dev_x || !dev_norm_w || !host_seq || !host_last || !dev_xn || !dev_hlast || R < 1 || R > MTTS_PFCAP || H < 16 ||
+        H % 16 || H > 8192 || Npad != round_up(H, 32) || ksplit < 1 || ksplit > 16 || nseq < 1)
+        return fail(MTTS_EINVAL, "resid_norm: need 1<=R<=MTTS_PFCAP, H%%16==0, H<=8192, Npad==round_up(H,32), 1<=ksplit<=16");
+    for (int r = 0; r < R; ++r)
+        if (host_seq[r] >= nseq) return fail(MTTS_EINVAL, "resid_norm: row %d: sequence %d outside [0, %d)", r, host_seq[r], nseq);
+    hipStream_t st = S(stream);
+    float* slabs = nullptr; RowMeta* meta = nullptr; uint16_t* xnp = nullptr;
+    DevBufs hb;
+    TRY(stage_slabs(hb, dev_slabs, ksplit, R, Npad, &slabs, st));
+    TRY(hb.get(&meta, R));
+    TRY(hb.get(&xnp, (size_t)round_up(R, 32) * H));
+    std::vector<RowMeta> hm(R);
+    for (int r = 0; r < R; ++r) hm[r] = RowMeta{host_seq[r] < 0 ? -1 : host_seq[r], 0, host_last[r] ? 1 : 0, 0};
+    HIPCHK(hipMemcpyAsync(meta, hm.data(), R * sizeof(RowMeta), hipMemcpyHostToDevice, st));
+    launch_resid_norm(slabs, ksplit, Npad, dev_x, dev_norm_w, xnp, dev_hlast, meta, R, H, eps, st);
+    launch_unpack_rows(xnp, dev_xn, R, H, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+int32_t mtts_k_gemv_small(int32_t epi, int32_t pro, const void* dev_w, int32_t rows, int32_t N, int32_t K, int32_t want_ksplit,
+                          const void* dev_x_in, const float* dev_slabs, int32_t slab_ksplit, const void* dev_norm_w, float eps,
+                          void* dev_x_out, const float* dev_opart, const int32_t* host_seq, const int32_t* host_pos, int32_t nq,
+                          int32_t nchunks_max, const void* dev_xrows, void* dev_y, int32_t* out_plan, void* stream) {
+    const bool pair = (epi == EPI_PARTIAL && (pro == PRO_NORM || pro == PRO_COMBINE || pro == PRO_ROWS)) ||
+                      ((epi == EPI_SILU_RM || epi == EPI_BF16) && pro == PRO_NORM);
+    if (!pair) return fail(MTTS_EINVAL, "gemv_small: (epi %d, pro %d) is not a pair the decode step uses", epi, pro);
+    if (!dev_w || !dev_y || rows < 1 || rows > SMALL_RP || N < 1 || K < 16 || K % 16)
+        return fail(MTTS_EINVAL, "gemv_small: need 1<=rows<=%d, N>=1, K%%16==0", SMALL_RP);
+    if (epi == EPI_SILU_RM && N % 32) return fail(MTTS_EINVAL, "gemv_small: the SwiGLU epilogue needs N%%32==0");
+    if (epi != EPI_PARTIAL && want_ksplit != 1) return fail(MTTS_EINVAL, "gemv_small: only the fp32 slab epilogue takes a split-K");
+    if (want_ksplit < 0 || want_ksplit > 16 || want_ksplit > K / 16) return fail(MTTS_EINVAL, "gemv_small: split-K %d outside 0..min(16, K/16)", want_ksplit);
+    const int Npad = round_up(N, 32), Kp = round_up(K, 32);
+    if (pro == PRO_NORM) {
+        if (!dev_x_in || !dev_norm_w || dev_x_in == dev_x_out || slab_ksplit < 0 || slab_ksplit > 16 || (slab_ksplit && !dev_slabs))
+            return fail(MTTS_EINVAL, "gemv_small: norm prologue needs x_in != x_out, norm_w, 0<=slab_ksplit<=16 slabs");
+    } else if (pro == PRO_COMBINE) {
+        if (!dev_opart || !host_seq || !host_pos || nq < 1 || K != nq * MTTS_HD || nchunks_max < 1)
+            return fail(MTTS_EINVAL, "gemv_small: combine prologue needs opart, seq, pos, K==nq*128, nchunks_max>=1");
+        for (int r = 0; r < rows; ++r) {
+            if (host_seq[r] < 0) continue;
+            const int npages = host_pos[r] < 0 ? -1 : host_pos[r] / MTTS_PAGE + 1;
+            if (npages < 0 || (npages + ATT_PB - 1) / ATT_PB > nchunks_max)
+                return fail(MTTS_EINVAL, "gemv_small: row %d: position %d needs more than %d chunks", r, host_pos[r], nchunks_max);
+        }
+    } else if (!dev_xrows) return fail(MTTS_EINVAL, "gemv_small: rows prologue needs xrows");
+    const GemmPlan p0 = mtts_plan_gemm(Npad, K, want_ksplit);
+    if (mtts_small_lds_bytes(p0, K, pro) > 64 * 1024 - 33 * 1024)                     // the budget of the engine's small_path_fits
+        return fail(MTTS_EINVAL, "gemv_small: the prologue's %d bytes of LDS exceed the small path's budget", mtts_small_lds_bytes(p0, K, pro));
+    hipStream_t st = S(stream);
+    uint16_t* wp = nullptr; float *part = nullptr, *slabs = nullptr; RowMeta* meta = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&wp, (size_t)Npad * K));
+    launch_pack_weight(dev_w, wp, N, K, Npad, 1, 0, st);
+    SmallPro pr{};
+    pr.rows = rows; pr.eps = eps;
+    if (pro == PRO_NORM) {
+        if (slab_ksplit) TRY(stage_slabs(hb, dev_slabs, slab_ksplit, rows, Kp, &slabs, st));
+        pr.x_in = (const uint16_t*)dev_x_in; pr.x_out = (uint16_t*)dev_x_out; pr.slabs = slabs; pr.ksplit = slab_ksplit; pr.slab_npad = Kp;
+        pr.norm_w = (const uint16_t*)dev_norm_w;
+    } else if (pro == PRO_COMBINE) {
+        TRY(hb.get(&meta, SMALL_RP));
+        std::vector<RowMeta> hm(SMALL_RP, RowMeta{-1, 0, 0, 0});
+        for (int r = 0; r < rows; ++r)
+            if (host_seq[r] >= 0) hm[r] = RowMeta{host_seq[r], host_pos[r], 1, 0};
+        HIPCHK(hipMemcpyAsync(meta, hm.data(), hm.size() * sizeof(RowMeta), hipMemcpyHostToDevice, st));
+        pr.opart = dev_opart; pr.meta = meta; pr.nchunks_max = nchunks_max; pr.nq = nq; pr.pages_per_chunk = ATT_PB;
+    } else pr.xrows = (const uint16_t*)dev_xrows;
+    if (epi == EPI_PARTIAL) {
+        // the slabs start as NaN: an element of a live row that the kernel leaves out shows in the reduced output
+        TRY(hb.get(&part, (size_t)p0.ksplit * MTTS_PFCAP * Npad, false));
+        for (int k = 0; k < p0.ksplit; ++k) HIPCHK(hipMemsetAsync(part + (size_t)k * MTTS_PFCAP * Npad, 0xff, (size_t)SMALL_RP * Npad * 4, st));
+    }
+    launch_gemv_small(epi, pro, p0, wp, K, Npad, N, part, epi == EPI_PARTIAL ? nullptr : (uint16_t*)dev_y, pr, st);
+    if (epi == EPI_PARTIAL) launch_reduce_partial_bf16(part, dev_y, p0.ksplit, Npad, N, rows, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    if (out_plan) { out_plan[0] = std::max(p0.waves, 4); out_plan[1] = p0.ksplit; }
+    return MTTS_OK;
+}
+
+int32_t mtts_k_gemm_tile(int32_t epi, const void* dev_w, const void* dev_x, void* dev_y, int32_t M, int32_t N, int32_t K,
+                         int32_t ksplit, void* stream) {
+    if ((epi != EPI_PARTIAL && epi != EPI_SILU) || !dev_w || !dev_x || !dev_y || M < 1 || M > MTTS_PFCAP || N < 1 || K < 16 || K % 16)
+        return fail(MTTS_EINVAL, "gemm_tile: need epi 0 or 2, 1<=M<=MTTS_PFCAP, N>=1, K%%16==0");
+    if (epi == EPI_SILU && (N % 32 || ksplit < 0 || ksplit > 1)) return fail(MTTS_EINVAL, "gemm_tile: the SwiGLU epilogue needs N%%32==0 and no split-K");
+    if (ksplit < 0 || ksplit > 16 || ksplit > K / 16) return fail(MTTS_EINVAL, "gemm_tile: split-K %d outside 0..min(16, K/16)", ksplit);
+    hipStream_t st = S(stream);
+    const int Npad = round_up(N, 32), tiles = (M + 31) / 32;
+    const int ks = epi == EPI_SILU ? 1 : (ksplit > 0 ? ksplit : mtts_tile_ksplit(Npad, K, M));
+    uint16_t *wp = nullptr, *xp = nullptr, *op = nullptr;
+    float* part = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&wp, (size_t)Npad * K));
+    TRY(hb.get(&xp, (size_t)tiles * 32 * K));
+    launch_pack_weight(dev_w, wp, N, K, Npad, 1, 0, st);
+    launch_pack_rows(dev_x, xp, M, K, tiles, st);
+    if (epi == EPI_PARTIAL) {
+        TRY(hb.get(&part, (size_t)ks * MTTS_PFCAP * Npad));
+        launch_gemm_tile(EPI_PARTIAL, M, ks, wp, xp, K, Npad, Npad, part, nullptr, st);
+        launch_reduce_partial_bf16(part, dev_y, ks, Npad, N, M, st);
+    } else {
+        TRY(hb.get(&op, (size_t)tiles * 32 * (N / 2)));
+        launch_gemm_tile(EPI_SILU, M, 1, wp, xp, K, N, N, nullptr, op, st);
+        launch_unpack_rows(op, dev_y, M, N / 2, st);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
 static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                     int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp, void* stream) {
     if (!logits || !cfg || !dev_tokens || rows < 1 || vocab < 1 || channel < 0 || channel > 7) return fail(MTTS_EINVAL, "sample: bad argument");

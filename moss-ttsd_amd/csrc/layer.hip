@@ -233,7 +233,10 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(
     }
 }
 
-// Standalone RMSNorm over rows (unit-test entry point mtts_k_rmsnorm).
+// Standalone RMSNorm over rows.  A TEST-ONLY entry point (mtts_k_rmsnorm, test_rmsnorm_kernel_bit_exact_vs_oracle): the
+// engine never launches it.  The RMSNorms the engine runs are the tails of embed_norm_kernel and resid_norm_kernel above
+// and the norm prologue of gemv_small_kernel (gemm.hip); tests/test_layer_kernels_gpu.py covers those, bit for bit
+// (test_embed_norm_kernel, test_resid_norm_kernel, test_gemv_small_norm_prologue_identity).
 __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
                                                            uint16_t* __restrict__ y, int n, float eps) {
     __shared__ float sh[4];

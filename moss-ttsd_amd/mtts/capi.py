@@ -102,6 +102,12 @@ _SIGS = {
                             [C.c_int32] * 6 + [C.c_void_p] * 6),
     "mtts_k_gemm_swiglu_bf16": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mtts_k_rmsnorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "mtts_k_embed_norm": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 3),
+    "mtts_k_resid_norm": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float] +
+                          [C.c_void_p] * 3),
+    "mtts_k_gemv_small": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_float] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "mtts_k_gemm_tile": (C.c_int32, [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
     "mtts_k_rope_kvwrite": (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 4),
     "mtts_k_paged_attn_decode": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
     "mtts_k_head_ce": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),

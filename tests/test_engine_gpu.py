@@ -49,6 +49,9 @@ def test_gemm_kernel_matches_fp32_reference():
 
 
 def test_rmsnorm_kernel_bit_exact_vs_oracle():
+    """mtts_k_rmsnorm launches rmsnorm_rows_kernel, a test-only entry point that the engine never launches.  The
+    RMSNorms the engine runs (embed_norm_kernel, resid_norm_kernel, the norm prologue of gemv_small_kernel) are covered by
+    test_layer_kernels_gpu.py: test_embed_norm_kernel, test_resid_norm_kernel, test_gemv_small_norm_prologue_identity."""
     rng = np.random.default_rng(1)
     lib = capi.lib()
     for rows, n in [(3, 256), (32, 2048), (7, 128)]:
