@@ -111,6 +111,39 @@ int32_t mtts_bind_weight(MttsEngine* e, const char* name, const void* dev_bf16,
  * Stream-ordered: the three tensors may be freed once `stream` has passed the call. */
 int32_t mtts_bind_weight_lora(MttsEngine* e, const char* name, const void* dev_base, int64_t rows, int64_t cols,
                               const float* dev_lora_a, const float* dev_lora_b, int32_t r, float scaling, void* stream);
+/* ---- resident adapters, one per dialogue (PEFT: load_adapter(path, adapter_name=...) + generate(adapter_names=[...])) ----
+ * Up to MTTS_MAX_ADAPTERS LoRA adapters stay resident UNMERGED next to whatever weights are bound, and every row of a run
+ * names the one it runs with (-1: none).  For a row with adapter a, every targeted projection computes
+ *     y = W x + scaling * B (A x)
+ * where W x is the engine's GEMM, untouched, and the low-rank term is added in fp32 before the Linear's output is rounded:
+ * it is delivered as one more split-K slab of the GEMM (csrc/multilora.hip).  Its arithmetic is a function of
+ * (x, A, B, scaling) alone, stated in numpy as mtts.adapters.delta_spec: a row's tokens and logits do not depend on what
+ * shares its batch, and a row without an adapter computes what it computes on an engine with an empty bank.  (Against
+ * the MERGED adapter of mtts_bind_weight_lora the results differ by the bf16 rounding of the merged weight.)
+ * mtts_adapter_load: one matrix pair of adapter `adapter` (0 .. MTTS_MAX_ADAPTERS-1) for the projection weight `name`
+ * ([rows][cols], as mtts_bind_weight_lora names it): dev_lora_a fp32 [r][cols], dev_lora_b fp32 [rows][r], 16-byte
+ * aligned, copied into engine-owned memory on `stream` (drained before the call returns); a pair loaded before for the
+ * same matrix is replaced.  Matrices an adapter never loads are not targeted.  mtts_adapter_clear frees an adapter.
+ * Both: MTTS_ESTATE while a run is open (the rule of mtts_bind_weight_lora), and the captured step graphs are dropped.
+ * MTTS_EINVAL, with the offending value in mtts_last_error: an index outside the bank, a name that is not a projection
+ * weight of a layer, a shape other than the weight's, r outside 1..MTTS_LORA_MAX_RANK, and an MTTS_DTYPE_F32 / _F16
+ * engine (the bank exists on the bf16 engine only).  The engine takes no memory for any of this before the first
+ * mtts_adapter_load (then: the bank's tables, one more split-K slab and the two unfused gate/up slabs). */
+#define MTTS_MAX_ADAPTERS 16
+#define MTTS_LORA_MAX_RANK 64
+int32_t mtts_adapter_load(MttsEngine* e, int32_t adapter, const char* name, const float* dev_lora_a, const float* dev_lora_b,
+                          int64_t rows, int64_t cols, int32_t r, float scaling, void* stream);
+int32_t mtts_adapter_clear(MttsEngine* e, int32_t adapter);
+/* The adapter of each row of the NEXT mtts_begin / mtts_generate (consumed by it, failures included, like
+ * mtts_set_row_ids; default: none): host_ids int32 [n], n = that call's B, -1 = no adapter.  With takes it is given per
+ * PROMPT and a prompt's takes inherit it (they share its KV pages, which depend on the adapter).  That call returns
+ * MTTS_EINVAL for n != B or an id that names an empty adapter.  mtts_score does not take adapters: with a list pending it
+ * returns MTTS_ESTATE and the list stays pending (score per adapter with mtts_bind_weight_lora). */
+int32_t mtts_set_row_adapters(MttsEngine* e, const int32_t* host_ids, int32_t n);
+/* Scheduler mode: the adapter (-1: none) of the next mtts_slot_submit* into `slot` (consumed by it, failures included;
+ * default none).  mtts_slot_fork gives the take its source's adapter.  MTTS_EINVAL at the submit when it names an empty
+ * adapter. */
+int32_t mtts_set_slot_adapter(MttsEngine* e, int32_t slot, int32_t adapter);
 /* RoPE table cos|sin, bf16 [max_position][64] each, computed by the host the
  * way Qwen3RotaryEmbedding does (fp32 -> bf16). */
 int32_t mtts_bind_rope(MttsEngine* e, const void* dev_cos_bf16, const void* dev_sin_bf16,
@@ -375,6 +408,22 @@ int32_t mtts_k_head_ce(const void* dev_w, const void* dev_x, const int32_t* host
 int32_t mtts_k_lora_pack(const void* dev_base, int32_t rows, int32_t cols, const float* dev_lora_a, const float* dev_lora_b,
                          int32_t r, float scaling, int32_t rows_pad, int32_t row_mul, int32_t row_off, int32_t dtype,
                          void* dev_out, void* stream);
+/* The per-row adapter kernels (csrc/multilora.hip) as the engine launches them, on caller buffers.  Synchronous.
+ * mtts_k_lora_delta: dev_x bf16 [R][K] row-major (packed by the hook like an activation buffer), R <= 2048, K % 16 == 0.
+ * The slab holds the outputs of nseg <= 3 matrices: host_segs int32 [nseg][3] = (col0, ncols, mul), row i of matrix s at
+ * column col0 + mul * i; columns of no matrix (up to Npad, % 32 == 0) are padding.  Adapter a's pair for matrix s:
+ * host_a / host_b [n_adapters][nseg] device pointers (fp32 [r][K] and [ncols][r]; NULL with r 0: not targeted), host_r and
+ * host_scaling [n_adapters][nseg]; host_row_adapter int32 [R]: -1 a row without adapter, -2 an idle row (RowMeta.seq -1).
+ * dev_slabs float [..][2048][Npad], the GEMMs' slab stride: slab `ks` gets rows [0, R) x columns [0, Npad) written
+ * (mtts.adapters.delta_spec, +0.0 where there is no delta) and nothing else is touched.
+ * mtts_k_swiglu_slabs: gate/up as a pass with adapters runs it, on the operands of mtts_k_gemm_swiglu_bf16: the GEMM
+ * writes fp32 slab 0 (copied to dev_slab0_out float [M][N] when not NULL), dev_delta float [M][N] (NULL: zeros) is slab 1,
+ * swiglu_slabs_kernel -> dev_y bf16 [M][N/2]. */
+int32_t mtts_k_lora_delta(const void* dev_x, int32_t R, int32_t K, int32_t Npad, int32_t nseg, const int32_t* host_segs,
+                          int32_t n_adapters, const void* const* host_a, const void* const* host_b, const int32_t* host_r,
+                          const float* host_scaling, const int32_t* host_row_adapter, float* dev_slabs, int32_t ks, void* stream);
+int32_t mtts_k_swiglu_slabs(const void* dev_w, const void* dev_x, const float* dev_delta, void* dev_y, float* dev_slab0_out,
+                            int32_t M, int32_t N, int32_t K, void* stream);
 /* One sampler call on fp32-from-bf16 logits (HF processors + engine draw). */
 int32_t mtts_k_sample(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
                       const void* dev_history_bitmap, const MttsSamplerCfg* cfg,

@@ -20,16 +20,8 @@
 #define LORA_KB 128       // columns per block: 8 k-tiles, two per wave
 #define LORA_G 2          // 16-byte groups (8 columns) per thread
 
-// The two operations of the definition.  hipcc contracts a * b + c into an fma by default, also through __fmul_rn /
-// __fadd_rn (plain operators in the headers): the pragma keeps them apart (tests/test_adapter_isa_cpu.py).
-__device__ __forceinline__ float lora_mul(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float lora_add(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
+// The two operations of the definition: lora_mul / lora_add (common.h), one IEEE multiply and one IEEE add, never an fma
+// (tests/test_adapter_isa_cpu.py).
 // W + acc * scaling, rounded to the model dtype and held as fp32: mode 0 bf16, 1 fp32, 2 fp16 (MTTS_DTYPE_*; f32path.hip: r16)
 __device__ __forceinline__ float lora_merge(float w, float acc, float scaling) { return lora_add(w, lora_mul(acc, scaling)); }
 __device__ __forceinline__ float lora_round_f16(float v) { return __half2float(__float2half_rn(v)); }

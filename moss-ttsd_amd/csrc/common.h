@@ -36,6 +36,18 @@ __device__ __forceinline__ float dot2bf(uint32_t a, uint32_t b, float c) {   // 
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
 }
 
+// One IEEE multiply and one IEEE add that stay two operations.  hipcc contracts a * b + c into an fma by default, also
+// through __fmul_rn / __fadd_rn (plain operators in the headers): the pragma keeps them apart.  The LoRA kernels
+// (adapter.hip, multilora.hip) are defined in these two, so that numpy float32 states the same sums (mtts/adapters.py).
+__device__ __forceinline__ float lora_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float lora_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 // Cross-lane moves without the LDS crossbar (__shfl_xor compiles to ds_bpermute_b32: ~100 cycles per dependent step):
 // DPP reaches lane ^ 1, ^ 2 (quad_perm), ^ 4 (row_shl:4 / row_shr:4 on alternate banks) and ^ 8 (row_ror:8) in one VALU
 // instruction (two for ^ 4).  tools/dpp_probe.hip checks the four partner patterns and the max sequence on the GPU.

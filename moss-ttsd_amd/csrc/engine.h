@@ -212,6 +212,15 @@ struct MttsEngine {
     size_t sc_cap_rows = 0;
     float* sc_part = nullptr;           // bf16 engine: (m, s, l_label) per row of a pass and 128-column block, head 0 then heads 1..7
     float* sc_logits = nullptr;         // fp32 / fp16 engines: fp32 logits of SCORE_F32_ROWS rows of one head
+    // resident adapters, one per dialogue (mtts_adapter_load; multilora.hip): no device memory before the first load
+    std::vector<LoraEnt> bank;          // host copy of d_bank [MTTS_MAX_ADAPTERS][L * 7]; r == 0: the adapter has no pair for the matrix
+    LoraEnt* d_bank = nullptr;
+    int bank_pairs[MTTS_MAX_ADAPTERS] = {0};     // matrix pairs each adapter holds (0: the adapter is empty)
+    int32_t* d_seq_adapter = nullptr;   // [MTTS_RCAP] adapter of the dialogue in each sequence slot (-1: none); kernels go RowMeta.seq -> here
+    std::vector<int32_t> seq_adapter = std::vector<int32_t>(MTTS_RCAP, -1);          // the host's copy
+    std::vector<int32_t> next_slot_adapter = std::vector<int32_t>(MTTS_RCAP, -1);    // mtts_set_slot_adapter, read by the slot's next submit
+    std::vector<int32_t> next_row_adapters;      // mtts_set_row_adapters, read by the next mtts_begin / mtts_generate
+    bool row_adapters_pending = false;
     int32_t* d_pf_tokens = nullptr;     // prefill staging
     RowMeta* d_pf_meta = nullptr;
     size_t pf_cap_rows = 0;
@@ -225,7 +234,7 @@ struct MttsEngine {
     uint64_t seed = 0;
     bool began = false, has_forced = false;
     // decode-step graphs: one captured step per (rows, KV page bound, ...) key, replayed by mtts_step
-    struct StepGraph { int B, pages, forced, ch0, scores, row; hipGraphExec_t exec; };
+    struct StepGraph { int B, pages, forced, ch0, scores, row, lora; hipGraphExec_t exec; };
     std::vector<StepGraph> graphs;
     hipStream_t cap_stream = nullptr;
     bool use_graphs = true;

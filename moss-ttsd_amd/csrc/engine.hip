@@ -363,6 +363,7 @@ struct WeightSlot {
     int* bound = nullptr;            // mask that records the binding; null: a name that is accepted and ignored
     int bit = 0;
     bool proj = false;               // one of a layer's seven projection matrices (what a LoRA adapter may target)
+    int layer = -1, proj_idx = -1;   // ... and which: layer, 0..6 = q k v o gate up down (the adapter bank's order)
 };
 
 static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
@@ -412,6 +413,7 @@ static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
             w.f32_to = t[i].f32; w.f32_row = t[i].f32_row;
             w.bound = &l.bound; w.bit = 1 << i;       // a complete layer has all 11 bits: 2047 (mtts_weights_ready)
             w.proj = t[i].cols != 1;
+            w.layer = n; w.proj_idx = i - 4;
             return MTTS_OK;
         }
     return fail(MTTS_EINVAL, "unknown tensor %s", name_c);
@@ -466,6 +468,139 @@ int32_t mtts_bind_weight_lora(MttsEngine* e, const char* name_c, const void* bas
     HIPCHK(hipGetLastError());
     *w.bound |= w.bit;
     return MTTS_OK;
+}
+
+// ---- resident adapters, one per dialogue (kernels: multilora.hip) ---------------------------------------------------
+// split-K slabs of a pass with adapters: one slab more than the 8 a GEMM may write, and gate/up's two slabs of 2 I columns
+// (mtts_engine_create sizes the buffer for the 8 slabs of an engine without a bank)
+static size_t bank_partial_elems(const MttsEngine* e) {
+    const size_t lin = std::max(e->qkv_rows, round_up(e->H, 32));
+    return std::max(9 * lin, (size_t)4 * e->I) * MTTS_PFCAP;
+}
+static int bank_check(MttsEngine* e, int adapter, const char* what) {
+    if (e->f32) return fail(MTTS_EINVAL, "%s: resident adapters exist on the bf16 engine only (this one is %s); merge one with mtts_bind_weight_lora", what, e->h16 ? "fp16" : "fp32");
+    if (adapter < 0 || adapter >= MTTS_MAX_ADAPTERS) return fail(MTTS_EINVAL, "%s: adapter index %d outside 0..%d", what, adapter, MTTS_MAX_ADAPTERS - 1);
+    bool open = false;
+    TRY(run_still_open(e, &open));
+    if (open) return fail(MTTS_ESTATE, "%s: the adapter bank cannot change while a run is open (the rule of mtts_bind_weight_lora)", what);
+    return MTTS_OK;
+}
+// an id a row or a slot may carry: -1, or an adapter that holds at least one pair
+static int adapter_id_check(MttsEngine* e, int id, const char* what, int at) {
+    if (id == -1) return MTTS_OK;
+    if (id < -1 || id >= MTTS_MAX_ADAPTERS) return fail(MTTS_EINVAL, "%s %d: adapter id %d outside -1..%d", what, at, id, MTTS_MAX_ADAPTERS - 1);
+    if (!e->bank_pairs[id]) return fail(MTTS_EINVAL, "%s %d: adapter %d is empty (mtts_adapter_load)", what, at, id);
+    return MTTS_OK;
+}
+static int bank_upload(MttsEngine* e, size_t first, size_t n, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(e->d_bank + first, e->bank.data() + first, n * sizeof(LoraEnt), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+int32_t mtts_adapter_load(MttsEngine* e, int32_t adapter, const char* name_c, const float* lora_a, const float* lora_b, int64_t rows,
+                          int64_t cols, int32_t r, float scaling, void* stream) {
+    if (!e || !name_c || !lora_a || !lora_b) return fail(MTTS_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(e->device));
+    TRY(bank_check(e, adapter, "mtts_adapter_load"));
+    if (r < 1 || r > MTTS_LORA_MAX_RANK) return fail(MTTS_EINVAL, "%s: adapter rank %d outside 1..%d", name_c, r, MTTS_LORA_MAX_RANK);
+    if (((uintptr_t)lora_a | (uintptr_t)lora_b) & 15) return fail(MTTS_EINVAL, "%s: tensors must be 16-byte aligned", name_c);
+    WeightSlot w;
+    TRY(resolve_weight(e, name_c, w));
+    if (!w.proj) return fail(MTTS_EINVAL, "%s is not a projection weight of a layer: an adapter cannot target it", name_c);
+    if (rows != w.rows || cols != w.cols)
+        return fail(MTTS_EINVAL, "%s: expected [%lld,%lld] got [%lld,%lld]", name_c, (long long)w.rows, (long long)w.cols, (long long)rows, (long long)cols);
+    if (cols > LORA_MAX_K) return fail(MTTS_EINVAL, "%s: rows of %lld elements, the delta kernel stages at most %d", name_c, (long long)cols, LORA_MAX_K);
+    drop_graphs(e);
+    hipStream_t st = S(stream);
+    const size_t per = (size_t)e->L * 7;
+    if (!e->d_bank) {           // the first load: the bank's tables, the per-slot ids, and room for the extra slabs
+        HIPCHK(hipDeviceSynchronize());
+        // all three or none: a failure gives back what it took and leaves the engine as it was, so the load can be retried
+        float* wider = nullptr;
+        int32_t* ids = nullptr;
+        LoraEnt* tab = nullptr;
+        int rc = e->mem.get(&wider, bank_partial_elems(e));
+        if (!rc) rc = e->mem.get(&ids, MTTS_RCAP, false);
+        if (!rc) rc = e->mem.get(&tab, MTTS_MAX_ADAPTERS * per);
+        if (!rc && hipMemset(ids, 0xff, MTTS_RCAP * sizeof(int32_t)) != hipSuccess) rc = fail(MTTS_EHIP, "mtts_adapter_load: hipMemset of the per-slot adapter ids failed");
+        if (rc) { e->mem.release(wider); e->mem.release(ids); e->mem.release(tab); return rc; }
+        e->mem.release(e->partial);
+        e->partial = wider;
+        e->d_seq_adapter = ids;
+        e->bank.assign(MTTS_MAX_ADAPTERS * per, LoraEnt{nullptr, nullptr, 0, 0.f});
+        e->d_bank = tab;
+    }
+    float *a = nullptr, *b = nullptr;
+    TRY(e->mem.get(&a, (size_t)r * cols, false));
+    if (const int rc = e->mem.get(&b, (size_t)rows * r, false)) { e->mem.release(a); return rc; }
+    if (hipMemcpyAsync(a, lora_a, (size_t)r * cols * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(b, lora_b, (size_t)rows * r * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        e->mem.release(a); e->mem.release(b);
+        return fail(MTTS_EHIP, "%s: copying the adapter matrices failed", name_c);
+    }
+    const size_t at = adapter * per + (size_t)w.layer * 7 + w.proj_idx;
+    LoraEnt& ent = e->bank[at];
+    if (ent.r) {                // replaced: nothing in flight reads the old pair (no run is open, the stream is drained below)
+        HIPCHK(hipDeviceSynchronize());
+        float *oa = const_cast<float*>(ent.A), *ob = const_cast<float*>(ent.B);
+        e->mem.release(oa); e->mem.release(ob);
+    } else e->bank_pairs[adapter]++;
+    ent = LoraEnt{a, b, r, scaling};
+    return bank_upload(e, at, 1, st);
+}
+
+int32_t mtts_adapter_clear(MttsEngine* e, int32_t adapter) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    HIPCHK(hipSetDevice(e->device));
+    TRY(bank_check(e, adapter, "mtts_adapter_clear"));
+    drop_graphs(e);
+    if (!e->d_bank || !e->bank_pairs[adapter]) return MTTS_OK;
+    HIPCHK(hipDeviceSynchronize());
+    const size_t per = (size_t)e->L * 7;
+    for (size_t i = adapter * per; i < (adapter + 1) * per; ++i) {
+        float *oa = const_cast<float*>(e->bank[i].A), *ob = const_cast<float*>(e->bank[i].B);
+        e->mem.release(oa); e->mem.release(ob);
+        e->bank[i] = LoraEnt{nullptr, nullptr, 0, 0.f};
+    }
+    e->bank_pairs[adapter] = 0;
+    return bank_upload(e, adapter * per, per, nullptr);
+}
+
+int32_t mtts_set_row_adapters(MttsEngine* e, const int32_t* host_ids, int32_t n) {
+    if (!e || (n > 0 && !host_ids) || n < 0 || n > MTTS_RCAP) return fail(MTTS_EINVAL, "set_row_adapters: bad argument");
+    if (e->f32) return fail(MTTS_EINVAL, "mtts_set_row_adapters: resident adapters exist on the bf16 engine only (this one is %s)", e->h16 ? "fp16" : "fp32");
+    e->next_row_adapters.assign(host_ids, host_ids + n);
+    e->row_adapters_pending = n > 0;
+    return MTTS_OK;
+}
+
+int32_t mtts_set_slot_adapter(MttsEngine* e, int32_t slot, int32_t adapter) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    if (e->f32) return fail(MTTS_EINVAL, "mtts_set_slot_adapter: resident adapters exist on the bf16 engine only (this one is %s)", e->h16 ? "fp16" : "fp32");
+    if (slot < 0 || slot >= MTTS_RCAP) return fail(MTTS_EINVAL, "set_slot_adapter: slot %d out of range", slot);
+    if (adapter < -1 || adapter >= MTTS_MAX_ADAPTERS) return fail(MTTS_EINVAL, "set_slot_adapter: adapter id %d outside -1..%d", adapter, MTTS_MAX_ADAPTERS - 1);
+    e->next_slot_adapter[slot] = adapter;
+    return MTTS_OK;
+}
+// the adapter of the dialogue in `slot` from now on: the host's copy now, the device's on `st`
+static int set_seq_adapter(MttsEngine* e, int slot, int id, hipStream_t st) {
+    e->seq_adapter[slot] = id;
+    if (e->d_seq_adapter) HIPCHK(hipMemcpyAsync(e->d_seq_adapter + slot, &e->seq_adapter[slot], sizeof(int32_t), hipMemcpyHostToDevice, st));
+    return MTTS_OK;
+}
+// the pending list of mtts_set_row_adapters, consumed
+static std::vector<int32_t> take_row_adapters(MttsEngine* e) {
+    std::vector<int32_t> v;
+    v.swap(e->next_row_adapters);
+    e->row_adapters_pending = false;
+    return v;
+}
+// a decode step of the current run carries adapters: a row of it has one
+static bool rows_carry_adapters(const MttsEngine* e) {
+    for (int b = 0; b < e->B; ++b)
+        if (e->seq_adapter[b] >= 0) return true;
+    return false;
 }
 
 template <typename T>
@@ -616,8 +751,13 @@ static int forward_small(MttsEngine* e, const RowMeta* d_meta, int pages_bound, 
 
 // ---- one forward pass: R rows = decode rows (<= MTTS_RCAP, one dialogue each) or a prefill pass (<= MTTS_PFCAP) ----
 // heads: 0 none, 1 from xn (rows are sequences: decode), 2 from hlast (end of prefill)
+// lora: a row of the pass has an adapter (mtts_set_row_adapters / mtts_set_slot_adapter).  The GEMMs, norms and attention
+// kernels are then the same launches with the same arguments, except that after the qkv, o_proj and down_proj GEMMs the
+// adapters' delta goes into the slab behind the GEMM's last one and the consumer sums one slab more, and that gate/up
+// writes a slab instead of running its SwiGLU epilogue (delta into slab 1, swiglu_slabs_kernel on the sum).  The small
+// path has no slabs to extend and is not taken; its arithmetic is forward_rows', so nothing depends on that.
 static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d_meta, int R, int pages_bound,
-                        int heads, hipStream_t st, int64_t kv_tokens_hint) {
+                        int heads, bool lora, hipStream_t st, int64_t kv_tokens_hint) {
     const int H = e->H, I = e->I, nq = e->nq, nkv = e->nkv;
     const float eps = e->cfg.rms_norm_eps;
     const int Hp = round_up(H, 32);
@@ -628,35 +768,52 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
     const bool tiled = heads != 1;
     if (e->f32) return forward_rows_f32(e, d_tokens, d_meta, heads == 1 ? e->B : R, heads, st);
     launch_embed_norm(d_tokens, d_meta, e->d_tables, e->layers[0].ln_in, e->x, e->xn, R, H, eps, st);
-    if (heads == 1 && e->B <= e->small_rows && small_path_fits(e)) return forward_small(e, d_meta, pages_bound, st, kv_tokens_hint);
+    if (heads == 1 && !lora && e->B <= e->small_rows && small_path_fits(e)) return forward_small(e, d_meta, pages_bound, st, kv_tokens_hint);
+    if (lora && !e->d_bank) return fail(MTTS_ESTATE, "a pass with adapters on an engine without a bank");
+    const int QD = nq * MTTS_HD, KD = nkv * MTTS_HD, EL = e->L * 7;
+    const LoraJob j_qkv{3, e->qkv_rows, H, EL, {{0, QD, 1, 0}, {QD, KD, 1, 1}, {QD + KD, KD, 1, 2}}};
+    const LoraJob j_o{1, Hp, QD, EL, {{0, H, 1, 3}}}, j_gu{2, 2 * I, H, EL, {{0, I, 2, 4}, {1, I, 2, 5}}}, j_d{1, Hp, I, EL, {{0, H, 1, 6}}};
     for (int n = 0; n < e->L; ++n) {
         Layer& l = e->layers[n];
+        // the adapters' delta of this layer's matrices in `job`, for the rows in `xp`, into slab `ks` of the partial buffer
+        auto delta = [&](const LoraJob& job, const void* xp, int ks) {
+            launch_lora_delta(xp, d_meta, e->d_seq_adapter, e->d_bank + (size_t)n * 7, job, e->partial + (size_t)ks * MTTS_PFCAP * job.Npad, R, st);
+        };
+        const int ex = lora ? 1 : 0;                     // slabs the consumers sum beyond the GEMM's
         const int ks_qkv = tiled ? mtts_tile_ksplit(e->qkv_rows, H, 1024) : e->p_qkv.ksplit;
         const int ks_o = tiled ? mtts_tile_ksplit(Hp, nq * MTTS_HD, 1024) : e->p_o.ksplit;
         const int ks_d = tiled ? mtts_tile_ksplit(Hp, I, 1024) : e->p_d.ksplit;
         if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_qkv, l.wqkv, e->xn, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, st);
         else launch_gemm(EPI_PARTIAL, mb, e->p_qkv, l.wqkv, e->xn, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, st);
+        if (lora) delta(j_qkv, e->xn, ks_qkv);
         // decode rows (one dialogue each): the q/k/v epilogue runs inside the attention kernels; prefill passes
         // need every K/V row of the pass in the cache before any of its attention runs, so they keep the launch
         // (fused where it pays: every attention block repeats the q epilogue, which costs more than the saved launch
         // once rows x pages is large -- break-even between 32 x 64 and 64 x 64 rows x pages since round 3; the results are bit-identical)
         // decode rows are one dialogue each and read complete pages in their sealed form; prefill tiles are 32 consecutive
         // positions of one dialogue, share their K/V pages (chunks of ATT_PF pages) and read the bf16 pages
-        TRY(attend_layer(e, n, d_meta, R, pages_bound, ks_qkv, 3, heads != 1 && pages_bound >= e->pf_mfma_pages,
+        TRY(attend_layer(e, n, d_meta, R, pages_bound, ks_qkv + ex, 3, heads != 1 && pages_bound >= e->pf_mfma_pages,
                          heads == 1 && e->B * pages_bound <= e->fuse_qkv_max, heads == 1, st, kv_tokens_hint));
         if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
         else launch_gemm(EPI_PARTIAL, mb, e->p_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
-        launch_resid_norm(e->partial, ks_o, Hp, e->x, l.ln_post, e->xn, nullptr, d_meta, R, H, eps, st);
-        if (tiled) {
-            launch_gemm_tile(EPI_SILU, R, 1, l.wgu, e->xn, H, 2 * I, 2 * I, nullptr, (uint16_t*)e->act_p, st);
-            launch_gemm_tile(EPI_PARTIAL, R, ks_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
-        } else {
-            launch_gemm(EPI_SILU, mb, e->p_gu, l.wgu, e->xn, H, 2 * I, 2 * I, nullptr, (uint16_t*)e->act_p, st);
-            launch_gemm(EPI_PARTIAL, mb, e->p_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
+        if (lora) delta(j_o, e->attn_p, ks_o);
+        launch_resid_norm(e->partial, ks_o + ex, Hp, e->x, l.ln_post, e->xn, nullptr, d_meta, R, H, eps, st);
+        // gate/up: the same plan with or without adapters (p_gu; one k-split of the tile GEMM), so slab 0 holds the sums
+        // the fused epilogue would have rounded
+        const int gu_epi = lora ? EPI_PARTIAL : EPI_SILU;
+        float* gu_slab = lora ? e->partial : nullptr;
+        if (tiled) launch_gemm_tile(gu_epi, R, 1, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
+        else launch_gemm(gu_epi, mb, e->p_gu, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
+        if (lora) {
+            delta(j_gu, e->xn, 1);
+            launch_swiglu_slabs(e->partial, e->partial + (size_t)MTTS_PFCAP * 2 * I, e->act_p, mb * 32, I, st);
         }
+        if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
+        else launch_gemm(EPI_PARTIAL, mb, e->p_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
+        if (lora) delta(j_d, e->act_p, ks_d);
         const bool lastl = (n == e->L - 1);
         const void* nw = lastl ? e->final_norm : e->layers[n + 1].ln_in;
-        launch_resid_norm(e->partial, ks_d, Hp, e->x, nw, e->xn, lastl ? e->hlast : nullptr, d_meta, R, H, eps, st);
+        launch_resid_norm(e->partial, ks_d + ex, Hp, e->x, nw, e->xn, lastl ? e->hlast : nullptr, d_meta, R, H, eps, st);
     }
     if (e->kpack)                                      // rows whose token completed a KV page: seal it (all layers)
         launch_kv_seal_rows(e->kcache, e->vcache, e->kpack, e->vpack, e->d_page_table, d_meta, R, e->max_pages, e->total_pages, nkv, e->L, e->d_seal_cnt, st);
@@ -677,11 +834,11 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
 
 // prefill of the first `Mpad` staged rows in passes of up to MTTS_PFCAP (a multiple of MTTS_RCAP each); K/V of a pass are
 // written before its attention runs.  `last_heads`: the heads argument of the last pass.
-static int prefill_staged(MttsEngine* e, size_t Mpad, int pages_bound, int last_heads, hipStream_t st) {
+static int prefill_staged(MttsEngine* e, size_t Mpad, int pages_bound, int last_heads, bool lora, hipStream_t st) {
     const size_t pfcap = e->f32 ? MTTS_PF32CAP : MTTS_PFCAP;
     for (size_t off = 0; off < Mpad; off += pfcap) {
         const int rows = (int)std::min<size_t>(pfcap, Mpad - off);
-        TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, off + rows >= Mpad ? last_heads : 0, st, 0));
+        TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, off + rows >= Mpad ? last_heads : 0, lora, st, 0));
     }
     return 0;
 }
@@ -782,11 +939,19 @@ static int launch_fork_job(MttsEngine* e, ForkJob& job, bool state_rows, hipStre
 
 // ---- begin: parse prompt, allocate pages, prefill --------------------------------------
 static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32_t B, int32_t T, int32_t max_length,
-                     const MttsSamplerCfg* sampler, uint64_t seed, int takes, void* stream) {
+                     const MttsSamplerCfg* sampler, uint64_t seed, int takes, const std::vector<int32_t>& row_adapters, void* stream) {
     if (!e || !ids || !mask || !sampler) return fail(MTTS_EINVAL, "null argument");
     TRY(mtts_weights_ready(e));
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = S(stream);
+    // one adapter id per prompt (mtts_set_row_adapters); none given: no row has one
+    if (!row_adapters.empty() && (int)row_adapters.size() != B)
+        return fail(MTTS_EINVAL, "mtts_set_row_adapters gave %d ids, the batch has %d prompts", (int)row_adapters.size(), B);
+    bool lora = false;
+    for (size_t b = 0; b < row_adapters.size(); ++b) {
+        TRY(adapter_id_check(e, row_adapters[b], "row", (int)b));
+        lora |= row_adapters[b] >= 0;
+    }
     // takes: row b*takes+j is take j of prompt b; only the B prompts are prefilled (into rows b*takes), the other takes
     // share their complete prompt pages and get a copy of the rest (fork_kernel)
     const int R = B * takes;
@@ -895,9 +1060,12 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
         for (int b = 0; b < R; ++b)
             ss[b] = SeqState{-1, 1, e->n_real[b], 0, base, max_length, e->next_row_ids.empty() ? b : e->next_row_ids[b], 1, seed};
         e->next_row_ids.clear();
+        // the rows' adapters: a prompt's takes share its KV pages and so its adapter
+        for (int b = 0; b < MTTS_RCAP; ++b) e->seq_adapter[b] = (b < R && !row_adapters.empty()) ? row_adapters[b / takes] : -1;
+        if (e->d_seq_adapter) HIPCHK(hipMemcpyAsync(e->d_seq_adapter, e->seq_adapter.data(), MTTS_RCAP * sizeof(int32_t), hipMemcpyHostToDevice, st));
         TRY(reset_run_state(e, ss, false, sampler, st));   // drains st: the host vectors above go out of scope
     }
-    TRY(prefill_staged(e, Mpad, (e->max_real + MTTS_PAGE - 1) / MTTS_PAGE, 2, st));
+    TRY(prefill_staged(e, Mpad, (e->max_real + MTTS_PAGE - 1) / MTTS_PAGE, 2, lora, st));
     // takes: the partially filled last prompt page of each source row into its takes' private pages, and the source
     // row's logits into theirs (bitmaps, teacher-forcing tails and states were uploaded for every row above)
     if (fork.nr) TRY(launch_fork_job(e, fork, false, st));
@@ -918,7 +1086,8 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
     if (!e) return fail(MTTS_EINVAL, "null argument");
     const int takes = e->next_takes;
     e->next_takes = 1;                 // consumed by this call, whatever its outcome
-    return begin_run(e, ids, mask, B, T, max_length, sampler, seed, takes, stream);
+    const std::vector<int32_t> row_adapters = take_row_adapters(e);
+    return begin_run(e, ids, mask, B, T, max_length, sampler, seed, takes, row_adapters, stream);
 }
 
 // One decode step: sample from the previous logits, advance the per-dialogue state machine, run the stack.
@@ -933,13 +1102,14 @@ static int step_body(MttsEngine* e, int pages_bound, hipStream_t st, int64_t kvt
                   e->d_seqs, e->d_meta, e->d_bitmaps, e->bm_words, e->d_ls, e->cfg.eos_token_id,
                   e->cfg.speech_pad_token, e->cfg.speech_range_lo, e->cfg.speech_range_hi,
                   e->scores_on ? e->sscr.lp : nullptr, e->scores_on ? e->d_lp : nullptr, st);
-    return forward_rows(e, e->d_cur, e->d_meta, round_up(e->B, 32), pages_bound, 1, st, kvtok);
+    return forward_rows(e, e->d_cur, e->d_meta, round_up(e->B, 32), pages_bound, 1, rows_carry_adapters(e), st, kvtok);
 }
 
 static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
-    const int forced = e->has_forced ? 1 : 0, row = attn_row_shape(e, pages) ? 1 : 0;
+    const int forced = e->has_forced ? 1 : 0, row = attn_row_shape(e, pages) ? 1 : 0, lora = rows_carry_adapters(e) ? 1 : 0;
     for (auto& g : e->graphs)
-        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled && g.scores == e->scores_on && g.row == row) {
+        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled && g.scores == e->scores_on && g.row == row &&
+            g.lora == lora) {
             *out = g.exec;
             return MTTS_OK;
         }
@@ -955,7 +1125,7 @@ static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     HIPCHK(ie);
-    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, e->scores_on, row, exec});
+    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, e->scores_on, row, lora, exec});
     *out = exec;
     return MTTS_OK;
 }
@@ -1170,6 +1340,8 @@ int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const
     if (B < 1 || B > e->cfg.max_batch) return fail(MTTS_EINVAL, "batch %d outside 1..max_batch %d", B, e->cfg.max_batch);
     if (T < 1 || T > e->cfg.max_seq_len) return fail(MTTS_EINVAL, "T %d outside 1..max_seq_len %d", T, e->cfg.max_seq_len);
     if (T > e->rope_rows) return fail(MTTS_EINVAL, "rope table has %d rows, need %d", e->rope_rows, T);
+    if (e->row_adapters_pending)
+        return fail(MTTS_ESTATE, "mtts_score takes no per-row adapters and a mtts_set_row_adapters list is pending (it stays so): score an adapter merged, with mtts_bind_weight_lora");
     bool open = false;
     TRY(run_still_open(e, &open));
     if (open) return fail(MTTS_ESTATE, "mtts_score while a run is open: its rows still own KV pages and the activation buffers");
@@ -1278,7 +1450,7 @@ int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const
         const int pages_bound = std::max(1, (max_len + MTTS_PAGE - 1) / MTTS_PAGE);
         for (size_t off = 0; off < Mpad; off += pfcap) {
             const int rows = (int)std::min<size_t>(pfcap, Mpad - off);
-            TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, 0, st, 0));
+            TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, 0, false, st, 0));
             TRY(score_pass(e, e->d_sc_labels + off * 8, e->d_sc_logp + off * 8, rows, st));
         }
     }
@@ -1312,9 +1484,10 @@ int32_t mtts_generate(MttsEngine* e, const int64_t* ids, const uint8_t* mask, in
     if (!e) return fail(MTTS_EINVAL, "null argument");
     const int takes = e->next_takes;
     e->next_takes = 1;                 // consumed by this call, whatever its outcome
+    const std::vector<int32_t> row_adapters = take_row_adapters(e);
     if (!out || !out_len) return fail(MTTS_EINVAL, "null output");
     if (forced && takes > 1) return fail(MTTS_EINVAL, "forced replay (reference fixtures) has no takes: %d takes per prompt", takes);
-    TRY(begin_run(e, ids, mask, B, T, max_length, sampler, seed, takes, stream));
+    TRY(begin_run(e, ids, mask, B, T, max_length, sampler, seed, takes, row_adapters, stream));
     hipStream_t st = S(stream);
     const int base = e->base_length;
     const int R = e->B;
@@ -1398,6 +1571,8 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     for (int b = 0; b < e->cfg.max_batch; ++b) { pool_release(e, b); e->slot_live[b] = 0; }
     e->pending_edits.n = 0;
     TRY(pack_policy_reset(e, st));
+    std::fill(e->seq_adapter.begin(), e->seq_adapter.end(), -1);
+    if (e->d_seq_adapter) HIPCHK(hipMemsetAsync(e->d_seq_adapter, 0xff, MTTS_RCAP * sizeof(int32_t), st));
     TRY(reset_run_state(e, std::vector<SeqState>(MTTS_RCAP, IDLE_SEQ), true, sampler, st));
     e->began = true;
     e->run_open = true;
@@ -1425,6 +1600,9 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = S(stream);
     if (slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "slot %d out of range", slot);
+    const int adapter = e->next_slot_adapter[slot];
+    e->next_slot_adapter[slot] = -1;                  // mtts_set_slot_adapter: consumed by this call, whatever its outcome
+    TRY(adapter_id_check(e, adapter, "slot", slot));
     if (T < 8) return fail(MTTS_EINVAL, "T must be >= 8");
     const int base = T - 7, n = base;
     if (max_length <= base) return fail(MTTS_EINVAL, "max_length leaves no room to generate");
@@ -1462,7 +1640,8 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
     HIPCHK(hipMemcpy(e->d_pf_meta, metas.data(), Mpad * sizeof(RowMeta), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_bitmaps + (size_t)slot * 8 * e->bm_words, bm.data(), bm.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_tf + (size_t)slot * 7 * 8, tf.data(), tf.size() * 4, hipMemcpyHostToDevice));
-    TRY(prefill_staged(e, Mpad, (n + MTTS_PAGE - 1) / MTTS_PAGE, 0, st));
+    TRY(set_seq_adapter(e, slot, adapter, st));
+    TRY(prefill_staged(e, Mpad, (n + MTTS_PAGE - 1) / MTTS_PAGE, 0, adapter >= 0, st));
     // logits of the dialogue's last prompt token only: heads on a one-row activation tile, copied into its slot
     // (the other slots' logits belong to dialogues that are mid-flight)
     if (e->f32) {            // fp32 engine: the GEMV writes the slot's logits rows directly
@@ -1525,6 +1704,7 @@ int32_t mtts_slot_fork(MttsEngine* e, int32_t src, int32_t dst, uint64_t seed, i
     SeqState ns = e->h_seqs[src];
     ns.row_id = row_id; ns.seed = seed;
     e->h_seqs[dst] = ns;                            // pinned staging of the upload
+    TRY(set_seq_adapter(e, dst, e->seq_adapter[src], st));       // the shared pages hold K/V computed with src's adapter
     HIPCHK(hipMemcpyAsync(e->d_seqs + dst, e->h_seqs + dst, sizeof(SeqState), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     e->n_real[dst] = e->n_real[src];
@@ -1545,7 +1725,7 @@ int32_t mtts_slot_states(MttsEngine* e, int32_t* host_state, void* stream) {
         host_state[b * 4 + 2] = ss[b].step; host_state[b * 4 + 3] = ss[b].kv_len;
         // a dialogue that has left the batch (scheduler mode) gives its pages back: the stream is idle, nothing
         // in flight reads them
-        if (e->continuous && e->slot_live[b] && !ss[b].active) { e->slot_live[b] = 0; pool_release(e, b); }
+        if (e->continuous && e->slot_live[b] && !ss[b].active) { e->slot_live[b] = 0; pool_release(e, b); e->seq_adapter[b] = -1; }
     }
     return MTTS_OK;
 }
@@ -1562,6 +1742,7 @@ int32_t mtts_slot_evict(MttsEngine* e, int32_t slot, void* stream) {
     RowMeta idle{-1, 0, 0, 0};
     HIPCHK(hipMemcpy(e->d_meta + slot, &idle, sizeof(idle), hipMemcpyHostToDevice));
     if (e->slot_live[slot]) { e->slot_live[slot] = 0; pool_release(e, slot); }
+    e->seq_adapter[slot] = -1;                      // (the host's copy picks the step's launches; the device's is rewritten by the next submit)
     return MTTS_OK;
 }
 

@@ -98,6 +98,86 @@ int32_t mtts_k_lora_pack(const void* base, int32_t rows, int32_t cols, const flo
     return MTTS_OK;
 }
 
+int32_t mtts_k_lora_delta(const void* dev_x, int32_t R, int32_t K, int32_t Npad, int32_t nseg, const int32_t* host_segs,
+                          int32_t n_adapters, const void* const* host_a, const void* const* host_b, const int32_t* host_r,
+                          const float* host_scaling, const int32_t* host_row_adapter, float* dev_slabs, int32_t ks, void* stream) {
+    if (!dev_x || !host_segs || !host_a || !host_b || !host_r || !host_scaling || !host_row_adapter || !dev_slabs)
+        return fail(MTTS_EINVAL, "lora_delta: null argument");
+    if (R < 1 || R > MTTS_PFCAP || K < 16 || K % 16 || K > LORA_MAX_K || Npad < 32 || Npad % 32 || nseg < 1 || nseg > LORA_SEGS ||
+        n_adapters < 1 || n_adapters > MTTS_MAX_ADAPTERS || ks < 0)
+        return fail(MTTS_EINVAL, "lora_delta: need 1<=R<=%d, K%%16==0, K<=%d, Npad%%32==0, 1<=nseg<=%d, 1<=n_adapters<=%d", MTTS_PFCAP,
+                    LORA_MAX_K, LORA_SEGS, MTTS_MAX_ADAPTERS);
+    LoraJob job{};
+    job.nseg = nseg; job.Npad = Npad; job.K = K; job.ent_stride = nseg;
+    for (int s = 0; s < nseg; ++s) {
+        const int32_t* g = host_segs + 3 * s;
+        if (g[0] < 0 || g[1] < 1 || g[2] < 1 || (int64_t)g[0] + (int64_t)(g[1] - 1) * g[2] >= Npad)
+            return fail(MTTS_EINVAL, "lora_delta: matrix %d (col0 %d, ncols %d, mul %d) does not fit %d columns", s, g[0], g[1], g[2], Npad);
+        job.seg[s] = LoraSeg{g[0], g[1], g[2], s};
+    }
+    std::vector<LoraEnt> ents((size_t)n_adapters * nseg);
+    for (size_t i = 0; i < ents.size(); ++i) {
+        if (host_r[i] < 0 || host_r[i] > MTTS_LORA_MAX_RANK || (host_r[i] && (!host_a[i] || !host_b[i])))
+            return fail(MTTS_EINVAL, "lora_delta: entry %zu: rank %d outside 0..%d, or a null matrix", i, host_r[i], MTTS_LORA_MAX_RANK);
+        if (((uintptr_t)host_a[i] | (uintptr_t)host_b[i]) & 15) return fail(MTTS_EINVAL, "lora_delta: matrices must be 16-byte aligned");
+        ents[i] = LoraEnt{(const float*)host_a[i], (const float*)host_b[i], host_r[i], host_scaling[i]};
+    }
+    std::vector<RowMeta> metas(R);
+    std::vector<int32_t> sa(R);
+    for (int r = 0; r < R; ++r) {
+        const int a = host_row_adapter[r];
+        if (a < -2 || a >= n_adapters) return fail(MTTS_EINVAL, "lora_delta: row %d names adapter %d of %d", r, a, n_adapters);
+        metas[r] = RowMeta{a == -2 ? -1 : r, 0, 0, 0};
+        sa[r] = a < 0 ? -1 : a;
+    }
+    hipStream_t st = S(stream);
+    DevBufs hb;
+    uint16_t* xp = nullptr;
+    LoraEnt* d_ents = nullptr;
+    RowMeta* d_meta = nullptr;
+    int32_t* d_sa = nullptr;
+    const int tiles = (R + 31) / 32;
+    TRY(hb.get(&xp, (size_t)tiles * 32 * K));
+    TRY(hb.get(&d_ents, ents.size(), false));
+    TRY(hb.get(&d_meta, (size_t)R, false));
+    TRY(hb.get(&d_sa, (size_t)R, false));
+    HIPCHK(hipMemcpyAsync(d_ents, ents.data(), ents.size() * sizeof(LoraEnt), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_meta, metas.data(), metas.size() * sizeof(RowMeta), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_sa, sa.data(), sa.size() * 4, hipMemcpyHostToDevice, st));
+    launch_pack_rows(dev_x, xp, R, K, tiles, st);
+    launch_lora_delta(xp, d_meta, d_sa, d_ents, job, dev_slabs + (size_t)ks * MTTS_PFCAP * Npad, R, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+int32_t mtts_k_swiglu_slabs(const void* w, const void* x, const float* dev_delta, void* y, float* dev_slab0_out, int32_t M, int32_t N,
+                            int32_t K, void* stream) {
+    if (!w || !x || !y || M < 1 || M > MTTS_RCAP || K % 16 || N < 32 || N % 32) return fail(MTTS_EINVAL, "swiglu_slabs: need 1<=M<=128, K%%16==0, N%%32==0");
+    hipStream_t st = S(stream);
+    void *wp = nullptr, *xp = nullptr, *op = nullptr;
+    float* part = nullptr;
+    GemmPlan p = mtts_plan_gemm(N, K, 1);          // as the engine plans gate/up: no split-K
+    p.depth = gemm_depth_env();
+    DevBufs hb;
+    const int tiles = (M + 31) / 32, tp = tiles == 3 ? 4 : tiles;
+    TRY(hb.get((uint16_t**)&wp, (size_t)N * K));
+    TRY(hb.get((uint16_t**)&xp, (size_t)tp * 32 * K));
+    TRY(hb.get((uint16_t**)&op, (size_t)tp * 32 * (N / 2)));
+    TRY(hb.get(&part, (size_t)2 * MTTS_PFCAP * N));
+    float* slab1 = part + (size_t)MTTS_PFCAP * N;
+    launch_pack_weight(w, wp, N, K, N, 1, 0, st);
+    launch_pack_rows(x, xp, M, K, tp, st);
+    launch_gemm(EPI_PARTIAL, tiles, p, wp, xp, K, N, N, part, nullptr, st);
+    if (dev_delta) HIPCHK(hipMemcpyAsync(slab1, dev_delta, (size_t)M * N * 4, hipMemcpyDeviceToDevice, st));
+    launch_swiglu_slabs(part, slab1, op, tiles * 32, N / 2, st);
+    launch_unpack_rows(op, y, M, N / 2, st);
+    if (dev_slab0_out) HIPCHK(hipMemcpyAsync(dev_slab0_out, part, (size_t)M * N * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
 int32_t mtts_k_rmsnorm(const void* x, const void* w, void* y, int32_t rows, int32_t n, float eps, void* stream) {
     if (!x || !w || !y || rows < 1 || n < 1) return fail(MTTS_EINVAL, "rmsnorm: bad argument");
     launch_rmsnorm_rows(x, w, y, rows, n, eps, S(stream));

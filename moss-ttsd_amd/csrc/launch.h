@@ -174,6 +174,24 @@ void launch_lora_pack(const void* base, const float* A, const float* B, int r, f
 void launch_lora_rows_f32(const float* base, const float* A, const float* B, int r, float scaling, float* dst, int rows, int cols,
                           int h16, hipStream_t st);
 
+// ---- multilora.hip --------------------------------------------------------------------------------------------------
+// Unmerged per-row adapters: the delta scaling * B (A x) of a row's adapter as one more split-K slab of a GEMM, and the
+// SwiGLU epilogue on the sum of two gate/up slabs.  One bank entry per (adapter, layer, projection): A fp32 [r][in],
+// B fp32 [out][r], r = 0: the adapter does not target the matrix.  A job names the matrices whose outputs share one slab:
+// matrix row i of segment s is slab column col0 + mul * i (q|k|v one after another; gate and up interleaved).
+#define LORA_SEGS 3
+#define LORA_MAX_K 16000       // row length a delta block can stage (fp32, in LDS)
+struct LoraEnt { const float* A; const float* B; int32_t r; float scaling; };
+struct LoraSeg { int32_t col0, ncols, mul, proj; };      // proj: entry of the layer (0..6: q k v o gate up down)
+struct LoraJob { int32_t nseg, Npad, K, ent_stride; LoraSeg seg[LORA_SEGS]; };
+static_assert(sizeof(LoraEnt) == 24 && std::is_trivially_copyable<LoraEnt>::value, "LoraEnt is memcpy'd to the device");
+// rows [0, R) x columns [0, Npad) of `slab` ([MTTS_PFCAP][Npad]) are written, nothing else; xp: packed activations of
+// row length job.K (% 16 == 0, <= LORA_MAX_K); ents: the bank at this layer, entry [adapter * job.ent_stride + proj]
+void launch_lora_delta(const void* xp, const RowMeta* meta, const int32_t* seq_adapter, const LoraEnt* ents, const LoraJob& job,
+                       float* slab, int R, hipStream_t st);
+// act (packed, row length I) = SwiGLU(slab0 + slab1), slabs [MTTS_PFCAP][2 I] with gate / up columns interleaved; I % 8 == 0
+void launch_swiglu_slabs(const float* slab0, const float* slab1, void* act_packed, int R, int I, hipStream_t st);
+
 // ---- codec.hip / codec_fused.hip ------------------------------------------------------------------------------------
 void mtts_gemm_f32_exact(hipStream_t st, const float* A, const float* W, float* C, int M, int N, int K, long ldc);
 void launch_split_pack_w2perm(hipStream_t st, const float* w2, uint16_t* hi, uint16_t* lo);

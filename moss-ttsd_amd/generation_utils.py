@@ -252,10 +252,12 @@ def normalize_text(text: str) -> str:
 
 
 # ---- the batch API -------------------------------------------------------------------------
-def process_batch(batch_items, tokenizer, model, spt, device, system_prompt, start_idx, use_normalize=False, indices=None):
+def process_batch(batch_items, tokenizer, model, spt, device, system_prompt, start_idx, use_normalize=False, indices=None,
+                  adapter_names=None):
     """-> (actual_texts_data, audio_results); a failed sample yields None, a batch-level failure re-raises.
     `indices` (not in the reference; used by inference_sharded.process_batch_sharded): the job-wide index of each item
-    when this call serves one rank's share of a larger batch; default start_idx + position, as in the reference."""
+    when this call serves one rank's share of a larger batch; default start_idx + position, as in the reference.
+    `adapter_names` (not in the reference): one resident adapter name per item, handed to model.generate."""
     try:
         n = len(batch_items)
         gidx = [start_idx + i for i in range(n)] if indices is None else [int(x) for x in indices]
@@ -278,7 +280,8 @@ def process_batch(batch_items, tokenizer, model, spt, device, system_prompt, sta
         input_ids, attention_mask = rpadding(seqs, MAX_CHANNELS, tokenizer)
         print("Starting batch audio generation...")
         start = input_ids.shape[1] - MAX_CHANNELS + 1
-        outputs = model.generate(input_ids=input_ids.to(device), attention_mask=attention_mask.to(device))
+        extra = {} if adapter_names is None else {"adapter_names": list(adapter_names)}
+        outputs = model.generate(input_ids=input_ids.to(device), attention_mask=attention_mask.to(device), **extra)
         print(f"Original outputs shape: {outputs.shape}")
         outputs = outputs[:, start:]
         seq_len = outputs.shape[1] - MAX_CHANNELS + 1

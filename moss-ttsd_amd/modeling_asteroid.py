@@ -152,6 +152,7 @@ class AsteroidTTSInstruct:
                                         # batch sets its rows' job-wide positions); None = 0..B-1
         self._calls = 0
         self._adapter = None            # the active LoRA adapter: (tensors {weight name: (A, B)}, scaling); load_adapter()
+        self._named = {}                # resident, unmerged adapters: name -> (bank index, tensors, scaling); load_adapter(adapter_name=)
         self.weights = [1 for _ in range(self.channels)]      # per-channel loss weights (modeling_asteroid.py:297)
 
     # ---- loading -----------------------------------------------------------------
@@ -192,6 +193,7 @@ class AsteroidTTSInstruct:
         self.device = torch.device(device)
         if self._adapter is not None:
             self._adapter = ({k: tuple(t.to(self.device) for t in ab) for k, ab in self._adapter[0].items()}, self._adapter[1])
+        self._named = {nm: (i, {k: tuple(t.to(self.device) for t in ab) for k, ab in ts.items()}, sc) for nm, (i, ts, sc) in self._named.items()}
         return self
 
     def is_speech_token(self, tokens):
@@ -216,6 +218,8 @@ class AsteroidTTSInstruct:
             self._engine_key = key
             if self._adapter is not None:
                 self._apply_adapter(self._engine, ())
+            for idx, tensors, scaling in self._named.values():
+                self._engine.load_bank_adapter(idx, tensors, scaling)
         return self._engine
 
     # ---- LoRA adapters (PEFT merge_and_unload on the resident engine: mtts/adapters.py, csrc/adapter.hip) ----------
@@ -231,12 +235,19 @@ class AsteroidTTSInstruct:
                 v = self._sd[name]
                 eng.bind(name, torch.from_numpy(v) if isinstance(v, np.ndarray) else v)
 
-    def load_adapter(self, path_or_tensors, scaling=None):
+    def load_adapter(self, path_or_tensors, scaling=None, adapter_name=None):
         """Make a LoRA adapter the active one: a PEFT checkpoint directory (adapter_config.json + adapter_model.safetensors
         | .bin; mtts.adapters.read_peft_dir lists what is refused), or {weight name: (lora_A [r, in], lora_B [out, r])}
         with `scaling` (lora_alpha / r, or / sqrt(r) for rsLoRA).  One adapter is active at a time: loading replaces the
         active one, and a weight the new adapter does not target goes back to its base.  On a resident engine this is one
-        merge-and-pack pass per targeted matrix; an engine built later gets the adapter after its weights."""
+        merge-and-pack pass per targeted matrix; an engine built later gets the adapter after its weights.
+
+        With `adapter_name` (PEFT: model.load_adapter(path, adapter_name=...)) the adapter is instead kept resident and
+        UNMERGED under that name, next to up to 15 others, for generate(adapter_names=[...]) to pick per prompt.  The same
+        files and tensors are accepted and refused; in addition the rank is at most 64 and the model bf16.  The bound
+        weights -- base, or merged with the active adapter -- stay as they are, and a named adapter's delta adds to them."""
+        if adapter_name is not None:
+            return self._load_named(str(adapter_name), path_or_tensors, scaling)
         if isinstance(path_or_tensors, (str, os.PathLike)):
             tensors, file_scaling, _ = adapters.read_peft_dir(os.fspath(path_or_tensors), self.config)
             scaling = file_scaling if scaling is None else scaling
@@ -260,6 +271,70 @@ class AsteroidTTSInstruct:
                 self._adapter = old         # (a run is open: the engine refused the first matrix and holds what it held)
                 raise
         return self
+
+    def _load_named(self, name, path_or_tensors, scaling):
+        if name == adapters.BASE_ADAPTER:
+            raise ValueError(f"adapter_name {name!r} is the name of the base model in generate(adapter_names=...)")
+        if self.dtype != "bf16":
+            raise ValueError(f"load_adapter(adapter_name=...): resident adapters exist on the bf16 engine only, this model is {self.dtype}; "
+                             "without adapter_name the adapter is merged, which every dtype supports")
+        if isinstance(path_or_tensors, (str, os.PathLike)):
+            tensors, file_scaling, _ = adapters.read_peft_dir(os.fspath(path_or_tensors), self.config)
+            scaling = file_scaling if scaling is None else scaling
+        else:
+            if scaling is None:
+                raise ValueError("load_adapter(tensors) needs scaling (lora_alpha / r, or lora_alpha / sqrt(r) with rsLoRA)")
+            tensors = {k: tuple(torch.as_tensor(t).detach() for t in ab) for k, ab in dict(path_or_tensors).items()}
+            adapters.check_tensors(tensors, self.config)
+        for k, (A, _) in tensors.items():
+            if int(A.shape[0]) > adapters.MAX_BANK_RANK:
+                raise ValueError(f"{k}: rank {int(A.shape[0])} is above {adapters.MAX_BANK_RANK}, the most a resident adapter may have "
+                                 "(merge it instead: load_adapter without adapter_name)")
+        used = {i for i, _, _ in self._named.values()}
+        idx = self._named[name][0] if name in self._named else next((i for i in range(adapters.MAX_BANK_ADAPTERS) if i not in used), None)
+        if idx is None:
+            raise ValueError(f"{adapters.MAX_BANK_ADAPTERS} adapters are resident already ({', '.join(self._named)}): delete_adapter() one first")
+        tensors = {k: tuple(torch.as_tensor(t).to(device=self.device, dtype=torch.float32).contiguous() for t in ab)
+                   for k, ab in tensors.items()}
+        scaling = float(np.float32(scaling))
+        if self._engine is not None:
+            self._engine.load_bank_adapter(idx, tensors, scaling)
+        self._named[name] = (idx, tensors, scaling)
+        return self
+
+    def delete_adapter(self, name):
+        """Drop the resident adapter `name` (load_adapter(adapter_name=...)); its memory on the engine is freed."""
+        if name not in self._named:
+            raise ValueError(f"no resident adapter {name!r} (have: {', '.join(self._named) or 'none'})")
+        idx = self._named[name][0]
+        if self._engine is not None:
+            self._engine.clear_bank_adapter(idx)
+        del self._named[name]
+        return self
+
+    def adapter_names(self):
+        """Names of the resident adapters, in the order they were loaded."""
+        return list(self._named)
+
+    def _row_adapters(self, adapter_names, B):
+        """generate(adapter_names=[...]) -> bank index per prompt (-1: base), or None; ValueError before any engine work."""
+        if adapter_names is None:
+            return None
+        names = list(adapter_names)
+        if len(names) != B:
+            raise ValueError(f"adapter_names has {len(names)} entries for a batch of {B} prompts")
+        if self.dtype != "bf16":
+            raise ValueError(f"generate(adapter_names=...): resident adapters exist on the bf16 engine only, this model is {self.dtype}")
+        out = []
+        for nm in names:
+            if nm is None or nm == adapters.BASE_ADAPTER:
+                out.append(-1)
+            elif nm in self._named:
+                out.append(self._named[nm][0])
+            else:
+                raise ValueError(f"adapter_names: no resident adapter {nm!r} (have: {', '.join(self._named) or 'none'}; "
+                                 f"{adapters.BASE_ADAPTER!r} or None for the base model)")
+        return out
 
     def unload_adapter(self):
         """Back to the base model: the projections the active adapter targets are rebound from the base state dict."""
@@ -348,13 +423,15 @@ class AsteroidTTSInstruct:
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,
-                 num_return_sequences=None, return_dict_in_generate=False, output_scores=False, **kw):
+                 num_return_sequences=None, return_dict_in_generate=False, output_scores=False, adapter_names=None, **kw):
         """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
         num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
         repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages.
         return_dict_in_generate=True -> GenerateOutput (.sequences = that tensor); with output_scores=True it carries
         the per-token log-probabilities from the device sampler (modeling_asteroid.py:69-80,171-195 of the reference
-        return full score rows; see GenerateOutput)."""
+        return full score rows; see GenerateOutput).
+        adapter_names (PEFT's mixed-batch inference): one name per PROMPT of a resident adapter (load_adapter(adapter_name=)),
+        "__base__" or None for none; the prompt's takes run with it.  A row's tokens are those of the single-prompt call."""
         if return_dict_in_generate:
             bad = [k for k in ("output_logits", "output_attentions", "output_hidden_states") if kw.get(k)]
             if bad:
@@ -386,6 +463,7 @@ class AsteroidTTSInstruct:
         rows = list(range(B)) if self.sample_rows is None else [int(r) for r in self.sample_rows]
         if len(rows) != B:
             raise ValueError(f"sample_rows has {len(rows)} entries for a batch of {B}")
+        row_adapters = self._row_adapters(adapter_names, B)
         R = B * n                       # take j of prompt b is row b*n+j and draws as row rows[b]*n+j of the expanded job
         # room for the reference's finished-row flushes past max_length: 14 steps at least, the whole chain
         # (6 * B + 8, include/mtts.h: mtts_generate) where that is cheap
@@ -393,9 +471,10 @@ class AsteroidTTSInstruct:
         if R <= self.MAX_ENGINE_BATCH:
             # one static batch, the reference's semantics: finished rows emit (eos, 1024 x 7) until the batch ends
             out = eng.generate(ids, msk, int(max_length), layers=layers, do_samples=do_samples, seed=seed,
-                               row_ids=[r * n + j for r in rows for j in range(n)], takes=n, output_scores=want_lp)
+                               row_ids=[r * n + j for r in rows for j in range(n)], takes=n, output_scores=want_lp,
+                               row_adapters=row_adapters)
         else:
-            out = self._generate_scheduled(eng, ids, msk, int(max_length), layers, do_samples, seed, rows, n, want_lp)
+            out = self._generate_scheduled(eng, ids, msk, int(max_length), layers, do_samples, seed, rows, n, want_lp, row_adapters)
         out, lp = out if want_lp else (out, None)
         seq = torch.from_numpy(out).to(input_ids.device)
         if not return_dict_in_generate:
@@ -414,7 +493,8 @@ class AsteroidTTSInstruct:
         self._calls += 1
         return int(seed)
 
-    def _generate_scheduled(self, eng, ids, msk, max_length, layers, do_samples, seed, rows, takes=1, output_scores=False):
+    def _generate_scheduled(self, eng, ids, msk, max_length, layers, do_samples, seed, rows, takes=1, output_scores=False,
+                            row_adapters=None):
         """More rows than one pass carries: the continuous batcher serves them through MAX_ENGINE_BATCH slots (a
         finished dialogue's slot and KV pages go to the next one).  Row i draws from the Philox stream
         (seed; step, rows[i], channel) -- the stream row i of one static batch would use, so the same seed and prompts
@@ -429,7 +509,8 @@ class AsteroidTTSInstruct:
         new = max_length - T
         cb = ContinuousBatcher(eng, slots=self.MAX_ENGINE_BATCH, gen_cap=max_length - base + 8, layers=layers,   # max_new + 7 flush steps
                                do_samples=do_samples)
-        res = cb.run(prompts, new, seeds=[seed] * B, row_ids=rows, takes=takes, output_scores=output_scores)     # row k = take k % takes of prompt k // takes
+        res = cb.run(prompts, new, seeds=[seed] * B, row_ids=rows, takes=takes, output_scores=output_scores,
+                     adapters=row_adapters)     # row k = take k % takes of prompt k // takes
         res, sc = res if output_scores else (res, None)
         G = max(r.shape[0] - (T - pads[k // takes] - 7) for k, r in enumerate(res))
         full = np.full((B * takes, base + G, C), self.config.speech_pad_token, dtype=np.int64)

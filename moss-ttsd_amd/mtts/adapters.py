@@ -137,6 +137,51 @@ def is_adapter_dir(path):
     return os.path.isfile(os.path.join(path, "adapter_config.json")) and not os.path.exists(os.path.join(path, "config.json"))
 
 
+BASE_ADAPTER = "__base__"          # generate(adapter_names=[...]): this row runs without an adapter (PEFT's name for it)
+MAX_BANK_RANK = 64                 # include/mtts.h: MTTS_LORA_MAX_RANK (resident, unmerged adapters)
+MAX_BANK_ADAPTERS = 16             # include/mtts.h: MTTS_MAX_ADAPTERS
+
+
+def delta_spec(x, A, B, scaling):
+    """The unmerged low-rank path of one projection by definition, numpy float32 (every + and * one IEEE operation):
+
+        t[j] = sum over k of A[j, k] * x[k]:  64 partial sums, number l taking k = 256 i + 4 l + c in the order i ascending,
+               then c = 0..3 (acc = acc + A[j, k] * x[k], from 0; k >= in: no term), reduced by the xor tree
+               v = v + v[l ^ m] for m = 32, 16, 8, 4, 2, 1
+        y[n] = (sum over j ascending of B[n, j] * t[j], from 0) * scaling
+
+    x [rows, in] (float32 holding the activation's bf16 values), A [r, in], B [out, r] -> float32 [rows, out].  A function
+    of one row of x and of (A, B, scaling) alone; csrc/multilora.hip computes it with one partial sum per lane and the
+    kernels' wave sum, and the tests compare bit for bit."""
+    x, A, B = (np.ascontiguousarray(v, dtype=np.float32) for v in (x, A, B))
+    one = x.ndim == 1
+    x = x.reshape(-1, x.shape[-1])
+    assert A.shape[0] == B.shape[1] and A.shape[1] == x.shape[1]
+    R, K = x.shape
+    r = A.shape[0]
+    Kp = -(-K // 256) * 256
+    xp = np.zeros((R, Kp), np.float32)
+    xp[:, :K] = x
+    Ap = np.zeros((r, Kp), np.float32)
+    Ap[:, :K] = A
+    xp, Ap = xp.reshape(R, 1, Kp // 256, 64, 4), Ap.reshape(1, r, Kp // 256, 64, 4)
+    v = np.zeros((R, r, 64), np.float32)
+    for i in range(Kp // 256):
+        for c in range(4):
+            # (a padded term adds +0.0 or -0.0 to a sum that is never -0.0: the same as no term)
+            v = v + Ap[:, :, i, :, c] * xp[:, :, i, :, c]
+    lanes = np.arange(64)
+    for m in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lanes ^ m]
+    t = v[:, :, 0]                                                       # [R, r]
+    acc = np.zeros((R, B.shape[0]), np.float32)
+    for j in range(r):
+        acc = acc + B[None, :, j] * t[:, j:j + 1]
+    y = acc * np.float32(scaling)
+    assert y.dtype == np.float32
+    return y[0] if one else y
+
+
 def merge_spec(W, A, B, scaling, dtype="bf16"):
     """The merged matrix by definition, numpy float32 (every + and * one IEEE operation):
 

@@ -55,6 +55,14 @@ _SIGS = {
                                           C.c_int32, C.c_float, C.c_void_p]),
     "mtts_k_lora_pack": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mtts_adapter_load": (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                      C.c_float, C.c_void_p]),
+    "mtts_adapter_clear": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "mtts_set_row_adapters": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "mtts_set_slot_adapter": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mtts_k_lora_delta": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] +
+                          [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
+    "mtts_k_swiglu_slabs": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p]),
     "mtts_bind_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mtts_weights_ready": (C.c_int32, [C.c_void_p]),
     "mtts_generate": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

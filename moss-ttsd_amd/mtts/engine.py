@@ -109,6 +109,31 @@ class Engine:
         if sync:
             torch.cuda.synchronize(self.device)     # the engine holds the merged matrix; the three tensors may go
 
+    def load_bank_adapter(self, idx, tensors, scaling):
+        """Adapter `idx` (0..15) of the engine's bank of resident, UNMERGED adapters (include/mtts.h: mtts_adapter_load):
+        tensors {engine weight name: (A [r, in], B [out, r])} as adapters.read_peft_dir returns them, r <= 64; scaling one
+        fp32 value.  Replaces whatever `idx` held.  A row that names it (row_adapters= / adapter=) computes
+        W x + scaling * B (A x) in every projection the adapter targets; the bound weights stay as they are.  bf16 only."""
+        self.clear_bank_adapter(idx)
+        as_t = lambda v: torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+        for name, (A, B) in tensors.items():
+            a, b = (as_t(v).to(device=self.device, dtype=torch.float32).contiguous() for v in (A, B))
+            if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1]:
+                raise ValueError(f"{name}: lora_A {tuple(a.shape)} and lora_B {tuple(b.shape)} are not [r, in] and [out, r]")
+            torch.cuda.synchronize(self.device)         # torch's copies have landed; the call copies and drains its stream
+            capi.check(self.lib.mtts_adapter_load(self._h, int(idx), name.encode(), a.data_ptr(), b.data_ptr(), b.shape[0], a.shape[1],
+                                                  int(a.shape[0]), C.c_float(float(scaling)), None))
+
+    def clear_bank_adapter(self, idx):
+        capi.check(self.lib.mtts_adapter_clear(self._h, int(idx)))
+
+    def _set_row_adapters(self, row_adapters, B):
+        if row_adapters is not None:
+            r = np.ascontiguousarray([-1 if a is None else int(a) for a in row_adapters], dtype=np.int32)
+            if r.shape != (B,):
+                raise ValueError(f"row_adapters has {r.size} entries, the batch has {B} prompts")
+            capi.check(self.lib.mtts_set_row_adapters(self._h, r.ctypes.data, B))
+
     def bind_state_dict(self, sd):
         for k, v in sd.items():
             if k.startswith("lm_heads.") or k.endswith("embed_tokens.weight"):
@@ -149,7 +174,7 @@ class Engine:
         capi.check(self.lib.mtts_set_output_scores(self._h, 1 if on else 0))
 
     def generate(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, forced=None,
-                 forced_as_draw=False, row_ids=None, takes=1, output_scores=False):
+                 forced_as_draw=False, row_ids=None, takes=1, output_scores=False, row_adapters=None):
         """forced (verification hook): int64 [B,G,8] full sequences of a reference run.  -> (ids, decisions [steps,B,8]).
         forced_as_draw: the forced row replaces each step's raw draw before the state machine (replay of a SAMPLED
         run); decisions are then the raw draws.  forced_as_draw="all": also for rows that max_length has cut off (the
@@ -158,7 +183,8 @@ class Engine:
         equal to the run of the repeat-interleaved batch; row_ids then has B*takes entries.
         output_scores: the return value gains a last element lp, float32 [B*takes, G, 8] aligned with ids[:, T-7:]:
         log_softmax(processed scores)[the sampler's decision], NaN where the appended token is not a model decision
-        (teacher forcing, EOS flush, finished-row padding)."""
+        (teacher forcing, EOS flush, finished-row padding).
+        row_adapters: one bank index per PROMPT (load_bank_adapter), -1 or None = no adapter; a prompt's takes inherit it."""
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
         R = B * int(takes)
@@ -172,6 +198,7 @@ class Engine:
         self.set_output_scores(output_scores)
         self._set_row_ids(row_ids, R)       # Philox row id of each row (default: its position in this batch)
         self._set_takes(takes)
+        self._set_row_adapters(row_adapters, B)
         fptr, flen, dptr, dec = None, 0, None, None
         if forced is not None:
             forced = np.ascontiguousarray(forced, dtype=np.int64)
@@ -200,15 +227,16 @@ class Engine:
         return out
 
     def begin(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, row_ids=None, takes=1,
-              output_scores=False):
-        """Prefill; takes as in generate() (the run then has B*takes rows); output_scores: keep log-probabilities
-        for read_scores()."""
+              output_scores=False, row_adapters=None):
+        """Prefill; takes and row_adapters as in generate() (the run then has B*takes rows); output_scores: keep
+        log-probabilities for read_scores()."""
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
         self._B, self._T = B * int(takes), T
         self.set_output_scores(output_scores)
         self._set_row_ids(row_ids, B * int(takes))
         self._set_takes(takes)
+        self._set_row_adapters(row_adapters, B)
         capi.check(self.lib.mtts_begin(self._h, ids.ctypes.data, m.ctypes.data, B, T, int(max_length),
                                        sampler_cfgs(layers, do_samples), C.c_uint64(seed), None))
 
@@ -254,11 +282,14 @@ class Engine:
         self.set_output_scores(output_scores)
         capi.check(self.lib.mtts_sched_open(self._h, int(slots), int(gen_cap), sampler_cfgs(layers, do_samples), None))
 
-    def submit(self, slot, ids, max_length, seed=0, row_id=0):
+    def submit(self, slot, ids, max_length, seed=0, row_id=0, adapter=None):
         """ids int64 [T,8]: one delay-shifted prompt without padding (what shifting_inputs returns).  The dialogue
-        draws from the Philox stream (seed; step, row_id, channel)."""
+        draws from the Philox stream (seed; step, row_id, channel).  adapter: bank index it runs with (None / -1: none);
+        fork() gives a take its source's."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         assert ids.ndim == 2 and ids.shape[1] == 8
+        if adapter is not None and int(adapter) >= 0:
+            capi.check(self.lib.mtts_set_slot_adapter(self._h, int(slot), int(adapter)))
         capi.check(self.lib.mtts_slot_submit_row(self._h, int(slot), ids.ctypes.data, ids.shape[0], int(max_length),
                                                  C.c_uint64(seed), int(row_id), None))
 

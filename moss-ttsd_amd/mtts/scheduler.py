@@ -38,7 +38,7 @@ class ContinuousBatcher:
         self._layers, self._do_samples, self._scores = layers, do_samples, False
         engine.sched_open(self.slots, self.gen_cap, layers=layers, do_samples=do_samples)
 
-    def run(self, prompts, max_new_tokens, seeds=None, base_seed=0, row_ids=None, takes=1, output_scores=False):
+    def run(self, prompts, max_new_tokens, seeds=None, base_seed=0, row_ids=None, takes=1, output_scores=False, adapters=None):
         """prompts: list of int64 [T_i,8] delay-shifted prompts (no padding); max_new_tokens: int or list
         (HF semantics: max_length = T_i + max_new).  seeds: one Philox key per dialogue (default base_seed + i, so
         that concurrent dialogues draw from different streams).  Returns a list of int64 [T_i-7+G_i, 8] in
@@ -49,7 +49,9 @@ class ContinuousBatcher:
         i at i * takes + j.
         output_scores: returns (results, scores), scores[k] float32 [G_k, 8] = the log-probabilities of job k's generated
         rows (Engine.generate: lp).  They are a function of (prompt, seed, row id) like the tokens: an evicted and re-run
-        dialogue, a forked take and a queued take all reproduce them."""
+        dialogue, a forked take and a queued take all reproduce them.
+        adapters: one bank index per prompt (Engine.load_bank_adapter; None / -1: none).  It is kept with the job: an
+        evicted and re-queued dialogue and a queued take are submitted with it again, a forked take inherits it."""
         takes = int(takes)
         if takes < 1:
             raise ValueError(f"takes must be >= 1 (got {takes})")
@@ -61,12 +63,16 @@ class ContinuousBatcher:
         mnt = [max_new_tokens] * n if np.isscalar(max_new_tokens) else list(max_new_tokens)
         seeds = list(seeds) if seeds is not None else [int(base_seed) + i for i in range(n)]
         row_ids = [0] * n if row_ids is None else [int(r) for r in row_ids]
+        adapters = [-1] * n if adapters is None else [-1 if a is None else int(a) for a in adapters]
+        if len(adapters) != n:
+            raise ValueError(f"adapters has {len(adapters)} entries, there are {n} prompts")
         # jobs k = i * takes + j; a queued job forks the prompt's other takes when it is admitted only if it is take 0 on
         # its first admission
         prompts = [prompts[k // takes] for k in range(n * takes)]
         mnt = [mnt[k // takes] for k in range(n * takes)]
         seeds = [seeds[k // takes] for k in range(n * takes)]
         row_ids = [row_ids[k // takes] * takes + k % takes for k in range(n * takes)]
+        adapters = [adapters[k // takes] for k in range(n * takes)]
         forks = set(range(0, n * takes, takes)) if takes > 1 else set()
         n *= takes
         results = [None] * n
@@ -88,7 +94,8 @@ class ContinuousBatcher:
                     if live and self.eng.kv_pool_state()[1] < (ids.shape[0] - 7 + 64) // 64 + live + 1:
                         break                                         # not enough headroom next to the residents
                     try:
-                        self.eng.submit(s, ids, ids.shape[0] + int(mnt[i]), seed=int(seeds[i]), row_id=row_ids[i])
+                        self.eng.submit(s, ids, ids.shape[0] + int(mnt[i]), seed=int(seeds[i]), row_id=row_ids[i],
+                                        adapter=adapters[i])
                     except capi.MttsError as err:
                         if err.code != capi.ENOMEM:
                             raise
