@@ -318,6 +318,23 @@ int32_t mtts_k_attn_section(const float* dev_slabs, int32_t ksplit, const void* 
                             const int32_t* host_page_table, int32_t R, int32_t Lmax, int32_t nq, int32_t nkv, int32_t sealed,
                             int32_t path, void* dev_out, void* dev_kcache, void* dev_vcache, void* dev_kpack, void* dev_vpack,
                             void* stream);
+/* Test hook: the attention section of one PREFILL pass (qkv_post_kernel over many rows of a dialogue, attn_prefill_scores /
+ * attn_prefill_pv on 32-row tiles, attn_combine with the prefill chunking) for B dialogues, launched as the engine's
+ * prefill launches it (tests/test_attn_prefill_gpu.py).  Dialogue b has host_cached[b] tokens cached (a multiple of 32,
+ * 0 <= cached < lens <= Lmax) and the pass carries its tokens cached[b] .. lens[b]-1; every dialogue starts on a 32-row
+ * tile boundary (the filler rows are idle), M = sum_b round_up(lens[b] - cached[b], 32) <= 2048, and the hook pads the pass
+ * to a multiple of 128 rows with idle tiles.  dev_slabs fp32 [ksplit][M][(nq + 2 nkv) * 128], 1 <= ksplit <= 8; dev_k /
+ * dev_v bf16 [B][Lmax][nkv][128]: ALL Lmax tokens go into the pools before the pass (the cached prefix, and whatever the
+ * caller wants behind a dialogue's end); dev_cos / dev_sin bf16 [Lmax][64]; host_page_table int32 [B][ceil(Lmax/64)] as
+ * in mtts_k_paged_attn_decode.  The q, scores, statistics and chunk-partial scratch starts as 0xff bytes (NaN).
+ * Out: dev_out bf16 [M][nq*128] row-major (idle rows: zeros), dev_q bf16 [M][nq][128] (idle rows: 0xff bytes), the bf16
+ * pools after the pass dev_kcache / dev_vcache [nkv][B*pages][64*128].  MTTS_EINVAL, with nothing written: a cached
+ * that is not a multiple of 32 or not below lens, lens > Lmax, nq % nkv != 0 or a group size other than 1, 2, 4, M > 2048,
+ * a page table that is not a permutation.  Synchronous. */
+int32_t mtts_k_attn_prefill(const float* dev_slabs, int32_t ksplit, const void* dev_qnw, const void* dev_knw, const void* dev_cos,
+                            const void* dev_sin, float eps, const void* dev_k, const void* dev_v, const int32_t* host_lens,
+                            const int32_t* host_cached, const int32_t* host_page_table, int32_t B, int32_t Lmax, int32_t nq,
+                            int32_t nkv, void* dev_out, void* dev_q, void* dev_kcache, void* dev_vcache, void* stream);
 /* The decode path's gate/up GEMM with its SwiGLU epilogue: W[N,K] holds gate and up rows interleaved (row 2i = gate i,
  * row 2i+1 = up i), Y[M,N/2] = bf16(bf16(silu(bf16(gate))) * bf16(up)), row-major.  M <= 128, N % 32 == 0, no split-K.
  * Like mtts_k_gemm_bf16 and mtts_k_gemm_bench it reads MTTS_GEMM_DEPTH on every call (0: gemm_skinny_kernel only). */

@@ -286,6 +286,10 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
         TRY(m.get(&e->vcache_f, e->layer_stride * e->L));
         TRY(m.get(&e->scores_f, (size_t)MTTS_PF32CAP * e->nq * e->max_pages * MTTS_PAGE, false));
     } else {
+        // Invariant: the pools are zeroed here and afterwards only ever hold values a kernel wrote (K / V rows, finite
+        // unless the model's own activations are not).  attn_prefill_pv_kernel relies on it: it multiplies the tokens behind
+        // a row's position by an exact 0 on the matrix cores, which hides any finite stale value but not a NaN or an inf
+        // (tests/test_attn_prefill_gpu.py: test_stale_pages_behind_a_dialogues_end_reach_nothing).
         TRY(m.get((uint16_t**)&e->kcache, e->layer_stride * e->L));
         TRY(m.get((uint16_t**)&e->vcache, e->layer_stride * e->L));
         if (e->kv_pack) {

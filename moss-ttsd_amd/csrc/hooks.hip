@@ -577,6 +577,102 @@ int32_t mtts_k_attn_section(const float* dev_slabs, int32_t ksplit, const void* 
 }
 int64_t mtts_debug_attn_row_launches(void) { return (int64_t)mtts_attn_row_launches(); }
 
+// Test hook: the attention section of one PREFILL pass (tests/test_attn_prefill_gpu.py) -- qkv_post_kernel over many rows
+// of one dialogue, attn_prefill_scores_kernel, attn_prefill_pv_kernel and attn_combine_kernel with the prefill chunking
+// (ATT_PF pages) -- for B dialogues on caller buffers.  Dialogue b has host_cached[b] tokens in its pages already (a
+// multiple of 32, 0 <= cached < lens <= Lmax: the state at the start of a later pass of a long prompt) and the pass
+// carries its tokens cached[b] .. lens[b] - 1.  The rows are staged as mtts_begin stages them (engine.hip):
+//     for (int b = 0; b < B; r = (r + MTTS_MAXR - 1) / MTTS_MAXR * MTTS_MAXR, ++b)
+//         for (int i = 0; i < e->n_real[b * takes]; ++i, ++r) ... metas[r] = RowMeta{b * takes, i, i == n_real - 1 ? 1 : 0, 0};
+// every dialogue on a 32-row tile boundary, filler rows RowMeta{-1, 0, 0, 0}, the pass padded to a multiple of MTTS_RCAP
+// rows (`size_t Mpad = (Mtot + MTTS_RCAP - 1) / MTTS_RCAP * MTTS_RCAP`) with wholly idle tiles, pages_bound =
+// max_b ceil(lens[b] / 64) (`prefill_staged(e, Mpad, (e->max_real + MTTS_PAGE - 1) / MTTS_PAGE, ...)`).  The launches are
+// attend_layer's for prefill == true, fused == false, sealed == false (engine.hip), with nchunks_max the engine's
+// `e->nchunks_max = (e->max_pages + ATT_PB - 1) / ATT_PB`:
+//     launch_qkv_post(e->partial, ks_qkv, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos, e->rope_sin, e->qbuf,
+//                     kc, vc, e->d_page_table, e->max_pages, e->total_pages, R, e->nq, e->nkv, eps, st);
+//     for (int i = 0; i < nphases; ++i)            // prefill_ph[3] = {ATTN_PF_SCORES, ATTN_PF_PV, ATTN_PF_COMBINE}
+//         launch_attn(e->qbuf, kc, vc, e->d_page_table, d_meta, e->scores, e->stats, e->opart, e->attn_p, R,
+//                     pages_bound, e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale,
+//                     fused ? &fz : nullptr, (prefill ? prefill_ph : decode_ph)[i], st, pkp);
+// dev_slabs fp32 [ksplit][M][Npad], Npad = (nq + 2 nkv) * 128, M = sum_b round_up(lens[b] - cached[b], 32) <= MTTS_PFCAP,
+// copied into the kernels' slab stride (MTTS_PFCAP rows); dev_k / dev_v bf16 [B][Lmax][nkv][128]: ALL Lmax tokens of every
+// dialogue are packed into the pools before the pass, so the caller decides what lies behind a dialogue's end; dev_cos /
+// dev_sin bf16 [Lmax][64]; host_page_table as in mtts_k_paged_attn_decode.  qbuf, scores, stats, opart (and the slab rows
+// the caller does not give) start as 0xff bytes (NaN): a slot the kernels may load but must not use shows in the result.
+// Out: dev_out bf16 [M][nq*128] row-major, dev_q bf16 [M][nq][128] (idle rows: the 0xff fill), the bf16 pools after the
+// pass dev_kcache / dev_vcache [nkv][B * pages][64 * 128].
+int32_t mtts_k_attn_prefill(const float* dev_slabs, int32_t ksplit, const void* dev_qnw, const void* dev_knw, const void* dev_cos,
+                            const void* dev_sin, float eps, const void* dev_k, const void* dev_v, const int32_t* host_lens,
+                            const int32_t* host_cached, const int32_t* host_page_table, int32_t B, int32_t Lmax, int32_t nq,
+                            int32_t nkv, void* dev_out, void* dev_q, void* dev_kcache, void* dev_vcache, void* stream) {
+    if (!dev_slabs || !dev_qnw || !dev_knw || !dev_cos || !dev_sin || !dev_k || !dev_v || !host_lens || !host_cached || !dev_out ||
+        !dev_q || !dev_kcache || !dev_vcache || B < 1 || B > MTTS_RCAP || Lmax < 1 || nq < 1 || nkv < 1 || nq % nkv || ksplit < 1 || ksplit > 8)
+        return fail(MTTS_EINVAL, "attn_prefill: bad argument (1..%d dialogues, nq %% nkv == 0, 1 <= ksplit <= 8)", MTTS_RCAP);
+    if (const int G = nq / nkv; G != 1 && G != 2 && G != 4) return fail(MTTS_EINVAL, "attention group size not built (1, 2, 4)");
+    const int max_pages = (Lmax + MTTS_PAGE - 1) / MTTS_PAGE, total_pages = B * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
+    const int nch_pf = (max_pages + ATT_PF - 1) / ATT_PF, Npad = (nq + 2 * nkv) * MTTS_HD;
+    int64_t M = 0;
+    int pages_bound = 1;
+    for (int b = 0; b < B; ++b) {
+        const int n = host_lens[b], c = host_cached[b];
+        if (c < 0 || c % MTTS_MAXR || c >= n || n > Lmax)
+            return fail(MTTS_EINVAL, "attn_prefill: dialogue %d: need cached %% 32 == 0 and 0 <= cached (%d) < lens (%d) <= Lmax (%d)", b, c, n, Lmax);
+        M += round_up(n - c, MTTS_MAXR);
+        pages_bound = std::max(pages_bound, (n + MTTS_PAGE - 1) / MTTS_PAGE);
+    }
+    if (M > MTTS_PFCAP) return fail(MTTS_EINVAL, "attn_prefill: %lld staged rows, a pass holds %d", (long long)M, MTTS_PFCAP);
+    std::vector<int32_t> hpt((size_t)total_pages);
+    std::vector<char> seen(total_pages, 0);
+    for (size_t i = 0; i < hpt.size(); ++i) {
+        hpt[i] = host_page_table ? host_page_table[i] : (int32_t)i;
+        if (hpt[i] < 0 || hpt[i] >= total_pages || seen[hpt[i]]) return fail(MTTS_EINVAL, "page table must be a permutation of 0..%d", total_pages - 1);
+        seen[hpt[i]] = 1;
+    }
+    const int R = round_up((int)M, MTTS_RCAP);
+    std::vector<RowMeta> hm(R, RowMeta{-1, 0, 0, 0});
+    {
+        int r = 0;
+        for (int b = 0; b < B; r = round_up(r, MTTS_MAXR), ++b)
+            for (int i = host_cached[b]; i < host_lens[b]; ++i, ++r) hm[r] = RowMeta{b, i, i == host_lens[b] - 1 ? 1 : 0, 0};
+    }
+    hipStream_t st = S(stream);
+    RowMeta* meta = nullptr; int32_t *pt = nullptr, *lens = nullptr; uint16_t *kc = nullptr, *vc = nullptr, *qbuf = nullptr, *scores = nullptr, *outp = nullptr;
+    float *stats = nullptr, *opart = nullptr, *slabs = nullptr;
+    const size_t cache_n = (size_t)total_pages * nkv * MTTS_PAGE * MTTS_HD;
+    const size_t q_n = (size_t)R * nq * MTTS_HD, sc_n = (size_t)R * nq * max_pages * MTTS_PAGE, st_n = (size_t)R * nq * max_pages * 2;
+    const size_t op_n = (size_t)R * nq * nch_pf * MTTS_HD, sl_n = (size_t)ksplit * MTTS_PFCAP * Npad;
+    DevBufs hb;
+    TRY(hb.get(&meta, (size_t)R, false)); TRY(hb.get(&pt, hpt.size(), false)); TRY(hb.get(&lens, (size_t)B, false));
+    TRY(hb.get(&kc, cache_n)); TRY(hb.get(&vc, cache_n));
+    TRY(hb.get(&qbuf, q_n, false)); TRY(hb.get(&scores, sc_n, false)); TRY(hb.get(&stats, st_n, false)); TRY(hb.get(&opart, op_n, false));
+    TRY(hb.get(&outp, q_n, false)); TRY(hb.get(&slabs, sl_n, false));
+    HIPCHK(hipMemsetAsync(qbuf, 0xff, q_n * 2, st)); HIPCHK(hipMemsetAsync(scores, 0xff, sc_n * 2, st));
+    HIPCHK(hipMemsetAsync(stats, 0xff, st_n * 4, st)); HIPCHK(hipMemsetAsync(opart, 0xff, op_n * 4, st));
+    HIPCHK(hipMemsetAsync(outp, 0xff, q_n * 2, st)); HIPCHK(hipMemsetAsync(slabs, 0xff, sl_n * 4, st));
+    std::vector<int32_t> full(B, Lmax);
+    HIPCHK(hipMemcpyAsync(meta, hm.data(), hm.size() * sizeof(RowMeta), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pt, hpt.data(), hpt.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(lens, full.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    for (int k = 0; k < ksplit; ++k)
+        HIPCHK(hipMemcpyAsync(slabs + (size_t)k * MTTS_PFCAP * Npad, dev_slabs + (size_t)k * M * Npad, (size_t)M * Npad * 4, hipMemcpyDeviceToDevice, st));
+    launch_pack_kv_pages(dev_k, dev_v, kc, vc, pt, lens, B, Lmax, nkv, max_pages, total_pages, st);
+    const float scale = 1.0f / sqrtf((float)MTTS_HD);
+    launch_qkv_post(slabs, ksplit, Npad, meta, dev_qnw, dev_knw, dev_cos, dev_sin, qbuf, kc, vc, pt, max_pages, total_pages, R, nq, nkv, eps, st);
+    static const AttnPhase prefill_ph[3] = {ATTN_PF_SCORES, ATTN_PF_PV, ATTN_PF_COMBINE};
+    for (int i = 0; i < 3; ++i)
+        if (launch_attn(qbuf, kc, vc, pt, meta, scores, stats, opart, outp, R, pages_bound, max_pages, total_pages, nch, nq, nkv, scale,
+                        nullptr, prefill_ph[i], st, nullptr))
+            return fail(MTTS_EINVAL, "attention group size not built (1, 2, 4)");
+    launch_unpack_rows(outp, dev_out, (int)M, nq * MTTS_HD, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dev_q, qbuf, (size_t)M * nq * MTTS_HD * 2, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(dev_kcache, kc, cache_n * 2, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(dev_vcache, vc, cache_n * 2, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
 // Test hook for the sealed page format (attn.hip: seal_lane): `npages` bf16 pages of 16 KiB -> sealed pages of 13 KiB.
 int32_t mtts_k_kv_seal(const void* dev_pages, int32_t npages, void* dev_sealed, int32_t as_k, void* stream) {
     if (!dev_pages || !dev_sealed || npages < 1) return fail(MTTS_EINVAL, "kv_seal: bad argument");

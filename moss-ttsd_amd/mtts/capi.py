@@ -108,6 +108,8 @@ _SIGS = {
     "mtts_debug_attn_row_launches": (C.c_int64, []),
     "mtts_k_attn_section": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 4 +
                             [C.c_int32] * 6 + [C.c_void_p] * 6),
+    "mtts_k_attn_prefill": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 5 +
+                            [C.c_int32] * 4 + [C.c_void_p] * 5),
     "mtts_k_gemm_swiglu_bf16": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mtts_k_rmsnorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "mtts_k_embed_norm": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 3),

@@ -281,7 +281,8 @@ def test_engine_long_run_crosses_kv_pages_vs_oracle(engines):
 def test_long_ragged_prefill_vs_oracle(monkeypatch, mfma_from_pages):
     """Prompts of 350..517 tokens, ragged, through both prefill attention paths: "0" = every prompt takes the
     tile-sharing matrix-core kernels (several 32-row tiles per dialogue, 9 pages, 5 pass-B chunks, dialogue
-    boundaries inside a pass; the engine's default sends prompts of >= 16 pages there), "1000" = row-by-row kernels.
+    boundaries inside a pass; this is the engine's default, pf_mfma_pages = 0: every prompt goes there), "1000" =
+    row-by-row kernels.
     The logits after the prefill and the decisions of the following steps must match the oracle."""
     from mtts.engine import Engine
     monkeypatch.setenv("MTTS_PREFILL_MFMA_PAGES", mfma_from_pages)
