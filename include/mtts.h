@@ -217,6 +217,25 @@ int32_t mtts_slot_read_scores(MttsEngine* e, int32_t slot, float* host_rows, int
  * (the rule of mtts_set_output_scores); MTTS_ENOMEM: the pool cannot hold the batch (reported before any launch). */
 int32_t mtts_score(MttsEngine* e, const int64_t* host_input_ids, const uint8_t* host_attention_mask,
                    const int64_t* host_labels, int32_t B, int32_t T, float* host_logp, void* stream);
+/* The same call that also returns, for every slot mtts_score can score (1 <= t < len_b, every channel c), the k most
+ * probable tokens of the distribution the label is scored under: host_top_ids int32 [B,T,8,k] and host_top_logp float
+ * [B,T,8,k], entry j = 0..k-1 in descending order of the logit, ties by ascending id (bf16 logits tie often); id -1 and
+ * NaN at t = 0, at padding and past a row's last token.  Labels play no part in it: a slot whose label is -100 is filled
+ * like any other, and host_labels may be NULL (then host_logp must be NULL too and is not written; otherwise both are
+ * given and host_logp is exactly what mtts_score writes).  host_top_logp[..., j] is bit for bit what mtts_score returns
+ * at that slot for the label host_top_ids[..., j], and the first k' entries of a call with k are the entries of a call
+ * with k' < k.  1 <= k <= MTTS_SCORE_MAX_TOPK, else MTTS_EINVAL; every other precondition, error code and guarantee is
+ * mtts_score's (synchronous, pages handed back, MTTS_ESTATE with a run open or an adapter list pending).  The logits are
+ * not materialised on a bf16 engine: the k best columns of each 128-column block are selected in the head GEMM's
+ * epilogue and merged per row.  Besides the staged results (8 x k ids and floats per staged row) those candidates are
+ * the one buffer the call adds, allocated by the first such call and bounded whatever the batch and k: 4 bytes x
+ * MTTS_SCORE_TOPK_ROWS rows x the 128-column blocks of head 0 (the speech heads reuse it) x 16 = 39 MB at 152 697
+ * columns -- a prefill pass goes through the heads MTTS_SCORE_TOPK_ROWS rows at a time. */
+#define MTTS_SCORE_MAX_TOPK 16
+#define MTTS_SCORE_TOPK_ROWS 512
+int32_t mtts_score_topk(MttsEngine* e, const int64_t* host_input_ids, const uint8_t* host_attention_mask,
+                        const int64_t* host_labels, int32_t B, int32_t T, float* host_logp, int32_t k,
+                        int32_t* host_top_ids, float* host_top_logp, void* stream);
 /* last forward's logits: bf16 bits, channel 0 [B,vocab_size], channels 1..7 [7,B,speech_vocab_size] */
 int32_t mtts_read_logits(MttsEngine* e, uint16_t* host_logits0, uint16_t* host_logits17, void* stream);
 /* the same for an MTTS_DTYPE_F32 engine: fp32 logits */
@@ -276,7 +295,7 @@ int32_t mtts_export_codes(MttsEngine* e, int32_t first, int32_t n, int64_t* dev_
 /* name of / time spent in the dominant decode kernel since the last reset, measured with hipEvents
  * on the launch stream (bench.py's roofline leg). */
 /* which: 0 attention scores, 1 P.V, 2 GEMM, 3 whole decode step, 4 the scoring kernels of mtts_score (head_ce_kernel +
- * ce_finish_kernel, one entry per prefill pass). */
+ * ce_finish_kernel, one entry per prefill pass; with top-k: head_topk_kernel, ce_finish_kernel and topk_finish_kernel). */
 int32_t mtts_profile_enable(MttsEngine* e, int32_t on);
 int32_t mtts_profile_read(MttsEngine* e, int32_t which, double* total_ms, int64_t* launches, int64_t* bytes);
 
@@ -417,6 +436,11 @@ int32_t mtts_k_kv_seal(const void* dev_pages, int32_t npages, void* dev_sealed, 
  * of 32 rows in the packed matrix; labels and logp are [M][segments].  M <= 2048, K % 16 == 0. */
 int32_t mtts_k_head_ce(const void* dev_w, const void* dev_x, const int32_t* host_labels, int32_t M, int32_t N, int32_t K,
                        int32_t n_valid, int32_t segments, float* dev_logp, void* stream);
+/* The top-k kernels of mtts_score_topk on the same operands, launched as the engine launches them (head_topk_kernel in
+ * chunks of MTTS_SCORE_TOPK_ROWS rows, topk_finish_kernel): dev_ids int32 and dev_logp float [M * segments * k], entry
+ * [(row * segments + s) * k + j].  1 <= k <= MTTS_SCORE_MAX_TOPK and k <= n_valid, else MTTS_EINVAL. */
+int32_t mtts_k_head_topk(const void* dev_w, const void* dev_x, int32_t M, int32_t N, int32_t K, int32_t n_valid,
+                         int32_t segments, int32_t k, int32_t* dev_ids, float* dev_logp, void* stream);
 /* The adapter-merge kernels the engine runs (mtts_bind_weight_lora), into a caller-supplied buffer.  dtype 0: dev_base bf16
  * [rows][cols] -> dev_out packed bf16 [rows_pad][cols] in fragment order, source row s on packed row s * row_mul + row_off;
  * only the 16-byte groups of those rows are written (the rest of dev_out keeps what it held).  dtype 1 / 2: dev_base fp32

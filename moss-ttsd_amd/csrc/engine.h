@@ -130,7 +130,7 @@ struct Layer {
 };
 
 enum { PROF_SCORES = 0, PROF_PV = 1, PROF_GEMM = 2, PROF_STEP = 3,
-       PROF_CE = 4,          // mtts_score: head_ce_kernel + ce_finish_kernel of a pass (both launches of the 8 heads)
+       PROF_CE = 4,          // mtts_score: head_ce_kernel + ce_finish_kernel of a pass (both launches of the 8 heads); mtts_score_topk: its kernels
        PROF_N = 5 };
 
 struct MttsEngine {
@@ -212,6 +212,11 @@ struct MttsEngine {
     size_t sc_cap_rows = 0;
     float* sc_part = nullptr;           // bf16 engine: (m, s, l_label) per row of a pass and 128-column block, head 0 then heads 1..7
     float* sc_logits = nullptr;         // fp32 / fp16 engines: fp32 logits of SCORE_F32_ROWS rows of one head
+    // mtts_score_topk only: allocated by the first such call
+    int32_t* d_sc_top_ids = nullptr;    // [staged rows][8][k]
+    float* d_sc_top_logp = nullptr;
+    size_t sc_top_cap = 0;              // elements of each
+    uint32_t* sc_cand = nullptr;        // bf16 engine: every block's k candidate keys of MTTS_SCORE_TOPK_ROWS rows of one head launch
     // resident adapters, one per dialogue (mtts_adapter_load; multilora.hip): no device memory before the first load
     std::vector<LoraEnt> bank;          // host copy of d_bank [MTTS_MAX_ADAPTERS][L * 7]; r == 0: the adapter has no pair for the matrix
     LoraEnt* d_bank = nullptr;

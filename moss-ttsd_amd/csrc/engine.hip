@@ -1311,14 +1311,22 @@ struct NoSeal {
 };
 
 // heads + log-softmax + label pick on the `rows` final-normed rows the pass has just left in xn (bf16: packed) / xnf
-static int score_pass(MttsEngine* e, const int32_t* labels, float* logp, int rows, hipStream_t st) {
+// k > 0 (mtts_score_topk): the k best tokens of every row and head as well, top_ids / top_logp [rows][8][k]; logp null
+// when the call has no labels (`labels` is then -100 throughout)
+static int score_pass(MttsEngine* e, const int32_t* labels, float* logp, int rows, hipStream_t st, int k = 0, int32_t* top_ids = nullptr,
+                      float* top_logp = nullptr) {
     const int H = e->H;
     if (!e->f32) {
         float* part17 = e->sc_part + head_ce_part_elems(MTTS_PFCAP, e->V0, 1);
         hipEvent_t ev = nullptr;
         prof_begin(e, PROF_CE, st, &ev);
-        launch_head_ce(e->head0, e->xn, rows, H, e->V0, 1, labels, 8, 0, e->sc_part, logp, 8, 0, st);
-        launch_head_ce(e->heads17, e->xn, rows, H, e->Vs, 7, labels, 8, 1, part17, logp, 8, 1, st);
+        if (k > 0) {
+            launch_head_topk(e->head0, e->xn, rows, H, e->V0, 1, labels, 8, 0, e->sc_part, logp, 8, 0, k, e->sc_cand, top_ids, top_logp, st);
+            launch_head_topk(e->heads17, e->xn, rows, H, e->Vs, 7, labels, 8, 1, part17, logp, 8, 1, k, e->sc_cand, top_ids, top_logp, st);
+        } else {
+            launch_head_ce(e->head0, e->xn, rows, H, e->V0, 1, labels, 8, 0, e->sc_part, logp, 8, 0, st);
+            launch_head_ce(e->heads17, e->xn, rows, H, e->Vs, 7, labels, 8, 1, part17, logp, 8, 1, st);
+        }
         prof_end(e, st, ev);
         if (e->prof) e->prof_bytes[PROF_CE] += ((int64_t)e->V0_pad + 7 * e->Vs_pad) * H * 2;       // one read of the heads
     } else {
@@ -1327,7 +1335,9 @@ static int score_pass(MttsEngine* e, const int32_t* labels, float* logp, int row
             for (int c = 0; c < 8; ++c) {
                 const int V = c == 0 ? e->V0 : e->Vs;
                 launch_f32_linear(e->embf[c], e->xnf + (size_t)r0 * H, e->sc_logits, n, V, H, e->V0_pad, e->h16, false, st);
-                launch_ce_rows_f32(e->sc_logits, e->V0_pad, n, V, labels + (size_t)r0 * 8, 8, c, logp + (size_t)r0 * 8, 8, c, st);
+                if (logp) launch_ce_rows_f32(e->sc_logits, e->V0_pad, n, V, labels + (size_t)r0 * 8, 8, c, logp + (size_t)r0 * 8, 8, c, st);
+                if (k > 0)
+                    launch_topk_rows_f32(e->sc_logits, e->V0_pad, n, V, k, top_ids + (size_t)r0 * 8 * k, top_logp + (size_t)r0 * 8 * k, 8, c, st);
             }
         }
     }
@@ -1335,9 +1345,10 @@ static int score_pass(MttsEngine* e, const int32_t* labels, float* logp, int row
     return MTTS_OK;
 }
 
-int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const int64_t* labels, int32_t B, int32_t T,
-                   float* host_logp, void* stream) {
-    if (!e || !ids || !mask || !labels || !host_logp) return fail(MTTS_EINVAL, "null argument");
+// mtts_score (k = 0: labels and host_logp given) and mtts_score_topk (k >= 1: labels and host_logp both given or both null)
+static int32_t score_call(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const int64_t* labels, int32_t B, int32_t T,
+                          float* host_logp, int32_t k, int32_t* host_top_ids, float* host_top_logp, void* stream) {
+    if (!e || !ids || !mask) return fail(MTTS_EINVAL, "null argument");
     TRY(mtts_weights_ready(e));
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = S(stream);
@@ -1367,7 +1378,7 @@ int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const
     for (int b = 0; b < B; ++b)
         for (int t = 0; t < T; ++t)
             for (int c = 0; c < 8; ++c) {
-                const int64_t V = c == 0 ? e->V0 : e->Vs, lb = labels[((size_t)b * T + t) * 8 + c], tk = ids[((size_t)b * T + t) * 8 + c];
+                const int64_t V = c == 0 ? e->V0 : e->Vs, lb = labels ? labels[((size_t)b * T + t) * 8 + c] : -100, tk = ids[((size_t)b * T + t) * 8 + c];
                 if (t >= len[b]) {
                     if (lb != -100) return fail(MTTS_EINVAL, "label %lld at a masked position (row %d, position %d, channel %d)", (long long)lb, b, t, c);
                     continue;
@@ -1394,7 +1405,7 @@ int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const
         for (int i = 0; i < len[b]; ++i, ++r) {
             for (int c = 0; c < 8; ++c) {
                 toks[r * 8 + c] = (int32_t)ids[((size_t)b * T + i) * 8 + c];
-                if (i + 1 < len[b]) labs[r * 8 + c] = (int32_t)labels[((size_t)b * T + i + 1) * 8 + c];
+                if (labels && i + 1 < len[b]) labs[r * 8 + c] = (int32_t)labels[((size_t)b * T + i + 1) * 8 + c];
             }
             metas[r] = RowMeta{b, i, 0, 0};
         }
@@ -1410,6 +1421,18 @@ int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const
     if (!e->f32 && !e->sc_part)
         TRY(e->mem.get(&e->sc_part, head_ce_part_elems(MTTS_PFCAP, e->V0, 1) + head_ce_part_elems(MTTS_PFCAP, e->Vs, 7), false));
     if (e->f32 && !e->sc_logits) TRY(e->mem.get(&e->sc_logits, (size_t)SCORE_F32_ROWS * e->V0_pad, false));
+    if (k > 0) {                       // top-k only: the staged results, and on the bf16 engine the blocks' candidates (head 0's is the larger need)
+        if (Mpad * 8 * k > e->sc_top_cap) {
+            e->mem.release(e->d_sc_top_ids); e->mem.release(e->d_sc_top_logp);
+            e->sc_top_cap = 0;
+            TRY(e->mem.get(&e->d_sc_top_ids, Mpad * 8 * k, false));
+            TRY(e->mem.get(&e->d_sc_top_logp, Mpad * 8 * k, false));
+            e->sc_top_cap = Mpad * 8 * k;
+        }
+        if (!e->f32 && !e->sc_cand)
+            TRY(e->mem.get(&e->sc_cand, std::max(head_topk_cand_elems(MTTS_PFCAP, e->V0, 1, MTTS_SCORE_MAX_TOPK),
+                                                 head_topk_cand_elems(MTTS_PFCAP, e->Vs, 7, MTTS_SCORE_MAX_TOPK)), false));
+    }
     // Sequence b borrows page-table row b.  The last run has ended, but a row may still list pages of it (they go back
     // with the next mtts_begin): those entries are set aside and put back, and the borrowed pages return to the free
     // list in the reverse of the order they were taken in, so the pool -- counts and page numbering -- is as before.
@@ -1455,19 +1478,51 @@ int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const
         for (size_t off = 0; off < Mpad; off += pfcap) {
             const int rows = (int)std::min<size_t>(pfcap, Mpad - off);
             TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, 0, false, st, 0));
-            TRY(score_pass(e, e->d_sc_labels + off * 8, e->d_sc_logp + off * 8, rows, st));
+            if (k > 0)
+                TRY(score_pass(e, e->d_sc_labels + off * 8, labels ? e->d_sc_logp + off * 8 : nullptr, rows, st, k,
+                               e->d_sc_top_ids + off * 8 * k, e->d_sc_top_logp + off * 8 * k));
+            else TRY(score_pass(e, e->d_sc_labels + off * 8, e->d_sc_logp + off * 8, rows, st));
         }
     }
-    std::vector<float> lp(Mpad * 8);
-    HIPCHK(hipMemcpyAsync(lp.data(), e->d_sc_logp, Mpad * 8 * sizeof(float), hipMemcpyDeviceToHost, st));
-    TRY(borrow.end());                 // drains st: the copy has landed, the pool and both page tables are as before
+    std::vector<float> lp(labels ? Mpad * 8 : 0), tlp(Mpad * 8 * k);
+    std::vector<int32_t> tid(Mpad * 8 * k);
+    if (labels) HIPCHK(hipMemcpyAsync(lp.data(), e->d_sc_logp, Mpad * 8 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (k > 0) {
+        HIPCHK(hipMemcpyAsync(tid.data(), e->d_sc_top_ids, tid.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(tlp.data(), e->d_sc_top_logp, tlp.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    TRY(borrow.end());                 // drains st: the copies have landed, the pool and both page tables are as before
     // logp[b][t] = what the row of position t - 1 computed; NaN at t = 0, at ignored labels and at padding
     const float nanv = __builtin_nanf("");
-    for (size_t i = 0; i < (size_t)B * T * 8; ++i) host_logp[i] = nanv;
-    for (int b = 0; b < B; ++b)
-        for (int t = 1; t < len[b]; ++t)
-            memcpy(host_logp + ((size_t)b * T + t) * 8, lp.data() + (row0[b] + t - 1) * 8, 8 * sizeof(float));
+    if (labels) {
+        for (size_t i = 0; i < (size_t)B * T * 8; ++i) host_logp[i] = nanv;
+        for (int b = 0; b < B; ++b)
+            for (int t = 1; t < len[b]; ++t)
+                memcpy(host_logp + ((size_t)b * T + t) * 8, lp.data() + (row0[b] + t - 1) * 8, 8 * sizeof(float));
+    }
+    if (k > 0) {                       // the same slots, whatever their label; -1 / NaN elsewhere
+        for (size_t i = 0; i < (size_t)B * T * 8 * k; ++i) { host_top_ids[i] = -1; host_top_logp[i] = nanv; }
+        for (int b = 0; b < B; ++b)
+            for (int t = 1; t < len[b]; ++t) {
+                memcpy(host_top_ids + ((size_t)b * T + t) * 8 * k, tid.data() + (row0[b] + t - 1) * 8 * k, (size_t)8 * k * sizeof(int32_t));
+                memcpy(host_top_logp + ((size_t)b * T + t) * 8 * k, tlp.data() + (row0[b] + t - 1) * 8 * k, (size_t)8 * k * sizeof(float));
+            }
+    }
     return MTTS_OK;
+}
+
+int32_t mtts_score(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const int64_t* labels, int32_t B, int32_t T,
+                   float* host_logp, void* stream) {
+    if (!labels || !host_logp) return fail(MTTS_EINVAL, "null argument");
+    return score_call(e, ids, mask, labels, B, T, host_logp, 0, nullptr, nullptr, stream);
+}
+
+int32_t mtts_score_topk(MttsEngine* e, const int64_t* ids, const uint8_t* mask, const int64_t* labels, int32_t B, int32_t T,
+                        float* host_logp, int32_t k, int32_t* host_top_ids, float* host_top_logp, void* stream) {
+    if (!host_top_ids || !host_top_logp) return fail(MTTS_EINVAL, "null argument");
+    if (!labels != !host_logp) return fail(MTTS_EINVAL, "mtts_score_topk: host_labels and host_logp are given together or both null");
+    if (k < 1 || k > MTTS_SCORE_MAX_TOPK) return fail(MTTS_EINVAL, "mtts_score_topk: k %d outside 1..%d", k, MTTS_SCORE_MAX_TOPK);
+    return score_call(e, ids, mask, labels, B, T, host_logp, k, host_top_ids, host_top_logp, stream);
 }
 
 int32_t mtts_read_logits_f32(MttsEngine* e, float* l0, float* l17, void* stream) {

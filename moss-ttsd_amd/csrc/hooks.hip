@@ -83,6 +83,38 @@ int32_t mtts_k_head_ce(const void* w, const void* x, const int32_t* host_labels,
     return MTTS_OK;
 }
 
+// The same packing, then head_topk_kernel + topk_finish_kernel through the engine's launcher (no labels: every one -100).
+int32_t mtts_k_head_topk(const void* w, const void* x, int32_t M, int32_t N, int32_t K, int32_t n_valid, int32_t segments, int32_t k,
+                         int32_t* dev_ids, float* dev_logp, void* stream) {
+    if (!w || !x || !dev_ids || !dev_logp || M < 1 || M > MTTS_PFCAP || K < 16 || K % 16 || n_valid < 1 || segments < 1 ||
+        (segments == 1 ? n_valid > N : N != segments * n_valid))
+        return fail(MTTS_EINVAL, "head_topk: need 1<=M<=MTTS_PFCAP, K%%16==0, n_valid<=N (one head) or N==segments*n_valid");
+    if (k < 1 || k > MTTS_SCORE_MAX_TOPK || k > n_valid)
+        return fail(MTTS_EINVAL, "head_topk: k %d outside 1..min(%d, n_valid %d)", k, MTTS_SCORE_MAX_TOPK, n_valid);
+    hipStream_t st = S(stream);
+    const int seg_pad = round_up(segments == 1 ? N : n_valid, 32), Mpad = round_up(M, 32);
+    uint16_t *wp = nullptr, *xp = nullptr;
+    int32_t* lab = nullptr;
+    float* part = nullptr;
+    uint32_t* cand = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&wp, (size_t)segments * seg_pad * K));
+    TRY(hb.get(&xp, (size_t)Mpad * K));
+    TRY(hb.get(&lab, (size_t)Mpad * segments, false));
+    TRY(hb.get(&part, head_ce_part_elems(M, n_valid, segments), false));
+    TRY(hb.get(&cand, head_topk_cand_elems(M, n_valid, segments, k), false));
+    HIPCHK(hipMemsetAsync(lab, 0xff, (size_t)Mpad * segments * 4, st));                    // -1: no label
+    if (segments == 1) launch_pack_weight(w, wp, N, K, seg_pad, 1, 0, st);
+    else
+        for (int s = 0; s < segments; ++s)
+            launch_pack_weight((const uint16_t*)w + (size_t)s * n_valid * K, wp, n_valid, K, segments * seg_pad, 1, s * seg_pad, st);
+    launch_pack_rows(x, xp, M, K, Mpad / 32, st);
+    launch_head_topk(wp, xp, M, K, n_valid, segments, lab, segments, 0, part, nullptr, segments, 0, k, cand, dev_ids, dev_logp, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
 int32_t mtts_k_lora_pack(const void* base, int32_t rows, int32_t cols, const float* lora_a, const float* lora_b, int32_t r, float scaling,
                          int32_t rows_pad, int32_t row_mul, int32_t row_off, int32_t dtype, void* out, void* stream) {
     if (!base || !lora_a || !lora_b || !out || rows < 1 || cols < 16 || cols % 16 || r < 1 || r > 256 || dtype < 0 || dtype > 2)

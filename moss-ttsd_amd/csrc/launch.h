@@ -163,6 +163,17 @@ void launch_head_ce(const void* Wp, const void* Xp, int R, int K, int n_valid, i
 // the same on R rows of materialised fp32 logits [R][ldy] of one head (fp32 / fp16 engines)
 void launch_ce_rows_f32(const float* logits, long ldy, int R, int n_valid, const int32_t* labels, int lab_stride, int lab_off,
                         float* logp, int out_stride, int out_off, hipStream_t st);
+// Top-k next to it (mtts_score_topk), 1 <= k <= MTTS_SCORE_MAX_TOPK: top_ids / top_logp [(row * out_stride + out_off + seg)
+// * k + j], j = 0..k-1 = the k columns with the largest logit, descending, ties by ascending column, and their
+// log-probabilities; `logp` as launch_head_ce fills it, or null (labels must still be readable: < 0 everywhere then).
+// The rows go through head_topk_kernel MTTS_SCORE_TOPK_ROWS at a time, so that `cand` -- every block's k candidates --
+// stays at head_topk_cand_elems(R, n_valid, segments, k) words.
+size_t head_topk_cand_elems(int rows, int n_valid, int segments, int k);
+void launch_head_topk(const void* Wp, const void* Xp, int R, int K, int n_valid, int segments, const int32_t* labels, int lab_stride,
+                      int lab_off, float* part, float* logp, int out_stride, int out_off, int k, uint32_t* cand, int32_t* top_ids,
+                      float* top_logp, hipStream_t st);
+void launch_topk_rows_f32(const float* logits, long ldy, int R, int n_valid, int k, int32_t* top_ids, float* top_logp, int out_stride,
+                          int out_off, hipStream_t st);
 
 // ---- adapter.hip ----------------------------------------------------------------------------------------------------
 // A LoRA adapter merged into a projection weight: merged = round(W + ((B A), r terms summed in ascending order) * scaling),

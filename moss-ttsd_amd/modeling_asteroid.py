@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from mtts import adapters, synth
+from mtts import adapters, synth, topk_spec
 from mtts.engine import Engine
 
 _CFG_KEYS = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads",
@@ -122,13 +122,17 @@ class GenerateOutput:
 class AsteroidTTSOutputWithPast:
     """The reference's output class (modeling_asteroid.py:30-37) as forward(labels=...) fills it with skip_logits: `loss`,
     `loss_all`, and None for everything the engine does not keep.  One field more: `token_logprobs` float32 [B,T,8], the
-    log-probability of every label (NaN at t = 0, at ignored labels and at padding)."""
+    log-probability of every label (NaN at t = 0, at ignored labels and at padding).  With forward(top_logprobs=k) two
+    more: `top_ids` int64 [B,T,8,k] and `top_logprobs` float32 [B,T,8,k], the k most probable tokens of the distribution
+    each slot is scored under, descending (ties by ascending id); -1 / NaN at t = 0 and at padding."""
 
-    def __init__(self, loss=None, loss_all=None, token_logprobs=None):
+    def __init__(self, loss=None, loss_all=None, token_logprobs=None, top_logprobs=None, top_ids=None):
         self.loss = loss
         self.loss_all = loss_all
         self.logits = self.logits_all = self.past_key_values = self.hidden_states = self.attentions = None
         self.token_logprobs = token_logprobs
+        self.top_logprobs = top_logprobs
+        self.top_ids = top_ids
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -348,15 +352,19 @@ class AsteroidTTSInstruct:
     def set_weights(self, weights):
         self.weights = weights
 
-    def _check_forward_args(self, input_ids, attention_mask, labels):
-        """-> numpy (ids int64 [B,T,8], mask uint8 [B,T], labels int64 [B,T,8]); ValueError before any engine exists."""
-        if labels is None:
+    def _check_forward_args(self, input_ids, attention_mask, labels, top_logprobs=None):
+        """-> numpy (ids int64 [B,T,8], mask uint8 [B,T], labels int64 [B,T,8] -- all -100 when the call has none, which
+        top_logprobs allows); ValueError before any engine exists."""
+        if labels is None and top_logprobs is None:
             raise ValueError("forward() without labels: the MI355X engine keeps no logits, so there is nothing to return; "
                              "use generate() to decode, or pass labels for the per-channel losses")
+        if top_logprobs is not None:
+            topk_spec.check_k(top_logprobs)
         if input_ids is None:
             raise ValueError("forward() needs input_ids (inputs_embeds is not supported)")
         as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-        ids, lab = as_np(input_ids), as_np(labels)
+        ids = as_np(input_ids)
+        lab = np.full(ids.shape, -100, dtype=np.int64) if labels is None else as_np(labels)
         if ids.ndim != 3:
             raise ValueError(f"input_ids must be [batch, seq, channels], got shape {tuple(ids.shape)}")
         B, T, C = ids.shape
@@ -382,13 +390,18 @@ class AsteroidTTSInstruct:
         return np.ascontiguousarray(ids), np.ascontiguousarray(msk), np.ascontiguousarray(lab)
 
     @torch.no_grad()
-    def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, **kw):
+    def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, top_logprobs=None, **kw):
         """The training-branch forward of the reference, forward only: LongTensor [B,T,8] ids and labels (-100 = ignore),
         mask [B,T] right-padded or unpadded -> AsteroidTTSOutputWithPast with `loss_all` (float32 [8]: the causal-LM loss of
         each channel, mean over its labelled slots; NaN for a channel without one), `loss` (their mean under
         `self.weights`) and `token_logprobs` [B,T,8]; return_dict=False -> (loss, loss_all, None).  The heads and the
         log-softmax run fused on the device (csrc/score.hip); logits are never materialised, as with the reference's
-        skip_logits.  A batch beyond MAX_ENGINE_BATCH is scored in slices whose sums and counts are combined."""
+        skip_logits.  A batch beyond MAX_ENGINE_BATCH is scored in slices whose sums and counts are combined.
+
+        top_logprobs=k (1..16): the output also carries `top_ids` [B,T,8,k] (int64, -1 where empty) and `top_logprobs`
+        [B,T,8,k] (float32, NaN where empty): the k most probable tokens at every slot t >= 1 of a row, labelled or not,
+        selected in the epilogue of the same head GEMM; top_logprobs[..., j] is bit for bit the token_logprobs value the
+        label top_ids[..., j] would get.  With it labels may be omitted: loss, loss_all and token_logprobs are then None."""
         # what would change the reference's result, or ask for what the engine does not keep, is refused, not dropped
         bad = [k for k in ("position_ids", "inputs_embeds", "past_key_values", "cache_position") if kw.get(k) is not None]
         bad += [k for k in ("output_attentions", "output_hidden_states", "use_cache") if kw.get(k)]
@@ -397,14 +410,28 @@ class AsteroidTTSInstruct:
         if bad:
             raise ValueError(f"forward(labels=...) does not take {', '.join(bad)}: positions are arange(T) over right-padded rows, "
                              "and the engine keeps no logits, cache, attentions or hidden states")
-        ids, msk, lab = self._check_forward_args(input_ids, attention_mask, labels)
+        ids, msk, lab = self._check_forward_args(input_ids, attention_mask, labels, top_logprobs)
         B, T, C = ids.shape
+        k = 0 if top_logprobs is None else int(top_logprobs)
         eng = self._get_engine(min(B, self.MAX_ENGINE_BATCH), T)
+        dev = input_ids.device if torch.is_tensor(input_ids) else self.device
+        top_ids, top_lp = np.empty((B, T, C, k), dtype=np.int64), np.empty((B, T, C, k), dtype=np.float32)
+        if labels is None:                                   # top-k alone: the first label-free forward
+            for b0 in range(0, B, self.MAX_ENGINE_BATCH):
+                sl = slice(b0, b0 + self.MAX_ENGINE_BATCH)
+                _, top_ids[sl], top_lp[sl] = eng.score(ids[sl], msk[sl], None, top_k=k)
+            if return_dict is not None and not return_dict:
+                return (None, None, None)
+            return AsteroidTTSOutputWithPast(None, None, None, torch.from_numpy(top_lp).to(dev), torch.from_numpy(top_ids).to(dev))
         lp = np.empty((B, T, C), dtype=np.float32)
         sums, counts = np.zeros(C, dtype=np.float64), np.zeros(C, dtype=np.int64)
         for b0 in range(0, B, self.MAX_ENGINE_BATCH):
             sl = slice(b0, b0 + self.MAX_ENGINE_BATCH)
-            part = lp[sl] = eng.score(ids[sl], msk[sl], lab[sl])
+            if k:
+                lp[sl], top_ids[sl], top_lp[sl] = eng.score(ids[sl], msk[sl], lab[sl], top_k=k)
+                part = lp[sl]
+            else:
+                part = lp[sl] = eng.score(ids[sl], msk[sl], lab[sl])
             ok = ~np.isnan(part)
             sums += np.where(ok, part, 0).astype(np.float64).sum(axis=(0, 1))
             counts += ok.sum(axis=(0, 1))
@@ -416,7 +443,9 @@ class AsteroidTTSInstruct:
             loss = loss + w * l
         if return_dict is not None and not return_dict:
             return (loss, loss_all, None)
-        dev = input_ids.device if torch.is_tensor(input_ids) else self.device
+        if k:
+            return AsteroidTTSOutputWithPast(loss, loss_all, torch.from_numpy(lp).to(dev), torch.from_numpy(top_lp).to(dev),
+                                             torch.from_numpy(top_ids).to(dev))
         return AsteroidTTSOutputWithPast(loss, loss_all, torch.from_numpy(lp).to(dev))
 
     __call__ = forward

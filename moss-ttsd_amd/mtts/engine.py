@@ -214,17 +214,33 @@ class Engine:
             ret += (np.ascontiguousarray(self.read_scores(out_len.value - (T - 7)).transpose(1, 0, 2)),)
         return ret if len(ret) > 1 else ret[0]
 
-    def score(self, input_ids, attention_mask, labels):
+    def score(self, input_ids, attention_mask, labels=None, top_k=0):
         """Teacher-forced scoring (include/mtts.h: mtts_score): int64 [B,T,8] ids and labels (-100 = ignore), mask [B,T]
         right-padded or unpadded -> float32 [B,T,8], logp[b,t,c] = log_softmax(logits_c(h[b,t-1]))[labels[b,t,c]], NaN at
-        t = 0, at ignored labels and at padding.  No run may be open; the engine's KV pool is as before afterwards."""
+        t = 0, at ignored labels and at padding.  No run may be open; the engine's KV pool is as before afterwards.
+
+        top_k > 0 (mtts_score_topk, 1..16): -> (logp, or None without labels; top_ids int32 [B,T,8,k]; top_logp float32
+        [B,T,8,k]): the k most probable tokens of the same distributions, descending logit and ascending id among equals,
+        whatever the label; -1 / NaN at t = 0 and at padding.  top_logp[..., j] has the bits logp would have for the label
+        top_ids[..., j]."""
         ids, m = self._host_inputs(input_ids, attention_mask)
-        lab = np.ascontiguousarray(np.asarray(labels.cpu() if torch.is_tensor(labels) else labels), dtype=np.int64)
-        assert lab.shape == ids.shape
         B, T, _ = ids.shape
-        out = np.empty((B, T, 8), dtype=np.float32)
-        capi.check(self.lib.mtts_score(self._h, ids.ctypes.data, m.ctypes.data, lab.ctypes.data, B, T, out.ctypes.data, None))
-        return out
+        lab = out = None
+        if labels is not None:
+            lab = np.ascontiguousarray(np.asarray(labels.cpu() if torch.is_tensor(labels) else labels), dtype=np.int64)
+            assert lab.shape == ids.shape
+            out = np.empty((B, T, 8), dtype=np.float32)
+        if not top_k:
+            if lab is None:
+                raise ValueError("score() needs labels, top_k > 0, or both")
+            capi.check(self.lib.mtts_score(self._h, ids.ctypes.data, m.ctypes.data, lab.ctypes.data, B, T, out.ctypes.data, None))
+            return out
+        k = int(top_k)
+        kk = max(k, 0)                                      # (a k the library refuses still gets buffers of a sane size)
+        top_ids, top_logp = np.empty((B, T, 8, kk), dtype=np.int32), np.empty((B, T, 8, kk), dtype=np.float32)
+        capi.check(self.lib.mtts_score_topk(self._h, ids.ctypes.data, m.ctypes.data, None if lab is None else lab.ctypes.data, B, T,
+                                            None if out is None else out.ctypes.data, k, top_ids.ctypes.data, top_logp.ctypes.data, None))
+        return out, top_ids, top_logp
 
     def begin(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, row_ids=None, takes=1,
               output_scores=False, row_adapters=None):
