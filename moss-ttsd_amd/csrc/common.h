@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "shapes.h"          // MTTS_MAXR / RCAP / PFCAP / PAGE and RowMeta: shared with the HIP-free host headers
+
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
@@ -11,11 +13,7 @@ typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
 #define MTTS_WAVE 64
-#define MTTS_MAXR 32          // rows per MFMA N-tile (one activation fragment tile)
-#define MTTS_RCAP 128         // dialogue slots; rows of a decode pass (up to 4 activation tiles share one weight stream)
-#define MTTS_PFCAP 2048       // rows of a prefill pass (tiled GEMM); also the row stride of the split-K slabs
-#define MTTS_PAGE 64          // tokens per KV page
-#define MTTS_HD 128           // head_dim the kernels are written for
+#define MTTS_HD 128          // head_dim the kernels are written for
 #define ATT_PB 8              // KV pages per pass-B chunk, decode rows (4 waves x 2 pages)
 #define ATT_PF 2              // KV pages per pass-B chunk, prefill tiles (one wave)
 
@@ -173,14 +171,6 @@ struct ForkJob {
     int32_t rsrc[FORK_CAP], rdst[FORK_CAP];
     uint8_t* base[FORK_ARR];
     int64_t stride[FORK_ARR], bytes[FORK_ARR];
-};
-
-// Per-row metadata of one forward pass.
-struct RowMeta {
-    int32_t seq;     // sequence slot (page-table row), -1 = inactive row
-    int32_t pos;     // position of this token = its index among the sequence's real tokens
-    int32_t last;    // 1 if logits are wanted for this row
-    int32_t pad;
 };
 
 // ---- small-batch decode path (1..SMALL_RP dialogues) --------------------------------------------------------------

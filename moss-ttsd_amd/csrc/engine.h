@@ -1,5 +1,7 @@
 // What engine.hip (engine object, C ABI of the product path) and hooks.hip (per-kernel test / bench entry points)
 // share: the engine's definition, error reporting, and the owner of device memory.  Only these two files include it.
+// The HIP-free host code sits apart, where a CPU test can include it: kvpool.h (the KV page pool; through launch.h) and
+// staging.h (prompt staging; engine.hip alone) -- besides those includers only tests/host/pool_stage_main.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,7 +19,7 @@
 // ---- errors -------------------------------------------------------------------
 #define MTTS_LOCAL __attribute__((visibility("hidden")))
 extern MTTS_LOCAL thread_local char g_err[512];          // engine.hip; mtts_last_error() of the calling thread
-MTTS_LOCAL int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// int fail(int code, const char* fmt, ...): declared by kvpool.h (the pool reports through it), defined in engine.hip
 #define HIPCHK(x)                                                                          \
     do {                                                                                   \
         hipError_t _e = (x);                                                               \
@@ -164,14 +166,10 @@ struct MttsEngine {
     size_t layer_stride = 0;           // elements per layer in each cache
     int total_pages = 0, max_pages = 0, nchunks_max = 0;
     int32_t* d_page_table = nullptr;
-    std::vector<int32_t> h_page_table;  // [slot][max_pages]: pages a slot owns, in position order
-    // KV page pool: pages are handed out on demand as a dialogue's length crosses a page boundary and come back
-    // when it finishes (free list = stack; initial order ascending, or shuffled by MTTS_PAGE_SHUFFLE for the tests)
-    std::vector<int32_t> free_pages;
-    std::vector<int32_t> n_pages;       // pages each slot owns
-    std::vector<int32_t> page_owners;   // slots whose table holds the page (> 1: a prompt page shared by takes, pool_share)
+    // KV page pool (kvpool.h): pages are handed out on demand as a dialogue's length crosses a page boundary and come back
+    // when it finishes; max_pages / total_pages above are its sizes, set once beside it (kernel arguments)
+    KvPool pool;
     std::vector<char> slot_live;        // host's view: the slot holds a dialogue that may still step
-    PageEdits pending_edits;            // table entries not yet on the device
     int forced_draw = 0;
     std::vector<int32_t> next_row_ids;  // Philox row ids of the next mtts_begin (mtts_set_row_ids); empty = 0..B-1
     int next_takes = 1;                 // takes per prompt of the next mtts_begin / mtts_generate (mtts_set_takes)

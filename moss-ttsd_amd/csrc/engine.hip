@@ -8,6 +8,7 @@
 //   CustomMixin._sample                             modeling_asteroid.py:83-169
 // and, third-party, transformers Qwen3Model.forward (models/qwen3/modeling_qwen3.py).
 #include "engine.h"
+#include "staging.h"
 
 #define FLUSH_STEPS 7          // a dialogue whose EOS falls within 7 steps of max_length still runs its delay-pattern flush (modeling_asteroid.py:165-168)
 #define LINGER_STEPS 14        // static batch: a row finished BY max_length can be resurrected for a flush while another row's flush is still running (sampler.hip: update_kernel), so a batch runs up to 6 + 8 steps past max_length after ONE resurrection
@@ -29,86 +30,15 @@ int fail(int code, const char* fmt, ...) {
 const char* mtts_last_error(void) { return g_err; }
 int32_t mtts_version(void) { return 202; }
 
-// ---- KV page pool -----------------------------------------------------------------------------------------------
-// Free list = stack whose top is the lowest page number (a fresh engine hands pages out in ascending order).
-// MTTS_PAGE_SHUFFLE=<seed> (test hook) shuffles it, so that page tables are arbitrary permutations.
-static void pool_reset(MttsEngine* e) {
-    e->free_pages.resize(e->total_pages);
-    for (int i = 0; i < e->total_pages; ++i) e->free_pages[i] = e->total_pages - 1 - i;
-    if (const char* g = getenv("MTTS_PAGE_SHUFFLE")) {
-        uint64_t x = 0x9E3779B97F4A7C15ull ^ (uint64_t)atoll(g);
-        for (int i = e->total_pages - 1; i > 0; --i) {
-            x = x * 6364136223846793005ull + 1442695040888963407ull;
-            std::swap(e->free_pages[i], e->free_pages[(x >> 33) % (uint64_t)(i + 1)]);
-        }
-    }
-    std::fill(e->n_pages.begin(), e->n_pages.end(), 0);
-    e->page_owners.assign(e->total_pages, 0);
-    e->pending_edits.n = 0;
-}
-// table entries reach the device as launch arguments of a one-wave kernel on the caller's stream: ordered with the
-// steps around it, and no host buffer has to outlive the call
-static int pool_flush(MttsEngine* e, hipStream_t st) {
-    if (e->pending_edits.n) {
-        launch_set_pages(e->d_page_table, e->pending_edits, st);
-        e->pending_edits.n = 0;
+// ---- KV page pool (kvpool.h) ---------------------------------------------------------------------------------------
+// How the pool's table edits reach the device: as launch arguments of a one-wave kernel on the caller's stream, ordered
+// with the steps around it, and no host buffer has to outlive the call
+static auto ship_on(MttsEngine* e, hipStream_t st) {
+    return [e, st](const PageEdits& ed) -> int {
+        launch_set_pages(e->d_page_table, ed, st);
         HIPCHK(hipGetLastError());
-    }
-    return 0;
-}
-// append `page` to slot b's table (host copy now, device copy with the next flush)
-static int pool_append(MttsEngine* e, int b, int page, hipStream_t st) {
-    const int at = b * e->max_pages + e->n_pages[b]++;
-    e->h_page_table[at] = page;
-    // one batch is written by the lanes of ONE store (set_pages_kernel): an index must not appear twice in it
-    for (int i = 0; i < e->pending_edits.n; ++i)
-        if (e->pending_edits.idx[i] == at) { e->pending_edits.val[i] = page; return 0; }
-    if (e->pending_edits.n == 31) TRY(pool_flush(e, st));
-    e->pending_edits.idx[e->pending_edits.n] = at;
-    e->pending_edits.val[e->pending_edits.n++] = page;
-    return 0;
-}
-// make slot b own at least `need` pages; MTTS_ENOMEM when the pool runs dry (nothing is taken back)
-static int pool_grow(MttsEngine* e, int b, int need, hipStream_t st) {
-    if (need > e->max_pages) return fail(MTTS_ENOMEM, "slot %d needs %d KV pages, a sequence holds at most %d (max_seq_len %d)", b, need, e->max_pages, e->cfg.max_seq_len);
-    while (e->n_pages[b] < need) {
-        if (e->free_pages.empty()) return fail(MTTS_ENOMEM, "KV page pool exhausted (%d pages of %d tokens): slot %d needs page %d", e->total_pages, MTTS_PAGE, b, e->n_pages[b]);
-        const int page = e->free_pages.back();
-        e->free_pages.pop_back();
-        e->page_owners[page] = 1;
-        TRY(pool_append(e, b, page, st));
-    }
-    return 0;
-}
-// Takes of one prompt (mtts_begin with takes, mtts_slot_fork): slot dst (empty) gets slot src's first `npages` table
-// entries, and each of those pages one more owner.  Invariant: a slot writes only pages that it alone owns.  Only
-// COMPLETE prompt pages are shared: every K/V write of a dialogue goes to a position >= its prompt length, and their
-// sealed form was made once, by the source's prefill, in the same page numbering.  The partially filled last page is
-// copied into a private page (launch_fork_job).
-static int pool_share(MttsEngine* e, int src, int dst, int npages, hipStream_t st) {
-    for (int i = 0; i < npages; ++i) {
-        const int page = e->h_page_table[(size_t)src * e->max_pages + i];
-        e->page_owners[page]++;
-        TRY(pool_append(e, dst, page, st));
-    }
-    return 0;
-}
-// every launch that could touch the slot's pages must have been issued before (stream order protects the rest:
-// the next owner's writes are enqueued after them); a page goes back on the free list with its last owner
-static void pool_release(MttsEngine* e, int b) {
-    for (int i = e->n_pages[b] - 1; i >= 0; --i) {
-        const int page = e->h_page_table[(size_t)b * e->max_pages + i];
-        if (--e->page_owners[page] == 0) e->free_pages.push_back(page);
-    }
-    e->n_pages[b] = 0;
-    // table entries of this slot that never reached the device (a grow that ended in MTTS_ENOMEM) are void now
-    int k = 0;
-    for (int i = 0; i < e->pending_edits.n; ++i)
-        if (e->pending_edits.idx[i] / e->max_pages != b) {
-            e->pending_edits.idx[k] = e->pending_edits.idx[i];
-            e->pending_edits.val[k++] = e->pending_edits.val[i];
-        }
-    e->pending_edits.n = k;
+        return 0;
+    };
 }
 
 // ---- MTTS_DTYPE_F32 engine: allocation, binding, forward (kernels: f32path.hip) -------------------------------------
@@ -277,7 +207,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
         TRY(m.get((uint16_t**)&e->join_logits17, (size_t)MTTS_MAXR * 7 * e->Vs_pad));
     }
     // KV pool
-    e->max_pages = (c->max_seq_len + MTTS_PAGE - 1) / MTTS_PAGE + 1;
+    e->max_pages = pages_for(c->max_seq_len) + 1;
     e->total_pages = c->kv_pool_pages > 0 ? c->kv_pool_pages : e->max_pages * c->max_batch;
     e->nchunks_max = (e->max_pages + ATT_PB - 1) / ATT_PB;
     e->layer_stride = (size_t)e->total_pages * e->nkv * MTTS_PAGE * MTTS_HD;
@@ -313,11 +243,10 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
         }
     }
     TRY(m.get(&e->d_page_table, (size_t)c->max_batch * e->max_pages));
-    e->h_page_table.assign((size_t)c->max_batch * e->max_pages, 0);
-    e->n_pages.assign(c->max_batch, 0);
     e->slot_live.assign(c->max_batch, 0);
-    e->pending_edits.n = 0;
-    pool_reset(e);
+    const char* shuffle = getenv("MTTS_PAGE_SHUFFLE");      // test hook: page tables become arbitrary permutations
+    const uint64_t shuffle_seed = shuffle ? (uint64_t)atoll(shuffle) : 0;
+    e->pool.init(e->total_pages, e->max_pages, c->max_batch, c->max_seq_len, shuffle ? &shuffle_seed : nullptr);
     if (!e->f32) {
         TRY(m.get((uint16_t**)&e->scores, (size_t)MTTS_PFCAP * e->nq * e->max_pages * MTTS_PAGE));
         TRY(m.get(&e->stats, (size_t)MTTS_PFCAP * e->nq * e->max_pages * 2));
@@ -880,14 +809,24 @@ static int start_scores(MttsEngine* e, hipStream_t st) {
     return 0;
 }
 
-// prefill staging: room for `rows` flattened prompt rows
-static int grow_prefill_staging(MttsEngine* e, size_t rows) {
-    if (rows <= e->pf_cap_rows) return 0;
-    e->mem.release(e->d_pf_tokens); e->mem.release(e->d_pf_meta);
-    e->pf_cap_rows = 0;
-    TRY(e->mem.get(&e->d_pf_tokens, rows * 8, false));
-    TRY(e->mem.get(&e->d_pf_meta, rows, false));
-    e->pf_cap_rows = rows;
+// staged rows (staging.h) into the prefill staging, which grows to hold them.  on_stream: asynchronously on `st`, which
+// the caller drains before `sr` dies (mtts_begin, mtts_score); else synchronously (mtts_slot_submit)
+static int upload_staged(MttsEngine* e, const StagedRows& sr, bool on_stream, hipStream_t st) {
+    if (sr.Mpad > e->pf_cap_rows) {
+        e->mem.release(e->d_pf_tokens); e->mem.release(e->d_pf_meta);
+        e->pf_cap_rows = 0;
+        TRY(e->mem.get(&e->d_pf_tokens, sr.Mpad * 8, false));
+        TRY(e->mem.get(&e->d_pf_meta, sr.Mpad, false));
+        e->pf_cap_rows = sr.Mpad;
+    }
+    const size_t tb = sr.Mpad * 8 * 4, mb = sr.Mpad * sizeof(RowMeta);
+    if (on_stream) {
+        HIPCHK(hipMemcpyAsync(e->d_pf_tokens, sr.toks.data(), tb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(e->d_pf_meta, sr.metas.data(), mb, hipMemcpyHostToDevice, st));
+    } else {
+        HIPCHK(hipMemcpy(e->d_pf_tokens, sr.toks.data(), tb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->d_pf_meta, sr.metas.data(), mb, hipMemcpyHostToDevice));
+    }
     return 0;
 }
 
@@ -970,43 +909,40 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
     e->seed = seed; e->steps_issued = 0; e->has_forced = false;
     e->n_real.assign(R, 0);
     e->max_real = 0;
-    // attention_mask must be the left-padded form rpadding() produces (generation_utils.py:221-237)
-    std::vector<int> pad(B, 0);
+    std::vector<StageSeq> seqs(B);     // prompt b: its real tokens, into row b*takes; the last one's logits start the run
     for (int b = 0; b < B; ++b) {
         int p = 0;
-        while (p < base && !mask[(size_t)b * T + p]) ++p;
-        for (int t = p; t < base; ++t)
-            if (!mask[(size_t)b * T + t]) return fail(MTTS_EINVAL, "attention_mask of row %d is not left-padded", b);
-        if (p >= base) return fail(MTTS_EINVAL, "row %d has no real token in the first T-7 slots", b);
-        pad[b] = p;
+        TRY(mask_left_padded(mask + (size_t)b * T, base, b, &p));
+        seqs[b] = StageSeq{ids + ((size_t)b * T + p) * 8, base - p, b * takes, true, nullptr};
         for (int j = 0; j < takes; ++j) e->n_real[b * takes + j] = base - p;
         e->max_real = std::max(e->max_real, base - p);
     }
     // pages: every earlier run has been synchronised by its caller or is ordered before us on `st`; the prompts'
     // pages are taken now, the rest on demand as the dialogues grow (issue_steps)
-    for (int b = 0; b < e->cfg.max_batch; ++b) { pool_release(e, b); e->slot_live[b] = b < R; }
-    e->pending_edits.n = 0;            // edits queued by a run that failed (MTTS_ENOMEM before its flush) belong to released pages
+    e->pool.release_all();             // (also the edits a failed run left queued: they belong to released pages)
+    for (int b = 0; b < e->cfg.max_batch; ++b) e->slot_live[b] = b < R;
     TRY(pack_policy_reset(e, st));
+    const auto ship = ship_on(e, st);
     ForkJob fork;
     fork.np = 0; fork.nr = 0;
     for (int b = 0; b < B; ++b) {
-        const int src = b * takes, len = e->n_real[src];
-        const int need = (len + max_steps + MTTS_PAGE - 1) / MTTS_PAGE;
+        const int src = b * takes, len = e->n_real[src], full = len / MTTS_PAGE;
+        const int need = pages_for(len + max_steps);
         if (need > e->max_pages) return fail(MTTS_ENOMEM, "row %d needs %d KV pages, a sequence holds at most %d (max_seq_len %d)", src, need, e->max_pages, e->cfg.max_seq_len);
-        TRY(pool_grow(e, src, (len + MTTS_PAGE - 1) / MTTS_PAGE, st));
+        TRY(e->pool.grow(src, pages_for(len), ship));
         for (int j = 1; j < takes; ++j) {
             const int dst = src + j;
-            TRY(pool_share(e, src, dst, len / MTTS_PAGE, st));
+            TRY(e->pool.share(src, dst, full, ship));
             if (len % MTTS_PAGE) {
-                TRY(pool_grow(e, dst, len / MTTS_PAGE + 1, st));
-                fork.psrc[fork.np] = e->h_page_table[(size_t)src * e->max_pages + len / MTTS_PAGE];
-                fork.pdst[fork.np++] = e->h_page_table[(size_t)dst * e->max_pages + len / MTTS_PAGE];
+                TRY(e->pool.grow(dst, full + 1, ship));
+                fork.psrc[fork.np] = e->pool.entry(src, full);
+                fork.pdst[fork.np++] = e->pool.entry(dst, full);
             }
             fork.rsrc[fork.nr] = src;
             fork.rdst[fork.nr++] = dst;
         }
     }
-    TRY(pool_flush(e, st));
+    TRY(e->pool.flush(ship));
     if (e->max_real + max_steps > e->rope_rows)
         return fail(MTTS_EINVAL, "rope table has %d rows, need %d", e->rope_rows, e->max_real + max_steps);
     // room for chained resurrections (linger_bound) as far as the page-table width and the RoPE table allow
@@ -1016,60 +952,33 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
     // generation buffers
     TRY(ensure_gen_storage(e, max_steps));
     TRY(start_scores(e, st));
-    // flattened prefill rows; every dialogue starts on a 32-row tile boundary so that a tile holds consecutive
-    // positions of one dialogue (the prefill attention kernels share K/V pages across a tile); filler rows are idle
-    size_t Mtot = 0;
-    for (int b = 0; b < B; ++b) Mtot += (size_t)round_up(e->n_real[b * takes], MTTS_MAXR);
-    size_t Mpad = (Mtot + MTTS_RCAP - 1) / MTTS_RCAP * MTTS_RCAP;
-    std::vector<int32_t> toks(Mpad * 8, 0);
-    std::vector<RowMeta> metas(Mpad, RowMeta{-1, 0, 0, 0});
-    size_t r = 0;
-    for (int b = 0; b < B; r = (r + MTTS_MAXR - 1) / MTTS_MAXR * MTTS_MAXR, ++b)
-        for (int i = 0; i < e->n_real[b * takes]; ++i, ++r) {
-            const int64_t* src = ids + ((size_t)b * T + pad[b] + i) * 8;
-            for (int c = 0; c < 8; ++c) {
-                int64_t t = src[c];
-                int64_t V = c == 0 ? e->V0 : e->Vs;
-                if (t < 0 || t >= V) return fail(MTTS_EINVAL, "token %lld out of range on channel %d", (long long)t, c);
-                toks[r * 8 + c] = (int32_t)t;
-            }
-            metas[r] = RowMeta{b * takes, i, i == e->n_real[b * takes] - 1 ? 1 : 0, 0};
-        }
-    TRY(grow_prefill_staging(e, Mpad));
-    HIPCHK(hipMemcpyAsync(e->d_pf_tokens, toks.data(), Mpad * 8 * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->d_pf_meta, metas.data(), Mpad * sizeof(RowMeta), hipMemcpyHostToDevice, st));
-    // history bitmaps (HF repetition penalty sees the whole channel incl. pads: modeling_asteroid.py:129)
+    StagedRows sr;
+    TRY(stage_rows(seqs, e->V0, e->Vs, false, &sr));
     {
+        // every row's history bitmap (over all the padded slots of its prompt), teacher-forcing tail and state: all the
+        // host work that can refuse the call comes before the first copy, so no copy is left reading a vector that died
         std::vector<uint32_t> bm((size_t)MTTS_RCAP * 8 * e->bm_words, 0u);
-        for (int rw = 0; rw < R; ++rw)
-            for (int t = 0, b = rw / takes; t < base; ++t)
-                for (int c = 0; c < 8; ++c) {
-                    int64_t tk = ids[((size_t)b * T + t) * 8 + c];
-                    if (tk >= 0 && tk < (int64_t)e->bm_words * 32) bm[((size_t)rw * 8 + c) * e->bm_words + (tk >> 5)] |= 1u << (tk & 31);
-                }
-        HIPCHK(hipMemcpyAsync(e->d_bitmaps, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, st));
-        // teacher-forcing tail tf_inputs[:, base+s, :] for s = 0..6 (modeling_asteroid.py:143-145)
         std::vector<int32_t> tf((size_t)MTTS_RCAP * 7 * 8, 0);
-        for (int rw = 0; rw < R; ++rw)
-            for (int s = 0, b = rw / takes; s < 7; ++s)
-                for (int c = 0; c < 8; ++c) {
-                    int64_t tk = ids[((size_t)b * T + base + s) * 8 + c];
-                    if (tk < 0 || tk >= (c == 0 ? e->V0 : e->Vs)) return fail(MTTS_EINVAL, "token %lld out of range on channel %d (delayed tail)", (long long)tk, c);
-                    tf[((size_t)rw * 7 + s) * 8 + c] = (int32_t)tk;
-                }
-        HIPCHK(hipMemcpyAsync(e->d_tf, tf.data(), tf.size() * 4, hipMemcpyHostToDevice, st));
+        for (int rw = 0; rw < R; ++rw) {
+            const int64_t* prompt = ids + (size_t)(rw / takes) * T * 8;
+            stage_bitmap(prompt, base, e->bm_words, bm.data() + (size_t)rw * 8 * e->bm_words);
+            TRY(stage_tail(prompt + (size_t)base * 8, e->V0, e->Vs, " (delayed tail)", tf.data() + (size_t)rw * 7 * 8));
+        }
         std::vector<SeqState> ss(MTTS_RCAP, IDLE_SEQ);
         if (!e->next_row_ids.empty() && (int)e->next_row_ids.size() != R)
             return fail(MTTS_EINVAL, "mtts_set_row_ids gave %d ids, the batch has %d rows", (int)e->next_row_ids.size(), R);
         for (int b = 0; b < R; ++b)
             ss[b] = SeqState{-1, 1, e->n_real[b], 0, base, max_length, e->next_row_ids.empty() ? b : e->next_row_ids[b], 1, seed};
         e->next_row_ids.clear();
+        TRY(upload_staged(e, sr, true, st));
+        HIPCHK(hipMemcpyAsync(e->d_bitmaps, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(e->d_tf, tf.data(), tf.size() * 4, hipMemcpyHostToDevice, st));
         // the rows' adapters: a prompt's takes share its KV pages and so its adapter
         for (int b = 0; b < MTTS_RCAP; ++b) e->seq_adapter[b] = (b < R && !row_adapters.empty()) ? row_adapters[b / takes] : -1;
         if (e->d_seq_adapter) HIPCHK(hipMemcpyAsync(e->d_seq_adapter, e->seq_adapter.data(), MTTS_RCAP * sizeof(int32_t), hipMemcpyHostToDevice, st));
         TRY(reset_run_state(e, ss, false, sampler, st));   // drains st: the host vectors above go out of scope
     }
-    TRY(prefill_staged(e, Mpad, (e->max_real + MTTS_PAGE - 1) / MTTS_PAGE, 2, lora, st));
+    TRY(prefill_staged(e, sr.Mpad, pages_for(e->max_real), 2, lora, st));
     // takes: the partially filled last prompt page of each source row into its takes' private pages, and the source
     // row's logits into theirs (bitmaps, teacher-forcing tails and states were uploaded for every row above)
     if (fork.nr) TRY(launch_fork_job(e, fork, false, st));
@@ -1141,14 +1050,15 @@ static int issue_steps(MttsEngine* e, int n, hipStream_t st) {
         // crosses a page boundary (the host's view of "live" lags the device by at most one poll: a dialogue that
         // has just finished may get one page it never writes, returned with the others)
         int len_bound = 1;
+        const auto ship = ship_on(e, st);
         for (int b = 0; b < e->B; ++b) {
             if (!e->slot_live[b]) continue;
             const int len = e->n_real[b] + e->steps_issued + 1;
             len_bound = std::max(len_bound, len);
-            TRY(pool_grow(e, b, (len + MTTS_PAGE - 1) / MTTS_PAGE, st));
+            TRY(e->pool.grow(b, pages_for(len), ship));
         }
-        TRY(pool_flush(e, st));
-        const int pages_bound = (len_bound + MTTS_PAGE - 1) / MTTS_PAGE;
+        TRY(e->pool.flush(ship));
+        const int pages_bound = pages_for(len_bound);
         if (e->use_graphs && !e->prof) {
             // the attention grids are sized by the page bound: round it up to a whole pass-B chunk so that one
             // graph serves ATT_PB pages (512 steps); blocks past a row's last page exit at once
@@ -1199,7 +1109,7 @@ int32_t mtts_sync_state(MttsEngine* e, int32_t* steps_done, int32_t* all_finishe
         // its KV pages again; everything issued so far has completed, so its pages go back to the pool
         const SeqState* ss = e->h_seqs;
         for (int b = 0; b < e->B; ++b)
-            if (e->slot_live[b] && ss[b].step > 0 && !ss[b].unfinished && ss[b].active != 2) { e->slot_live[b] = 0; pool_release(e, b); }
+            if (e->slot_live[b] && ss[b].step > 0 && !ss[b].unfinished && ss[b].active != 2) { e->slot_live[b] = 0; e->pool.release(b); }
     }
     if (steps_done) *steps_done = e->h_ls->step;
     if (all_finished) *all_finished = e->h_ls->done;
@@ -1360,57 +1270,31 @@ static int32_t score_call(MttsEngine* e, const int64_t* ids, const uint8_t* mask
     bool open = false;
     TRY(run_still_open(e, &open));
     if (open) return fail(MTTS_ESTATE, "mtts_score while a run is open: its rows still own KV pages and the activation buffers");
-    // masks: ones, then zeros (real token i sits at position i, the reference's arange(T) positions)
+    // sequence b = the ones of mask row b (real token i sits at position i), staged for page-table row b
+    std::vector<StageSeq> seqs(B);
     std::vector<int> len(B, 0);
-    int max_len = 0;
+    size_t need = 0;
     for (int b = 0; b < B; ++b) {
-        const uint8_t* m = mask + (size_t)b * T;
-        int n = 0;
-        while (n < T && m[n]) ++n;
-        for (int t = n; t < T; ++t)
-            if (m[t]) {
-                if (n == 0) return fail(MTTS_EINVAL, "attention_mask of row %d is left-padded: mtts_score takes right-padded or unpadded rows (ones, then zeros)", b);
-                return fail(MTTS_EINVAL, "attention_mask of row %d is not ones followed by zeros (right-padded or unpadded rows only)", b);
-            }
-        len[b] = n;
-        max_len = std::max(max_len, n);
+        TRY(mask_ones_then_zeros(mask + (size_t)b * T, T, b, &len[b]));
+        seqs[b] = StageSeq{ids + (size_t)b * T * 8, len[b], b, false, labels ? labels + (size_t)b * T * 8 : nullptr};
+        need += (size_t)pages_for(len[b]);
     }
-    for (int b = 0; b < B; ++b)
+    const int max_len = *std::max_element(len.begin(), len.end());
+    for (int b = 0; labels && b < B; ++b)
         for (int t = 0; t < T; ++t)
             for (int c = 0; c < 8; ++c) {
-                const int64_t V = c == 0 ? e->V0 : e->Vs, lb = labels ? labels[((size_t)b * T + t) * 8 + c] : -100, tk = ids[((size_t)b * T + t) * 8 + c];
-                if (t >= len[b]) {
-                    if (lb != -100) return fail(MTTS_EINVAL, "label %lld at a masked position (row %d, position %d, channel %d)", (long long)lb, b, t, c);
-                    continue;
-                }
-                if (tk < 0 || tk >= V) return fail(MTTS_EINVAL, "token %lld out of range on channel %d", (long long)tk, c);
-                if (lb != -100 && (lb < 0 || lb >= V)) return fail(MTTS_EINVAL, "label %lld outside [0, %lld) on channel %d", (long long)lb, (long long)V, c);
+                const int64_t V = c == 0 ? e->V0 : e->Vs, lb = labels[((size_t)b * T + t) * 8 + c];
+                if (lb == -100) continue;
+                if (t >= len[b]) return fail(MTTS_EINVAL, "label %lld at a masked position (row %d, position %d, channel %d)", (long long)lb, b, t, c);
+                if (lb < 0 || lb >= V) return fail(MTTS_EINVAL, "label %lld outside [0, %lld) on channel %d", (long long)lb, (long long)V, c);
             }
+    StagedRows sr;
+    TRY(stage_rows(seqs, e->V0, e->Vs, true, &sr));
+    const size_t Mpad = sr.Mpad;
+    const std::vector<size_t>& row0 = sr.row0;
     // pages: the need is checked against the pool before anything is launched
-    size_t need = 0;
-    for (int b = 0; b < B; ++b) need += (size_t)(len[b] + MTTS_PAGE - 1) / MTTS_PAGE;
-    if (need > e->free_pages.size())
-        return fail(MTTS_ENOMEM, "scoring needs %zu KV pages, the pool has %zu free (%d pages of %d tokens)", need, e->free_pages.size(), e->total_pages, MTTS_PAGE);
-    // staged rows as in begin_run: every sequence starts on a 32-row tile boundary, filler rows are idle; the row of
-    // position t carries labels[t + 1] (the HF shift), the last position of a sequence and the fillers carry none
-    size_t Mtot = 0;
-    for (int b = 0; b < B; ++b) Mtot += (size_t)round_up(len[b], MTTS_MAXR);
-    const size_t Mpad = std::max<size_t>((Mtot + MTTS_RCAP - 1) / MTTS_RCAP * MTTS_RCAP, MTTS_RCAP);
-    std::vector<int32_t> toks(Mpad * 8, 0), labs(Mpad * 8, -100);
-    std::vector<RowMeta> metas(Mpad, RowMeta{-1, 0, 0, 0});
-    std::vector<size_t> row0(B, 0);
-    size_t r = 0;
-    for (int b = 0; b < B; r = (r + MTTS_MAXR - 1) / MTTS_MAXR * MTTS_MAXR, ++b) {
-        row0[b] = r;
-        for (int i = 0; i < len[b]; ++i, ++r) {
-            for (int c = 0; c < 8; ++c) {
-                toks[r * 8 + c] = (int32_t)ids[((size_t)b * T + i) * 8 + c];
-                if (labels && i + 1 < len[b]) labs[r * 8 + c] = (int32_t)labels[((size_t)b * T + i + 1) * 8 + c];
-            }
-            metas[r] = RowMeta{b, i, 0, 0};
-        }
-    }
-    TRY(grow_prefill_staging(e, Mpad));
+    if (need > (size_t)e->pool.free_count())
+        return fail(MTTS_ENOMEM, "scoring needs %zu KV pages, the pool has %zu free (%d pages of %d tokens)", need, (size_t)e->pool.free_count(), e->total_pages, MTTS_PAGE);
     if (Mpad > e->sc_cap_rows) {
         e->mem.release(e->d_sc_labels); e->mem.release(e->d_sc_logp);
         e->sc_cap_rows = 0;
@@ -1437,14 +1321,9 @@ static int32_t score_call(MttsEngine* e, const int64_t* ids, const uint8_t* mask
     // with the next mtts_begin): those entries are set aside and put back, and the borrowed pages return to the free
     // list in the reverse of the order they were taken in, so the pool -- counts and page numbering -- is as before.
     struct Borrow {
-        MttsEngine* e; int B; hipStream_t st;
-        std::vector<std::vector<int32_t>> kept;
-        Borrow(MttsEngine* e_, int B_, hipStream_t st_) : e(e_), B(B_), st(st_), kept(B_) {
-            for (int b = 0; b < B; ++b) {
-                kept[b].assign(e->h_page_table.begin() + (size_t)b * e->max_pages, e->h_page_table.begin() + (size_t)b * e->max_pages + e->n_pages[b]);
-                e->n_pages[b] = 0;
-            }
-        }
+        MttsEngine* e; hipStream_t st;
+        KvPool::Kept kept;
+        Borrow(MttsEngine* e_, int B_, hipStream_t st_) : e(e_), st(st_), kept(e_->pool.set_aside(B_)) {}
         // Every return path: first wait for what was enqueued (launches that touch the borrowed pages, copies from the
         // caller's host vectors), then give the pages back, restore the rows and wait for the device table to follow.
         int end() {
@@ -1452,10 +1331,7 @@ static int32_t score_call(MttsEngine* e, const int64_t* ids, const uint8_t* mask
             done = true;
             auto note = [&](int r) { if (!rc) rc = r; };
             if (hipStreamSynchronize(st) != hipSuccess) note(fail(MTTS_EHIP, "mtts_score: the stream failed while the pass ran"));
-            for (int b = B - 1; b >= 0; --b) pool_release(e, b);
-            for (int b = 0; b < B; ++b)
-                for (int32_t page : kept[b]) note(pool_append(e, b, page, st));
-            note(pool_flush(e, st));
+            note(e->pool.restore(kept, ship_on(e, st)));
             if (hipStreamSynchronize(st) != hipSuccess) note(fail(MTTS_EHIP, "mtts_score: restoring the page table failed"));
             return rc;
         }
@@ -1466,15 +1342,15 @@ static int32_t score_call(MttsEngine* e, const int64_t* ids, const uint8_t* mask
         }
         bool done = false; int rc = 0;
     } borrow(e, B, st);
-    for (int b = 0; b < B; ++b) TRY(pool_grow(e, b, (len[b] + MTTS_PAGE - 1) / MTTS_PAGE, st));
-    TRY(pool_flush(e, st));
-    HIPCHK(hipMemcpyAsync(e->d_pf_tokens, toks.data(), Mpad * 8 * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->d_pf_meta, metas.data(), Mpad * sizeof(RowMeta), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->d_sc_labels, labs.data(), Mpad * 8 * 4, hipMemcpyHostToDevice, st));
+    const auto ship = ship_on(e, st);
+    for (int b = 0; b < B; ++b) TRY(e->pool.grow(b, pages_for(len[b]), ship));
+    TRY(e->pool.flush(ship));
+    TRY(upload_staged(e, sr, true, st));
+    HIPCHK(hipMemcpyAsync(e->d_sc_labels, sr.labs.data(), Mpad * 8 * 4, hipMemcpyHostToDevice, st));
     {
         NoSeal ns(e);
         const size_t pfcap = e->f32 ? MTTS_PF32CAP : MTTS_PFCAP;
-        const int pages_bound = std::max(1, (max_len + MTTS_PAGE - 1) / MTTS_PAGE);
+        const int pages_bound = std::max(1, pages_for(max_len));
         for (size_t off = 0; off < Mpad; off += pfcap) {
             const int rows = (int)std::min<size_t>(pfcap, Mpad - off);
             TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, 0, false, st, 0));
@@ -1627,8 +1503,8 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     e->n_real.assign(B, 0);
     e->max_real = 0;
     HIPCHK(hipStreamSynchronize(st));
-    for (int b = 0; b < e->cfg.max_batch; ++b) { pool_release(e, b); e->slot_live[b] = 0; }
-    e->pending_edits.n = 0;
+    e->pool.release_all();
+    std::fill(e->slot_live.begin(), e->slot_live.end(), 0);
     TRY(pack_policy_reset(e, st));
     std::fill(e->seq_adapter.begin(), e->seq_adapter.end(), -1);
     if (e->d_seq_adapter) HIPCHK(hipMemsetAsync(e->d_seq_adapter, 0xff, MTTS_RCAP * sizeof(int32_t), st));
@@ -1667,7 +1543,7 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
     if (max_length <= base) return fail(MTTS_EINVAL, "max_length leaves no room to generate");
     const int max_new = max_length - base + FLUSH_STEPS;      // incl. a delay-pattern flush that starts at max_length
     if (max_new > e->gen_cap) return fail(MTTS_EINVAL, "dialogue may run %d steps, slot storage holds %d", max_new, e->gen_cap);
-    if ((n + max_new + MTTS_PAGE - 1) / MTTS_PAGE > e->max_pages) return fail(MTTS_ENOMEM, "dialogue needs more KV pages than a sequence may hold");
+    if (pages_for(n + max_new) > e->max_pages) return fail(MTTS_ENOMEM, "dialogue needs more KV pages than a sequence may hold");
     if (n + max_new > e->rope_rows) return fail(MTTS_EINVAL, "rope table too short");
     HIPCHK(hipStreamSynchronize(st));
     {   // the slot must be empty
@@ -1676,31 +1552,23 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
         if (cur.active) return fail(MTTS_ESTATE, "slot %d is occupied", slot);
     }
     // admission: the prompt's pages plus the page its first step may open must be free now
-    if (e->slot_live[slot]) { e->slot_live[slot] = 0; pool_release(e, slot); }      // finished, not collected yet
-    if ((int)e->free_pages.size() < (n + 1 + MTTS_PAGE - 1) / MTTS_PAGE)
-        return fail(MTTS_ENOMEM, "KV page pool: %d pages free, the prompt needs %d", (int)e->free_pages.size(), (n + 1 + MTTS_PAGE - 1) / MTTS_PAGE);
-    TRY(pool_grow(e, slot, (n + MTTS_PAGE - 1) / MTTS_PAGE, st));
-    TRY(pool_flush(e, st));
-    const size_t Mpad = ((size_t)n + MTTS_RCAP - 1) / MTTS_RCAP * MTTS_RCAP;
-    std::vector<int32_t> toks(Mpad * 8, 0);
-    std::vector<RowMeta> metas(Mpad, RowMeta{-1, 0, 0, 0});
+    if (e->slot_live[slot]) { e->slot_live[slot] = 0; e->pool.release(slot); }      // finished, not collected yet
+    if (e->pool.free_count() < pages_for(n + 1))
+        return fail(MTTS_ENOMEM, "KV page pool: %d pages free, the prompt needs %d", e->pool.free_count(), pages_for(n + 1));
+    const auto ship = ship_on(e, st);
+    TRY(e->pool.grow(slot, pages_for(n), ship));
+    TRY(e->pool.flush(ship));
+    StagedRows sr;
     std::vector<uint32_t> bm((size_t)8 * e->bm_words, 0u);
     std::vector<int32_t> tf(7 * 8, 0);
-    for (int i = 0; i < T; ++i)
-        for (int c = 0; c < 8; ++c) {
-            int64_t t = ids[(size_t)i * 8 + c];
-            if (t < 0 || t >= (c == 0 ? e->V0 : e->Vs)) return fail(MTTS_EINVAL, "token %lld out of range on channel %d", (long long)t, c);
-            if (i < n) { toks[(size_t)i * 8 + c] = (int32_t)t; bm[(size_t)c * e->bm_words + (t >> 5)] |= 1u << (t & 31); }
-            else tf[(i - n) * 8 + c] = (int32_t)t;
-        }
-    for (int i = 0; i < n; ++i) metas[i] = RowMeta{slot, i, i == n - 1 ? 1 : 0, 0};
-    TRY(grow_prefill_staging(e, Mpad));
-    HIPCHK(hipMemcpy(e->d_pf_tokens, toks.data(), Mpad * 8 * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_pf_meta, metas.data(), Mpad * sizeof(RowMeta), hipMemcpyHostToDevice));
+    TRY(stage_rows({StageSeq{ids, n, slot, true, nullptr}}, e->V0, e->Vs, false, &sr));
+    TRY(stage_tail(ids + (size_t)n * 8, e->V0, e->Vs, "", tf.data()));
+    stage_bitmap(ids, n, e->bm_words, bm.data());
+    TRY(upload_staged(e, sr, false, st));
     HIPCHK(hipMemcpy(e->d_bitmaps + (size_t)slot * 8 * e->bm_words, bm.data(), bm.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_tf + (size_t)slot * 7 * 8, tf.data(), tf.size() * 4, hipMemcpyHostToDevice));
     TRY(set_seq_adapter(e, slot, adapter, st));
-    TRY(prefill_staged(e, Mpad, (n + MTTS_PAGE - 1) / MTTS_PAGE, 0, adapter >= 0, st));
+    TRY(prefill_staged(e, sr.Mpad, pages_for(n), 0, adapter >= 0, st));
     // logits of the dialogue's last prompt token only: heads on a one-row activation tile, copied into its slot
     // (the other slots' logits belong to dialogues that are mid-flight)
     if (e->f32) {            // fp32 engine: the GEMV writes the slot's logits rows directly
@@ -1729,7 +1597,7 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
 }
 
 // Take of a just-submitted dialogue: dst starts where src starts (same prompt, KV, logits, history, teacher-forcing tail)
-// and draws from (seed; step, row_id, channel).  src's complete prompt pages are shared (pool_share), its partially filled
+// and draws from (seed; step, row_id, channel).  src's complete prompt pages are shared (KvPool::share), its partially filled
 // last page is copied into one fresh page; everything rides `stream` (one fork_kernel launch, one state upload).
 int32_t mtts_slot_fork(MttsEngine* e, int32_t src, int32_t dst, uint64_t seed, int32_t row_id, void* stream) {
     if (!e || !e->began || !e->continuous) return fail(MTTS_ESTATE, "mtts_sched_open has not run");
@@ -1743,23 +1611,24 @@ int32_t mtts_slot_fork(MttsEngine* e, int32_t src, int32_t dst, uint64_t seed, i
     HIPCHK(hipStreamSynchronize(st));
     if (!e->h_seqs[src].active || e->h_seqs[src].step) return fail(MTTS_ESTATE, "fork: slot %d has stepped", src);
     if (e->h_seqs[dst].active) return fail(MTTS_ESTATE, "fork: slot %d is occupied", dst);
-    if (e->slot_live[dst]) { e->slot_live[dst] = 0; pool_release(e, dst); }      // finished, not collected yet
+    if (e->slot_live[dst]) { e->slot_live[dst] = 0; e->pool.release(dst); }      // finished, not collected yet
     const int len = e->n_real[src] + e->steps_issued, full = len / MTTS_PAGE, tail = len % MTTS_PAGE != 0;
-    if ((int)e->free_pages.size() < tail)
+    if (e->pool.free_count() < tail)
         return fail(MTTS_ENOMEM, "KV page pool: no free page for the take's copy of the last prompt page");
+    const auto ship = ship_on(e, st);
     ForkJob job;
     job.np = 0; job.nr = 1;
     job.rsrc[0] = src; job.rdst[0] = dst;
-    int rc = pool_share(e, src, dst, full, st);
+    int rc = e->pool.share(src, dst, full, ship);
     if (!rc && tail) {
-        rc = pool_grow(e, dst, full + 1, st);
-        job.psrc[0] = e->h_page_table[(size_t)src * e->max_pages + full];
-        job.pdst[0] = e->h_page_table[(size_t)dst * e->max_pages + full];
+        rc = e->pool.grow(dst, full + 1, ship);
+        job.psrc[0] = e->pool.entry(src, full);
+        job.pdst[0] = e->pool.entry(dst, full);
         job.np = 1;
     }
-    if (!rc) rc = pool_flush(e, st);
+    if (!rc) rc = e->pool.flush(ship);
     if (!rc) rc = launch_fork_job(e, job, true, st);
-    if (rc) { pool_release(e, dst); return rc; }    // the share is undone with the slot (counts, unshipped edits)
+    if (rc) { e->pool.release(dst); return rc; }    // the share is undone with the slot (counts, unshipped edits)
     SeqState ns = e->h_seqs[src];
     ns.row_id = row_id; ns.seed = seed;
     e->h_seqs[dst] = ns;                            // pinned staging of the upload
@@ -1784,7 +1653,7 @@ int32_t mtts_slot_states(MttsEngine* e, int32_t* host_state, void* stream) {
         host_state[b * 4 + 2] = ss[b].step; host_state[b * 4 + 3] = ss[b].kv_len;
         // a dialogue that has left the batch (scheduler mode) gives its pages back: the stream is idle, nothing
         // in flight reads them
-        if (e->continuous && e->slot_live[b] && !ss[b].active) { e->slot_live[b] = 0; pool_release(e, b); e->seq_adapter[b] = -1; }
+        if (e->continuous && e->slot_live[b] && !ss[b].active) { e->slot_live[b] = 0; e->pool.release(b); e->seq_adapter[b] = -1; }
     }
     return MTTS_OK;
 }
@@ -1800,23 +1669,23 @@ int32_t mtts_slot_evict(MttsEngine* e, int32_t slot, void* stream) {
     HIPCHK(hipMemcpy(e->d_seqs + slot, &cur, sizeof(cur), hipMemcpyHostToDevice));
     RowMeta idle{-1, 0, 0, 0};
     HIPCHK(hipMemcpy(e->d_meta + slot, &idle, sizeof(idle), hipMemcpyHostToDevice));
-    if (e->slot_live[slot]) { e->slot_live[slot] = 0; pool_release(e, slot); }
+    if (e->slot_live[slot]) { e->slot_live[slot] = 0; e->pool.release(slot); }
     e->seq_adapter[slot] = -1;                      // (the host's copy picks the step's launches; the device's is rewritten by the next submit)
     return MTTS_OK;
 }
 
-int32_t mtts_kv_pool_state(MttsEngine* e, int32_t* total_pages, int32_t* free_pages, int32_t* max_pages_per_seq) {
+int32_t mtts_kv_pool_state(MttsEngine* e, int32_t* total_pages, int32_t* n_free, int32_t* max_pages_per_seq) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     if (total_pages) *total_pages = e->total_pages;
-    if (free_pages) *free_pages = (int32_t)e->free_pages.size();
+    if (n_free) *n_free = e->pool.free_count();
     if (max_pages_per_seq) *max_pages_per_seq = e->max_pages;
     return MTTS_OK;
 }
 
-int32_t mtts_read_page_table(MttsEngine* e, int32_t* host_table, int32_t* host_n_pages) {
-    if (!e || !host_table || !host_n_pages) return fail(MTTS_EINVAL, "null argument");
-    memcpy(host_table, e->h_page_table.data(), e->h_page_table.size() * 4);
-    memcpy(host_n_pages, e->n_pages.data(), e->n_pages.size() * 4);
+int32_t mtts_read_page_table(MttsEngine* e, int32_t* host_table, int32_t* host_counts) {
+    if (!e || !host_table || !host_counts) return fail(MTTS_EINVAL, "null argument");
+    memcpy(host_table, e->pool.table().data(), e->pool.table().size() * 4);
+    memcpy(host_counts, e->pool.counts().data(), e->pool.counts().size() * 4);
     return MTTS_OK;
 }
 
@@ -1824,8 +1693,8 @@ int32_t mtts_read_page_table(MttsEngine* e, int32_t* host_table, int32_t* host_n
 int32_t mtts_debug_read_device_page_table(MttsEngine* e, int32_t* host_table, void* stream) {
     if (!e || !host_table) return fail(MTTS_EINVAL, "null argument");
     HIPCHK(hipSetDevice(e->device));
-    TRY(pool_flush(e, S(stream)));
-    HIPCHK(hipMemcpyAsync(host_table, e->d_page_table, e->h_page_table.size() * 4, hipMemcpyDeviceToHost, S(stream)));
+    TRY(e->pool.flush(ship_on(e, S(stream))));
+    HIPCHK(hipMemcpyAsync(host_table, e->d_page_table, e->pool.table().size() * 4, hipMemcpyDeviceToHost, S(stream)));
     HIPCHK(hipStreamSynchronize(S(stream)));
     return MTTS_OK;
 }

@@ -478,7 +478,7 @@ int32_t mtts_k_paged_attn_decode(const void* dev_q, const void* dev_k, const voi
     if (!dev_q || !dev_k || !dev_v || !host_lens || !dev_out || R < 1 || R > MTTS_MAXR || Lmax < 1 || nq < 1 || nkv < 1 || nq % nkv)
         return fail(MTTS_EINVAL, "paged_attn_decode: bad argument (1..32 rows)");
     hipStream_t st = S(stream);
-    const int max_pages = (Lmax + MTTS_PAGE - 1) / MTTS_PAGE, total_pages = R * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
+    const int max_pages = pages_for(Lmax), total_pages = R * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
     std::vector<int32_t> hpt((size_t)R * max_pages);
     std::vector<char> seen(total_pages, 0);
     for (size_t i = 0; i < hpt.size(); ++i) {
@@ -491,7 +491,7 @@ int32_t mtts_k_paged_attn_decode(const void* dev_q, const void* dev_k, const voi
     for (int r = 0; r < R; ++r) {
         if (host_lens[r] < 1 || host_lens[r] > Lmax) return fail(MTTS_EINVAL, "row %d: length %d outside 1..%d", r, host_lens[r], Lmax);
         hm[r] = RowMeta{r, host_lens[r] - 1, 1, 0};
-        pages_bound = std::max(pages_bound, (host_lens[r] + MTTS_PAGE - 1) / MTTS_PAGE);
+        pages_bound = std::max(pages_bound, pages_for(host_lens[r]));
     }
     RowMeta* meta = nullptr; int32_t *pt = nullptr, *lens = nullptr; uint16_t *kc = nullptr, *vc = nullptr, *scores = nullptr, *outp = nullptr;
     float *stats = nullptr, *opart = nullptr;
@@ -545,7 +545,7 @@ int32_t mtts_k_attn_section(const float* dev_slabs, int32_t ksplit, const void* 
         !dev_vcache || R < 1 || R > MTTS_MAXR || Lmax < 1 || nq < 1 || nkv < 1 || nq % nkv || ksplit < 1 || (path != 0 && path != 1))
         return fail(MTTS_EINVAL, "attn_section: bad argument (1..32 rows, path 0 or 1)");
     hipStream_t st = S(stream);
-    const int max_pages = (Lmax + MTTS_PAGE - 1) / MTTS_PAGE, total_pages = R * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
+    const int max_pages = pages_for(Lmax), total_pages = R * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
     const int Npad = (nq + 2 * nkv) * MTTS_HD;
     std::vector<int32_t> hpt((size_t)R * max_pages);
     std::vector<char> seen(total_pages, 0);
@@ -562,7 +562,7 @@ int32_t mtts_k_attn_section(const float* dev_slabs, int32_t ksplit, const void* 
         if (!host_lens[r]) continue;
         hm[r] = RowMeta{r, host_lens[r] - 1, 1, 0};
         cached[r] = host_lens[r] - 1;
-        pages_bound = std::max(pages_bound, (host_lens[r] + MTTS_PAGE - 1) / MTTS_PAGE);
+        pages_bound = std::max(pages_bound, pages_for(host_lens[r]));
     }
     pages_bound = std::min(round_up(pages_bound, ATT_PB), max_pages);      // as a captured decode step sizes its launches
     RowMeta* meta = nullptr; int32_t *pt = nullptr, *lens = nullptr; uint16_t *kc = nullptr, *vc = nullptr, *scores = nullptr, *outp = nullptr;
@@ -618,7 +618,7 @@ int64_t mtts_debug_attn_row_launches(void) { return (int64_t)mtts_attn_row_launc
 //         for (int i = 0; i < e->n_real[b * takes]; ++i, ++r) ... metas[r] = RowMeta{b * takes, i, i == n_real - 1 ? 1 : 0, 0};
 // every dialogue on a 32-row tile boundary, filler rows RowMeta{-1, 0, 0, 0}, the pass padded to a multiple of MTTS_RCAP
 // rows (`size_t Mpad = (Mtot + MTTS_RCAP - 1) / MTTS_RCAP * MTTS_RCAP`) with wholly idle tiles, pages_bound =
-// max_b ceil(lens[b] / 64) (`prefill_staged(e, Mpad, (e->max_real + MTTS_PAGE - 1) / MTTS_PAGE, ...)`).  The launches are
+// max_b ceil(lens[b] / 64) (`prefill_staged(e, sr.Mpad, pages_for(e->max_real), ...)`).  The launches are
 // attend_layer's for prefill == true, fused == false, sealed == false (engine.hip), with nchunks_max the engine's
 // `e->nchunks_max = (e->max_pages + ATT_PB - 1) / ATT_PB`:
 //     launch_qkv_post(e->partial, ks_qkv, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos, e->rope_sin, e->qbuf,
@@ -642,7 +642,7 @@ int32_t mtts_k_attn_prefill(const float* dev_slabs, int32_t ksplit, const void* 
         !dev_q || !dev_kcache || !dev_vcache || B < 1 || B > MTTS_RCAP || Lmax < 1 || nq < 1 || nkv < 1 || nq % nkv || ksplit < 1 || ksplit > 8)
         return fail(MTTS_EINVAL, "attn_prefill: bad argument (1..%d dialogues, nq %% nkv == 0, 1 <= ksplit <= 8)", MTTS_RCAP);
     if (const int G = nq / nkv; G != 1 && G != 2 && G != 4) return fail(MTTS_EINVAL, "attention group size not built (1, 2, 4)");
-    const int max_pages = (Lmax + MTTS_PAGE - 1) / MTTS_PAGE, total_pages = B * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
+    const int max_pages = pages_for(Lmax), total_pages = B * max_pages, nch = (max_pages + ATT_PB - 1) / ATT_PB;
     const int nch_pf = (max_pages + ATT_PF - 1) / ATT_PF, Npad = (nq + 2 * nkv) * MTTS_HD;
     int64_t M = 0;
     int pages_bound = 1;
@@ -651,7 +651,7 @@ int32_t mtts_k_attn_prefill(const float* dev_slabs, int32_t ksplit, const void* 
         if (c < 0 || c % MTTS_MAXR || c >= n || n > Lmax)
             return fail(MTTS_EINVAL, "attn_prefill: dialogue %d: need cached %% 32 == 0 and 0 <= cached (%d) < lens (%d) <= Lmax (%d)", b, c, n, Lmax);
         M += round_up(n - c, MTTS_MAXR);
-        pages_bound = std::max(pages_bound, (n + MTTS_PAGE - 1) / MTTS_PAGE);
+        pages_bound = std::max(pages_bound, pages_for(n));
     }
     if (M > MTTS_PFCAP) return fail(MTTS_EINVAL, "attn_prefill: %lld staged rows, a pass holds %d", (long long)M, MTTS_PFCAP);
     std::vector<int32_t> hpt((size_t)total_pages);
@@ -726,7 +726,7 @@ int32_t mtts_debug_kv_pack_stats(MttsEngine* e, int64_t* out6) {
     HIPCHK(hipMemcpy(ss.data(), e->d_seqs, ss.size() * sizeof(SeqState), hipMemcpyDeviceToHost));
     std::vector<int32_t> complete(e->B, 0);
     for (int b = 0; b < e->B; ++b)
-        if (e->slot_live[b]) complete[b] = std::min(ss[b].kv_len >> 6, e->n_pages[b]);
+        if (e->slot_live[b]) complete[b] = std::min(ss[b].kv_len >> 6, e->pool.pages_of(b));
     DevBufs hb;
     int32_t* dc = nullptr; unsigned long long* dout = nullptr;
     TRY(hb.get(&dc, e->B)); TRY(hb.get(&dout, 4));
@@ -779,7 +779,7 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
     const float scale = 1.0f / sqrtf((float)MTTS_HD);
     const int R = round_up(e->B, 32);
     const int len_bound = e->max_real + e->steps_issued + 1;
-    const int pages_bound = (len_bound + MTTS_PAGE - 1) / MTTS_PAGE;
+    const int pages_bound = pages_for(len_bound);
     if (phase == ATTN_ROW) {
         if (attn_row_prepare()) return fail(MTTS_EINVAL, "attn_row_kernel: the dynamic LDS limit could not be raised");
         const QkvFuse f0{e->partial, e->p_qkv.ksplit, e->qkv_rows, nullptr, nullptr, nullptr, nullptr, 0.f};

@@ -6,6 +6,7 @@
 
 #include "../../include/mtts.h"
 #include "common.h"
+#include "kvpool.h"          // PageEdits (launch_set_pages) and the KV page pool that fills it: HIP-free
 
 // ---- gemm.hip -------------------------------------------------------------------------------------------------------
 enum { EPI_PARTIAL = 0, EPI_BF16 = 1, EPI_SILU = 2,
@@ -30,8 +31,6 @@ void launch_pack_rows(const void* src, void* dst, int R, int K, int tiles, hipSt
 void launch_reduce_partial_bf16(const float* partial, void* out, int ksplit, int Npad, int n_valid, int R, hipStream_t st);
 
 // ---- layer.hip ------------------------------------------------------------------------------------------------------
-struct PageEdits { int32_t n; int32_t idx[31]; int32_t val[31]; };     // page-table entries handed over as launch arguments
-static_assert(sizeof(PageEdits) == 252, "PageEdits is a kernel argument: one 32-bit count + 31 (index, value) pairs");
 void launch_embed_norm(const int32_t* tokens, const RowMeta* meta, const uint16_t* const* tables, const void* norm_w,
                        void* x, void* xn_packed, int R, int H, float eps, hipStream_t st);
 void launch_resid_norm(const float* partial, int ksplit, int Npad, void* x, const void* norm_w, void* xn_packed,

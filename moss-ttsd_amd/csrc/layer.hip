@@ -292,7 +292,7 @@ void launch_fill_random_bf16(void* p, size_t n, uint32_t seed, hipStream_t st) {
     hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(4096), dim3(256), 0, st, (uint16_t*)p, n, seed);
 }
 
-// Page-table edits handed over as launch arguments (engine.hip: pool_flush).
+// Page-table edits handed over as launch arguments (kvpool.h: KvPool::flush, through engine.hip: ship_on).
 __global__ void set_pages_kernel(int32_t* __restrict__ table, PageEdits ed) {
     if ((int)threadIdx.x < ed.n) table[ed.idx[threadIdx.x]] = ed.val[threadIdx.x];
 }
