@@ -316,13 +316,40 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
 int32_t mtts_k_gemm_bench(int32_t N, int32_t K, int32_t epi, int32_t ksplit, int32_t waves, int32_t copies,
                           int32_t iters, float* avg_us);
 
+/* Sealed weight streams (csrc/gemm_sealed.hip): gate/up, down_proj and the heads also exist in the sealed
+ * 13-bit form and the one-row-tile decode GEMMs read that.  out12 = per kind (gate/up, down_proj, head 0, heads 1-7):
+ * {groups, groups NOT sealed (a lane held more than 8 distinct high bytes: its wave reads the bf16 tiles), 1 if the
+ * kind's decode GEMMs currently read the twin}.  Runs mtts_weights_ready (the counts are taken there, after a bind).
+ * MTTS_ESTATE when the engine keeps no twins (fp32 / fp16 engines, MTTS_W_SEAL=0, MTTS_GEMM_DEPTH=0). */
+int32_t mtts_debug_wseal_stats(MttsEngine* e, int64_t* out12);
+/* number of GEMM launches of this process that took a sealed kernel (they also count as depth-specialised launches,
+ * mtts_debug_gemm_depth_launches below); under graph replay a launch counts once, when it is captured */
+int64_t mtts_debug_wseal_launches(void);
+/* mtts_k_gemm_bench's launch train on `copies` packed copies of W [N][K] bf16 row-major (NULL: a constant), 32 rows, 8
+ * waves, split-K as given: sealed != 0 the sealed kernel on the copies' twins (head_form, epi 1 only: 1 the persistent
+ * kernel, 0 one tile per block), 0 launch_gemm on the bf16 copies.  epi 0 partial / 1 bf16 / 2 SwiGLU; only the shapes
+ * the sealed kernels take.  out2 (may be NULL) = {groups, groups not sealed} of one copy. */
+int32_t mtts_k_gemm_sealed_bench(const void* dev_w, int32_t N, int32_t K, int32_t epi, int32_t ksplit, int32_t copies,
+                                 int32_t iters, int32_t sealed, int32_t head_form, float* avg_us, int64_t* out2);
+
 /* ---- per-kernel entry points (unit tests; device pointers) ---------------- */
+/* The bind-time sealer: a packed weight array of `ntiles` N-tiles ([ntiles][K/16][64 lanes][16 B]) -> its sealed twin
+ * [ntiles][K/16/ktw][13 or 10 units][64][16 B], groups of ktw = 16 or 12 k-tiles.  A 16-tile group is a page of
+ * mtts_k_kv_seal's plain form; a 12-tile group is the 16-unit form of the lane's 96 values followed by 32 copies of its
+ * first value, units 0-5, 8-10 and 12 kept (oracle/kv_seal_oracle.py is the specification of both). */
+int32_t mtts_k_wseal(const void* dev_packed, int32_t ntiles, int32_t K, int32_t ktw, void* dev_sealed, void* stream);
+/* One decode GEMM of 1 <= M <= 32 rows, W [N][K] and X [M][K] bf16 row-major, packed and sealed by the hook, through the
+ * sealed kernel (sealed != 0) or through launch_gemm on the same packed array (0).  dev_out receives the kernel's raw
+ * output, which starts as 0xa5 bytes: epi 0 fp32 [ksplit][32][Npad]; 1 bf16 [32][Npad] (columns >= N keep the sentinel);
+ * 2 bf16 32 * Npad / 2 in the X-fragment layout (Npad = N rounded up to 32).  out2 (may be NULL) as above. */
+int32_t mtts_k_gemm_sealed(const void* dev_w, const void* dev_x, void* dev_out, int32_t M, int32_t N, int32_t K, int32_t epi,
+                           int32_t ksplit, int32_t sealed, int32_t head_form, int64_t* out2, void* stream);
 /* Y[M,N] = X[M,K] * W[N,K]^T, bf16 in, fp32 accumulate, bf16 out.  M <= 128: skinny decode kernel; 128 < M <= 512:
  * tiled prefill kernel. */
 int32_t mtts_k_gemm_bf16(const void* dev_w, const void* dev_x, void* dev_y,
                          int32_t M, int32_t N, int32_t K, int32_t ksplit, void* stream);
-/* number of GEMM launches of this process that took a depth-specialised kernel (gemm_depth_kernel / gemm_gateup48_kernel)
- * instead of gemm_skinny_kernel; under graph replay a launch counts once, when it is captured (tests: did the dispatch fire) */
+/* number of GEMM launches of this process that took a depth-specialised kernel (gemm_depth_kernel / gemm_gateup48_kernel,
+ * or one of their sealed twins) instead of gemm_skinny_kernel; under graph replay a launch counts once, when it is captured (tests: did the dispatch fire) */
 int64_t mtts_debug_gemm_depth_launches(void);
 /* number of whole-row decode attention launches (attn_row_kernel) of this process; counted like the above */
 int64_t mtts_debug_attn_row_launches(void);

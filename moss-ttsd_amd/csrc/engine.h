@@ -35,6 +35,12 @@ static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 // MTTS_GEMM_DEPTH=0: every decode GEMM runs gemm_skinny_kernel, as before the depth-specialised kernels (gemm.hip);
 // the engine reads it at creation, the per-kernel hooks per call
+// Sealed weight streams, MTTS_W_SEAL=1: a kind's decode GEMMs read the twin while at most this share of its groups did not
+// seal (gate/up, down_proj, head 0, heads 1-7).  A group that did not seal costs its wave more round trips in kernels that
+// are one round trip long, so the bounds are small; each is the largest share at which the sealed launch train still beat
+// the bf16 one by more than the spread of both (profiles/wseal_ab.json).  gate/up did not beat it at the
+// share Gaussian weights have (1 group in 3 072): negative = never, and no twin is kept for it.
+static const double WSEAL_MAX_UNSEALED[4] = {-1.0, 1.0 / 512, 1.0 / 8, 1.0 / 64};
 static inline int gemm_depth_env() {
     const char* g = getenv("MTTS_GEMM_DEPTH");
     return (g && atoi(g) == 0) ? 0 : 1;
@@ -127,6 +133,7 @@ static inline int alloc_lp_scratch(DevBufs& m, SampleScratch& sc, int rows) {
 // ---- the engine ------------------------------------------------------------------------------------------------
 struct Layer {
     void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr;     // packed
+    void *wgu_s = nullptr, *wd_s = nullptr;                                 // their sealed twins (gemm_sealed.hip), or null
     void *ln_in = nullptr, *ln_post = nullptr, *qn = nullptr, *kn = nullptr; // bf16 vectors
     int bound = 0;
 };
@@ -157,6 +164,17 @@ struct MttsEngine {
     void *x2 = nullptr, *act_rm = nullptr;   // small-batch path: second residual buffer (ping-pong), row-major SwiGLU output
     int small_rows = SMALL_RP;          // decode batches up to this many dialogues take the small-batch path (0 = off)
     int gemm_depth = 1;                 // depth-specialised decode GEMMs (gemm.hip; MTTS_GEMM_DEPTH=0: off)
+    // Sealed weight streams (gemm_sealed.hip): gate/up, down_proj and the heads also exist in the sealed
+    // 13-bit form, made by every bind of such a matrix on the bind's stream, and the one-row-tile decode GEMMs read that
+    // instead of the bf16 array.  MTTS_W_SEAL: 0 never (no twin is allocated), 1 per matrix kind by the share of groups that
+    // did not seal (counted at mtts_weights_ready after a bind; WSEAL_MAX_UNSEALED above), 2 whenever the shape fits.
+    int w_seal = 1;
+    int w_seal_head = 1;                // the heads' sealed kernel: 1 persistent over N-tiles, 0 one tile per block (MTTS_W_SEAL_HEAD, a tuning aid)
+    void *head0_s = nullptr, *heads17_s = nullptr;
+    int wseal_ktw[WSEAL_KINDS] = {0, 0, 0, 0};      // k-tiles per sealed group of each kind (0: the kind has no twin)
+    bool wseal_dirty = false;           // a matrix with a twin was bound since the last count
+    char wseal_on[WSEAL_KINDS] = {0, 0, 0, 0};      // the kind's decode GEMMs read the twin (decided at mtts_weights_ready)
+    unsigned long long *d_wseal_cnt = nullptr, *h_wseal_cnt = nullptr;     // per kind {groups, groups not sealed}
     void *x = nullptr, *xn = nullptr, *attn_p = nullptr, *act_p = nullptr, *qbuf = nullptr, *hlast = nullptr, *xh = nullptr;
     void *logits0 = nullptr, *logits17 = nullptr, *join_logits0 = nullptr, *join_logits17 = nullptr;
     void* scores = nullptr;

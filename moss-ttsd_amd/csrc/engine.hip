@@ -187,6 +187,28 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     e->p_h0 = mtts_plan_gemm(e->V0_pad, H, 1);
     e->p_h17 = mtts_plan_gemm(7 * e->Vs_pad, H, 1);
     for (GemmPlan* p : {&e->p_qkv, &e->p_o, &e->p_gu, &e->p_d, &e->p_h0, &e->p_h17}) p->depth = e->gemm_depth;
+    // sealed twins of gate/up, down_proj and the heads, where the decode plan is one the sealed kernels take (they are
+    // depth-specialised kernels: MTTS_GEMM_DEPTH=0 switches them off as well)
+    if (const char* g = getenv("MTTS_W_SEAL")) e->w_seal = std::min(std::max(atoi(g), 0), 2);
+    if (const char* g = getenv("MTTS_W_SEAL_HEAD")) e->w_seal_head = atoi(g) != 0;
+    if (!e->f32 && e->w_seal && e->gemm_depth) {
+        const int Hp = round_up(H, 32);
+        const auto wanted = [&](int kind) { return e->w_seal == 2 || WSEAL_MAX_UNSEALED[kind] >= 0.0; };
+        if (wanted(WSEAL_GU) && wseal_shape(e->p_gu, H, 2 * I, EPI_SILU)) e->wseal_ktw[WSEAL_GU] = e->p_gu.kt_per_wave;
+        if (wanted(WSEAL_DOWN) && wseal_shape(e->p_d, I, Hp, EPI_PARTIAL)) e->wseal_ktw[WSEAL_DOWN] = e->p_d.kt_per_wave;
+        if (wanted(WSEAL_HEAD0) && wseal_shape(e->p_h0, H, e->V0_pad, EPI_BF16)) e->wseal_ktw[WSEAL_HEAD0] = e->p_h0.kt_per_wave;
+        if (wanted(WSEAL_HEADS) && wseal_shape(e->p_h17, H, 7 * e->Vs_pad, EPI_BF16)) e->wseal_ktw[WSEAL_HEADS] = e->p_h17.kt_per_wave;
+        for (auto& l : e->layers) {
+            if (e->wseal_ktw[WSEAL_GU]) TRY(m.get((uint8_t**)&l.wgu_s, wseal_bytes(2 * I, H, e->wseal_ktw[WSEAL_GU])));
+            if (e->wseal_ktw[WSEAL_DOWN]) TRY(m.get((uint8_t**)&l.wd_s, wseal_bytes(Hp, I, e->wseal_ktw[WSEAL_DOWN])));
+        }
+        if (e->wseal_ktw[WSEAL_HEAD0]) TRY(m.get((uint8_t**)&e->head0_s, wseal_bytes(e->V0_pad, H, e->wseal_ktw[WSEAL_HEAD0])));
+        if (e->wseal_ktw[WSEAL_HEADS]) TRY(m.get((uint8_t**)&e->heads17_s, wseal_bytes(7 * e->Vs_pad, H, e->wseal_ktw[WSEAL_HEADS])));
+        TRY(m.get(&e->d_wseal_cnt, (size_t)WSEAL_KINDS * 2));
+        TRY(m.get_pinned(&e->h_wseal_cnt, (size_t)WSEAL_KINDS * 2));
+        // the zeroed twins are the sealed form of the zeroed bf16 arrays (padding rows, a matrix not yet bound)
+        e->wseal_dirty = true;
+    }
     // activations hold a whole prefill pass (MTTS_PFCAP rows); split-K slabs: up to 8 of [MTTS_PFCAP][Npad] fp32
     size_t pmax = (size_t)8 * std::max(e->qkv_rows, round_up(H, 32));
     if (!e->f32) {
@@ -297,7 +319,15 @@ struct WeightSlot {
     int bit = 0;
     bool proj = false;               // one of a layer's seven projection matrices (what a LoRA adapter may target)
     int layer = -1, proj_idx = -1;   // ... and which: layer, 0..6 = q k v o gate up down (the adapter bank's order)
+    void* seal_to = nullptr;         // bf16: the packed matrix's sealed twin (gemm_sealed.hip), re-made by every bind ...
+    int seal_ktw = 0, seal_nt0 = 0, seal_nt = 0;     // ... for the N-tiles the source rows land in
 };
+// after a bind wrote w.pack_to: the same stream re-seals the tiles it touched; the counts are taken at mtts_weights_ready
+static void reseal(MttsEngine* e, const WeightSlot& w, hipStream_t st) {
+    if (!w.seal_to) return;
+    launch_wseal(w.pack_to, w.seal_to, (int)w.cols, w.seal_ktw, w.seal_nt0, w.seal_nt, st);
+    e->wseal_dirty = true;
+}
 
 static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
     const std::string name(name_c);
@@ -311,6 +341,9 @@ static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
         w.pack_to = ch == 0 ? e->head0 : e->heads17;
         w.rows_pad = ch == 0 ? e->V0_pad : 7 * e->Vs_pad;
         w.row_off = ch == 0 ? 0 : (ch - 1) * e->Vs_pad;
+        w.seal_to = ch == 0 ? e->head0_s : e->heads17_s;
+        w.seal_ktw = e->wseal_ktw[ch == 0 ? WSEAL_HEAD0 : WSEAL_HEADS];
+        w.seal_nt0 = w.row_off / 32; w.seal_nt = (ch == 0 ? e->V0_pad : e->Vs_pad) / 32;
         w.bound = &e->emb_bound; w.bit = 1 << ch;
         return MTTS_OK;
     }
@@ -347,6 +380,9 @@ static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
             w.bound = &l.bound; w.bit = 1 << i;       // a complete layer has all 11 bits: 2047 (mtts_weights_ready)
             w.proj = t[i].cols != 1;
             w.layer = n; w.proj_idx = i - 4;
+            if (t[i].bf == l.wgu) { w.seal_to = l.wgu_s; w.seal_ktw = e->wseal_ktw[WSEAL_GU]; }      // (gate and up rows interleave: every tile)
+            if (t[i].bf == l.wd) { w.seal_to = l.wd_s; w.seal_ktw = e->wseal_ktw[WSEAL_DOWN]; }
+            w.seal_nt0 = 0; w.seal_nt = w.rows_pad / 32;
             return MTTS_OK;
         }
     return fail(MTTS_EINVAL, "unknown tensor %s", name_c);
@@ -369,6 +405,7 @@ int32_t mtts_bind_weight(MttsEngine* e, const char* name_c, const void* src, int
     } else {
         if (w.copy_to) HIPCHK(hipMemcpyAsync(w.copy_to, src, n * 2, hipMemcpyDeviceToDevice, st));
         if (w.pack_to) launch_pack_weight(src, w.pack_to, (int)w.rows, (int)w.cols, w.rows_pad, w.row_mul, w.row_off, st);
+        reseal(e, w, st);
         HIPCHK(hipGetLastError());
     }
     *w.bound |= w.bit;
@@ -396,8 +433,10 @@ int32_t mtts_bind_weight_lora(MttsEngine* e, const char* name_c, const void* bas
     if (e->f32)
         launch_lora_rows_f32((const float*)base, lora_a, lora_b, r, scaling, w.f32_to + w.f32_row * w.cols, (int)w.rows, (int)w.cols,
                              e->h16 ? 1 : 0, st);
-    else
+    else {
         launch_lora_pack(base, lora_a, lora_b, r, scaling, w.pack_to, (int)w.rows, (int)w.cols, w.row_mul, w.row_off, st);
+        reseal(e, w, st);
+    }
     HIPCHK(hipGetLastError());
     *w.bound |= w.bit;
     return MTTS_OK;
@@ -556,6 +595,35 @@ int32_t mtts_bind_rope(MttsEngine* e, const void* cosb, const void* sinb, int32_
     return bind_rope_tables(e, e->rope_cos, e->rope_sin, cosb, sinb, rows, S(stream));
 }
 
+// Sealed weight streams: after a bind, count every kind's groups and those that did not seal (from the twins' dictionary
+// units; the binds' streams are drained first) and decide which kinds the decode GEMMs read sealed.  Nothing per step.
+static int wseal_policy(MttsEngine* e) {
+    if (!e->wseal_dirty || !e->d_wseal_cnt) return MTTS_OK;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemsetAsync(e->d_wseal_cnt, 0, WSEAL_KINDS * 2 * sizeof(unsigned long long), nullptr));
+    const int H = e->H, I = e->I, Hp = round_up(H, 32);
+    for (auto& l : e->layers) {
+        if (l.wgu_s) launch_wseal_count(l.wgu_s, 2 * I, H, e->wseal_ktw[WSEAL_GU], e->d_wseal_cnt + 2 * WSEAL_GU, nullptr);
+        if (l.wd_s) launch_wseal_count(l.wd_s, Hp, I, e->wseal_ktw[WSEAL_DOWN], e->d_wseal_cnt + 2 * WSEAL_DOWN, nullptr);
+    }
+    if (e->head0_s) launch_wseal_count(e->head0_s, e->V0_pad, H, e->wseal_ktw[WSEAL_HEAD0], e->d_wseal_cnt + 2 * WSEAL_HEAD0, nullptr);
+    if (e->heads17_s) launch_wseal_count(e->heads17_s, 7 * e->Vs_pad, H, e->wseal_ktw[WSEAL_HEADS], e->d_wseal_cnt + 2 * WSEAL_HEADS, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(e->h_wseal_cnt, e->d_wseal_cnt, WSEAL_KINDS * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    bool changed = false;
+    for (int k = 0; k < WSEAL_KINDS; ++k) {
+        const unsigned long long groups = e->h_wseal_cnt[2 * k], bad = e->h_wseal_cnt[2 * k + 1];
+        const char on = e->wseal_ktw[k] && groups && (e->w_seal == 2 || (double)bad <= WSEAL_MAX_UNSEALED[k] * (double)groups);
+        changed |= on != e->wseal_on[k];
+        e->wseal_on[k] = on;
+    }
+    if (changed) drop_graphs(e);                     // captured steps hold the old choice of kernels
+    e->wseal_dirty = false;
+    return MTTS_OK;
+}
+
 int32_t mtts_weights_ready(MttsEngine* e) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     if (e->emb_bound != 0xff) return fail(MTTS_ESTATE, "embedding tables missing (mask %x)", e->emb_bound);
@@ -563,7 +631,7 @@ int32_t mtts_weights_ready(MttsEngine* e) {
     if (!e->rope_rows) return fail(MTTS_ESTATE, "rope table missing");
     for (int n = 0; n < e->L; ++n)
         if (e->layers[n].bound != 2047) return fail(MTTS_ESTATE, "layer %d incomplete (mask %x)", n, e->layers[n].bound);
-    return MTTS_OK;
+    return wseal_policy(e);
 }
 
 // ---- profiling helpers ------------------------------------------------------------
@@ -713,6 +781,8 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
             launch_lora_delta(xp, d_meta, e->d_seq_adapter, e->d_bank + (size_t)n * 7, job, e->partial + (size_t)ks * MTTS_PFCAP * job.Npad, R, st);
         };
         const int ex = lora ? 1 : 0;                     // slabs the consumers sum beyond the GEMM's
+        // one row tile without adapters: gate/up and down_proj read their sealed twins where the policy says so (same bits)
+        const bool sealed_gu = !lora && e->wseal_on[WSEAL_GU], sealed_d = !lora && e->wseal_on[WSEAL_DOWN];
         const int ks_qkv = tiled ? mtts_tile_ksplit(e->qkv_rows, H, 1024) : e->p_qkv.ksplit;
         const int ks_o = tiled ? mtts_tile_ksplit(Hp, nq * MTTS_HD, 1024) : e->p_o.ksplit;
         const int ks_d = tiled ? mtts_tile_ksplit(Hp, I, 1024) : e->p_d.ksplit;
@@ -736,13 +806,15 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
         const int gu_epi = lora ? EPI_PARTIAL : EPI_SILU;
         float* gu_slab = lora ? e->partial : nullptr;
         if (tiled) launch_gemm_tile(gu_epi, R, 1, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
-        else launch_gemm(gu_epi, mb, e->p_gu, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
+        else if (!sealed_gu || !launch_gemm_sealed(EPI_SILU, mb, e->p_gu, l.wgu_s, l.wgu, e->xn, H, 2 * I, 2 * I, nullptr, (uint16_t*)e->act_p, 0, st))
+            launch_gemm(gu_epi, mb, e->p_gu, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
         if (lora) {
             delta(j_gu, e->xn, 1);
             launch_swiglu_slabs(e->partial, e->partial + (size_t)MTTS_PFCAP * 2 * I, e->act_p, mb * 32, I, st);
         }
         if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
-        else launch_gemm(EPI_PARTIAL, mb, e->p_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
+        else if (!sealed_d || !launch_gemm_sealed(EPI_PARTIAL, mb, e->p_d, l.wd_s, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, 0, st))
+            launch_gemm(EPI_PARTIAL, mb, e->p_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
         if (lora) delta(j_d, e->act_p, ks_d);
         const bool lastl = (n == e->L - 1);
         const void* nw = lastl ? e->final_norm : e->layers[n + 1].ln_in;
@@ -758,8 +830,12 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
             launch_pack_rows(e->hlast, e->xh, e->B, H, hmb, st);
             xin = e->xh;
         }
-        launch_gemm(EPI_BF16, hmb, e->p_h0, e->head0, xin, H, e->V0_pad, e->V0, nullptr, (uint16_t*)e->logits0, st);
-        launch_gemm(EPI_BF16, hmb, e->p_h17, e->heads17, xin, H, 7 * e->Vs_pad, 7 * e->Vs_pad, nullptr, (uint16_t*)e->logits17, st);
+        if (lora || !e->wseal_on[WSEAL_HEAD0] ||
+            !launch_gemm_sealed(EPI_BF16, hmb, e->p_h0, e->head0_s, e->head0, xin, H, e->V0_pad, e->V0, nullptr, (uint16_t*)e->logits0, e->w_seal_head, st))
+            launch_gemm(EPI_BF16, hmb, e->p_h0, e->head0, xin, H, e->V0_pad, e->V0, nullptr, (uint16_t*)e->logits0, st);
+        if (lora || !e->wseal_on[WSEAL_HEADS] ||
+            !launch_gemm_sealed(EPI_BF16, hmb, e->p_h17, e->heads17_s, e->heads17, xin, H, 7 * e->Vs_pad, 7 * e->Vs_pad, nullptr, (uint16_t*)e->logits17, e->w_seal_head, st))
+            launch_gemm(EPI_BF16, hmb, e->p_h17, e->heads17, xin, H, 7 * e->Vs_pad, 7 * e->Vs_pad, nullptr, (uint16_t*)e->logits17, st);
     }
     HIPCHK(hipGetLastError());
     return MTTS_OK;

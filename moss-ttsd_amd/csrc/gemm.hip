@@ -11,6 +11,7 @@
 // With v_mfma_f32_32x32x16_bf16, A = W tile (32 n x 16 k), B = X^T (16 k x 32
 // rows): D[n][row], lane holds column `row = lane&31` and 16 n values.
 #include "launch.h"
+#include "gemm_epi.h"
 
 
 // grid = (N/32, ksplit); block = WAVES*64.  MB = row tiles (of 32) that share the weight stream.
@@ -114,29 +115,6 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_kernel(
 // which the compiler's counted waits let start as tile i lands.  Same wave -> k-tile assignment, same order of
 // products into one accumulator, same LDS reduction in wave order, same epilogues as gemm_skinny_kernel: same bits.
 // ---------------------------------------------------------------------------------------------------
-template <int EPI>
-__device__ __forceinline__ void skinny_store(const float (&v)[4], int row, int n0, int ks, float* __restrict__ partial,
-                                             uint16_t* __restrict__ out, int Npad, int n_valid) {
-    if (EPI == EPI_PARTIAL) {
-        *(float4*)(partial + ((size_t)ks * MTTS_PFCAP + row) * Npad + n0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else if (EPI == EPI_BF16) {
-        uint16_t* o = out + (size_t)row * Npad + n0;
-        if (n0 + 3 < n_valid) *(u32x2_t*)o = u32x2_t{pack2(v[0], v[1]), pack2(v[2], v[3])};
-        else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (n0 + j < n_valid) o[j] = f2bf(v[j]);
-        }
-    } else {                                                   // SwiGLU, rounding points and layout of gemm_skinny_kernel
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            float g = rbf(v[2 * j]), u = rbf(v[2 * j + 1]);
-            float a = rbf(g / (1.0f + expf(-g)));
-            out[xpack_off(row, (n0 >> 1) + j, Npad >> 1)] = f2bf(a * u);
-        }
-    }
-}
-
 // grid = (N/32, ksplit); block = WAVES*64; requires KT == ksplit * WAVES * KTW (no wave has a short or empty range).
 template <int WAVES, int KTW, int EPI>
 __global__ __launch_bounds__(WAVES * 64) void gemm_depth_kernel(
@@ -626,6 +604,7 @@ static void launch_gemm_mb(int mb, const GemmPlan& p, const void* Wp, const void
 // split (every wave owns exactly KTW k-tiles).  Returns false for every other call: the caller runs gemm_skinny_kernel.
 static long long g_depth_launches = 0;      // launches that took a depth-specialised kernel (test hook: mtts_debug_gemm_depth_launches)
 long long mtts_gemm_depth_launches() { return g_depth_launches; }
+void mtts_gemm_depth_note() { ++g_depth_launches; }      // (gemm_sealed.hip: its kernels are depth-specialised ones reading the sealed twin)
 static bool launch_gemm_depth(int epi, int mb, const GemmPlan& p, const void* Wp, const void* Xp, int K, int Npad,
                               int n_valid, float* partial, uint16_t* out, hipStream_t st) {
     const int KT = K / 16;

@@ -863,3 +863,140 @@ int32_t mtts_k_gemm_bench(int32_t N, int32_t K, int32_t epi, int32_t ksplit, int
     hipEventDestroy(e0); hipEventDestroy(e1);
     return MTTS_OK;
 }
+
+// ---- sealed weight streams (gemm_sealed.hip) ----------------------------------------------------------------------------
+int64_t mtts_debug_wseal_launches(void) { return (int64_t)mtts_wseal_launches(); }
+
+// out12 = per kind (gate/up, down_proj, head 0, heads 1-7): {groups, groups not sealed, 1 if the decode GEMMs read the twin},
+// as of the last mtts_weights_ready (which this call runs: MTTS_ESTATE from it when a tensor is missing)
+int32_t mtts_debug_wseal_stats(MttsEngine* e, int64_t* out12) {
+    if (!e || !out12) return fail(MTTS_EINVAL, "null argument");
+    if (!e->d_wseal_cnt) return fail(MTTS_ESTATE, "the engine keeps no sealed weights (fp32 / fp16 engine, MTTS_W_SEAL=0 or MTTS_GEMM_DEPTH=0)");
+    TRY(mtts_weights_ready(e));
+    for (int k = 0; k < WSEAL_KINDS; ++k) {
+        out12[3 * k] = (int64_t)e->h_wseal_cnt[2 * k];
+        out12[3 * k + 1] = (int64_t)e->h_wseal_cnt[2 * k + 1];
+        out12[3 * k + 2] = e->wseal_on[k];
+    }
+    return MTTS_OK;
+}
+
+// The bind-time sealer on a packed weight array of `ntiles` N-tiles: groups of ktw (16 or 12) k-tiles -> 13 or 10 units each.
+int32_t mtts_k_wseal(const void* dev_packed, int32_t ntiles, int32_t K, int32_t ktw, void* dev_sealed, void* stream) {
+    if (!dev_packed || !dev_sealed || ntiles < 1 || (ktw != 16 && ktw != 12) || K < 16 * ktw || K % (16 * ktw))
+        return fail(MTTS_EINVAL, "wseal: need ktw 16 or 12 and K a multiple of 16 ktw");
+    launch_wseal(dev_packed, dev_sealed, K, ktw, 0, ntiles, S(stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(S(stream)));
+    return MTTS_OK;
+}
+
+static int wseal_hook_plan(int epi, int N, int K, int ksplit, GemmPlan* p, int* Npad) {
+    if (epi != EPI_PARTIAL && epi != EPI_BF16 && epi != EPI_SILU) return fail(MTTS_EINVAL, "gemm_sealed: epi 0 (partial), 1 (bf16) or 2 (SwiGLU)");
+    if (N < 1 || K < 16 || K % 16 || ksplit < 1) return fail(MTTS_EINVAL, "gemm_sealed: bad shape");
+    *Npad = round_up(N, 32);
+    *p = mtts_plan_gemm_forced(*Npad, K, ksplit, 8);
+    if (!wseal_shape(*p, K, *Npad, epi)) return fail(MTTS_EINVAL, "gemm_sealed: not a shape the sealed kernels take (8 waves of 16 k-tiles, or 12 with split-K; SwiGLU: N %% 96 == 0)");
+    if (epi == EPI_SILU && N != *Npad) return fail(MTTS_EINVAL, "gemm_sealed: SwiGLU takes whole tiles");
+    return MTTS_OK;
+}
+
+// One decode GEMM of 1 <= M <= 32 rows through the sealed kernel (sealed != 0; head_form as launch_gemm_sealed) or through
+// launch_gemm on the same packed array (sealed == 0): W [N][K] and X [M][K] bf16 row-major.  dev_out receives the kernel's
+// raw output, which starts as 0xa5 bytes: epi 0 fp32 [ksplit][32][Npad]; 1 bf16 [32][Npad] (columns >= N keep the sentinel);
+// 2 bf16 32 * Npad / 2 in the X-fragment layout.  out2 = {groups, groups not sealed}.
+int32_t mtts_k_gemm_sealed(const void* dev_w, const void* dev_x, void* dev_out, int32_t M, int32_t N, int32_t K, int32_t epi,
+                           int32_t ksplit, int32_t sealed, int32_t head_form, int64_t* out2, void* stream) {
+    if (!dev_w || !dev_x || !dev_out || M < 1 || M > 32) return fail(MTTS_EINVAL, "gemm_sealed: null argument or M outside 1..32");
+    GemmPlan p;
+    int Npad = 0;
+    TRY(wseal_hook_plan(epi, N, K, ksplit, &p, &Npad));
+    hipStream_t st = S(stream);
+    DevBufs hb;
+    uint16_t *wp = nullptr, *xp = nullptr, *out = nullptr;
+    uint8_t* ws = nullptr;
+    float* part = nullptr;
+    unsigned long long* cnt = nullptr;
+    const int ktw = p.kt_per_wave;
+    TRY(hb.get(&wp, (size_t)Npad * K));
+    TRY(hb.get(&ws, wseal_bytes(Npad, K, ktw)));
+    TRY(hb.get(&xp, (size_t)32 * K));
+    TRY(hb.get(&out, (size_t)32 * Npad, false));
+    TRY(hb.get(&cnt, 2));
+    if (epi == EPI_PARTIAL) {
+        TRY(hb.get(&part, (size_t)ksplit * MTTS_PFCAP * Npad, false));
+        HIPCHK(hipMemsetAsync(part, 0xa5, (size_t)ksplit * MTTS_PFCAP * Npad * 4, st));
+    }
+    HIPCHK(hipMemsetAsync(out, 0xa5, (size_t)32 * Npad * 2, st));
+    launch_pack_weight(dev_w, wp, N, K, Npad, 1, 0, st);
+    launch_wseal(wp, ws, K, ktw, 0, Npad / 32, st);
+    launch_wseal_count(ws, Npad, K, ktw, cnt, st);
+    launch_pack_rows(dev_x, xp, M, K, 1, st);
+    if (sealed) {
+        if (!launch_gemm_sealed(epi, 1, p, ws, wp, xp, K, Npad, N, part, out, head_form, st)) return fail(MTTS_EINVAL, "gemm_sealed: the sealed launch was refused");
+    } else launch_gemm(epi, 1, p, wp, xp, K, Npad, N, part, out, st);
+    HIPCHK(hipGetLastError());
+    if (epi == EPI_PARTIAL) {
+        for (int ks = 0; ks < ksplit; ++ks)
+            HIPCHK(hipMemcpyAsync((float*)dev_out + (size_t)ks * 32 * Npad, part + (size_t)ks * MTTS_PFCAP * Npad, (size_t)32 * Npad * 4, hipMemcpyDeviceToDevice, st));
+    } else HIPCHK(hipMemcpyAsync(dev_out, out, (size_t)32 * (epi == EPI_SILU ? Npad / 2 : Npad) * 2, hipMemcpyDeviceToDevice, st));
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(h, cnt, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (out2) { out2[0] = (int64_t)h[0]; out2[1] = (int64_t)h[1]; }
+    return MTTS_OK;
+}
+
+// Measurement hook: mtts_k_gemm_bench's launch train over `copies` packed copies of W [N][K] (dev_w null: every value
+// 0x3c3c), sealed != 0 through the sealed kernel and its twins, else through launch_gemm on the bf16 arrays.
+int32_t mtts_k_gemm_sealed_bench(const void* dev_w, int32_t N, int32_t K, int32_t epi, int32_t ksplit, int32_t copies, int32_t iters,
+                                 int32_t sealed, int32_t head_form, float* avg_us, int64_t* out2) {
+    if (copies < 1 || iters < 1 || !avg_us) return fail(MTTS_EINVAL, "gemm_sealed_bench: bad argument");
+    GemmPlan p;
+    int Npad = 0;
+    TRY(wseal_hook_plan(epi, N, K, ksplit, &p, &Npad));
+    DevBufs hb;
+    const int ktw = p.kt_per_wave;
+    std::vector<uint16_t*> w(copies, nullptr);
+    std::vector<uint8_t*> ws(copies, nullptr);
+    unsigned long long* cnt = nullptr;
+    TRY(hb.get(&cnt, 2));
+    for (int c = 0; c < copies; ++c) {
+        TRY(hb.get(&w[c], (size_t)Npad * K));
+        if (dev_w) launch_pack_weight(dev_w, w[c], N, K, Npad, 1, 0, nullptr);
+        else HIPCHK(hipMemset(w[c], 0x3c, (size_t)Npad * K * 2));
+        TRY(hb.get(&ws[c], wseal_bytes(Npad, K, ktw)));
+        launch_wseal(w[c], ws[c], K, ktw, 0, Npad / 32, nullptr);
+    }
+    launch_wseal_count(ws[0], Npad, K, ktw, cnt, nullptr);
+    uint16_t *x = nullptr, *out = nullptr;
+    float* part = nullptr;
+    TRY(hb.get(&x, (size_t)32 * K, false));
+    HIPCHK(hipMemset(x, 0x3c, (size_t)32 * K * 2));
+    TRY(hb.get(&out, (size_t)32 * Npad));
+    if (epi == EPI_PARTIAL) TRY(hb.get(&part, (size_t)ksplit * MTTS_PFCAP * Npad));
+    HIPCHK(hipGetLastError());
+    bool refused = false;
+    auto go = [&](int i) {
+        if (!sealed) launch_gemm(epi, 1, p, w[i % copies], x, K, Npad, N, part, out, nullptr);
+        else if (!launch_gemm_sealed(epi, 1, p, ws[i % copies], w[i % copies], x, K, Npad, N, part, out, head_form, nullptr)) refused = true;
+    };
+    for (int i = 0; i < copies; ++i) go(i);
+    HIPCHK(hipDeviceSynchronize());
+    if (refused) return fail(MTTS_EINVAL, "gemm_sealed_bench: the sealed launch was refused");
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) go(i);
+    hipEventRecord(e1, nullptr);
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    *avg_us = ms * 1000.f / iters;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(hipMemcpy(h, cnt, 16, hipMemcpyDeviceToHost));
+    if (out2) { out2[0] = (int64_t)h[0]; out2[1] = (int64_t)h[1]; }
+    HIPCHK(hipGetLastError());
+    return MTTS_OK;
+}

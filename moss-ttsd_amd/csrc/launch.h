@@ -26,9 +26,22 @@ int mtts_small_lds_bytes(const GemmPlan& p, int K, int pro);
 void launch_gemv_small(int epi, int pro, const GemmPlan& p, const void* Wp, int K, int Npad, int n_valid, float* partial,
                        uint16_t* out, const SmallPro& pr, hipStream_t st);
 long long mtts_gemm_depth_launches();
+void mtts_gemm_depth_note();
 void launch_pack_weight(const void* src, void* dst, int rows, int cols, int rows_pad, int row_mul, int row_off, hipStream_t st);
 void launch_pack_rows(const void* src, void* dst, int R, int K, int tiles, hipStream_t st);
 void launch_reduce_partial_bf16(const float* partial, void* out, int ksplit, int Npad, int n_valid, int R, hipStream_t st);
+
+// ---- gemm_sealed.hip ------------------------------------------------------------------------------------------------
+// The sealed twin of a packed weight array, for the decode shapes whose waves own 16 or 12 k-tiles (gate/up, the heads;
+// down_proj).  wseal_shape: the plan / shape is one the sealed kernels take, and kt_per_wave is its group size.
+enum { WSEAL_GU = 0, WSEAL_DOWN = 1, WSEAL_HEAD0 = 2, WSEAL_HEADS = 3, WSEAL_KINDS = 4 };
+bool wseal_shape(const GemmPlan& p, int K, int Npad, int epi);
+size_t wseal_bytes(int Npad, int K, int ktw);
+void launch_wseal(const void* Wp, void* Ws, int K, int ktw, int nt0, int ntiles, hipStream_t st);     // N-tiles nt0 .. nt0 + ntiles - 1
+void launch_wseal_count(const void* Ws, int Npad, int K, int ktw, unsigned long long* out2, hipStream_t st);   // out2 += {groups, not sealed}
+bool launch_gemm_sealed(int epi, int mb, const GemmPlan& p, const void* Ws, const void* Wp, const void* Xp, int K, int Npad,
+                        int n_valid, float* partial, uint16_t* out, int head_form, hipStream_t st);
+long long mtts_wseal_launches();
 
 // ---- layer.hip ------------------------------------------------------------------------------------------------------
 void launch_embed_norm(const int32_t* tokens, const RowMeta* meta, const uint16_t* const* tables, const void* norm_w,

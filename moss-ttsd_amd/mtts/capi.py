@@ -107,6 +107,11 @@ _SIGS = {
     "mtts_k_gemm_bf16": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p]),
     "mtts_debug_gemm_depth_launches": (C.c_int64, []),
+    "mtts_debug_wseal_launches": (C.c_int64, []),
+    "mtts_debug_wseal_stats": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mtts_k_wseal": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mtts_k_gemm_sealed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_void_p]),
+    "mtts_k_gemm_sealed_bench": (C.c_int32, [C.c_void_p] + [C.c_int32] * 8 + [C.POINTER(C.c_float), C.c_void_p]),
     "mtts_debug_attn_row_launches": (C.c_int64, []),
     "mtts_k_attn_section": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 4 +
                             [C.c_int32] * 6 + [C.c_void_p] * 6),

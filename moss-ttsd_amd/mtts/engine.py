@@ -379,6 +379,15 @@ class Engine:
         capi.check(self.lib.mtts_debug_kv_pack_stats(self._h, o.ctypes.data))
         return dict(zip(("k_pages", "k_unsealed", "v_pages", "v_unsealed", "k_layers_on", "v_layers_on"), (int(x) for x in o)))
 
+    def wseal_stats(self):
+        """Sealed weight streams -> {kind: dict(groups, unsealed, on)} for gate_up, down, head0, heads17 (groups of 16 or 12
+        k-tiles x lanes; `unsealed` = a lane did not fit the 13-bit form, that wave reads its bf16 tiles; `on` = the decode
+        GEMMs of the kind read the sealed twin).  All tensors must be bound."""
+        o = np.zeros(12, dtype=np.int64)
+        capi.check(self.lib.mtts_debug_wseal_stats(self._h, o.ctypes.data))
+        return {k: dict(groups=int(o[3 * i]), unsealed=int(o[3 * i + 1]), on=bool(o[3 * i + 2]))
+                for i, k in enumerate(("gate_up", "down", "head0", "heads17"))}
+
     def debug_set_kv_len(self, n):
         capi.check(self.lib.mtts_debug_set_kv_len(self._h, int(n)))
 
