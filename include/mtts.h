@@ -200,6 +200,32 @@ int32_t mtts_read_generated(MttsEngine* e, int64_t* host_gen, int32_t capacity_s
 int32_t mtts_set_output_scores(MttsEngine* e, int32_t on);
 int32_t mtts_read_scores(MttsEngine* e, float* host_lp, int32_t capacity_steps, int32_t* n_steps);
 int32_t mtts_slot_read_scores(MttsEngine* e, int32_t slot, float* host_rows, int32_t capacity_steps, int32_t* n_steps);
+/* ---- top_logprobs of a generation: the model's own distribution at every decision (HF generate(output_logits=True)
+ * reduced to the chosen token and the k most probable ones; what mtts_score_topk is to a prompt) ----
+ * For step g, row r, channel c: L = the logits row the step's forward wrote, upcast to fp32, with the two hard-coded masks
+ * applied (modeling_asteroid.py:124-128 `next_token_logits`) and NO repetition penalty, temperature, top-k or top-p;
+ * d = the sampler's raw decision, the d of mtts_set_output_scores.
+ *   logp[g][r][c]        = log_softmax(L)[d]
+ *   top_ids[g][r][c][j], top_logp[g][r][c][j], j < k: the first k tokens of L by descending logit, ties by ascending id
+ *                          (-0 = +0), and their log_softmax(L)
+ * top_logp[..., j] is bit for bit the logp of a decision top_ids[..., j]; the first k' entries do not depend on k.  A slot
+ * whose appended token is not a model decision holds NaN (ids: -1): exactly the slots where mtts_read_scores holds NaN,
+ * and in the forced replay modes the values are taken at the engine's own decision, as there.  Sums run in a fixed order
+ * without atomics: values are run-to-run bit-identical, the same under graph replay and stream launches, and a function
+ * of (prompt, seed, row id) alone -- an evicted and re-run dialogue, a forked take (mtts_slot_fork copies nothing: values
+ * start at the first generated step) and a queued take reproduce them.  Switching it on changes no token and no lp.
+ * mtts_set_top_logprobs: sticky, k = 0 off (default) or 1..MTTS_SCORE_MAX_TOPK, else MTTS_EINVAL; read by the next
+ * mtts_begin / mtts_generate / mtts_sched_open; MTTS_ESTATE (setting unchanged) while a run is open, the rule of
+ * mtts_set_output_scores, of which it is independent.  Off, the step launches what it launched before and neither the
+ * scratch nor the buffers exist; they are allocated by the first run that asks and again when k changes.
+ * mtts_read_top_logprobs: host_logp float [capacity_steps][rows][8], host_top_ids int32 and host_top_logp float
+ * [capacity_steps][rows][8][k], the row space and step range of mtts_read_generated; MTTS_ESTATE when the run was started
+ * with k = 0.  mtts_slot_read_top_logprobs: scheduler mode, [steps][8] and [steps][8][k], like mtts_slot_read_scores. */
+int32_t mtts_set_top_logprobs(MttsEngine* e, int32_t k);
+int32_t mtts_read_top_logprobs(MttsEngine* e, float* host_logp, int32_t* host_top_ids, float* host_top_logp,
+                               int32_t capacity_steps, int32_t* n_steps);
+int32_t mtts_slot_read_top_logprobs(MttsEngine* e, int32_t slot, float* host_logp, int32_t* host_top_ids, float* host_top_logp,
+                                    int32_t capacity_steps, int32_t* n_steps);
 /* ---- teacher-forced scoring: the labels branch of AsteroidTTSInstruct.forward (modeling_asteroid.py:382-410: per channel
  * lm_heads[i](hidden_states) and ForCausalLMLoss) reduced to one float per label; what inference engines call prompt
  * log-probabilities.  host_input_ids int64 [B,T,8], host_attention_mask uint8 [B,T], host_labels int64 [B,T,8] (-100 =
@@ -502,6 +528,14 @@ int32_t mtts_k_sample_scores(const void* dev_logits_bf16, int32_t rows, int32_t 
                              const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
                              int32_t* dev_tokens, float* dev_logp, void* stream);
+/* The kernels of mtts_set_top_logprobs on bare logits, launched as the engine launches them (the slice pass and the merge
+ * when vocab > 4096, the single-block path otherwise): dev_logits [rows][vocab] bf16 bits, or fp32 when is_f32; mask_id
+ * the one id at -inf (-1: none); dev_decisions int32 [rows].  dev_logp float [rows] = log_softmax(L)[decision],
+ * dev_top_ids int32 and dev_top_logp float [rows][k].  rows <= 128, 1 <= k <= MTTS_SCORE_MAX_TOPK and k <= vocab,
+ * else MTTS_EINVAL; a decision outside [0, vocab) gives NaN in dev_logp.  Synchronous. */
+int32_t mtts_k_gen_topk(const void* dev_logits, int32_t is_f32, int32_t rows, int32_t vocab, int32_t mask_id,
+                        const int32_t* dev_decisions, int32_t k, float* dev_logp, int32_t* dev_top_ids, float* dev_top_logp,
+                        void* stream);
 
 /* ======================================================================================
  * XY_Tokenizer decode path (codes -> 24 kHz waveform), fp32.

@@ -129,6 +129,17 @@ static inline int alloc_lp_scratch(DevBufs& m, SampleScratch& sc, int rows) {
     TRY(m.get(&sc.lp, (size_t)rows * 8));
     return 0;
 }
+// top_logprobs scratch (gen_topk.hip: GenTopkScratch): only when asked for, again when k outgrows it
+static inline int alloc_gen_topk_scratch(DevBufs& m, GenTopkScratch& sc, int rows, int k) {
+    if (sc.kcap >= k) return 0;
+    m.release(sc.cand); m.release(sc.smax); m.release(sc.ssum);
+    sc.kcap = 0;
+    TRY(m.get(&sc.cand, (size_t)rows * SAMP_NS * k));
+    TRY(m.get(&sc.smax, (size_t)rows * SAMP_NS));
+    TRY(m.get(&sc.ssum, (size_t)rows * SAMP_NS));
+    sc.kcap = k;
+    return 0;
+}
 
 // ---- the engine ------------------------------------------------------------------------------------------------
 struct Layer {
@@ -222,6 +233,15 @@ struct MttsEngine {
     int scores_next = 0;                // mtts_set_output_scores: read by the next mtts_begin / mtts_generate / mtts_sched_open
     int scores_on = 0;                  // of the current run
     bool run_open = false;              // a run has begun and has not been seen to end (mtts_set_output_scores)
+    // top_logprobs (gen_topk.hip): raw log-probability of every decision [slot][gen_cap][8] and the k most probable tokens
+    // [slot][gen_cap][8][k] (ids, log-probabilities); scratch and buffers exist only once a run asked for them
+    GenTopkScratch gtscr;
+    float* d_gt_logp = nullptr;
+    int32_t* d_gt_ids = nullptr;
+    float* d_gt_tlp = nullptr;
+    int gt_cap = 0, gt_k = 0;           // gen_cap and k the three buffers were allocated for
+    int topk_next = 0;                  // mtts_set_top_logprobs: read by the next mtts_begin / mtts_generate / mtts_sched_open
+    int topk_on = 0;                    // k of the current run (0: off)
     // teacher-forced scoring (mtts_score; score.hip): allocated by the first call
     int32_t* d_sc_labels = nullptr;     // [staged rows][8]: the label of the row's NEXT position, -100 = none
     float* d_sc_logp = nullptr;         // [staged rows][8]
@@ -255,7 +275,7 @@ struct MttsEngine {
     uint64_t seed = 0;
     bool began = false, has_forced = false;
     // decode-step graphs: one captured step per (rows, KV page bound, ...) key, replayed by mtts_step
-    struct StepGraph { int B, pages, forced, ch0, scores, row, lora; hipGraphExec_t exec; };
+    struct StepGraph { int B, pages, forced, ch0, scores, topk, row, lora; hipGraphExec_t exec; };
     std::vector<StepGraph> graphs;
     hipStream_t cap_stream = nullptr;
     bool use_graphs = true;

@@ -885,6 +885,32 @@ static int start_scores(MttsEngine* e, hipStream_t st) {
     return 0;
 }
 
+// top_logprobs: the k of the run that starts now (0: off, nothing below exists or is touched).  The scratch grows with k,
+// the three buffers follow (gen_cap, k) -- k is their innermost stride -- and start as NaN / -1 (0xff bytes) in every slot
+static int start_top_logprobs(MttsEngine* e, hipStream_t st) {
+    e->topk_on = e->topk_next;
+    const int k = e->topk_on;
+    if (!k) return 0;
+    if (e->gtscr.kcap < k) {
+        drop_graphs(e);                  // (captured steps hold the scratch pointers by value)
+        TRY(alloc_gen_topk_scratch(e->mem, e->gtscr, e->cfg.max_batch, k));
+    }
+    const size_t n = (size_t)e->cfg.max_batch * e->gen_cap * 8;
+    if (!e->d_gt_logp || e->gt_cap != e->gen_cap || e->gt_k != k) {
+        e->mem.release(e->d_gt_logp); e->mem.release(e->d_gt_ids); e->mem.release(e->d_gt_tlp);
+        drop_graphs(e);                  // captured steps hold the old pointers
+        e->gt_cap = e->gt_k = 0;
+        TRY(e->mem.get(&e->d_gt_logp, n, false));
+        TRY(e->mem.get(&e->d_gt_ids, n * k, false));
+        TRY(e->mem.get(&e->d_gt_tlp, n * k, false));
+        e->gt_cap = e->gen_cap; e->gt_k = k;
+    }
+    HIPCHK(hipMemsetAsync(e->d_gt_logp, 0xff, n * sizeof(float), st));
+    HIPCHK(hipMemsetAsync(e->d_gt_ids, 0xff, n * k * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(e->d_gt_tlp, 0xff, n * k * sizeof(float), st));
+    return 0;
+}
+
 // staged rows (staging.h) into the prefill staging, which grows to hold them.  on_stream: asynchronously on `st`, which
 // the caller drains before `sr` dies (mtts_begin, mtts_score); else synchronously (mtts_slot_submit)
 static int upload_staged(MttsEngine* e, const StagedRows& sr, bool on_stream, hipStream_t st) {
@@ -1028,6 +1054,7 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
     // generation buffers
     TRY(ensure_gen_storage(e, max_steps));
     TRY(start_scores(e, st));
+    TRY(start_top_logprobs(e, st));
     StagedRows sr;
     TRY(stage_rows(seqs, e->V0, e->Vs, false, &sr));
     {
@@ -1087,17 +1114,23 @@ static int step_body(MttsEngine* e, int pages_bound, hipStream_t st, int64_t kvt
     launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
                   e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, e->B, e->sscr, e->ch0_sampled,
                   full_cap_for(e->V0), e->scores_on, st);
+    GenTopkOut gt;                       // top_logprobs: the raw distribution at the decisions just written, into this step's row
+    if (e->topk_on) {
+        gt = GenTopkOut{e->topk_on, e->d_gt_logp, e->d_gt_ids, e->d_gt_tlp};
+        launch_gen_topk(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_scfg, e->d_ls, e->d_seqs, e->d_decisions, e->B,
+                        e->gtscr, gt, st);
+    }
     launch_update(e->d_decisions, e->d_declog, e->has_forced ? e->d_forced : nullptr, e->d_tf, e->d_gen, e->d_cur,
                   e->d_seqs, e->d_meta, e->d_bitmaps, e->bm_words, e->d_ls, e->cfg.eos_token_id,
                   e->cfg.speech_pad_token, e->cfg.speech_range_lo, e->cfg.speech_range_hi,
-                  e->scores_on ? e->sscr.lp : nullptr, e->scores_on ? e->d_lp : nullptr, st);
+                  e->scores_on ? e->sscr.lp : nullptr, e->scores_on ? e->d_lp : nullptr, gt, st);
     return forward_rows(e, e->d_cur, e->d_meta, round_up(e->B, 32), pages_bound, 1, rows_carry_adapters(e), st, kvtok);
 }
 
 static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     const int forced = e->has_forced ? 1 : 0, row = attn_row_shape(e, pages) ? 1 : 0, lora = rows_carry_adapters(e) ? 1 : 0;
     for (auto& g : e->graphs)
-        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled && g.scores == e->scores_on && g.row == row &&
+        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled && g.scores == e->scores_on && g.topk == e->topk_on && g.row == row &&
             g.lora == lora) {
             *out = g.exec;
             return MTTS_OK;
@@ -1114,7 +1147,7 @@ static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     HIPCHK(ie);
-    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, e->scores_on, row, lora, exec});
+    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, e->scores_on, e->topk_on, row, lora, exec});
     *out = exec;
     return MTTS_OK;
 }
@@ -1193,35 +1226,35 @@ int32_t mtts_sync_state(MttsEngine* e, int32_t* steps_done, int32_t* all_finishe
     return MTTS_OK;
 }
 
-// `nslots` slots from `slot0` of a device array [slot][gen_cap][8] -> host [step][slot - slot0][8]
+// `nslots` slots from `slot0` of a device array [slot][gen_cap][w] -> host [step][slot - slot0][w] (w = 8, or 8 k: top_logprobs)
 template <typename Src, typename Dst>
-static int read_slots(MttsEngine* e, const Src* d_src, int slot0, int nslots, int steps, Dst* host) {
-    std::vector<Src> tmp((size_t)std::max(steps, 1) * 8);
+static int read_slots(MttsEngine* e, const Src* d_src, int slot0, int nslots, int steps, Dst* host, int w = 8) {
+    std::vector<Src> tmp((size_t)std::max(steps, 1) * w);
     for (int b = 0; b < nslots; ++b) {
-        if (steps) HIPCHK(hipMemcpy(tmp.data(), d_src + (size_t)(slot0 + b) * e->gen_cap * 8, (size_t)steps * 8 * sizeof(Src), hipMemcpyDeviceToHost));
+        if (steps) HIPCHK(hipMemcpy(tmp.data(), d_src + (size_t)(slot0 + b) * e->gen_cap * w, (size_t)steps * w * sizeof(Src), hipMemcpyDeviceToHost));
         for (int s = 0; s < steps; ++s)
-            for (int c = 0; c < 8; ++c) host[((size_t)s * nslots + b) * 8 + c] = tmp[(size_t)s * 8 + c];
+            for (int c = 0; c < w; ++c) host[((size_t)s * nslots + b) * w + c] = tmp[(size_t)s * w + c];
     }
     return MTTS_OK;
 }
 // every row of the run, all steps so far
 template <typename Src, typename Dst>
-static int read_rows(MttsEngine* e, const Src* d_src, Dst* host, int capacity_steps, int* n_steps) {
+static int read_rows(MttsEngine* e, const Src* d_src, Dst* host, int capacity_steps, int* n_steps, int w = 8) {
     const int steps = e->h_ls->step;
     if (steps > capacity_steps) return fail(MTTS_EINVAL, "output buffer holds %d steps, need %d", capacity_steps, steps);
-    TRY(read_slots(e, d_src, 0, e->B, steps, host));
+    TRY(read_slots(e, d_src, 0, e->B, steps, host, w));
     if (n_steps) *n_steps = steps;
     return MTTS_OK;
 }
 // one slot of a scheduler run, the steps its dialogue has run
 template <typename Src, typename Dst>
-static int slot_read(MttsEngine* e, const Src* d_src, int slot, Dst* host_rows, int capacity_steps, int* n_steps) {
+static int slot_read(MttsEngine* e, const Src* d_src, int slot, Dst* host_rows, int capacity_steps, int* n_steps, int w = 8) {
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipDeviceSynchronize());
     SeqState cur;
     HIPCHK(hipMemcpy(&cur, e->d_seqs + slot, sizeof(cur), hipMemcpyDeviceToHost));
     if (cur.step > capacity_steps) return fail(MTTS_EINVAL, "buffer holds %d steps, need %d", capacity_steps, cur.step);
-    TRY(read_slots(e, d_src, slot, 1, cur.step, host_rows));
+    TRY(read_slots(e, d_src, slot, 1, cur.step, host_rows, w));
     if (n_steps) *n_steps = cur.step;
     return MTTS_OK;
 }
@@ -1283,6 +1316,29 @@ int32_t mtts_read_scores(MttsEngine* e, float* host_lp, int32_t capacity_steps, 
     HIPCHK(hipSetDevice(e->device));
     TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
     return read_rows(e, e->d_lp, host_lp, capacity_steps, n_steps);
+}
+
+int32_t mtts_set_top_logprobs(MttsEngine* e, int32_t k) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    if (k < 0 || k > MTTS_SCORE_MAX_TOPK) return fail(MTTS_EINVAL, "top_logprobs must be 0 (off) or 1..%d (got %d)", MTTS_SCORE_MAX_TOPK, k);
+    if (k == e->topk_next) return MTTS_OK;
+    bool open = false;
+    TRY(run_still_open(e, &open));
+    if (open) return fail(MTTS_ESTATE, "top_logprobs cannot change while a run is open (it is read when a run begins)");
+    e->topk_next = k;
+    return MTTS_OK;
+}
+
+// host_logp float [capacity_steps][rows][8], host_top_ids int32 / host_top_logp float [capacity_steps][rows][8][k]
+int32_t mtts_read_top_logprobs(MttsEngine* e, float* host_logp, int32_t* host_top_ids, float* host_top_logp, int32_t capacity_steps,
+                               int32_t* n_steps) {
+    if (!e || !e->began || !host_logp || !host_top_ids || !host_top_logp) return fail(MTTS_ESTATE, "nothing generated");
+    if (!e->topk_on) return fail(MTTS_ESTATE, "the run was started with top_logprobs off (mtts_set_top_logprobs)");
+    HIPCHK(hipSetDevice(e->device));
+    TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
+    TRY(read_rows(e, e->d_gt_logp, host_logp, capacity_steps, n_steps));
+    TRY(read_rows(e, e->d_gt_ids, host_top_ids, capacity_steps, n_steps, 8 * e->topk_on));
+    return read_rows(e, e->d_gt_tlp, host_top_logp, capacity_steps, n_steps, 8 * e->topk_on);
 }
 
 // ---- teacher-forced scoring (the labels branch of AsteroidTTSInstruct.forward, modeling_asteroid.py:382-410) ---------
@@ -1574,6 +1630,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     if (gen_cap < 8) return fail(MTTS_EINVAL, "gen_cap too small");
     TRY(ensure_gen_storage(e, gen_cap));
     TRY(start_scores(e, st));
+    TRY(start_top_logprobs(e, st));
     e->B = B; e->steps_issued = 0; e->has_forced = false; e->continuous = true;
     e->max_steps = 1 << 30;
     e->n_real.assign(B, 0);
@@ -1793,6 +1850,16 @@ int32_t mtts_slot_read_scores(MttsEngine* e, int32_t slot, float* host_rows, int
     if (!e || !e->began || !host_rows || slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "bad argument");
     if (!e->scores_on) return fail(MTTS_ESTATE, "the run was started with output_scores off (mtts_set_output_scores)");
     return slot_read(e, e->d_lp, slot, host_rows, capacity_steps, n_steps);
+}
+
+// the same of one slot's generated rows: host_logp float [steps][8], host_top_ids int32 / host_top_logp float [steps][8][k]
+int32_t mtts_slot_read_top_logprobs(MttsEngine* e, int32_t slot, float* host_logp, int32_t* host_top_ids, float* host_top_logp,
+                                    int32_t capacity_steps, int32_t* n_steps) {
+    if (!e || !e->began || !host_logp || !host_top_ids || !host_top_logp || slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "bad argument");
+    if (!e->topk_on) return fail(MTTS_ESTATE, "the run was started with top_logprobs off (mtts_set_top_logprobs)");
+    TRY(slot_read(e, e->d_gt_logp, slot, host_logp, capacity_steps, n_steps));
+    TRY(slot_read(e, e->d_gt_ids, slot, host_top_ids, capacity_steps, n_steps, 8 * e->topk_on));
+    return slot_read(e, e->d_gt_tlp, slot, host_top_logp, capacity_steps, n_steps, 8 * e->topk_on);
 }
 
 // Frames first..first+n-1 of every sequence as codec codes int64 [8][B][n] on the device (delay pattern undone,

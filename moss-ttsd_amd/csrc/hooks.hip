@@ -422,6 +422,23 @@ int32_t mtts_k_sample_scores(const void* logits, int32_t rows, int32_t vocab, co
     return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, stream);
 }
 
+// The top_logprobs kernels of a decode step (gen_topk.hip) on bare logits, with a scratch of their own.
+int32_t mtts_k_gen_topk(const void* dev_logits, int32_t is_f32, int32_t rows, int32_t vocab, int32_t mask_id,
+                        const int32_t* dev_decisions, int32_t k, float* dev_logp, int32_t* dev_top_ids, float* dev_top_logp,
+                        void* stream) {
+    if (!dev_logits || !dev_decisions || !dev_logp || !dev_top_ids || !dev_top_logp) return fail(MTTS_EINVAL, "gen_topk: null argument");
+    if (rows < 1 || rows > MTTS_RCAP || vocab < 1 || k < 1 || k > MTTS_SCORE_MAX_TOPK || k > vocab || mask_id >= vocab)
+        return fail(MTTS_EINVAL, "gen_topk: rows 1..%d, 1 <= k <= min(%d, vocab), mask_id < vocab", MTTS_RCAP, MTTS_SCORE_MAX_TOPK);
+    hipStream_t st = S(stream);
+    DevBufs hb;
+    GenTopkScratch sc;
+    TRY(alloc_gen_topk_scratch(hb, sc, rows, k));
+    launch_gen_topk_single(dev_logits, is_f32 ? 1 : 0, rows, vocab, mask_id, dev_decisions, sc, GenTopkOut{k, dev_logp, dev_top_ids, dev_top_logp}, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
 // ---- per-kernel entry points for attention and RoPE / cache write (unit tests) ----------------------------------------
 
 // q/k/v epilogue of one token per row (qkv_post_kernel): dev_qkv bf16 [R][(nq+2*nkv)*128] = the three Linears' outputs,

@@ -140,11 +140,42 @@ void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, in
 void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
                           const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
                           int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp, hipStream_t st);
+// generate(top_logprobs=k): where a step's results go.  In the engine the per-slot buffers, laid out like gen: logp
+// [slot][gen_cap][8], ids / tlp [slot][gen_cap][8][k]; gen_topk_finish_kernel writes the step's row of every evaluated
+// dialogue, update_kernel<true> then puts NaN / -1 over the slots that are not model decisions, by the rule it applies
+// to lp.  k == 0: off, update_kernel<false> runs and looks at nothing here.
+struct GenTopkOut {
+    int32_t k = 0;
+    float* logp = nullptr;
+    int32_t* ids = nullptr;
+    float* tlp = nullptr;
+};
 void launch_update(const int32_t* decisions, int32_t* dec_log, const int32_t* forced, const int32_t* tf_tail,
                    int32_t* gen, int32_t* cur_tokens, SeqState* seqs, RowMeta* meta, uint32_t* bitmaps, int bm_words,
-                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out, hipStream_t st);
+                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out,
+                   const GenTopkOut& gt, hipStream_t st);
 void launch_export_codes(const int32_t* gen, int64_t* codes, int B, int first, int n, int speech_offset, int clamp_hi,
                          int cap, hipStream_t st);
+
+// ---- gen_topk.hip ---------------------------------------------------------------------------------------------------
+// generate(top_logprobs=k): per (row, channel) of a decode step, on the RAW logits row with the two hard-coded masks
+// applied (no penalty, temperature, top-k, top-p): logp[row][c] = log_softmax(L)[decisions[row][c]], and ids / tlp
+// [row][c][j], j < k, the first k tokens of L in the order of topk.h with their log_softmax(L).  A vocabulary above
+// SAMP_CAND goes through one pass over the row's SAMP_NS slices (gen_topk_slice_kernel) and a merge in slice order; a
+// smaller one is scanned by the finish block itself.  Rows the sampler does not evaluate are left alone (their slots keep
+// the NaN / -1 the buffers start with).
+struct GenTopkScratch {                  // exists only once a run asked for top_logprobs
+    unsigned long long* cand = nullptr;  // [rows][SAMP_NS][kcap] a slice's best (value, id) pairs, descending, 0 = none (stride: the run's k)
+    float* smax = nullptr;               // [rows][SAMP_NS] max of the slice's logits (-inf: nothing finite)
+    double* ssum = nullptr;              // [rows][SAMP_NS] sum of exp(l - smax) over the slice
+    int kcap = 0;
+};
+void launch_gen_topk(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const MttsSamplerCfg* cfgs,
+                     const LoopState* ls, const SeqState* seqs, const int32_t* decisions, int B, const GenTopkScratch& sc,
+                     const GenTopkOut& out, hipStream_t st);
+// one logits matrix [rows][vocab] (bf16 bits or fp32), decisions [rows]; out.logp [rows], out.ids / out.tlp [rows][k]
+void launch_gen_topk_single(const void* logits, int is_f32, int rows, int vocab, int mask_id, const int32_t* decisions,
+                            const GenTopkScratch& sc, const GenTopkOut& out, hipStream_t st);
 
 // ---- f32path.hip ----------------------------------------------------------------------------------------------------
 #define MTTS_PF32CAP 256       // rows of a prefill pass in the fp32 engine (bounds its fp32 score scratch)

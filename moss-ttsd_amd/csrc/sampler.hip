@@ -5,7 +5,8 @@
 //                   order, then argmax or a multinomial draw).
 // update_kernel   : reference modeling_asteroid.py:139-169 (EOS flush via
 //                   needs_additional_steps, teacher forcing of the delayed prompt
-//                   tail, finished-row padding, stopping criteria).
+//                   tail, finished-row padding, stopping criteria).  Also commits what the step keeps per decision:
+//                   lp (output_scores) and, as update_kernel<true>, the NaN slots of gen_topk.hip's results (top_logprobs).
 //
 // Draw definition (torch.multinomial's stream cannot be reproduced): Philox4x32-10,
 // key = seed, counter = (step, row, channel, 0), u = (x0 >> 8) * 2^-24; kept tokens
@@ -13,6 +14,7 @@
 // exp(score - max) exceeds u * total is taken.  oracle/asteroid_oracle.py
 // (sample_from_scores) states the same rule.
 #include "launch.h"
+#include "sample_ctx.h"       // LogitsPtr, SampleCtx, sample_ctx: shared with gen_topk.hip
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t* out) {
@@ -38,7 +40,6 @@ __device__ __forceinline__ uint32_t fkey(float f) {
 }
 
 // Processed score of token i (everything except top-k / top-p, which act on the set).
-struct LogitsPtr { const void* p; int f32; };     // one row of logits: bf16 bit patterns, or fp32 in the fp32 engine
 __device__ __forceinline__ float proc_score(LogitsPtr logits, int i, int mask_id,
                                             const uint32_t* __restrict__ bitmap, float penalty, float temperature) {
     if (i == mask_id) return -INFINITY;
@@ -63,52 +64,6 @@ __device__ __forceinline__ float proc_score(LogitsPtr logits, int i, int mask_id
 // first whose running sum of exp(score - max) exceeds u * total wins.
 // ---------------------------------------------------------------------------
 #define SAMP_T 256
-
-struct SampleCtx {         // resolved per (row, channel)
-    LogitsPtr lg;
-    const uint32_t* bm;
-    int V, mask_id, step, c;
-    float penalty, temp;
-    uint64_t seed;
-    uint32_t row_id;
-};
-
-__device__ __forceinline__ bool sample_ctx(SampleCtx& x, int b, int c_in, const uint16_t* logits0,
-                                           const uint16_t* logits17, int V0, int Vs, int Vs_pad,
-                                           const uint32_t* bitmaps, int bm_words, const MttsSamplerCfg* cfgs,
-                                           const LoopState* ls, const SeqState* seqs, int single_vocab, int single_mask,
-                                           int single_step, int single_channel) {
-    if (single_vocab > 0) {            // unit-test entry: one logits matrix [rows][vocab]
-        x.c = single_channel; x.step = single_step; x.V = single_vocab; x.mask_id = single_mask;
-        x.seed = 0; x.row_id = (uint32_t)b;
-        x.lg = LogitsPtr{logits0 + (size_t)b * x.V, 0};
-        x.bm = bitmaps ? bitmaps + (size_t)b * bm_words : nullptr;
-    } else {
-        if (ls->done) return false;
-        const SeqState sq = seqs[b];
-        // finished rows get padding from the state machine; a row that finished AT max_length without a flush behind it
-        // (active == 2) is still evaluated, as in the reference: see update_kernel
-        if (!sq.active || !(sq.unfinished || sq.active == 2)) return false;
-        x.c = c_in; x.step = sq.step;
-        x.seed = sq.seed; x.row_id = (uint32_t)sq.row_id;
-        x.V = (x.c == 0) ? V0 : Vs;
-        {
-            // channel-0 rows are padded to a multiple of 32 tokens (aligned rows: the head GEMM stores 8 bytes per lane)
-            const size_t off = (x.c == 0) ? (size_t)b * ((V0 + 31) & ~31) : ((size_t)b * 7 + (x.c - 1)) * Vs_pad;
-            const char* base = (const char*)((x.c == 0) ? logits0 : logits17);
-            x.lg = LogitsPtr{base + off * (ls->logits_f32 ? 4 : 2), ls->logits_f32};
-        }
-        // modeling_asteroid.py:124-128 (hard-coded ids 1024 / 152694 as in the reference)
-        x.mask_id = -1;
-        if (x.c != 0 && x.step >= x.c) x.mask_id = 1024;
-        if (x.c == 0 && x.step <= 6) x.mask_id = 152694;
-        x.bm = bitmaps ? bitmaps + ((size_t)b * 8 + x.c) * bm_words : nullptr;
-    }
-    const MttsSamplerCfg cfg = cfgs[x.c];
-    x.penalty = (x.bm && cfg.repetition_penalty > 0.f) ? cfg.repetition_penalty : 0.f;
-    x.temp = cfg.temperature;
-    return true;
-}
 
 __device__ __forceinline__ void argmax_merge(float& bv, int& bi, float ov, int oi) {
     if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
@@ -793,12 +748,15 @@ __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
 
 // One block; thread b handles sequence slot b.  Restates modeling_asteroid.py:139-169 with a per-dialogue clock.
 // gen / dec_log / forced: [slot][gen_cap][8]; tf_tail: [slot][7][8] = tf_inputs[:, base_length + s, :].
+// GT (generate(top_logprobs=k)): gen_topk.hip has written this step's row of gt.logp / gt.ids / gt.tlp for every evaluated
+// dialogue; this instantiation puts NaN / -1 over the slots that are not decisions.  The plain one does not look at `gt`.
+template <bool GT>
 __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __restrict__ dec_log,
                               const int32_t* __restrict__ forced, const int32_t* __restrict__ tf_tail,
                               int32_t* __restrict__ gen, int32_t* __restrict__ cur_tokens,
                               SeqState* __restrict__ seqs, RowMeta* __restrict__ meta, uint32_t* __restrict__ bitmaps,
                               int bm_words, LoopState* __restrict__ ls, int eos, int spad, int sp_lo, int sp_hi,
-                              const float* __restrict__ lp_in, float* __restrict__ lp_out) {
+                              const float* __restrict__ lp_in, float* __restrict__ lp_out, GenTopkOut gt) {
     __shared__ int any_unfinished;
     if (ls->done) return;
     const int b = threadIdx.x, B = ls->B;
@@ -860,12 +818,25 @@ __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __
             // output_scores (lp_out [slot][gen_cap][8], laid out like gen): the sampler's log-probability where the appended
             // token is the model's decision, NaN where teacher forcing, the EOS flush or finished-row padding replaced it.
             // The rule is the one applied to tok[] above; the replay hook (forced) has no part in it.
+            const bool flush = s.nas > 0 && s.nas < 7;
+            auto used = [&](int c) { return s.unfinished && !(step < 7 && c >= step + 1) && !(flush && (c == 0 || s.nas < 8 - c)); };
             if (lp_out) {
-                const bool flush = s.nas > 0 && s.nas < 7;
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const bool used = s.unfinished && !(step < 7 && c >= step + 1) && !(flush && (c == 0 || s.nas < 8 - c));
-                    lp_out[slot + c] = used ? lp_in[b * 8 + c] : __uint_as_float(0x7fc00000u);
+                for (int c = 0; c < 8; ++c) lp_out[slot + c] = used(c) ? lp_in[b * 8 + c] : __uint_as_float(0x7fc00000u);
+            }
+            // top_logprobs ([slot][gen_cap][8] and [slot][gen_cap][8][k]): the same rule.  Only an evaluated row has values to
+            // cover (the buffers start as NaN / -1), and on most steps every slot of it is a decision: nothing to do
+            if constexpr (GT) {
+                if (s.unfinished || linger) {
+#pragma unroll
+                    for (int c = 0; c < 8; ++c)
+                        if (!used(c)) {
+                            gt.logp[slot + c] = __uint_as_float(0x7fc00000u);
+                            for (int j = 0; j < gt.k; ++j) {
+                                gt.ids[(slot + c) * gt.k + j] = -1;
+                                gt.tlp[(slot + c) * gt.k + j] = __uint_as_float(0x7fc00000u);
+                            }
+                        }
                 }
             }
             if (dec_log && !as_draw) {
@@ -954,9 +925,10 @@ void launch_sample_single(const void* logits, int rows, int vocab, const uint32_
 }
 void launch_update(const int32_t* decisions, int32_t* dec_log, const int32_t* forced, const int32_t* tf_tail,
                    int32_t* gen, int32_t* cur_tokens, SeqState* seqs, RowMeta* meta, uint32_t* bitmaps, int bm_words,
-                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out, hipStream_t st) {
-    hipLaunchKernelGGL(update_kernel, dim3(1), dim3(MTTS_RCAP), 0, st, decisions, dec_log, forced, tf_tail, gen,
-                       cur_tokens, seqs, meta, bitmaps, bm_words, ls, eos, spad, sp_lo, sp_hi, lp_in, lp_out);
+                   LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out, const GenTopkOut& gt,
+                   hipStream_t st) {
+    hipLaunchKernelGGL(gt.k ? update_kernel<true> : update_kernel<false>, dim3(1), dim3(MTTS_RCAP), 0, st, decisions, dec_log, forced,
+                       tf_tail, gen, cur_tokens, seqs, meta, bitmaps, bm_words, ls, eos, spad, sp_lo, sp_hi, lp_in, lp_out, gt);
 }
 
 // Un-shift the delay pattern on the device (reference generation_utils.py:416-425):

@@ -19,64 +19,22 @@
 #include <math.h>
 
 #include "launch.h"
+#include "topk.h"
 
 // weight of a partial (max m, sum s) inside a merged maximum M: exp(m - M), 0 for an empty partial (m = -inf, whatever M)
 __device__ __forceinline__ float ce_scale(float m, float M) { return m == -INFINITY ? 0.f : expf(m - M); }
 
-// ---- top-k: the order "descending logit, ties by ascending column" as an unsigned compare --------------------------------
-// f32_sortable: a monotone map of the floats onto uint32 (-0 counts as +0: the two compare equal, so the column decides).
-__device__ __forceinline__ uint32_t f32_sortable(float v) {
-    uint32_t u = __float_as_uint(v);
-    u = u == 0x80000000u ? 0u : u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float f32_unsortable(uint32_t s) { return __uint_as_float((s & 0x80000000u) ? (s ^ 0x80000000u) : ~s); }
+// ---- top-k: the order "descending logit, ties by ascending column" as an unsigned compare (topk.h: f32_sortable, the 64-bit
+// pairs, wave_umax64, TopList) ----------------------------------------------------------------------------------------
 // A bf16 logit (the low 16 bits of its fp32 form are zero) and its column inside a 128-column block in one word: the larger
 // key is the better candidate, and 0 is below every key of a valid column.
 __device__ __forceinline__ uint32_t topk_key16(float v, int off) { return (f32_sortable(v) & 0xffff0000u) | (uint32_t)(127 - off); }
 // the logit of a key (or of its upper half): a negative value's 16 dropped bits were ones in the sortable form
 __device__ __forceinline__ float topk_key16_value(uint32_t key) { return f32_unsortable(key & 0x80000000u ? key & 0xffff0000u : key | 0xffffu); }
-// (value, column of the head) in 64 bits, the same order; 0 = nothing
-__device__ __forceinline__ uint64_t topk_pair(uint32_t sortable, int col) { return ((uint64_t)sortable << 32) | (uint32_t)~(uint32_t)col; }
-__device__ __forceinline__ int topk_pair_col(uint64_t c) { return c ? (int)~(uint32_t)c : -1; }
 __device__ __forceinline__ uint32_t umax_xor32(uint32_t v) {
     const u32x2s_t t = __builtin_amdgcn_permlane32_swap(v, v, false, false);
     return max(t.x, t.y);
 }
-// max over the wave, in every lane (an order-free reduction, like wave_max)
-__device__ __forceinline__ uint64_t wave_umax64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint64_t o = ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-// A thread's KL best pairs, descending, in registers: every index is a compile-time constant.
-template <int KL>
-struct TopList {
-    uint64_t v[KL];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int j = 0; j < KL; ++j) v[j] = 0;
-    }
-    __device__ __forceinline__ uint64_t last() const { return v[KL - 1]; }
-    __device__ __forceinline__ void insert(uint64_t c) {      // (c <= last() falls out again)
-#pragma unroll
-        for (int j = 0; j < KL; ++j) {
-            const bool gt = c > v[j];
-            const uint64_t t = gt ? v[j] : c;
-            v[j] = gt ? c : v[j];
-            c = t;
-        }
-    }
-    __device__ __forceinline__ void pop_if(bool own) {
-#pragma unroll
-        for (int j = 0; j + 1 < KL; ++j) v[j] = own ? v[j + 1] : v[j];
-        v[KL - 1] = own ? 0 : v[KL - 1];
-    }
-};
-
 // grid = (segments * blocks_per_seg, ceil(rtiles / 4)); block = 256 (2 x 2 waves, 64 rows x 64 columns each).
 // Wp: `segments` heads one after another, each tiles_per_seg 32-row tiles (head0: 1 segment; heads17: 7 of Vs_pad rows),
 // columns >= n_valid of a head are padding.  labels[row * lab_stride + lab_off + seg] (< 0: none), rows < rtiles * 32.
@@ -381,15 +339,6 @@ void launch_ce_rows_f32(const float* logits, long ldy, int R, int n_valid, const
 size_t head_topk_cand_elems(int rows, int n_valid, int segments, int k) {
     return (size_t)std::min(round_up32(rows), MTTS_SCORE_TOPK_ROWS) * segments * head_ce_blocks(n_valid) * k;
 }
-
-// list length of the finish kernels: the smallest of 1, 4, 8, 16 that holds k (the result does not depend on it)
-#define TOPK_DISPATCH(K, CALL)      \
-    do {                            \
-        if ((K) <= 1) { CALL(1); }  \
-        else if ((K) <= 4) { CALL(4); } \
-        else if ((K) <= 8) { CALL(8); } \
-        else { CALL(16); }          \
-    } while (0)
 
 void launch_head_topk(const void* Wp, const void* Xp, int R, int K, int n_valid, int segments, const int32_t* labels, int lab_stride,
                       int lab_off, float* part, float* logp, int out_stride, int out_off, int k, uint32_t* cand, int32_t* top_ids,

@@ -107,13 +107,20 @@ class GenerateOutput:
     of the reference), reduced to what the engine keeps: `sequences` and, with output_scores=True,
     `transition_scores` float32 [B*n, G, 8] = compute_transition_scores(sequences, scores, normalize_logits=True)
     per channel (NaN where the token is not a model decision) and `sequences_scores` [B*n] = their nansum.  The full
-    per-step score rows are not materialised: `scores` is None."""
+    per-step score rows are not materialised: `scores` is None.  With top_logprobs=k three more, the reduced form of
+    output_logits (`logits` stays None): `logprobs` float32 [B*n, G, 8] = log_softmax(the step's raw logits, hard-coded
+    masks only)[the sampler's decision], `top_ids` int64 [B*n, G, 8, k] and `top_logprobs` float32 [B*n, G, 8, k] = the k
+    most probable tokens of that distribution, descending (ties by ascending id); NaN / -1 where transition_scores is NaN."""
 
-    def __init__(self, sequences, transition_scores=None):
+    def __init__(self, sequences, transition_scores=None, logprobs=None, top_ids=None, top_logprobs=None):
         self.sequences = sequences
         self.scores = None
+        self.logits = None
         self.transition_scores = transition_scores
         self.sequences_scores = None if transition_scores is None else torch.nansum(transition_scores, dim=(1, 2))
+        self.logprobs = logprobs
+        self.top_ids = top_ids
+        self.top_logprobs = top_logprobs
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -452,7 +459,8 @@ class AsteroidTTSInstruct:
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,
-                 num_return_sequences=None, return_dict_in_generate=False, output_scores=False, adapter_names=None, **kw):
+                 num_return_sequences=None, return_dict_in_generate=False, output_scores=False, adapter_names=None,
+                 top_logprobs=None, **kw):
         """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
         num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
         repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages.
@@ -460,7 +468,15 @@ class AsteroidTTSInstruct:
         the per-token log-probabilities from the device sampler (modeling_asteroid.py:69-80,171-195 of the reference
         return full score rows; see GenerateOutput).
         adapter_names (PEFT's mixed-batch inference): one name per PROMPT of a resident adapter (load_adapter(adapter_name=)),
-        "__base__" or None for none; the prompt's takes run with it.  A row's tokens are those of the single-prompt call."""
+        "__base__" or None for none; the prompt's takes run with it.  A row's tokens are those of the single-prompt call.
+        top_logprobs=k (1..16, needs return_dict_in_generate=True): the output also carries `logprobs`, `top_ids` and
+        `top_logprobs` (GenerateOutput), the model's own distribution at every decision, selected on the device in the
+        decode step; it changes no token and no transition score."""
+        k = 0
+        if top_logprobs is not None:
+            k = topk_spec.check_k(top_logprobs)
+            if not return_dict_in_generate:
+                raise ValueError("top_logprobs needs return_dict_in_generate=True: a plain tensor of sequences cannot carry it")
         if return_dict_in_generate:
             bad = [k for k in ("output_logits", "output_attentions", "output_hidden_states") if kw.get(k)]
             if bad:
@@ -501,14 +517,21 @@ class AsteroidTTSInstruct:
             # one static batch, the reference's semantics: finished rows emit (eos, 1024 x 7) until the batch ends
             out = eng.generate(ids, msk, int(max_length), layers=layers, do_samples=do_samples, seed=seed,
                                row_ids=[r * n + j for r in rows for j in range(n)], takes=n, output_scores=want_lp,
-                               row_adapters=row_adapters)
+                               row_adapters=row_adapters, top_logprobs=k)
+            out = out if isinstance(out, tuple) else (out,)
+            out, lp, top = out[0], (out[1] if want_lp else None), (out[-1] if k else None)
         else:
-            out = self._generate_scheduled(eng, ids, msk, int(max_length), layers, do_samples, seed, rows, n, want_lp, row_adapters)
-        out, lp = out if want_lp else (out, None)
+            out, lp, top = self._generate_scheduled(eng, ids, msk, int(max_length), layers, do_samples, seed, rows, n, want_lp,
+                                                    row_adapters, k)
         seq = torch.from_numpy(out).to(input_ids.device)
         if not return_dict_in_generate:
             return seq
-        return GenerateOutput(seq, None if lp is None else torch.from_numpy(lp).to(input_ids.device))
+        dev = input_ids.device
+        go = GenerateOutput(seq, None if lp is None else torch.from_numpy(lp).to(dev))
+        if top is not None:
+            go.logprobs, go.top_logprobs = torch.from_numpy(top[0]).to(dev), torch.from_numpy(top[2]).to(dev)
+            go.top_ids = torch.from_numpy(top[1].astype(np.int64)).to(dev)
+        return go
 
     def _next_seed(self, seed):
         """Philox key of this call.  Explicit `seed=` / `generation_config.seed` / `model.sample_seed` win; otherwise it
@@ -523,13 +546,14 @@ class AsteroidTTSInstruct:
         return int(seed)
 
     def _generate_scheduled(self, eng, ids, msk, max_length, layers, do_samples, seed, rows, takes=1, output_scores=False,
-                            row_adapters=None):
+                            row_adapters=None, top_logprobs=0):
         """More rows than one pass carries: the continuous batcher serves them through MAX_ENGINE_BATCH slots (a
         finished dialogue's slot and KV pages go to the next one).  Row i draws from the Philox stream
         (seed; step, rows[i], channel) -- the stream row i of one static batch would use, so the same seed and prompts
         give the same tokens on either side of the 128-row limit (what differs: a dialogue cut off by max_length leaves
         at once here, while the reference keeps evaluating it and may resurrect it for a flush while another row is
-        still flushing, modeling_asteroid.py:140-141,168)."""
+        still flushing, modeling_asteroid.py:140-141,168).  -> (sequences, lp or None, (logprobs, top_ids, top_logprobs) or
+        None), the per-row arrays padded with NaN / -1 behind each dialogue's own end."""
         from mtts.scheduler import ContinuousBatcher
         B, T, C = ids.shape
         base = T - 7
@@ -539,8 +563,11 @@ class AsteroidTTSInstruct:
         cb = ContinuousBatcher(eng, slots=self.MAX_ENGINE_BATCH, gen_cap=max_length - base + 8, layers=layers,   # max_new + 7 flush steps
                                do_samples=do_samples)
         res = cb.run(prompts, new, seeds=[seed] * B, row_ids=rows, takes=takes, output_scores=output_scores,
-                     adapters=row_adapters)     # row k = take k % takes of prompt k // takes
-        res, sc = res if output_scores else (res, None)
+                     adapters=row_adapters, top_logprobs=top_logprobs or None)     # row k = take k % takes of prompt k // takes
+        if top_logprobs:
+            res, sc, tops = res
+        else:
+            (res, sc), tops = (res if output_scores else (res, None)), None
         G = max(r.shape[0] - (T - pads[k // takes] - 7) for k, r in enumerate(res))
         full = np.full((B * takes, base + G, C), self.config.speech_pad_token, dtype=np.int64)
         full[:, :, 0] = self.config.eos_token_id            # finished-row padding (modeling_asteroid.py:155-158)
@@ -549,9 +576,15 @@ class AsteroidTTSInstruct:
             full[k, :base] = ids[b, :base]
             gen = r[T - pads[b] - 7:]
             full[k, base:base + gen.shape[0]] = gen
-        if not output_scores:
-            return full
-        lp = np.full((B * takes, G, C), np.nan, dtype=np.float32)      # NaN: padding after a dialogue has left
-        for k, v in enumerate(sc):
-            lp[k, :v.shape[0]] = v
-        return full, lp
+        lp = top = None
+        if output_scores:
+            lp = np.full((B * takes, G, C), np.nan, dtype=np.float32)      # NaN: padding after a dialogue has left
+            for k, v in enumerate(sc):
+                lp[k, :v.shape[0]] = v
+        if top_logprobs:
+            top = (np.full((B * takes, G, C), np.nan, dtype=np.float32), np.full((B * takes, G, C, top_logprobs), -1, dtype=np.int32),
+                   np.full((B * takes, G, C, top_logprobs), np.nan, dtype=np.float32))
+            for dst, src in zip(top, tops):
+                for k, v in enumerate(src):
+                    dst[k, :v.shape[0]] = v
+        return full, lp, top

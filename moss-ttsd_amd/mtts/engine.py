@@ -65,6 +65,7 @@ class Engine:
         c.kv_pool_pages = int(kv_pool_pages)          # 0: every slot can reach max_seq_len at once
         c.dtype = {"bf16": 0, "fp32": 1, "fp16": 2}[dtype]
         self._h = C.c_void_p()
+        self._topk = 0
         capi.check(self.lib.mtts_engine_create(C.byref(c), self.device.index or 0, C.byref(self._h)))
         cos, sin = (t.to(self.tdtype) for t in rope_tables(cfg["head_dim"], float(cfg["rope_theta"]), c.max_position,
                                                            self.device, self.model_dtype))
@@ -173,8 +174,15 @@ class Engine:
         own `output_scores` argument, so the same holds for them."""
         capi.check(self.lib.mtts_set_output_scores(self._h, 1 if on else 0))
 
+    def set_top_logprobs(self, k):
+        """Sticky engine switch like set_output_scores, and independent of it (include/mtts.h: mtts_set_top_logprobs): k = 0
+        off, 1..16 the number of most probable tokens kept per decision.  begin / generate / sched_open call this with
+        their own `top_logprobs` argument."""
+        capi.check(self.lib.mtts_set_top_logprobs(self._h, int(k)))
+        self._topk = int(k)             # (the run that starts next; the read functions size their buffers by it)
+
     def generate(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, forced=None,
-                 forced_as_draw=False, row_ids=None, takes=1, output_scores=False, row_adapters=None):
+                 forced_as_draw=False, row_ids=None, takes=1, output_scores=False, row_adapters=None, top_logprobs=0):
         """forced (verification hook): int64 [B,G,8] full sequences of a reference run.  -> (ids, decisions [steps,B,8]).
         forced_as_draw: the forced row replaces each step's raw draw before the state machine (replay of a SAMPLED
         run); decisions are then the raw draws.  forced_as_draw="all": also for rows that max_length has cut off (the
@@ -184,7 +192,12 @@ class Engine:
         output_scores: the return value gains a last element lp, float32 [B*takes, G, 8] aligned with ids[:, T-7:]:
         log_softmax(processed scores)[the sampler's decision], NaN where the appended token is not a model decision
         (teacher forcing, EOS flush, finished-row padding).
-        row_adapters: one bank index per PROMPT (load_bank_adapter), -1 or None = no adapter; a prompt's takes inherit it."""
+        row_adapters: one bank index per PROMPT (load_bank_adapter), -1 or None = no adapter; a prompt's takes inherit it.
+        top_logprobs=k (1..16): the return value gains, after lp, a tuple (logprobs float32 [B*takes, G, 8], top_ids int32
+        [B*takes, G, 8, k], top_logprobs float32 [B*takes, G, 8, k]): the model's own distribution at every decision --
+        log_softmax of the step's raw logits (hard-coded masks only; no penalty, temperature, top-k, top-p) at the
+        sampler's decision and at the k most probable tokens (descending logit, ascending id among equals); NaN / -1
+        exactly where lp is NaN."""
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
         R = B * int(takes)
@@ -196,6 +209,7 @@ class Engine:
         out_len = C.c_int32(0)
         scfg = sampler_cfgs(layers, do_samples)
         self.set_output_scores(output_scores)
+        self.set_top_logprobs(top_logprobs)
         self._set_row_ids(row_ids, R)       # Philox row id of each row (default: its position in this batch)
         self._set_takes(takes)
         self._set_row_adapters(row_adapters, B)
@@ -212,6 +226,8 @@ class Engine:
         ret = (res,) if forced is None else (res, dec[:out_len.value - (T - 7)].copy())
         if output_scores:
             ret += (np.ascontiguousarray(self.read_scores(out_len.value - (T - 7)).transpose(1, 0, 2)),)
+        if top_logprobs:
+            ret += (tuple(np.ascontiguousarray(np.swapaxes(a, 0, 1)) for a in self.read_top_logprobs(out_len.value - (T - 7))),)
         return ret if len(ret) > 1 else ret[0]
 
     def score(self, input_ids, attention_mask, labels=None, top_k=0):
@@ -243,13 +259,14 @@ class Engine:
         return out, top_ids, top_logp
 
     def begin(self, input_ids, attention_mask, max_length, layers=None, do_samples=None, seed=0, row_ids=None, takes=1,
-              output_scores=False, row_adapters=None):
+              output_scores=False, row_adapters=None, top_logprobs=0):
         """Prefill; takes and row_adapters as in generate() (the run then has B*takes rows); output_scores: keep
-        log-probabilities for read_scores()."""
+        log-probabilities for read_scores(); top_logprobs=k: keep the raw distribution's for read_top_logprobs()."""
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
         self._B, self._T = B * int(takes), T
         self.set_output_scores(output_scores)
+        self.set_top_logprobs(top_logprobs)
         self._set_row_ids(row_ids, B * int(takes))
         self._set_takes(takes)
         self._set_row_adapters(row_adapters, B)
@@ -279,6 +296,17 @@ class Engine:
         capi.check(self.lib.mtts_read_scores(self._h, buf.ctypes.data, buf.shape[0], C.byref(n)))
         return buf[:n.value]
 
+    def read_top_logprobs(self, capacity_steps):
+        """-> (logprobs float32 [steps, rows, 8], top_ids int32 [steps, rows, 8, k], top_logprobs float32 [steps, rows, 8, k])
+        of the run's generated rows (row space of read_generated); k is the run's."""
+        cap, k = max(int(capacity_steps), 1), max(self._topk, 1)
+        lp = np.zeros((cap, self._B, 8), dtype=np.float32)
+        ids = np.zeros((cap, self._B, 8, k), dtype=np.int32)
+        tlp = np.zeros((cap, self._B, 8, k), dtype=np.float32)
+        n = C.c_int32(0)
+        capi.check(self.lib.mtts_read_top_logprobs(self._h, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data, cap, C.byref(n)))
+        return lp[:n.value], ids[:n.value], tlp[:n.value]
+
     def read_logits(self):
         V0, Vs = self.cfg["vocab_size"], self.cfg["speech_vocab_size"]
         if self.dtype != "bf16":
@@ -293,9 +321,10 @@ class Engine:
         return f(l0), f(l17)
 
     # ---- continuous batching ---------------------------------------------------------
-    def sched_open(self, slots, gen_cap, layers=None, do_samples=None, output_scores=False):
+    def sched_open(self, slots, gen_cap, layers=None, do_samples=None, output_scores=False, top_logprobs=0):
         self._B = int(slots)
         self.set_output_scores(output_scores)
+        self.set_top_logprobs(top_logprobs)
         capi.check(self.lib.mtts_sched_open(self._h, int(slots), int(gen_cap), sampler_cfgs(layers, do_samples), None))
 
     def submit(self, slot, ids, max_length, seed=0, row_id=0, adapter=None):
@@ -332,6 +361,18 @@ class Engine:
         n = C.c_int32(0)
         capi.check(self.lib.mtts_slot_read_scores(self._h, int(slot), buf.ctypes.data, buf.shape[0], C.byref(n)))
         return buf[:n.value].copy()
+
+    def slot_read_top_logprobs(self, slot, capacity):
+        """-> (logprobs float32 [steps, 8], top_ids int32 [steps, 8, k], top_logprobs float32 [steps, 8, k]) of the slot's
+        generated rows (like slot_read_scores)."""
+        cap, k = max(int(capacity), 1), max(self._topk, 1)
+        lp = np.zeros((cap, 8), dtype=np.float32)
+        ids = np.zeros((cap, 8, k), dtype=np.int32)
+        tlp = np.zeros((cap, 8, k), dtype=np.float32)
+        n = C.c_int32(0)
+        capi.check(self.lib.mtts_slot_read_top_logprobs(self._h, int(slot), lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data, cap,
+                                                        C.byref(n)))
+        return lp[:n.value].copy(), ids[:n.value].copy(), tlp[:n.value].copy()
 
     def evict(self, slot):
         """Scheduler mode: drop the dialogue in `slot` and return its KV pages (it is re-submitted later)."""

@@ -35,10 +35,11 @@ class ContinuousBatcher:
         self.steps_per_poll = int(steps_per_poll)
         self.evictions = 0
         self.forks = 0                                                # takes started by Engine.fork (no prefill of their own)
-        self._layers, self._do_samples, self._scores = layers, do_samples, False
+        self._layers, self._do_samples, self._scores, self._topk = layers, do_samples, False, 0
         engine.sched_open(self.slots, self.gen_cap, layers=layers, do_samples=do_samples)
 
-    def run(self, prompts, max_new_tokens, seeds=None, base_seed=0, row_ids=None, takes=1, output_scores=False, adapters=None):
+    def run(self, prompts, max_new_tokens, seeds=None, base_seed=0, row_ids=None, takes=1, output_scores=False, adapters=None,
+            top_logprobs=None):
         """prompts: list of int64 [T_i,8] delay-shifted prompts (no padding); max_new_tokens: int or list
         (HF semantics: max_length = T_i + max_new).  seeds: one Philox key per dialogue (default base_seed + i, so
         that concurrent dialogues draw from different streams).  Returns a list of int64 [T_i-7+G_i, 8] in
@@ -51,14 +52,18 @@ class ContinuousBatcher:
         rows (Engine.generate: lp).  They are a function of (prompt, seed, row id) like the tokens: an evicted and re-run
         dialogue, a forked take and a queued take all reproduce them.
         adapters: one bank index per prompt (Engine.load_bank_adapter; None / -1: none).  It is kept with the job: an
-        evicted and re-queued dialogue and a queued take are submitted with it again, a forked take inherits it."""
+        evicted and re-queued dialogue and a queued take are submitted with it again, a forked take inherits it.
+        top_logprobs=k (1..16): returns (results, scores or None, (logprobs, top_ids, top_logprobs)), each of the three a
+        per-job list like scores: float32 [G_k, 8], int32 [G_k, 8, k], float32 [G_k, 8, k] (Engine.generate: top_logprobs),
+        reproduced by re-runs, forks and queued takes like the scores.  Without the argument the return value is as above."""
         takes = int(takes)
         if takes < 1:
             raise ValueError(f"takes must be >= 1 (got {takes})")
-        if bool(output_scores) != self._scores:                       # the switch is read when the scheduler opens
-            self._scores = bool(output_scores)
+        topk = 0 if top_logprobs is None else int(top_logprobs)
+        if bool(output_scores) != self._scores or topk != self._topk:  # the switches are read when the scheduler opens
+            self._scores, self._topk = bool(output_scores), topk
             self.eng.sched_open(self.slots, self.gen_cap, layers=self._layers, do_samples=self._do_samples,
-                                output_scores=self._scores)
+                                output_scores=self._scores, top_logprobs=self._topk)
         n = len(prompts)
         mnt = [max_new_tokens] * n if np.isscalar(max_new_tokens) else list(max_new_tokens)
         seeds = list(seeds) if seeds is not None else [int(base_seed) + i for i in range(n)]
@@ -77,6 +82,7 @@ class ContinuousBatcher:
         n *= takes
         results = [None] * n
         scores = [None] * n
+        tops = ([None] * n, [None] * n, [None] * n)
         owner = [-1] * self.slots
         queue = list(range(n)) if takes == 1 else list(range(0, n, takes))
         steps = 0
@@ -131,11 +137,15 @@ class ContinuousBatcher:
                     rows = self.eng.slot_read(s, self.gen_cap)
                     if self._scores:
                         scores[i] = self.eng.slot_read_scores(s, self.gen_cap)
+                    if self._topk:
+                        tops[0][i], tops[1][i], tops[2][i] = self.eng.slot_read_top_logprobs(s, self.gen_cap)
                     ids = np.asarray(prompts[i], dtype=np.int64)
                     results[i] = np.concatenate([ids[:ids.shape[0] - 7], rows], axis=0)
                     owner[s] = -1
                     hold = False
         self.engine_steps = steps
+        if top_logprobs is not None:
+            return results, (scores if self._scores else None), tops
         return (results, scores) if self._scores else results
 
     def _fork_takes(self, s, i, takes, T, owner, queue, seeds, row_ids):

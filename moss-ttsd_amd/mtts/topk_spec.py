@@ -35,6 +35,24 @@ def topk_order(logits, k):
     return out.reshape(lg.shape[:-1] + (k,))
 
 
+def gen_logprobs_spec(logits, mask_id, decisions, k):
+    """generate(top_logprobs=k) on one step's logits (csrc/gen_topk.hip), in float64.  logits [R, V] (the fp32 view of the
+    rows the forward wrote), mask_id the one id the reference's hard-coded masks put at -inf (None or < 0: none),
+    decisions int [R] -> (logp float64 [R] = log_softmax(L)[decision], top_ids int64 [R, k] = the first k tokens of L
+    under topk_order, top_logp float64 [R, k] = their log_softmax(L)).  No repetition penalty, temperature, top-k or
+    top-p: L is what output_logits would return."""
+    L = np.array(logits, dtype=np.float64)
+    assert L.ndim == 2
+    if mask_id is not None and int(mask_id) >= 0:
+        L[:, int(mask_id)] = -np.inf
+    m = L.max(-1, keepdims=True)
+    with np.errstate(divide="ignore"):
+        logp = L - (m + np.log(np.exp(L - m).sum(-1, keepdims=True)))
+    ids = topk_order(L, k)
+    d = np.asarray(decisions, dtype=np.int64).reshape(-1, 1)
+    return np.take_along_axis(logp, d, -1)[:, 0], ids, np.take_along_axis(logp, ids, -1)
+
+
 def topk_of_logprobs(logp, k):
     """A full row of log-probabilities [..., V] (float32) -> (ids int64 [..., k], their values [..., k]) under the same
     order: what a sweep of the label over the whole vocabulary must agree with."""
