@@ -377,6 +377,27 @@ int32_t mtts_k_gemm_bf16(const void* dev_w, const void* dev_x, void* dev_y,
 /* number of GEMM launches of this process that took a depth-specialised kernel (gemm_depth_kernel / gemm_gateup48_kernel,
  * or one of their sealed twins) instead of gemm_skinny_kernel; under graph replay a launch counts once, when it is captured (tests: did the dispatch fire) */
 int64_t mtts_debug_gemm_depth_launches(void);
+/* number of launches of this process that took one of gemm_fold.hip's kernels (the o_proj that finishes the residual
+ * stream, the gate/up that normalises it: MTTS_FOLD_NORM); counted like the above */
+int64_t mtts_debug_fold_norm_launches(void);
+/* oproj_resid_kernel alone: dev_x bf16 [R][N] += bf16(dev_attn [R][2048] * dev_wo [N][2048]^T), in place, with o_proj's
+ * split-K 4 sum tree and resid_norm_kernel's two roundings; dev_x_packed (bf16, 32 * N, the X-fragment layout of one
+ * 32-row tile) receives the same rows, the rest of it keeps what the caller put there.  1 <= R <= 32, N % 32 == 0. */
+int32_t mtts_k_oproj_resid(const void* dev_wo, const void* dev_attn, void* dev_x, void* dev_x_packed, int32_t R, int32_t N,
+                           void* stream);
+/* The pair at H = 2048: the producer as above (N = 2048), then gemm_gateup48_norm_kernel on dev_wgu [N_gu][2048] (gate
+ * and up rows interleaved, N_gu % 96 == 0) with dev_norm_w bf16 [2048].  Out: dev_x updated in place, dev_y bf16
+ * [R][N_gu / 2] row-major = the SwiGLU output. */
+int32_t mtts_k_fold_pair(const void* dev_wo, const void* dev_attn, void* dev_x, const void* dev_norm_w, const void* dev_wgu,
+                         float eps, int32_t R, int32_t N_gu, void* dev_y, void* stream);
+/* pack2_rn (csrc/norm_ops.h: v_cvt_pk_bf16_f32, what resid_norm_kernel and the kernels of gemm_fold.hip round with) against
+ * f2bf (csrc/common.h) on all 2^32 fp32 bit patterns: out2 = {inputs that are not NaN on which they differ, NaN inputs on
+ * which they differ}.  Both must be 0 (tests/test_bf16_round_gpu.py). */
+int32_t mtts_k_bf16_round_check(int64_t* out2, void* stream);
+/* launch trains of the seam at H = 2048 over `copies` rotating copies of both weight arrays: mode 0 the three launches
+ * (o_proj split-K 4, resid_norm, gate/up), 1 producer + consumer, 10 .. 14 one of those five launches alone; avg_us = one
+ * pass through the seam (tools/fold_norm_ab.py) */
+int32_t mtts_k_fold_bench(int32_t N_gu, int32_t copies, int32_t iters, int32_t mode, float* avg_us);
 /* number of whole-row decode attention launches (attn_row_kernel) of this process; counted like the above */
 int64_t mtts_debug_attn_row_launches(void);
 /* Test hook: the attention section of one decode layer (fused q/k/v epilogue, scores, P.V, sum of the chunk partials) on

@@ -8,7 +8,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = ["gemm.hip", "gemm_sealed.hip", "layer.hip", "attn.hip", "sampler.hip", "gen_topk.hip", "f32path.hip", "score.hip", "adapter.hip", "multilora.hip", "engine.hip", "hooks.hip", "codec.hip", "codec_fused.hip"]
+SRC = ["gemm.hip", "gemm_sealed.hip", "gemm_fold.hip", "layer.hip", "attn.hip", "sampler.hip", "gen_topk.hip", "f32path.hip", "score.hip", "adapter.hip", "multilora.hip", "engine.hip", "hooks.hip", "codec.hip", "codec_fused.hip"]
 OUT = os.path.join(HERE, "lib", "libmtts.so")
 OBJ = os.path.join(HERE, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]

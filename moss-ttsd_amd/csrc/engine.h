@@ -41,6 +41,13 @@ static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 // the bf16 one by more than the spread of both (profiles/wseal_ab.json).  gate/up did not beat it at the
 // share Gaussian weights have (1 group in 3 072): negative = never, and no twin is kept for it.
 static const double WSEAL_MAX_UNSEALED[4] = {-1.0, 1.0 / 512, 1.0 / 8, 1.0 / 64};
+// MTTS_FOLD_NORM: the one-row-tile decode step runs o_proj -> post-attention norm -> gate/up as the two launches of
+// gemm_fold.hip instead of three (same bits).  Read like MTTS_GEMM_DEPTH.
+#define MTTS_FOLD_NORM_DEFAULT 0
+static inline int fold_norm_env() {
+    const char* g = getenv("MTTS_FOLD_NORM");
+    return g ? (atoi(g) != 0) : MTTS_FOLD_NORM_DEFAULT;
+}
 static inline int gemm_depth_env() {
     const char* g = getenv("MTTS_GEMM_DEPTH");
     return (g && atoi(g) == 0) ? 0 : 1;
@@ -175,6 +182,8 @@ struct MttsEngine {
     void *x2 = nullptr, *act_rm = nullptr;   // small-batch path: second residual buffer (ping-pong), row-major SwiGLU output
     int small_rows = SMALL_RP;          // decode batches up to this many dialogues take the small-batch path (0 = off)
     int gemm_depth = 1;                 // depth-specialised decode GEMMs (gemm.hip; MTTS_GEMM_DEPTH=0: off)
+    int fold_norm = MTTS_FOLD_NORM_DEFAULT;   // o_proj finishes the residual, gate/up normalises it (gemm_fold.hip; MTTS_FOLD_NORM)
+    void* xres_p = nullptr;             // ... and the x' it hands over: one 32-row tile in the X-fragment layout
     // Sealed weight streams (gemm_sealed.hip): gate/up, down_proj and the heads also exist in the sealed
     // 13-bit form, made by every bind of such a matrix on the bind's stream, and the one-row-tile decode GEMMs read that
     // instead of the bf16 array.  MTTS_W_SEAL: 0 never (no twin is allocated), 1 per matrix kind by the share of groups that

@@ -149,6 +149,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     }
     if (const char* g = getenv("MTTS_SMALL_ROWS")) e->small_rows = std::min(std::max(atoi(g), 0), SMALL_RP);
     e->gemm_depth = gemm_depth_env();
+    e->fold_norm = fold_norm_env();
     e->H = c->hidden_size; e->I = c->intermediate_size; e->L = c->num_hidden_layers;
     e->nq = c->num_attention_heads; e->nkv = c->num_key_value_heads;
     e->V0 = c->vocab_size; e->Vs = c->speech_vocab_size;
@@ -218,6 +219,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
         TRY(m.get((uint16_t**)&e->act_rm, (size_t)MTTS_MAXR * I));
         TRY(m.get((uint16_t**)&e->x, (size_t)MTTS_PFCAP * H));
         TRY(m.get((uint16_t**)&e->xn, (size_t)MTTS_PFCAP * H));
+        TRY(m.get((uint16_t**)&e->xres_p, (size_t)32 * H));
         TRY(m.get((uint16_t**)&e->xh, (size_t)MTTS_RCAP * H));
         TRY(m.get((uint16_t**)&e->hlast, (size_t)MTTS_RCAP * H));
         TRY(m.get((uint16_t**)&e->attn_p, (size_t)MTTS_PFCAP * e->nq * MTTS_HD));
@@ -772,6 +774,10 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
     if (heads == 1 && !lora && e->B <= e->small_rows && small_path_fits(e)) return forward_small(e, d_meta, pages_bound, st, kv_tokens_hint);
     if (lora && !e->d_bank) return fail(MTTS_ESTATE, "a pass with adapters on an engine without a bank");
     const int QD = nq * MTTS_HD, KD = nkv * MTTS_HD, EL = e->L * 7;
+    // decode rows in one row tile, no adapter row: o_proj -> post-attention norm -> gate/up as gemm_fold.hip's two launches
+    // where both GEMMs have the shape those kernels are built for (everything else issues the three launches below)
+    const bool fold = e->fold_norm && heads == 1 && mb == 1 && !lora && e->gemm_depth && !e->wseal_on[WSEAL_GU] &&
+                      fold_norm_shape(e->p_o, nq * MTTS_HD, e->p_gu, H, 2 * I);
     const LoraJob j_qkv{3, e->qkv_rows, H, EL, {{0, QD, 1, 0}, {QD, KD, 1, 1}, {QD + KD, KD, 1, 2}}};
     const LoraJob j_o{1, Hp, QD, EL, {{0, H, 1, 3}}}, j_gu{2, 2 * I, H, EL, {{0, I, 2, 4}, {1, I, 2, 5}}}, j_d{1, Hp, I, EL, {{0, H, 1, 6}}};
     for (int n = 0; n < e->L; ++n) {
@@ -797,17 +803,25 @@ static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d
         // positions of one dialogue, share their K/V pages (chunks of ATT_PF pages) and read the bf16 pages
         TRY(attend_layer(e, n, d_meta, R, pages_bound, ks_qkv + ex, 3, heads != 1 && pages_bound >= e->pf_mfma_pages,
                          heads == 1 && e->B * pages_bound <= e->fuse_qkv_max, heads == 1, st, kv_tokens_hint));
-        if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
-        else launch_gemm(EPI_PARTIAL, mb, e->p_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
-        if (lora) delta(j_o, e->attn_p, ks_o);
-        launch_resid_norm(e->partial, ks_o + ex, Hp, e->x, l.ln_post, e->xn, nullptr, d_meta, R, H, eps, st);
         // gate/up: the same plan with or without adapters (p_gu; one k-split of the tile GEMM), so slab 0 holds the sums
         // the fused epilogue would have rounded
         const int gu_epi = lora ? EPI_PARTIAL : EPI_SILU;
         float* gu_slab = lora ? e->partial : nullptr;
-        if (tiled) launch_gemm_tile(gu_epi, R, 1, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
-        else if (!sealed_gu || !launch_gemm_sealed(EPI_SILU, mb, e->p_gu, l.wgu_s, l.wgu, e->xn, H, 2 * I, 2 * I, nullptr, (uint16_t*)e->act_p, 0, st))
-            launch_gemm(gu_epi, mb, e->p_gu, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
+        if (fold) {
+            // o_proj leaves no slabs: it finishes x' (rows < R), gate/up normalises it.  Both buffers hold a whole tile; rows >= R
+            // of xres_p keep zeros or the x' of an earlier, larger batch (finite), which gate/up normalises and multiplies like the
+            // stale xn rows of the three launches: nothing reads the result rows >= R
+            launch_oproj_resid(l.wo, e->attn_p, e->x, e->xres_p, R, Hp, st);
+            launch_gateup_norm(l.wgu, e->xres_p, l.ln_post, eps, e->act_p, 2 * I, st);
+        } else {
+            if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
+            else launch_gemm(EPI_PARTIAL, mb, e->p_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
+            if (lora) delta(j_o, e->attn_p, ks_o);
+            launch_resid_norm(e->partial, ks_o + ex, Hp, e->x, l.ln_post, e->xn, nullptr, d_meta, R, H, eps, st);
+            if (tiled) launch_gemm_tile(gu_epi, R, 1, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
+            else if (!sealed_gu || !launch_gemm_sealed(EPI_SILU, mb, e->p_gu, l.wgu_s, l.wgu, e->xn, H, 2 * I, 2 * I, nullptr, (uint16_t*)e->act_p, 0, st))
+                launch_gemm(gu_epi, mb, e->p_gu, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
+        }
         if (lora) {
             delta(j_gu, e->xn, 1);
             launch_swiglu_slabs(e->partial, e->partial + (size_t)MTTS_PFCAP * 2 * I, e->act_p, mb * 32, I, st);

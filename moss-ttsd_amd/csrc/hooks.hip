@@ -881,6 +881,133 @@ int32_t mtts_k_gemm_bench(int32_t N, int32_t K, int32_t epi, int32_t ksplit, int
     return MTTS_OK;
 }
 
+// ---- o_proj -> post-attention norm -> gate/up as two launches (gemm_fold.hip) ----------------------------------------------
+int64_t mtts_debug_fold_norm_launches(void) { return (int64_t)mtts_fold_norm_launches(); }
+
+static int fold_hook_args(const char* who, int R, int N) {
+    if (R < 1 || R > 32 || N < 32 || N % 32) return fail(MTTS_EINVAL, "%s: need 1<=R<=32, N%%32==0 (K is 2048)", who);
+    return MTTS_OK;
+}
+
+// The producer alone: x [R][N] += attn [R][2048] * Wo [N][2048]^T (all bf16 row-major), in place, and the packed copy.
+int32_t mtts_k_oproj_resid(const void* dev_wo, const void* dev_attn, void* dev_x, void* dev_x_packed, int32_t R, int32_t N,
+                           void* stream) {
+    if (!dev_wo || !dev_attn || !dev_x || !dev_x_packed) return fail(MTTS_EINVAL, "oproj_resid: null argument");
+    TRY(fold_hook_args("oproj_resid", R, N));
+    hipStream_t st = S(stream);
+    const int K = 2048;
+    uint16_t *wp = nullptr, *ap = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&wp, (size_t)N * K));
+    TRY(hb.get(&ap, (size_t)32 * K));
+    launch_pack_weight(dev_wo, wp, N, K, N, 1, 0, st);
+    launch_pack_rows(dev_attn, ap, R, K, 1, st);
+    launch_oproj_resid(wp, ap, dev_x, dev_x_packed, R, N, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+// The pair: the producer as above with N = H = 2048, then gate/up with the norm prologue on Wgu [N_gu][2048] (gate and up
+// rows interleaved, N_gu % 96 == 0).  The hook's x' tile starts as zeros (rows >= R stay zero: the consumer reads all 32).
+int32_t mtts_k_fold_pair(const void* dev_wo, const void* dev_attn, void* dev_x, const void* dev_norm_w, const void* dev_wgu,
+                         float eps, int32_t R, int32_t N_gu, void* dev_y, void* stream) {
+    if (!dev_wo || !dev_attn || !dev_x || !dev_norm_w || !dev_wgu || !dev_y) return fail(MTTS_EINVAL, "fold_pair: null argument");
+    const int H = 2048, K = 2048;
+    TRY(fold_hook_args("fold_pair", R, H));
+    const GemmPlan p_o = mtts_plan_gemm(H, K, 0), p_gu = mtts_plan_gemm(N_gu > 0 ? N_gu : 32, H, 1);
+    if (N_gu < 96 || N_gu % 96) return fail(MTTS_EINVAL, "fold_pair: gate/up needs N %% 96 == 0");
+    if (!fold_norm_shape(p_o, K, p_gu, H, N_gu)) return fail(MTTS_EINVAL, "fold_pair: the planner does not give these GEMMs the shapes the pair is built for");
+    hipStream_t st = S(stream);
+    uint16_t *wp = nullptr, *ap = nullptr, *gp = nullptr, *xp = nullptr, *op = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&wp, (size_t)H * K));
+    TRY(hb.get(&ap, (size_t)32 * K));
+    TRY(hb.get(&gp, (size_t)N_gu * H));
+    TRY(hb.get(&xp, (size_t)32 * H));
+    TRY(hb.get(&op, (size_t)32 * (N_gu / 2)));
+    launch_pack_weight(dev_wo, wp, H, K, H, 1, 0, st);
+    launch_pack_rows(dev_attn, ap, R, K, 1, st);
+    launch_pack_weight(dev_wgu, gp, N_gu, H, N_gu, 1, 0, st);
+    launch_oproj_resid(wp, ap, dev_x, xp, R, H, st);
+    launch_gateup_norm(gp, xp, dev_norm_w, eps, op, N_gu, st);
+    launch_unpack_rows(op, dev_y, R, N_gu / 2, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+// Measurement hook: launch trains of the seam at H = K = 2048 over `copies` rotating copies of both weight arrays (every
+// value 0x3c3c).  mode 0: o_proj (split-K 4) + resid_norm + gate/up, the three launches; 1: producer + consumer; 10 .. 14: one
+// launch of the above alone (o_proj, resid_norm, gate/up, producer, consumer).  avg_us is the time of one pass through the
+// seam.  (The residual stream keeps adding the same bf16 increment and stops growing once that falls below half an ulp: it stays finite.)
+int32_t mtts_k_fold_bench(int32_t N_gu, int32_t copies, int32_t iters, int32_t mode, float* avg_us) {
+    const int H = 2048, K = 2048;
+    if (copies < 1 || iters < 1 || mode < 0 || (mode > 1 && mode < 10) || mode > 14 || !avg_us) return fail(MTTS_EINVAL, "fold_bench: bad argument");
+    GemmPlan p_o = mtts_plan_gemm(H, K, 0), p_gu = mtts_plan_gemm(N_gu > 0 ? N_gu : 32, H, 1);
+    p_o.depth = p_gu.depth = 1;
+    if (N_gu < 96 || N_gu % 96) return fail(MTTS_EINVAL, "fold_bench: gate/up needs N %% 96 == 0");
+    if (!fold_norm_shape(p_o, K, p_gu, H, N_gu)) return fail(MTTS_EINVAL, "fold_bench: the planner does not give these GEMMs the shapes the pair is built for");
+    DevBufs hb;
+    std::vector<uint16_t*> wo(copies, nullptr), wgu(copies, nullptr);
+    for (int c = 0; c < copies; ++c) {
+        TRY(hb.get(&wo[c], (size_t)H * K, false)); HIPCHK(hipMemset(wo[c], 0x3c, (size_t)H * K * 2));
+        TRY(hb.get(&wgu[c], (size_t)N_gu * H, false)); HIPCHK(hipMemset(wgu[c], 0x3c, (size_t)N_gu * H * 2));
+    }
+    uint16_t *attn = nullptr, *x = nullptr, *xn = nullptr, *xp = nullptr, *act = nullptr, *nw = nullptr;
+    float* part = nullptr;
+    RowMeta* meta = nullptr;
+    TRY(hb.get(&attn, (size_t)32 * K, false)); HIPCHK(hipMemset(attn, 0x3c, (size_t)32 * K * 2));
+    TRY(hb.get(&x, (size_t)32 * H));
+    TRY(hb.get(&xn, (size_t)32 * H));
+    TRY(hb.get(&xp, (size_t)32 * H));
+    TRY(hb.get(&act, (size_t)32 * (N_gu / 2)));
+    TRY(hb.get(&nw, (size_t)H, false)); HIPCHK(hipMemset(nw, 0x3c, (size_t)H * 2));
+    TRY(hb.get(&part, (size_t)p_o.ksplit * MTTS_PFCAP * H));
+    TRY(hb.get(&meta, 32));
+    const float eps = 1e-6f;
+    auto go = [&](int i) {
+        const int c = i % copies;
+        if (mode == 0 || mode == 10) launch_gemm(EPI_PARTIAL, 1, p_o, wo[c], attn, K, H, H, part, nullptr, nullptr);
+        if (mode == 0 || mode == 11) launch_resid_norm(part, p_o.ksplit, H, x, nw, xn, nullptr, meta, 32, H, eps, nullptr);
+        if (mode == 0 || mode == 12) launch_gemm(EPI_SILU, 1, p_gu, wgu[c], xn, H, N_gu, N_gu, nullptr, act, nullptr);
+        if (mode == 1 || mode == 13) launch_oproj_resid(wo[c], attn, x, xp, 32, H, nullptr);
+        if (mode == 1 || mode == 14) launch_gateup_norm(wgu[c], xp, nw, eps, act, N_gu, nullptr);
+    };
+    for (int i = 0; i < copies; ++i) go(i);
+    HIPCHK(hipDeviceSynchronize());
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) go(i);
+    hipEventRecord(e1, nullptr);
+    const hipError_t waited = hipEventSynchronize(e1);
+    float ms = 0;
+    if (waited == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
+    hipEventDestroy(e0); hipEventDestroy(e1);           // on the error path too
+    HIPCHK(waited);
+    *avg_us = ms * 1000.f / iters;
+    HIPCHK(hipGetLastError());
+    return MTTS_OK;
+}
+
+// pack2_rn (norm_ops.h: the hardware's fp32 -> bf16 conversion) against f2bf (common.h) on all 2^32 inputs:
+// out2 = {inputs that are not NaN on which they differ, NaN inputs on which they differ}
+int32_t mtts_k_bf16_round_check(int64_t* out2, void* stream) {
+    if (!out2) return fail(MTTS_EINVAL, "bf16_round_check: null argument");
+    hipStream_t st = S(stream);
+    unsigned long long* cnt = nullptr;
+    DevBufs hb;
+    TRY(hb.get(&cnt, 2));
+    launch_bf16_round_check(cnt, st);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(h, cnt, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    out2[0] = (int64_t)h[0]; out2[1] = (int64_t)h[1];
+    return MTTS_OK;
+}
+
 // ---- sealed weight streams (gemm_sealed.hip) ----------------------------------------------------------------------------
 int64_t mtts_debug_wseal_launches(void) { return (int64_t)mtts_wseal_launches(); }
 

@@ -43,6 +43,14 @@ bool launch_gemm_sealed(int epi, int mb, const GemmPlan& p, const void* Ws, cons
                         int n_valid, float* partial, uint16_t* out, int head_form, hipStream_t st);
 long long mtts_wseal_launches();
 
+// ---- gemm_fold.hip --------------------------------------------------------------------------------------------------
+// o_proj -> post-attention RMSNorm -> gate/up of a one-row-tile decode step as two launches: the first finishes the
+// residual stream x' (row-major in place, and in the X-fragment layout), the second normalises it in its X prologue.
+bool fold_norm_shape(const GemmPlan& p_o, int K_o, const GemmPlan& p_gu, int H, int N_gu);      // the pair takes these two GEMMs
+void launch_oproj_resid(const void* Wp, const void* Xp, void* x, void* x_packed, int R, int N, hipStream_t st);
+void launch_gateup_norm(const void* Wp, const void* x_packed, const void* norm_w, float eps, void* out, int Npad, hipStream_t st);
+long long mtts_fold_norm_launches();
+
 // ---- layer.hip ------------------------------------------------------------------------------------------------------
 void launch_embed_norm(const int32_t* tokens, const RowMeta* meta, const uint16_t* const* tables, const void* norm_w,
                        void* x, void* xn_packed, int R, int H, float eps, hipStream_t st);
@@ -61,6 +69,7 @@ void launch_pack_kv_pages(const void* K, const void* V, void* kcache, void* vcac
                           int S, int Lmax, int nkv, int max_pages, int total_pages, hipStream_t st);
 void launch_bf16_to_f32(const void* a, float* b, size_t n, hipStream_t st);
 void launch_unpack_rows(const void* packed, void* out, int R, int K, hipStream_t st);
+void launch_bf16_round_check(unsigned long long* cnt2, hipStream_t st);      // cnt2 += {non-NaN, NaN} inputs on which pack2_rn != f2bf
 
 // ---- attn.hip -------------------------------------------------------------------------------------------------------
 // One launch_attn call = one phase: scores / P.V / combine for decode-style rows (one dialogue per row), the same three

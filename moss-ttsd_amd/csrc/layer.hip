@@ -2,13 +2,14 @@
 // split-K reduction of the GEMM in front of it.  All rounding points follow the
 // reference's CPU bf16 execution (oracle/asteroid_oracle.py lists them).
 #include "launch.h"
+#include "norm_ops.h"
 
 // block-wide sum over 256 threads
 __device__ __forceinline__ float block_sum_256(float v, float* sh) {
     v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
-    float t = sh[0] + sh[1] + sh[2] + sh[3];
+    float t = norm_total(sh[0], sh[1], sh[2], sh[3]);
     __syncthreads();
     return t;
 }
@@ -127,30 +128,19 @@ __global__ __launch_bounds__(256) void resid_norm_kernel(
                         b.x += tb[j].x; b.y += tb[j].y; b.z += tb[j].z; b.w += tb[j].w;
                     }
             }
-            v[c][0] = rbf(bflo(xo.x) + rbf(a.x)); v[c][1] = rbf(bfhi(xo.x) + rbf(a.y));
-            v[c][2] = rbf(bflo(xo.y) + rbf(a.z)); v[c][3] = rbf(bfhi(xo.y) + rbf(a.w));
-            v[c][4] = rbf(bflo(xo.z) + rbf(b.x)); v[c][5] = rbf(bfhi(xo.z) + rbf(b.y));
-            v[c][6] = rbf(bflo(xo.w) + rbf(b.z)); v[c][7] = rbf(bfhi(xo.w) + rbf(b.w));
-            u32x4_t xn;
-            xn.x = pack2(v[c][0], v[c][1]); xn.y = pack2(v[c][2], v[c][3]);
-            xn.z = pack2(v[c][4], v[c][5]); xn.w = pack2(v[c][6], v[c][7]);
+            const u32x4_t xn = resid_add8(xo, a, b);
+            group_unpack(xn, v[c]);
             *(u32x4_t*)(x + (size_t)r * H + i0) = xn;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ss += v[c][j] * v[c][j];
+            ss = group_ss(ss, v[c]);
         }
     }
     float tot = block_sum_256(ss, sh);
-    float inv = 1.0f / sqrtf(tot / (float)H + eps);
+    float inv = norm_inv(tot, H, eps);
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int i0 = c * 2048 + threadIdx.x * 8;
         if (i0 < H) {
-            const u32x4_t w = nw[c];
-            u32x4_t y;
-            y.x = pack2(bflo(w.x) * rbf(v[c][0] * inv), bfhi(w.x) * rbf(v[c][1] * inv));
-            y.y = pack2(bflo(w.y) * rbf(v[c][2] * inv), bfhi(w.y) * rbf(v[c][3] * inv));
-            y.z = pack2(bflo(w.z) * rbf(v[c][4] * inv), bfhi(w.z) * rbf(v[c][5] * inv));
-            y.w = pack2(bflo(w.w) * rbf(v[c][6] * inv), bfhi(w.w) * rbf(v[c][7] * inv));
+            const u32x4_t y = group_scale(nw[c], v[c], inv);
             if (xn_packed) *(u32x4_t*)(xn_packed + xpack_off(r, i0, H)) = y;
             if (hlast && m.seq >= 0 && m.last) *(u32x4_t*)(hlast + (size_t)m.seq * H + i0) = y;
         }
@@ -386,4 +376,24 @@ __global__ void unpack_rows_kernel(const uint16_t* __restrict__ packed, uint16_t
 void launch_unpack_rows(const void* packed, void* out, int R, int K, hipStream_t st) {
     const size_t n = (size_t)R * K;
     hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint16_t*)packed, (uint16_t*)out, R, K);
+}
+
+// Test kernel (mtts_k_bf16_round_check): norm_ops.h's pack2_rn against common.h's f2bf on every fp32 bit pattern, in both
+// halves of the pair.  What resid_norm_kernel's bits rest on since it rounds with pack2_rn.
+__global__ __launch_bounds__(256) void bf16_round_check_kernel(unsigned long long* __restrict__ cnt2) {
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, n = gridDim.x * blockDim.x;
+    unsigned long long bad = 0, badnan = 0;
+    for (uint64_t u = tid; u < (1ull << 32); u += n) {
+        const float f = __uint_as_float((uint32_t)u);
+        const uint32_t hw = pack2_rn(f, f), sw = f2bf(f);
+        if ((hw & 0xffffu) != sw || (hw >> 16) != sw) {
+            if (((uint32_t)u & 0x7fffffffu) > 0x7f800000u) ++badnan;
+            else ++bad;
+        }
+    }
+    if (bad) atomicAdd(cnt2, bad);
+    if (badnan) atomicAdd(cnt2 + 1, badnan);
+}
+void launch_bf16_round_check(unsigned long long* cnt2, hipStream_t st) {
+    hipLaunchKernelGGL(bf16_round_check_kernel, dim3(4096), dim3(256), 0, st, cnt2);
 }

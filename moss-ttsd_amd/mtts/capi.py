@@ -119,6 +119,11 @@ _SIGS = {
     "mtts_k_gemm_sealed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_void_p]),
     "mtts_k_gemm_sealed_bench": (C.c_int32, [C.c_void_p] + [C.c_int32] * 8 + [C.POINTER(C.c_float), C.c_void_p]),
     "mtts_debug_attn_row_launches": (C.c_int64, []),
+    "mtts_debug_fold_norm_launches": (C.c_int64, []),
+    "mtts_k_oproj_resid": (C.c_int32, [C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p]),
+    "mtts_k_fold_pair": (C.c_int32, [C.c_void_p] * 5 + [C.c_float] + [C.c_int32] * 2 + [C.c_void_p, C.c_void_p]),
+    "mtts_k_bf16_round_check": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mtts_k_fold_bench": (C.c_int32, [C.c_int32] * 4 + [C.POINTER(C.c_float)]),
     "mtts_k_attn_section": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 4 +
                             [C.c_int32] * 6 + [C.c_void_p] * 6),
     "mtts_k_attn_prefill": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 5 +
