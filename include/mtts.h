@@ -333,6 +333,11 @@ int32_t mtts_debug_set_kv_len(MttsEngine* e, int32_t kv_len);   /* also fills th
  * reads when more than 1 in 8 of its pages did not seal)}.  MTTS_ESTATE when the engine keeps none (fp32 / fp16 engines,
  * MTTS_KV_PACK=0). */
 int32_t mtts_debug_kv_pack_stats(MttsEngine* e, int64_t* out6);
+/* How a step chooses its kernels (csrc/stepplan.h): the plan of the decode step the engine would run now
+ * at `pages_bound` KV pages -- its current rows, run options and read policies -- as text into buf[cap], NUL-terminated,
+ * one line per distinct launch group in issue order ("attn[0..27]: row sealed", "down: depth sealed", ...).
+ * MTTS_EINVAL when `cap` is too small. */
+int32_t mtts_debug_step_plan(MttsEngine* e, int32_t pages_bound, char* buf, int32_t cap);
 /* train of `iters` launches of one decode attention pass (1 scores, 2 P.V, 3 combine, 0 = the three in a row, 4 = the
  * whole-row kernel that does all three in one launch) at the current state; when the product would
  * run the fused q/k/v epilogue at this size the train does too and overwrites the current position's K/V rows:

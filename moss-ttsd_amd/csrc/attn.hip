@@ -539,9 +539,7 @@ __global__ __launch_bounds__(256) PK_OCC(PK) void attn_scores_kernel(
     }
 }
 
-#ifndef PV_WAVES
-#define PV_WAVES 4            // waves per pass-B block (ATT_PB / PV_WAVES pages each)
-#endif
+// PV_WAVES waves per pass-B block, ATT_PB / PV_WAVES pages each (shapes.h).
 // grid = (ceil(pages/ATT_PB), nkv, R); block PV_WAVES x 64.  V page is [token pair][d][2]: one dword holds
 // (v[2i][d], v[2i+1][d]) so that P.V is a v_dot2c_f32_bf16 against the packed (already bf16-rounded,
 // hence exact) probability pair: out[d] += p[2i]*v[2i][d] + p[2i+1]*v[2i+1][d].  Lane l covers
@@ -778,20 +776,12 @@ __global__ __launch_bounds__(512) void attn_combine_kernel(const float* __restri
 //   V phase     work item i = pages 2i, 2i+1 = attn_pv_kernel's (chunk i / 4, wave i % 4), dealt round-robin; one
 //               accumulator set across both pages, add_xor32, the item's G x 128 fp32 vector -> LDS
 //   epilogue    per chunk ((r0 + r1) + r2) + r3, chunks added in ascending order from 0.f, f2bf at xpack_off
-// Dynamic LDS (attn_row_lds_bytes): q, the new K / V rows, the per-wave rescaled q and probability pairs, then per page
-// of the launch's bound G x (8 B of pairs + 128 B of scores) and per chunk 4 x G x 512 B of item vectors.
+// Dynamic LDS: attn_row_lds_bytes (shapes.h).
 // ---------------------------------------------------------------------------------------------------
-#ifndef ROW_WAVES
-#define ROW_WAVES 12          // waves per whole-row block: 3 per SIMD, at most 168 registers each (the sealed-page bodies take
-                              // 138-152; 16 waves would have to fit 128, spill, and lose: profiles/attn_row_ab.json; 8 is no faster)
-#endif
+// (ROW_WAVES waves per block and attn_row_lds_bytes: shapes.h, where the step planner reads them too)
 static_assert(ROW_WAVES >= 6 && ROW_WAVES <= 16, "one wave per q head + the K row + the V row; at most 1024 threads");
 static std::atomic<long long> g_row_launches{0};
 long long mtts_attn_row_launches() { return g_row_launches.load(); }
-int attn_row_lds_bytes(int G, bool pk, int pages_bound) {
-    const int nch = (pages_bound + ATT_PB - 1) / ATT_PB;
-    return G * 256 + 512 + (pk ? ROW_WAVES * G * 256 : 0) + ROW_WAVES * G * 128 + G * pages_bound * (8 + 128) + PV_WAVES * nch * G * 512;
-}
 
 template <int G, bool PK>
 __global__ __launch_bounds__(ROW_WAVES * 64) void attn_row_kernel(

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "shapes.h"          // MTTS_MAXR / RCAP / PFCAP / PAGE and RowMeta: shared with the HIP-free host headers
+#include "shapes.h"          // MTTS_MAXR / RCAP / PFCAP / PAGE, ATT_PB / ATT_PF, SMALL_RP and RowMeta: shared with the HIP-free host headers
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -14,8 +14,6 @@ typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
 #define MTTS_WAVE 64
 #define MTTS_HD 128          // head_dim the kernels are written for
-#define ATT_PB 8              // KV pages per pass-B chunk, decode rows (4 waves x 2 pages)
-#define ATT_PF 2              // KV pages per pass-B chunk, prefill tiles (one wave)
 
 // bf16 bit pattern <-> fp32.  Round-to-nearest-even, NaN stays NaN, inf stays inf.
 __device__ __forceinline__ float bf2f(uint16_t u) { return __uint_as_float(((uint32_t)u) << 16); }
@@ -177,7 +175,6 @@ struct ForkJob {
 // With a handful of rows the activation is a few KiB, so the work of the small kernels between two GEMMs (split-K
 // reduce + residual + RMSNorm; the sum of the P.V chunk partials) is cheap enough to be redone by every GEMM block as
 // a prologue that leaves the MFMA B operand in LDS: three launches per layer disappear (gemm.hip: gemv_small_kernel).
-#define SMALL_RP 4
 enum { PRO_NONE = 0, PRO_NORM = 1, PRO_COMBINE = 2, PRO_ROWS = 3 };
 struct SmallPro {
     int rows;                  // live rows (<= SMALL_RP); only these are stored

@@ -1,7 +1,8 @@
 // What engine.hip (engine object, C ABI of the product path) and hooks.hip (per-kernel test / bench entry points)
 // share: the engine's definition, error reporting, and the owner of device memory.  Only these two files include it.
-// The HIP-free host code sits apart, where a CPU test can include it: kvpool.h (the KV page pool; through launch.h) and
-// staging.h (prompt staging; engine.hip alone) -- besides those includers only tests/host/pool_stage_main.cpp.
+// The HIP-free host code sits apart, where a CPU test can include it: kvpool.h (the KV page pool; through launch.h),
+// staging.h (prompt staging; engine.hip alone) and stepplan.h (how a pass chooses its kernels; included here) -- besides
+// those includers only tests/host/pool_stage_main.cpp and tests/host/step_plan_main.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "launch.h"
+#include "stepplan.h"
 
 // ---- errors -------------------------------------------------------------------
 #define MTTS_LOCAL __attribute__((visibility("hidden")))
@@ -33,25 +35,12 @@ extern MTTS_LOCAL thread_local char g_err[512];          // engine.hip; mtts_las
 
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 static inline hipStream_t S(void* s) { return (hipStream_t)s; }
-// MTTS_GEMM_DEPTH=0: every decode GEMM runs gemm_skinny_kernel, as before the depth-specialised kernels (gemm.hip);
-// the engine reads it at creation, the per-kernel hooks per call
 // Sealed weight streams, MTTS_W_SEAL=1: a kind's decode GEMMs read the twin while at most this share of its groups did not
 // seal (gate/up, down_proj, head 0, heads 1-7).  A group that did not seal costs its wave more round trips in kernels that
 // are one round trip long, so the bounds are small; each is the largest share at which the sealed launch train still beat
 // the bf16 one by more than the spread of both (profiles/wseal_ab.json).  gate/up did not beat it at the
 // share Gaussian weights have (1 group in 3 072): negative = never, and no twin is kept for it.
 static const double WSEAL_MAX_UNSEALED[4] = {-1.0, 1.0 / 512, 1.0 / 8, 1.0 / 64};
-// MTTS_FOLD_NORM: the one-row-tile decode step runs o_proj -> post-attention norm -> gate/up as the two launches of
-// gemm_fold.hip instead of three (same bits).  Read like MTTS_GEMM_DEPTH.
-#define MTTS_FOLD_NORM_DEFAULT 0
-static inline int fold_norm_env() {
-    const char* g = getenv("MTTS_FOLD_NORM");
-    return g ? (atoi(g) != 0) : MTTS_FOLD_NORM_DEFAULT;
-}
-static inline int gemm_depth_env() {
-    const char* g = getenv("MTTS_GEMM_DEPTH");
-    return (g && atoi(g) == 0) ? 0 : 1;
-}
 
 template <typename T>
 static int dalloc(T** p, size_t n, bool zero = true) {
@@ -180,16 +169,15 @@ struct MttsEngine {
     float* partial = nullptr;
     float* partial2 = nullptr;          // small-batch path: o_proj / down_proj slabs (the qkv slabs stay in `partial`)
     void *x2 = nullptr, *act_rm = nullptr;   // small-batch path: second residual buffer (ping-pong), row-major SwiGLU output
-    int small_rows = SMALL_RP;          // decode batches up to this many dialogues take the small-batch path (0 = off)
-    int gemm_depth = 1;                 // depth-specialised decode GEMMs (gemm.hip; MTTS_GEMM_DEPTH=0: off)
-    int fold_norm = MTTS_FOLD_NORM_DEFAULT;   // o_proj finishes the residual, gate/up normalises it (gemm_fold.hip; MTTS_FOLD_NORM)
-    void* xres_p = nullptr;             // ... and the x' it hands over: one 32-row tile in the X-fragment layout
+    // how a pass chooses its kernels (stepplan.h): the switches of the environment as read at creation (attn_row and
+    // kv_pack go to 0 there when the device refuses what they need), and what is fixed from then on
+    StepKnobs knobs;
+    StepCaps caps;
+    void* xres_p = nullptr;             // gemm_fold.hip: the x' o_proj hands to gate/up, one 32-row tile in the X-fragment layout
     // Sealed weight streams (gemm_sealed.hip): gate/up, down_proj and the heads also exist in the sealed
     // 13-bit form, made by every bind of such a matrix on the bind's stream, and the one-row-tile decode GEMMs read that
     // instead of the bf16 array.  MTTS_W_SEAL: 0 never (no twin is allocated), 1 per matrix kind by the share of groups that
     // did not seal (counted at mtts_weights_ready after a bind; WSEAL_MAX_UNSEALED above), 2 whenever the shape fits.
-    int w_seal = 1;
-    int w_seal_head = 1;                // the heads' sealed kernel: 1 persistent over N-tiles, 0 one tile per block (MTTS_W_SEAL_HEAD, a tuning aid)
     void *head0_s = nullptr, *heads17_s = nullptr;
     int wseal_ktw[WSEAL_KINDS] = {0, 0, 0, 0};      // k-tiles per sealed group of each kind (0: the kind has no twin)
     bool wseal_dirty = false;           // a matrix with a twin was bound since the last count
@@ -283,14 +271,12 @@ struct MttsEngine {
     int max_real = 0;
     uint64_t seed = 0;
     bool began = false, has_forced = false;
-    // decode-step graphs: one captured step per (rows, KV page bound, ...) key, replayed by mtts_step
-    struct StepGraph { int B, pages, forced, ch0, scores, topk, row, lora; hipGraphExec_t exec; };
+    // decode-step graphs: one captured step per (plan, KV page bound), replayed by mtts_step
+    struct StepGraph { StepPlan plan; int pages; hipGraphExec_t exec; };
     std::vector<StepGraph> graphs;
     hipStream_t cap_stream = nullptr;
-    bool use_graphs = true;
     // sealed KV pages (attn.hip: kv_seal): every COMPLETE page also kept in a lossless 13-bit form the decode attention
     // reads instead of the bf16 page (MTTS_KV_PACK=0: off, no second pool)
-    int kv_pack = 1;
     void *kpack = nullptr, *vpack = nullptr;
     size_t pk_layer_stride = 0;         // bytes per layer of a sealed pool
     // read policy: a page that did not seal costs a wasted sealed read + the bf16 read (29 units instead of 16), so a
@@ -298,38 +284,37 @@ struct MttsEngine {
     // counts per layer {K sealed, K not, V sealed, V not}, mtts_sync_state looks at the counts (MTTS_KV_PACK=2: no policy)
     unsigned long long *d_seal_cnt = nullptr, *h_seal_cnt = nullptr;
     std::vector<char> pack_k_on, pack_v_on;
-    int pack_min_work = 512;            // sealed reads from this many rows x KV pages up (MTTS_KV_PACK_MIN)
-    int fuse_qkv_max = 2560;            // decode: q/k/v epilogue inside the attention kernels while rows x KV pages <= this (round 3: 1024 -> 2560 = 32 rows x 80 pages, once its loads go out before the page's: wins at 32 x 64, loses at 64 x 64)
-    // whole-row decode attention (attn.hip: attn_row_kernel), MTTS_ATTN_ROW: 0 never, 1 by the shape (attn_row_auto), 2 whenever it fits
-    int attn_row = 1;
-    int n_cus = 0;                      // compute units of the device
-    int pf_mfma_pages = 0;              // prefill attention: tile-sharing MFMA kernels from this many KV pages up (0 = always; a dialogue's numerics must not depend on its batch)
     // profiling
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[PROF_N];
     int64_t prof_bytes[PROF_N] = {0, 0, 0, 0, 0};
 };
 
-// MTTS_ATTN_ROW=1: the shapes at which one block per (row, kv head) beats the two-pass kernels -- a function of the shape
-// only (both paths give the same bits, so it may depend on the batch): the blocks have to fill the machine.  No bound on
-// the context: at 32 rows it wins from 3 pages (most waves idle) to 8 k (profiles/attn_row_ab.json), and attn_row_fits
-// ends it where the LDS does
-static inline bool attn_row_auto(int rows, int nkv, int pages_bound, int n_cus) {
-    (void)pages_bound;
-    return n_cus > 0 && rows * nkv >= n_cus;
+// a decode step of the current run carries adapters: a row of it has one
+static inline bool rows_carry_adapters(const MttsEngine* e) {
+    for (int b = 0; b < e->B; ++b)
+        if (e->seq_adapter[b] >= 0) return true;
+    return false;
 }
-static inline bool attn_row_shape(const MttsEngine* e, int pages_bound) {
-    if (e->attn_row == 0 || e->f32) return false;
-    return e->attn_row == 2 || attn_row_auto(e->B, e->nkv, pages_bound, e->n_cus);
+// What plan_step is asked about a pass of R rows: the run's options and the two read policies as they stand now.  The
+// only place that gathers one.
+static inline StepState step_state(const MttsEngine* e, int heads, int R, int pages_bound, bool lora) {
+    StepState s;
+    s.heads = heads; s.B = e->B; s.R = R; s.pages_bound = pages_bound; s.lora = lora;
+    s.forced = e->has_forced; s.ch0_sampled = e->ch0_sampled != 0; s.scores_on = e->scores_on != 0; s.topk = e->topk_on;
+    for (int k = 0; k < WSEAL_KINDS; ++k) s.wseal_on[k] = e->wseal_on[k] != 0;
+    if (e->kpack) s.pack_k_on = e->pack_k_on.data();
+    if (e->vpack) s.pack_v_on = e->pack_v_on.data();
+    return s;
+}
+// the plan of the decode step the engine would run now at this page bound
+static inline StepPlan decode_plan(const MttsEngine* e, int pages_bound) {
+    return plan_step(e->knobs, e->caps, step_state(e, 1, round_up(e->B, 32), pages_bound, rows_carry_adapters(e)));
 }
 
-// this layer's sealed pools, each null where the read policy (or MTTS_KV_PACK=0) says bf16 pages
-static inline KvPack layer_pack(MttsEngine* e, int n, int pages_bound) {
-    KvPack pk{nullptr, nullptr};
-    // few rows x pages: the passes are latency-bound and the unpack sits on the critical path (B=1 at 2 k: +4 %; break-even
-    // at 8 rows x 64 pages, -6 % at 16 x 64: profiles/r03_kv_pack_ab.txt)
-    if (e->B * pages_bound < e->pack_min_work) return pk;
-    if (e->kpack && e->pack_k_on[n]) pk.k = (uint8_t*)e->kpack + e->pk_layer_stride * n;
-    if (e->vpack && e->pack_v_on[n]) pk.v = (uint8_t*)e->vpack + e->pk_layer_stride * n;
-    return pk;
+// layer n's sealed pools, each null where the plan says bf16 pages
+static inline KvPack layer_pack(const MttsEngine* e, const StepPlan& plan, int n) {
+    const LayerPlan& l = plan.layers[n];
+    return KvPack{l.k_sealed ? (uint8_t*)e->kpack + e->pk_layer_stride * n : nullptr,
+                  l.v_sealed ? (uint8_t*)e->vpack + e->pk_layer_stride * n : nullptr};
 }

@@ -107,6 +107,15 @@ static void drop_graphs(MttsEngine* e) {
     e->graphs.clear();
 }
 
+// the small-batch kernels' LDS holds this model's rows (StepCaps.small_fits)
+static bool small_path_fits(MttsEngine* e) {
+    const int H = e->H;
+    if (H > 8192 || H % 8 || e->I % 8) return false;
+    const int lim = 64 * 1024 - 33 * 1024;            // default dynamic-LDS budget next to the kernel's static 32.1 KiB
+    return mtts_small_lds_bytes(e->p_qkv, H, PRO_NORM) <= lim && mtts_small_lds_bytes(e->p_d, e->I, PRO_ROWS) <= lim &&
+           mtts_small_lds_bytes(e->p_o, e->nq * MTTS_HD, PRO_COMBINE) <= lim;
+}
+
 int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out) {
     if (!c || !out) return fail(MTTS_EINVAL, "null argument");
     if (c->head_dim != MTTS_HD) return fail(MTTS_EINVAL, "head_dim must be 128 (got %d)", c->head_dim);
@@ -136,20 +145,15 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     DevBufs& m = e->mem;
     e->cfg = *c;
     e->device = device;
-    if (const char* g = getenv("MTTS_GRAPHS")) e->use_graphs = atoi(g) != 0;
-    if (const char* g = getenv("MTTS_FUSE_QKV_MAX")) e->fuse_qkv_max = atoi(g);
-    if (const char* g = getenv("MTTS_KV_PACK")) e->kv_pack = atoi(g);
-    if (const char* g = getenv("MTTS_KV_PACK_MIN")) e->pack_min_work = atoi(g);
-    if (const char* g = getenv("MTTS_PREFILL_MFMA_PAGES")) e->pf_mfma_pages = atoi(g);
-    if (const char* g = getenv("MTTS_ATTN_ROW")) e->attn_row = std::min(std::max(atoi(g), 0), 2);
-    HIPCHK(hipDeviceGetAttribute(&e->n_cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (e->attn_row && attn_row_prepare()) {       // auto goes on without the row kernel; asking for it outright is an error
-        if (e->attn_row == 2) return fail(MTTS_EINVAL, "attn_row_kernel: the dynamic LDS limit could not be raised");
-        e->attn_row = 0;
+    StepKnobs& kn = e->knobs;
+    StepCaps& caps = e->caps;
+    kn = step_knobs_from_env();
+    HIPCHK(hipDeviceGetAttribute(&caps.n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (kn.attn_row && attn_row_prepare()) {       // auto goes on without the row kernel; asking for it outright is an error
+        if (kn.attn_row == 2) return fail(MTTS_EINVAL, "attn_row_kernel: the dynamic LDS limit could not be raised");
+        kn.attn_row = 0;
     }
-    if (const char* g = getenv("MTTS_SMALL_ROWS")) e->small_rows = std::min(std::max(atoi(g), 0), SMALL_RP);
-    e->gemm_depth = gemm_depth_env();
-    e->fold_norm = fold_norm_env();
+    caps.row_lds_limit = kn.attn_row ? attn_row_lds_limit() : 0;
     e->H = c->hidden_size; e->I = c->intermediate_size; e->L = c->num_hidden_layers;
     e->nq = c->num_attention_heads; e->nkv = c->num_key_value_heads;
     e->V0 = c->vocab_size; e->Vs = c->speech_vocab_size;
@@ -187,14 +191,12 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     e->p_d = mtts_plan_gemm(round_up(H, 32), I, 0);
     e->p_h0 = mtts_plan_gemm(e->V0_pad, H, 1);
     e->p_h17 = mtts_plan_gemm(7 * e->Vs_pad, H, 1);
-    for (GemmPlan* p : {&e->p_qkv, &e->p_o, &e->p_gu, &e->p_d, &e->p_h0, &e->p_h17}) p->depth = e->gemm_depth;
+    for (GemmPlan* p : {&e->p_qkv, &e->p_o, &e->p_gu, &e->p_d, &e->p_h0, &e->p_h17}) p->depth = kn.gemm_depth;
     // sealed twins of gate/up, down_proj and the heads, where the decode plan is one the sealed kernels take (they are
     // depth-specialised kernels: MTTS_GEMM_DEPTH=0 switches them off as well)
-    if (const char* g = getenv("MTTS_W_SEAL")) e->w_seal = std::min(std::max(atoi(g), 0), 2);
-    if (const char* g = getenv("MTTS_W_SEAL_HEAD")) e->w_seal_head = atoi(g) != 0;
-    if (!e->f32 && e->w_seal && e->gemm_depth) {
+    if (!e->f32 && kn.w_seal && kn.gemm_depth) {
         const int Hp = round_up(H, 32);
-        const auto wanted = [&](int kind) { return e->w_seal == 2 || WSEAL_MAX_UNSEALED[kind] >= 0.0; };
+        const auto wanted = [&](int kind) { return kn.w_seal == 2 || WSEAL_MAX_UNSEALED[kind] >= 0.0; };
         if (wanted(WSEAL_GU) && wseal_shape(e->p_gu, H, 2 * I, EPI_SILU)) e->wseal_ktw[WSEAL_GU] = e->p_gu.kt_per_wave;
         if (wanted(WSEAL_DOWN) && wseal_shape(e->p_d, I, Hp, EPI_PARTIAL)) e->wseal_ktw[WSEAL_DOWN] = e->p_d.kt_per_wave;
         if (wanted(WSEAL_HEAD0) && wseal_shape(e->p_h0, H, e->V0_pad, EPI_BF16)) e->wseal_ktw[WSEAL_HEAD0] = e->p_h0.kt_per_wave;
@@ -209,6 +211,21 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
         TRY(m.get_pinned(&e->h_wseal_cnt, (size_t)WSEAL_KINDS * 2));
         // the zeroed twins are the sealed form of the zeroed bf16 arrays (padding rows, a matrix not yet bound)
         e->wseal_dirty = true;
+    }
+    // what plan_step (stepplan.h) needs to know of this engine, fixed from here on
+    {
+        const int Hp = round_up(H, 32), QD = e->nq * MTTS_HD;
+        caps.G = G; caps.nkv = e->nkv; caps.L = e->L; caps.f32 = e->f32;
+        caps.small_fits = small_path_fits(e);
+        caps.fold_shape = fold_norm_shape(e->p_o, QD, e->p_gu, H, 2 * I);
+        for (int k = 0; k < WSEAL_KINDS; ++k) caps.wseal_kind[k] = e->wseal_ktw[k] != 0;
+        caps.gemm_form[GEMM_QKV] = mtts_gemm_form(EPI_PARTIAL, 1, e->p_qkv, H, e->qkv_rows, e->qkv_rows);
+        caps.gemm_form[GEMM_O] = mtts_gemm_form(EPI_PARTIAL, 1, e->p_o, QD, Hp, Hp);
+        caps.gemm_form[GEMM_GU] = mtts_gemm_form(EPI_SILU, 1, e->p_gu, H, 2 * I, 2 * I);
+        caps.gemm_form[GEMM_GU_SLAB] = mtts_gemm_form(EPI_PARTIAL, 1, e->p_gu, H, 2 * I, 2 * I);
+        caps.gemm_form[GEMM_DOWN] = mtts_gemm_form(EPI_PARTIAL, 1, e->p_d, I, Hp, Hp);
+        caps.gemm_form[GEMM_HEAD0] = mtts_gemm_form(EPI_BF16, 1, e->p_h0, H, e->V0_pad, e->V0);
+        caps.gemm_form[GEMM_HEADS] = mtts_gemm_form(EPI_BF16, 1, e->p_h17, H, 7 * e->Vs_pad, 7 * e->Vs_pad);
     }
     // activations hold a whole prefill pass (MTTS_PFCAP rows); split-K slabs: up to 8 of [MTTS_PFCAP][Npad] fp32
     size_t pmax = (size_t)8 * std::max(e->qkv_rows, round_up(H, 32));
@@ -246,7 +263,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
         // (tests/test_attn_prefill_gpu.py: test_stale_pages_behind_a_dialogues_end_reach_nothing).
         TRY(m.get((uint16_t**)&e->kcache, e->layer_stride * e->L));
         TRY(m.get((uint16_t**)&e->vcache, e->layer_stride * e->L));
-        if (e->kv_pack) {
+        if (kn.kv_pack) {
             // the second pool is an optimisation: when the card cannot hold it beside everything else (a very large
             // kv_pool_pages), the engine runs on bf16 pages alone instead of failing
             e->pk_layer_stride = (size_t)e->total_pages * e->nkv * MTTS_PKU * 64 * 16;
@@ -254,10 +271,10 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
             const size_t need = 2 * e->pk_layer_stride * e->L;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need + ((size_t)8 << 30) > free_b) {
                 fprintf(stderr, "mtts: sealed KV pages off: %.1f GB needed, %.1f GB free (8 GB kept for the run)\n", need / 1e9, free_b / 1e9);
-                e->kv_pack = 0;
+                kn.kv_pack = 0;
             }
         }
-        if (e->kv_pack) {
+        if (kn.kv_pack) {
             TRY(m.get((uint8_t**)&e->kpack, e->pk_layer_stride * e->L));
             TRY(m.get((uint8_t**)&e->vpack, e->pk_layer_stride * e->L));
             TRY(m.get(&e->d_seal_cnt, (size_t)e->L * 4));
@@ -570,12 +587,6 @@ static std::vector<int32_t> take_row_adapters(MttsEngine* e) {
     e->row_adapters_pending = false;
     return v;
 }
-// a decode step of the current run carries adapters: a row of it has one
-static bool rows_carry_adapters(const MttsEngine* e) {
-    for (int b = 0; b < e->B; ++b)
-        if (e->seq_adapter[b] >= 0) return true;
-    return false;
-}
 
 template <typename T>
 static int bind_rope_tables(MttsEngine* e, T*& c, T*& s, const void* cosb, const void* sinb, int rows, hipStream_t st) {
@@ -614,14 +625,10 @@ static int wseal_policy(MttsEngine* e) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(e->h_wseal_cnt, e->d_wseal_cnt, WSEAL_KINDS * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
     HIPCHK(hipStreamSynchronize(nullptr));
-    bool changed = false;
-    for (int k = 0; k < WSEAL_KINDS; ++k) {
+    for (int k = 0; k < WSEAL_KINDS; ++k) {      // (a changed choice changes the steps' plans: their old graphs no longer match)
         const unsigned long long groups = e->h_wseal_cnt[2 * k], bad = e->h_wseal_cnt[2 * k + 1];
-        const char on = e->wseal_ktw[k] && groups && (e->w_seal == 2 || (double)bad <= WSEAL_MAX_UNSEALED[k] * (double)groups);
-        changed |= on != e->wseal_on[k];
-        e->wseal_on[k] = on;
+        e->wseal_on[k] = e->wseal_ktw[k] && groups && (e->knobs.w_seal == 2 || (double)bad <= WSEAL_MAX_UNSEALED[k] * (double)groups);
     }
-    if (changed) drop_graphs(e);                     // captured steps hold the old choice of kernels
     e->wseal_dirty = false;
     return MTTS_OK;
 }
@@ -650,38 +657,30 @@ static void prof_end(MttsEngine* e, hipStream_t st, hipEvent_t a) {
     hipEventRecord(a, st);
 }
 
-// ---- decode step for 1..SMALL_RP dialogues: six launches per layer instead of nine ---------------------------------
-// qkv GEMM [prologue: residual + slabs + input norm] -> scores -> P.V -> o_proj [prologue: chunk sum] ->
-// gate/up + SwiGLU [prologue: residual + slabs + post-attention norm] -> down_proj; the heads take the final norm as
-// their prologue.  The residual stream alternates between two buffers (a prologue's block (0,0) writes x' while the
-// other blocks still read x); the qkv slabs live in `partial` (the fused attention epilogue reads them), the o_proj /
-// down_proj slabs in `partial2`.  Same arithmetic as forward_rows, operation for operation.
-// a new run: sealed reads everywhere, counts from zero
+// a new run: sealed reads everywhere, counts from zero (steps whose plan this changes no longer match their old graphs)
 static int pack_policy_reset(MttsEngine* e, hipStream_t st) {
     if (!e->d_seal_cnt) return 0;
     HIPCHK(hipMemsetAsync(e->d_seal_cnt, 0, (size_t)e->L * 4 * sizeof(unsigned long long), st));
-    bool changed = false;
-    for (int n = 0; n < e->L; ++n) { changed |= !e->pack_k_on[n] || !e->pack_v_on[n]; e->pack_k_on[n] = 1; e->pack_v_on[n] = 1; }
-    if (changed) drop_graphs(e);
+    e->pack_k_on.assign(e->L, 1);
+    e->pack_v_on.assign(e->L, 1);
     return 0;
 }
-// The attention section of layer n, after its qkv GEMM left `ks_qkv` slabs in `partial`: the q/k/v epilogue (a launch of
-// its own, or `fused` into the attention kernels: decode rows only), then `nphases` attention launches: scores, P.V and
-// (3) the combine that forward_small leaves to its o_proj prologue.  `prefill`: the tile-sharing kernels; `sealed`: rows
-// may read complete pages in their sealed form (decode rows; a prefill pass may complete a page itself).
-static int attend_layer(MttsEngine* e, int n, const RowMeta* d_meta, int R, int pages_bound, int ks_qkv, int nphases, bool prefill,
-                        bool fused, bool sealed, hipStream_t st, int64_t kv_tokens_hint) {
+// The attention section of layer n, after its qkv GEMM left `ks_qkv` slabs in `partial`, in the form the plan gives the
+// layer: the whole section as one launch, or the q/k/v epilogue (a launch of its own, or fused into the attention kernels)
+// and then scores, P.V and -- except on the small path, which leaves it to its o_proj prologue -- the combine.
+static int attend_layer(MttsEngine* e, const StepPlan& plan, int n, const RowMeta* d_meta, int R, int pages_bound, int ks_qkv,
+                        hipStream_t st, int64_t kv_tokens_hint) {
     static const AttnPhase decode_ph[3] = {ATTN_SCORES, ATTN_PV, ATTN_COMBINE}, prefill_ph[3] = {ATTN_PF_SCORES, ATTN_PF_PV, ATTN_PF_COMBINE};
     Layer& l = e->layers[n];
+    const AttnForm form = plan.layers[n].attn;
     const float eps = e->cfg.rms_norm_eps, scale = 1.0f / sqrtf((float)MTTS_HD);
     uint16_t* kc = (uint16_t*)e->kcache + e->layer_stride * n;
     uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * n;
     const QkvFuse fz{e->partial, ks_qkv, e->qkv_rows, (const uint16_t*)l.qn, (const uint16_t*)l.kn, e->rope_cos, e->rope_sin, eps};
-    const KvPack pk = layer_pack(e, n, pages_bound);
-    const KvPack* pkp = (sealed && (pk.k || pk.v)) ? &pk : nullptr;
-    // decode rows of a full-width batch: the whole section as one launch (the q/k/v epilogue is always inside), timed
-    // under the scores slot with the K + V bytes
-    if (!prefill && sealed && nphases == 3 && attn_row_shape(e, pages_bound) && attn_row_fits(e->nq / e->nkv, &fz, pkp, pages_bound)) {
+    const KvPack pk = layer_pack(e, plan, n);
+    const KvPack* pkp = (pk.k || pk.v) ? &pk : nullptr;
+    // one launch (the q/k/v epilogue is always inside), timed under the scores slot with the K + V bytes
+    if (form == ATTN_FORM_ROW) {
         hipEvent_t ev = nullptr;
         prof_begin(e, PROF_SCORES, st, &ev);
         if (const int rc = launch_attn(e->qbuf, kc, vc, e->d_page_table, d_meta, e->scores, e->stats, e->opart, e->attn_p, R, pages_bound,
@@ -691,6 +690,9 @@ static int attend_layer(MttsEngine* e, int n, const RowMeta* d_meta, int R, int 
         if (e->prof) e->prof_bytes[PROF_SCORES] += 2 * kv_tokens_hint * e->nkv * MTTS_HD * 2;
         return 0;
     }
+    const bool fused = form == ATTN_FORM_TWO_PASS_FUSED;
+    const AttnPhase* ph = form == ATTN_FORM_PREFILL_MFMA ? prefill_ph : decode_ph;
+    const int nphases = plan.path == PATH_SMALL ? 2 : 3;
     if (!fused)
         launch_qkv_post(e->partial, ks_qkv, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos, e->rope_sin, e->qbuf,
                         kc, vc, e->d_page_table, e->max_pages, e->total_pages, R, e->nq, e->nkv, eps, st);
@@ -699,7 +701,7 @@ static int attend_layer(MttsEngine* e, int n, const RowMeta* d_meta, int R, int 
         if (i < 2) prof_begin(e, i == 0 ? PROF_SCORES : PROF_PV, st, &ev);
         if (launch_attn(e->qbuf, kc, vc, e->d_page_table, d_meta, e->scores, e->stats, e->opart, e->attn_p, R,
                         pages_bound, e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale,
-                        fused ? &fz : nullptr, (prefill ? prefill_ph : decode_ph)[i], st, pkp))
+                        fused ? &fz : nullptr, ph[i], st, pkp))
             return fail(MTTS_EINVAL, "attention group size not built");
         if (i < 2) prof_end(e, st, ev);
     }
@@ -709,27 +711,31 @@ static int attend_layer(MttsEngine* e, int n, const RowMeta* d_meta, int R, int 
     }
     return 0;
 }
-static bool small_path_fits(MttsEngine* e) {
-    const int H = e->H;
-    if (H > 8192 || H % 8 || e->I % 8) return false;
-    const int lim = 64 * 1024 - 33 * 1024;            // default dynamic-LDS budget next to the kernel's static 32.1 KiB
-    return mtts_small_lds_bytes(e->p_qkv, H, PRO_NORM) <= lim && mtts_small_lds_bytes(e->p_d, e->I, PRO_ROWS) <= lim &&
-           mtts_small_lds_bytes(e->p_o, e->nq * MTTS_HD, PRO_COMBINE) <= lim;
+// rows whose token completed a KV page: seal it (all layers)
+static void seal_completed_pages(MttsEngine* e, const RowMeta* d_meta, int R, hipStream_t st) {
+    if (e->kpack)
+        launch_kv_seal_rows(e->kcache, e->vcache, e->kpack, e->vpack, e->d_page_table, d_meta, R, e->max_pages, e->total_pages, e->nkv, e->L, e->d_seal_cnt, st);
 }
-static int forward_small(MttsEngine* e, const RowMeta* d_meta, int pages_bound, hipStream_t st, int64_t kv_tokens_hint) {
-    const int H = e->H, I = e->I, nq = e->nq, nkv = e->nkv, Hp = round_up(H, 32), R = MTTS_MAXR;
+
+// ---- decode step for 1..SMALL_RP dialogues: six launches per layer instead of nine ---------------------------------
+// qkv GEMM [prologue: residual + slabs + input norm] -> scores -> P.V -> o_proj [prologue: chunk sum] ->
+// gate/up + SwiGLU [prologue: residual + slabs + post-attention norm] -> down_proj; the heads take the final norm as
+// their prologue.  The residual stream alternates between two buffers (a prologue's block (0,0) writes x' while the
+// other blocks still read x); the qkv slabs live in `partial` (the fused attention epilogue reads them), the o_proj /
+// down_proj slabs in `partial2`.  Same arithmetic as forward_rows, operation for operation.
+static int forward_small(MttsEngine* e, const StepPlan& plan, const RowMeta* d_meta, int pages_bound, hipStream_t st, int64_t kv_tokens_hint) {
+    const int H = e->H, I = e->I, nq = e->nq, Hp = round_up(H, 32), R = MTTS_MAXR;
     const float eps = e->cfg.rms_norm_eps;
     uint16_t* xa = (uint16_t*)e->x;                    // embed_norm has left the embedding sum here
     uint16_t* xb = (uint16_t*)e->x2;
     SmallPro base{};
-    base.rows = e->B; base.eps = eps; base.slab_npad = Hp;
+    base.rows = plan.B; base.eps = eps; base.slab_npad = Hp;
     for (int n = 0; n < e->L; ++n) {
         Layer& l = e->layers[n];
         SmallPro pq = base;                            // input norm (+ the previous layer's down_proj slabs)
         pq.x_in = xa; pq.x_out = xb; pq.slabs = e->partial2; pq.ksplit = n ? e->p_d.ksplit : 0; pq.norm_w = (const uint16_t*)l.ln_in;
         launch_gemv_small(EPI_PARTIAL, PRO_NORM, e->p_qkv, l.wqkv, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, pq, st);
-        TRY(attend_layer(e, n, d_meta, R, pages_bound, e->p_qkv.ksplit, 2, false, e->B * pages_bound <= e->fuse_qkv_max, true, st,
-                         kv_tokens_hint));
+        TRY(attend_layer(e, plan, n, d_meta, R, pages_bound, e->p_qkv.ksplit, st, kv_tokens_hint));
         SmallPro po = base;                            // o_proj: the chunk partials of P.V are summed in its prologue
         po.opart = e->opart; po.meta = d_meta; po.nchunks_max = e->nchunks_max; po.nq = nq; po.pages_per_chunk = ATT_PB;
         launch_gemv_small(EPI_PARTIAL, PRO_COMBINE, e->p_o, l.wo, nq * MTTS_HD, Hp, Hp, e->partial2, nullptr, po, st);
@@ -740,8 +746,7 @@ static int forward_small(MttsEngine* e, const RowMeta* d_meta, int pages_bound, 
         pd.xrows = (const uint16_t*)e->act_rm;
         launch_gemv_small(EPI_PARTIAL, PRO_ROWS, e->p_d, l.wd, I, Hp, Hp, e->partial2, nullptr, pd, st);
     }
-    if (e->kpack)                                      // rows whose token completed a KV page: seal it (all layers)
-        launch_kv_seal_rows(e->kcache, e->vcache, e->kpack, e->vpack, e->d_page_table, d_meta, R, e->max_pages, e->total_pages, nkv, e->L, e->d_seal_cnt, st);
+    seal_completed_pages(e, d_meta, R, st);
     SmallPro ph = base;                                // final norm (+ the last down_proj slabs) in front of the 8 heads
     ph.x_in = xa; ph.x_out = nullptr; ph.slabs = e->partial2; ph.ksplit = e->p_d.ksplit; ph.norm_w = (const uint16_t*)e->final_norm;
     // (same plan as the general path: a different K partition over the waves would change the fp32 sums, and with them
@@ -752,107 +757,100 @@ static int forward_small(MttsEngine* e, const RowMeta* d_meta, int pages_bound, 
     return MTTS_OK;
 }
 
-// ---- one forward pass: R rows = decode rows (<= MTTS_RCAP, one dialogue each) or a prefill pass (<= MTTS_PFCAP) ----
-// heads: 0 none, 1 from xn (rows are sequences: decode), 2 from hlast (end of prefill)
-// lora: a row of the pass has an adapter (mtts_set_row_adapters / mtts_set_slot_adapter).  The GEMMs, norms and attention
+// One GEMM of forward_rows on `tiles` activation row tiles, by the plan's choice for it: the tiled kernel with `ks`
+// k-splits (prefill passes), the sealed twin `Ws`, or launch_gemm, which picks among its kernels by the shape.  A sealed
+// launch that the launcher refuses is an error, never a silent bf16 launch.  It cannot happen today: plan_step asks only
+// at one row tile without adapters and for a kind whose policy is on; wseal_on[k] implies wseal_ktw[k] (wseal_policy),
+// which implies a twin, wseal_shape of this very GemmPlan and gemm_depth (mtts_engine_create) -- all the launcher checks.
+static int run_gemm(int epi, bool tiled, int R, int ks, bool sealed, int head_form, const GemmPlan& p, const void* Ws, const void* Wp,
+                    const void* Xp, int K, int Npad, int n_valid, float* partial, uint16_t* out, hipStream_t st) {
+    const int mb = (R + 31) / 32;
+    if (tiled) launch_gemm_tile(epi, R, ks, Wp, Xp, K, Npad, n_valid, partial, out, st);
+    else if (!sealed) launch_gemm(epi, mb, p, Wp, Xp, K, Npad, n_valid, partial, out, st);
+    else if (!launch_gemm_sealed(epi, mb, p, Ws, Wp, Xp, K, Npad, n_valid, partial, out, head_form, st))
+        return fail(MTTS_ESTATE, "the plan asks for a sealed weight read that the launcher does not take (K %d, N %d, %d row tiles)", K, Npad, mb);
+    return 0;
+}
+
+// ---- one forward pass: plan.R rows = decode rows (<= MTTS_RCAP, one dialogue each) or a prefill pass (<= MTTS_PFCAP) ----
+// plan.heads: 0 none, 1 from xn (rows are sequences: decode), 2 from hlast (end of prefill)
+// plan.lora: a row of the pass has an adapter (mtts_set_row_adapters / mtts_set_slot_adapter).  The GEMMs, norms and attention
 // kernels are then the same launches with the same arguments, except that after the qkv, o_proj and down_proj GEMMs the
 // adapters' delta goes into the slab behind the GEMM's last one and the consumer sums one slab more, and that gate/up
-// writes a slab instead of running its SwiGLU epilogue (delta into slab 1, swiglu_slabs_kernel on the sum).  The small
-// path has no slabs to extend and is not taken; its arithmetic is forward_rows', so nothing depends on that.
-static int forward_rows(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d_meta, int R, int pages_bound,
-                        int heads, bool lora, hipStream_t st, int64_t kv_tokens_hint) {
-    const int H = e->H, I = e->I, nq = e->nq, nkv = e->nkv;
+// writes a slab instead of running its SwiGLU epilogue (delta into slab 1, swiglu_slabs_kernel on the sum).
+// Which launches: plan_step (stepplan.h).  Nothing below decides.
+static int forward_rows(MttsEngine* e, const StepPlan& plan, const int32_t* d_tokens, const RowMeta* d_meta, int pages_bound,
+                        hipStream_t st, int64_t kv_tokens_hint) {
+    const int H = e->H, I = e->I, nq = e->nq, nkv = e->nkv, R = plan.R, mb = plan.mb;
     const float eps = e->cfg.rms_norm_eps;
     const int Hp = round_up(H, 32);
-    const int mb = (R + 31) / 32;                    // activation row tiles sharing each weight stream
-    // prefill passes always take the tiled GEMM with a split-K that depends on the shape only (chosen for a
-    // 1024-row pass: good from one dialogue's prompt up to a full pass): a prompt's hidden states then do not
-    // depend on how many rows (other dialogues) share its pass
-    const bool tiled = heads != 1;
-    if (e->f32) return forward_rows_f32(e, d_tokens, d_meta, heads == 1 ? e->B : R, heads, st);
+    const bool tiled = plan.tiled, lora = plan.lora;
+    if (plan.path == PATH_F32) return forward_rows_f32(e, d_tokens, d_meta, plan.heads == 1 ? plan.B : R, plan.heads, st);
     launch_embed_norm(d_tokens, d_meta, e->d_tables, e->layers[0].ln_in, e->x, e->xn, R, H, eps, st);
-    if (heads == 1 && !lora && e->B <= e->small_rows && small_path_fits(e)) return forward_small(e, d_meta, pages_bound, st, kv_tokens_hint);
+    if (plan.path == PATH_SMALL) return forward_small(e, plan, d_meta, pages_bound, st, kv_tokens_hint);
     if (lora && !e->d_bank) return fail(MTTS_ESTATE, "a pass with adapters on an engine without a bank");
     const int QD = nq * MTTS_HD, KD = nkv * MTTS_HD, EL = e->L * 7;
-    // decode rows in one row tile, no adapter row: o_proj -> post-attention norm -> gate/up as gemm_fold.hip's two launches
-    // where both GEMMs have the shape those kernels are built for (everything else issues the three launches below)
-    const bool fold = e->fold_norm && heads == 1 && mb == 1 && !lora && e->gemm_depth && !e->wseal_on[WSEAL_GU] &&
-                      fold_norm_shape(e->p_o, nq * MTTS_HD, e->p_gu, H, 2 * I);
     const LoraJob j_qkv{3, e->qkv_rows, H, EL, {{0, QD, 1, 0}, {QD, KD, 1, 1}, {QD + KD, KD, 1, 2}}};
     const LoraJob j_o{1, Hp, QD, EL, {{0, H, 1, 3}}}, j_gu{2, 2 * I, H, EL, {{0, I, 2, 4}, {1, I, 2, 5}}}, j_d{1, Hp, I, EL, {{0, H, 1, 6}}};
+    // prefill passes take the tiled GEMM with a split-K that depends on the shape only (chosen for a 1024-row pass: good
+    // from one dialogue's prompt up to a full pass): a prompt's hidden states then do not depend on how many rows (other
+    // dialogues) share its pass
+    const int ks_qkv = tiled ? mtts_tile_ksplit(e->qkv_rows, H, 1024) : e->p_qkv.ksplit;
+    const int ks_o = tiled ? mtts_tile_ksplit(Hp, QD, 1024) : e->p_o.ksplit;
+    const int ks_d = tiled ? mtts_tile_ksplit(Hp, I, 1024) : e->p_d.ksplit;
+    const int ex = lora ? 1 : 0;                     // slabs the consumers sum beyond the GEMM's
+    // gate/up: the same plan with or without adapters (p_gu; one k-split of the tile GEMM), so slab 0 holds the sums
+    // the fused epilogue would have rounded
+    const int gu_epi = lora ? EPI_PARTIAL : EPI_SILU;
+    float* gu_slab = lora ? e->partial : nullptr;
     for (int n = 0; n < e->L; ++n) {
         Layer& l = e->layers[n];
         // the adapters' delta of this layer's matrices in `job`, for the rows in `xp`, into slab `ks` of the partial buffer
         auto delta = [&](const LoraJob& job, const void* xp, int ks) {
             launch_lora_delta(xp, d_meta, e->d_seq_adapter, e->d_bank + (size_t)n * 7, job, e->partial + (size_t)ks * MTTS_PFCAP * job.Npad, R, st);
         };
-        const int ex = lora ? 1 : 0;                     // slabs the consumers sum beyond the GEMM's
-        // one row tile without adapters: gate/up and down_proj read their sealed twins where the policy says so (same bits)
-        const bool sealed_gu = !lora && e->wseal_on[WSEAL_GU], sealed_d = !lora && e->wseal_on[WSEAL_DOWN];
-        const int ks_qkv = tiled ? mtts_tile_ksplit(e->qkv_rows, H, 1024) : e->p_qkv.ksplit;
-        const int ks_o = tiled ? mtts_tile_ksplit(Hp, nq * MTTS_HD, 1024) : e->p_o.ksplit;
-        const int ks_d = tiled ? mtts_tile_ksplit(Hp, I, 1024) : e->p_d.ksplit;
-        if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_qkv, l.wqkv, e->xn, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, st);
-        else launch_gemm(EPI_PARTIAL, mb, e->p_qkv, l.wqkv, e->xn, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, st);
+        TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_qkv, false, 0, e->p_qkv, nullptr, l.wqkv, e->xn, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, st));
         if (lora) delta(j_qkv, e->xn, ks_qkv);
-        // decode rows (one dialogue each): the q/k/v epilogue runs inside the attention kernels; prefill passes
-        // need every K/V row of the pass in the cache before any of its attention runs, so they keep the launch
-        // (fused where it pays: every attention block repeats the q epilogue, which costs more than the saved launch
-        // once rows x pages is large -- break-even between 32 x 64 and 64 x 64 rows x pages since round 3; the results are bit-identical)
-        // decode rows are one dialogue each and read complete pages in their sealed form; prefill tiles are 32 consecutive
-        // positions of one dialogue, share their K/V pages (chunks of ATT_PF pages) and read the bf16 pages
-        TRY(attend_layer(e, n, d_meta, R, pages_bound, ks_qkv + ex, 3, heads != 1 && pages_bound >= e->pf_mfma_pages,
-                         heads == 1 && e->B * pages_bound <= e->fuse_qkv_max, heads == 1, st, kv_tokens_hint));
-        // gate/up: the same plan with or without adapters (p_gu; one k-split of the tile GEMM), so slab 0 holds the sums
-        // the fused epilogue would have rounded
-        const int gu_epi = lora ? EPI_PARTIAL : EPI_SILU;
-        float* gu_slab = lora ? e->partial : nullptr;
-        if (fold) {
+        TRY(attend_layer(e, plan, n, d_meta, R, pages_bound, ks_qkv + ex, st, kv_tokens_hint));
+        if (plan.fold) {
             // o_proj leaves no slabs: it finishes x' (rows < R), gate/up normalises it.  Both buffers hold a whole tile; rows >= R
             // of xres_p keep zeros or the x' of an earlier, larger batch (finite), which gate/up normalises and multiplies like the
             // stale xn rows of the three launches: nothing reads the result rows >= R
             launch_oproj_resid(l.wo, e->attn_p, e->x, e->xres_p, R, Hp, st);
             launch_gateup_norm(l.wgu, e->xres_p, l.ln_post, eps, e->act_p, 2 * I, st);
         } else {
-            if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
-            else launch_gemm(EPI_PARTIAL, mb, e->p_o, l.wo, e->attn_p, nq * MTTS_HD, Hp, Hp, e->partial, nullptr, st);
+            TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_o, false, 0, e->p_o, nullptr, l.wo, e->attn_p, QD, Hp, Hp, e->partial, nullptr, st));
             if (lora) delta(j_o, e->attn_p, ks_o);
             launch_resid_norm(e->partial, ks_o + ex, Hp, e->x, l.ln_post, e->xn, nullptr, d_meta, R, H, eps, st);
-            if (tiled) launch_gemm_tile(gu_epi, R, 1, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
-            else if (!sealed_gu || !launch_gemm_sealed(EPI_SILU, mb, e->p_gu, l.wgu_s, l.wgu, e->xn, H, 2 * I, 2 * I, nullptr, (uint16_t*)e->act_p, 0, st))
-                launch_gemm(gu_epi, mb, e->p_gu, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st);
+            TRY(run_gemm(gu_epi, tiled, R, 1, plan.sealed[WSEAL_GU], 0, e->p_gu, l.wgu_s, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st));
         }
         if (lora) {
             delta(j_gu, e->xn, 1);
             launch_swiglu_slabs(e->partial, e->partial + (size_t)MTTS_PFCAP * 2 * I, e->act_p, mb * 32, I, st);
         }
-        if (tiled) launch_gemm_tile(EPI_PARTIAL, R, ks_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
-        else if (!sealed_d || !launch_gemm_sealed(EPI_PARTIAL, mb, e->p_d, l.wd_s, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, 0, st))
-            launch_gemm(EPI_PARTIAL, mb, e->p_d, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st);
+        TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_d, plan.sealed[WSEAL_DOWN], 0, e->p_d, l.wd_s, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st));
         if (lora) delta(j_d, e->act_p, ks_d);
         const bool lastl = (n == e->L - 1);
         const void* nw = lastl ? e->final_norm : e->layers[n + 1].ln_in;
         launch_resid_norm(e->partial, ks_d + ex, Hp, e->x, nw, e->xn, lastl ? e->hlast : nullptr, d_meta, R, H, eps, st);
     }
-    if (e->kpack)                                      // rows whose token completed a KV page: seal it (all layers)
-        launch_kv_seal_rows(e->kcache, e->vcache, e->kpack, e->vpack, e->d_page_table, d_meta, R, e->max_pages, e->total_pages, nkv, e->L, e->d_seal_cnt, st);
-    if (heads) {
+    seal_completed_pages(e, d_meta, R, st);
+    if (plan.heads) {
         const void* xin = e->xn;
-        int hmb = mb;
-        if (heads == 2) {
-            hmb = (e->B + 31) / 32;
-            launch_pack_rows(e->hlast, e->xh, e->B, H, hmb, st);
+        if (plan.heads == 2) {                         // the dialogues' last rows, packed into tiles of their own
+            launch_pack_rows(e->hlast, e->xh, plan.B, H, plan.hmb, st);
             xin = e->xh;
         }
-        if (lora || !e->wseal_on[WSEAL_HEAD0] ||
-            !launch_gemm_sealed(EPI_BF16, hmb, e->p_h0, e->head0_s, e->head0, xin, H, e->V0_pad, e->V0, nullptr, (uint16_t*)e->logits0, e->w_seal_head, st))
-            launch_gemm(EPI_BF16, hmb, e->p_h0, e->head0, xin, H, e->V0_pad, e->V0, nullptr, (uint16_t*)e->logits0, st);
-        if (lora || !e->wseal_on[WSEAL_HEADS] ||
-            !launch_gemm_sealed(EPI_BF16, hmb, e->p_h17, e->heads17_s, e->heads17, xin, H, 7 * e->Vs_pad, 7 * e->Vs_pad, nullptr, (uint16_t*)e->logits17, e->w_seal_head, st))
-            launch_gemm(EPI_BF16, hmb, e->p_h17, e->heads17, xin, H, 7 * e->Vs_pad, 7 * e->Vs_pad, nullptr, (uint16_t*)e->logits17, st);
+        const int hr = plan.hmb * 32, form = plan.head_persistent ? 1 : 0;
+        TRY(run_gemm(EPI_BF16, false, hr, 0, plan.sealed[WSEAL_HEAD0], form, e->p_h0, e->head0_s, e->head0, xin, H, e->V0_pad, e->V0, nullptr, (uint16_t*)e->logits0, st));
+        TRY(run_gemm(EPI_BF16, false, hr, 0, plan.sealed[WSEAL_HEADS], form, e->p_h17, e->heads17_s, e->heads17, xin, H, 7 * e->Vs_pad, 7 * e->Vs_pad, nullptr, (uint16_t*)e->logits17, st));
     }
     HIPCHK(hipGetLastError());
     return MTTS_OK;
+}
+// a pass that is not a decode step: R staged rows, heads 0 or 2
+static int forward_staged(MttsEngine* e, const int32_t* d_tokens, const RowMeta* d_meta, int R, int pages_bound, int heads, bool lora, hipStream_t st) {
+    return forward_rows(e, plan_step(e->knobs, e->caps, step_state(e, heads, R, pages_bound, lora)), d_tokens, d_meta, pages_bound, st, 0);
 }
 
 // prefill of the first `Mpad` staged rows in passes of up to MTTS_PFCAP (a multiple of MTTS_RCAP each); K/V of a pass are
@@ -861,7 +859,7 @@ static int prefill_staged(MttsEngine* e, size_t Mpad, int pages_bound, int last_
     const size_t pfcap = e->f32 ? MTTS_PF32CAP : MTTS_PFCAP;
     for (size_t off = 0; off < Mpad; off += pfcap) {
         const int rows = (int)std::min<size_t>(pfcap, Mpad - off);
-        TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, off + rows >= Mpad ? last_heads : 0, lora, st, 0));
+        TRY(forward_staged(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, off + rows >= Mpad ? last_heads : 0, lora, st));
     }
     return 0;
 }
@@ -1124,28 +1122,28 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
 // Nothing in it depends on the host (step counters, lengths and the stop flag live on the device), so the same
 // launches repeat until the KV page bound grows: they are captured once per bound into a hipGraph and replayed --
 // a dependent kernel costs ~1.5 us inside a graph against ~2.9 us launched on a stream (tools/latency_probe.hip).
-static int step_body(MttsEngine* e, int pages_bound, hipStream_t st, int64_t kvtok) {
+// The plan (decode_plan) says which launches; it is also what a captured step is found by.
+static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipStream_t st, int64_t kvtok) {
     launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
-                  e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, e->B, e->sscr, e->ch0_sampled,
-                  full_cap_for(e->V0), e->scores_on, st);
+                  e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, plan.B, e->sscr, plan.ch0_sampled,
+                  full_cap_for(e->V0), plan.scores_on, st);
     GenTopkOut gt;                       // top_logprobs: the raw distribution at the decisions just written, into this step's row
-    if (e->topk_on) {
-        gt = GenTopkOut{e->topk_on, e->d_gt_logp, e->d_gt_ids, e->d_gt_tlp};
-        launch_gen_topk(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_scfg, e->d_ls, e->d_seqs, e->d_decisions, e->B,
+    if (plan.topk) {
+        gt = GenTopkOut{plan.topk, e->d_gt_logp, e->d_gt_ids, e->d_gt_tlp};
+        launch_gen_topk(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_scfg, e->d_ls, e->d_seqs, e->d_decisions, plan.B,
                         e->gtscr, gt, st);
     }
-    launch_update(e->d_decisions, e->d_declog, e->has_forced ? e->d_forced : nullptr, e->d_tf, e->d_gen, e->d_cur,
+    launch_update(e->d_decisions, e->d_declog, plan.forced ? e->d_forced : nullptr, e->d_tf, e->d_gen, e->d_cur,
                   e->d_seqs, e->d_meta, e->d_bitmaps, e->bm_words, e->d_ls, e->cfg.eos_token_id,
                   e->cfg.speech_pad_token, e->cfg.speech_range_lo, e->cfg.speech_range_hi,
-                  e->scores_on ? e->sscr.lp : nullptr, e->scores_on ? e->d_lp : nullptr, gt, st);
-    return forward_rows(e, e->d_cur, e->d_meta, round_up(e->B, 32), pages_bound, 1, rows_carry_adapters(e), st, kvtok);
+                  plan.scores_on ? e->sscr.lp : nullptr, plan.scores_on ? e->d_lp : nullptr, gt, st);
+    return forward_rows(e, plan, e->d_cur, e->d_meta, pages_bound, st, kvtok);
 }
 
 static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
-    const int forced = e->has_forced ? 1 : 0, row = attn_row_shape(e, pages) ? 1 : 0, lora = rows_carry_adapters(e) ? 1 : 0;
+    StepPlan plan = decode_plan(e, pages);
     for (auto& g : e->graphs)
-        if (g.B == e->B && g.pages == pages && g.forced == forced && g.ch0 == e->ch0_sampled && g.scores == e->scores_on && g.topk == e->topk_on && g.row == row &&
-            g.lora == lora) {
+        if (g.pages == pages && g.plan == plan) {
             *out = g.exec;
             return MTTS_OK;
         }
@@ -1153,7 +1151,7 @@ static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     if (!e->cap_stream) HIPCHK(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
-    int rc = step_body(e, pages, e->cap_stream, 0);
+    int rc = step_body(e, plan, pages, e->cap_stream, 0);
     hipError_t ce = hipStreamEndCapture(e->cap_stream, &g);
     if (rc) { if (g) hipGraphDestroy(g); return rc; }
     HIPCHK(ce);
@@ -1161,7 +1159,7 @@ static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     HIPCHK(ie);
-    e->graphs.push_back({e->B, pages, forced, e->ch0_sampled, e->scores_on, e->topk_on, row, lora, exec});
+    e->graphs.push_back({std::move(plan), pages, exec});
     *out = exec;
     return MTTS_OK;
 }
@@ -1182,7 +1180,7 @@ static int issue_steps(MttsEngine* e, int n, hipStream_t st) {
         }
         TRY(e->pool.flush(ship));
         const int pages_bound = pages_for(len_bound);
-        if (e->use_graphs && !e->prof) {
+        if (e->knobs.use_graphs && !e->prof) {
             // the attention grids are sized by the page bound: round it up to a whole pass-B chunk so that one
             // graph serves ATT_PB pages (512 steps); blocks past a row's last page exit at once
             hipGraphExec_t exec = nullptr;
@@ -1194,7 +1192,7 @@ static int issue_steps(MttsEngine* e, int n, hipStream_t st) {
             // rough KV token count for the profile's byte figure: every row at its current length
             int64_t kvtok = 0;
             for (int b = 0; b < e->B; ++b) if (e->slot_live[b]) kvtok += e->n_real[b] + e->steps_issued + 1;
-            TRY(step_body(e, pages_bound, st, kvtok));
+            TRY(step_body(e, decode_plan(e, pages_bound), pages_bound, st, kvtok));
             prof_end(e, st, ev);
         }
         e->steps_issued++;
@@ -1216,15 +1214,12 @@ int32_t mtts_sync_state(MttsEngine* e, int32_t* steps_done, int32_t* all_finishe
     if (!e->continuous) HIPCHK(hipMemcpyAsync(e->h_seqs, e->d_seqs, e->B * sizeof(SeqState), hipMemcpyDeviceToHost, S(stream)));
     if (e->d_seal_cnt) HIPCHK(hipMemcpyAsync(e->h_seal_cnt, e->d_seal_cnt, (size_t)e->L * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, S(stream)));
     HIPCHK(hipStreamSynchronize(S(stream)));
-    if (e->d_seal_cnt && e->kv_pack == 1) {
-        bool changed = false;
+    if (e->d_seal_cnt && e->knobs.kv_pack == 1) {    // the read policy per layer; the next step's plan follows it, and with it its graph
         for (int n = 0; n < e->L; ++n) {
             const unsigned long long* c = e->h_seal_cnt + (size_t)n * 4;
-            const bool k_on = c[0] + c[1] < 16 || c[1] * 8 <= c[0] + c[1], v_on = c[2] + c[3] < 16 || c[3] * 8 <= c[2] + c[3];
-            changed |= (k_on != (bool)e->pack_k_on[n]) || (v_on != (bool)e->pack_v_on[n]);
-            e->pack_k_on[n] = k_on; e->pack_v_on[n] = v_on;
+            e->pack_k_on[n] = c[0] + c[1] < 16 || c[1] * 8 <= c[0] + c[1];
+            e->pack_v_on[n] = c[2] + c[3] < 16 || c[3] * 8 <= c[2] + c[3];
         }
-        if (changed) drop_graphs(e);                 // the captured steps hold the old choice of kernels
     }
     if (e->h_ls->error) return fail(MTTS_EINVAL, "device sampler error %d: more than 4096 candidate tokens (set top_k so that the k-th score's radix bin holds <= 4096 tokens)", e->h_ls->error);
     if (!e->continuous) {
@@ -1499,7 +1494,7 @@ static int32_t score_call(MttsEngine* e, const int64_t* ids, const uint8_t* mask
         const int pages_bound = std::max(1, pages_for(max_len));
         for (size_t off = 0; off < Mpad; off += pfcap) {
             const int rows = (int)std::min<size_t>(pfcap, Mpad - off);
-            TRY(forward_rows(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, 0, false, st, 0));
+            TRY(forward_staged(e, e->d_pf_tokens + off * 8, e->d_pf_meta + off, rows, pages_bound, 0, false, st));
             if (k > 0)
                 TRY(score_pass(e, e->d_sc_labels + off * 8, labels ? e->d_sc_logp + off * 8 : nullptr, rows, st, k,
                                e->d_sc_top_ids + off * 8 * k, e->d_sc_top_logp + off * 8 * k));

@@ -605,12 +605,22 @@ static void launch_gemm_mb(int mb, const GemmPlan& p, const void* Wp, const void
 static long long g_depth_launches = 0;      // launches that took a depth-specialised kernel (test hook: mtts_debug_gemm_depth_launches)
 long long mtts_gemm_depth_launches() { return g_depth_launches; }
 void mtts_gemm_depth_note() { ++g_depth_launches; }      // (gemm_sealed.hip: its kernels are depth-specialised ones reading the sealed twin)
-static bool launch_gemm_depth(int epi, int mb, const GemmPlan& p, const void* Wp, const void* Xp, int K, int Npad,
-                              int n_valid, float* partial, uint16_t* out, hipStream_t st) {
+// which kernel launch_gemm gives the call (the step planner's describe() names it; launch_gemm_depth dispatches on it)
+int mtts_gemm_form(int epi, int mb, const GemmPlan& p, int K, int Npad, int n_valid) {
     const int KT = K / 16;
     if (!p.depth || mb > 1 || p.waves != 8 || K % 16 || KT != p.ksplit * 8 * p.kt_per_wave || p.kt_per_split != 8 * p.kt_per_wave)
-        return false;
-    if (epi == EPI_PARTIAL) {
+        return GEMM_SKINNY;
+    // o_proj (4 k-tiles per wave) and down_proj (12).  8 (qkv: one unrolled pass of gemm_skinny_kernel already) was
+    // built and timed: 5.32 against 5.47 us, inside the spread of either leg, so it is not instantiated.
+    if (epi == EPI_PARTIAL) return (p.kt_per_wave == 4 || p.kt_per_wave == 12) ? GEMM_DEPTH : GEMM_SKINNY;
+    if (epi == EPI_SILU && p.ksplit == 1 && p.kt_per_wave == 16 && Npad % 96 == 0 && n_valid == Npad) return GEMM_GATEUP48;
+    return GEMM_SKINNY;
+}
+static bool launch_gemm_depth(int epi, int mb, const GemmPlan& p, const void* Wp, const void* Xp, int K, int Npad,
+                              int n_valid, float* partial, uint16_t* out, hipStream_t st) {
+    const int KT = K / 16, form = mtts_gemm_form(epi, mb, p, K, Npad, n_valid);
+    if (form == GEMM_SKINNY) return false;
+    if (form == GEMM_DEPTH) {
         dim3 grid(Npad / 32, p.ksplit);
 #define MTTS_DEPTH_CASE(KTW)                                                                                        \
     case KTW:                                                                                                       \
@@ -618,8 +628,6 @@ static bool launch_gemm_depth(int epi, int mb, const GemmPlan& p, const void* Wp
                            (const u32x4_t*)Xp, KT, partial, out, Npad, n_valid);                                    \
         ++g_depth_launches;                                                                                         \
         return true;
-        // o_proj (4 k-tiles per wave) and down_proj (12).  8 (qkv: one unrolled pass of gemm_skinny_kernel already) was
-        // built and timed: 5.32 against 5.47 us, inside the spread of either leg, so it is not instantiated.
         switch (p.kt_per_wave) {
             MTTS_DEPTH_CASE(4)
             MTTS_DEPTH_CASE(12)
@@ -627,13 +635,10 @@ static bool launch_gemm_depth(int epi, int mb, const GemmPlan& p, const void* Wp
 #undef MTTS_DEPTH_CASE
         return false;
     }
-    if (epi == EPI_SILU && p.ksplit == 1 && p.kt_per_wave == 16 && Npad % 96 == 0 && n_valid == Npad) {
-        hipLaunchKernelGGL((gemm_gateup48_kernel<8, 16>), dim3(Npad / 48), dim3(512), 0, st, (const u32x4_t*)Wp,
-                           (const u32x4_t*)Xp, KT, out, Npad);
-        ++g_depth_launches;
-        return true;
-    }
-    return false;
+    hipLaunchKernelGGL((gemm_gateup48_kernel<8, 16>), dim3(Npad / 48), dim3(512), 0, st, (const u32x4_t*)Wp,
+                       (const u32x4_t*)Xp, KT, out, Npad);
+    ++g_depth_launches;
+    return true;
 }
 
 // mb = number of 32-row activation tiles (1..4) that share the weight stream

@@ -797,11 +797,12 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
     const int R = round_up(e->B, 32);
     const int len_bound = e->max_real + e->steps_issued + 1;
     const int pages_bound = pages_for(len_bound);
+    const StepPlan plan = decode_plan(e, pages_bound);      // the step's sealed reads per layer
     if (phase == ATTN_ROW) {
         if (attn_row_prepare()) return fail(MTTS_EINVAL, "attn_row_kernel: the dynamic LDS limit could not be raised");
         const QkvFuse f0{e->partial, e->p_qkv.ksplit, e->qkv_rows, nullptr, nullptr, nullptr, nullptr, 0.f};
         for (int n = 0; n < e->L; ++n) {
-            const KvPack pk = layer_pack(e, n, pages_bound);
+            const KvPack pk = layer_pack(e, plan, n);
             if (!attn_row_fits(e->nq / e->nkv, &f0, (pk.k || pk.v) ? &pk : nullptr, pages_bound))
                 return fail(MTTS_EINVAL, "attn_bench: the whole-row kernel does not take this shape");
         }
@@ -816,9 +817,9 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
             // the product's decode launch: q/k/v epilogue fused (the slabs are whatever the last step left there)
             const QkvFuse fz{e->partial, e->p_qkv.ksplit, e->qkv_rows, (const uint16_t*)e->layers[layer].qn,
                              (const uint16_t*)e->layers[layer].kn, e->rope_cos, e->rope_sin, e->cfg.rms_norm_eps};
-            const KvPack pk = layer_pack(e, layer, pages_bound);
+            const KvPack pk = layer_pack(e, plan, layer);
             launch_attn(e->qbuf, kc, vc, e->d_page_table, e->d_meta, e->scores, e->stats, e->opart, e->attn_p, R, pages_bound,
-                        e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale, (phase == ATTN_ROW || e->B * pages_bound <= e->fuse_qkv_max) ? &fz : nullptr, (AttnPhase)phase, nullptr,
+                        e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale, (phase == ATTN_ROW || e->B * pages_bound <= e->knobs.fuse_qkv_max) ? &fz : nullptr, (AttnPhase)phase, nullptr,
                         (pk.k || pk.v) ? &pk : nullptr);
         }
     };
@@ -1005,6 +1006,16 @@ int32_t mtts_k_bf16_round_check(int64_t* out2, void* stream) {
     HIPCHK(hipMemcpyAsync(h, cnt, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     out2[0] = (int64_t)h[0]; out2[1] = (int64_t)h[1];
+    return MTTS_OK;
+}
+
+// describe() (stepplan.h) of the decode step the engine would run now at this KV page bound -- its current rows, run
+// options and read policies -- as text into buf[cap], NUL-terminated; MTTS_EINVAL when it does not fit
+int32_t mtts_debug_step_plan(MttsEngine* e, int32_t pages_bound, char* buf, int32_t cap) {
+    if (!e || !buf || cap < 1 || pages_bound < 1) return fail(MTTS_EINVAL, "step_plan: bad argument");
+    const std::string text = describe(decode_plan(e, pages_bound));
+    if ((size_t)cap <= text.size()) return fail(MTTS_EINVAL, "step_plan: %d bytes needed, %d given", (int)text.size() + 1, cap);
+    memcpy(buf, text.c_str(), text.size() + 1);
     return MTTS_OK;
 }
 

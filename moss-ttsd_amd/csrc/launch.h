@@ -19,6 +19,7 @@ GemmPlan mtts_plan_gemm(int Npad, int K, int want_ksplit);
 GemmPlan mtts_plan_gemm_forced(int Npad, int K, int ksplit, int waves);
 void launch_gemm(int epi, int mb, const GemmPlan& p, const void* Wp, const void* Xp, int K, int Npad, int n_valid,
                  float* partial, uint16_t* out, hipStream_t st);
+int mtts_gemm_form(int epi, int mb, const GemmPlan& p, int K, int Npad, int n_valid);      // GEMM_SKINNY / GEMM_DEPTH / GEMM_GATEUP48 (shapes.h) of that call
 int mtts_tile_ksplit(int Npad, int K, int R);
 void launch_gemm_tile(int epi, int R, int ksplit, const void* Wp, const void* Xp, int K, int Npad, int n_valid,
                       float* partial, uint16_t* out, hipStream_t st);
@@ -34,7 +35,7 @@ void launch_reduce_partial_bf16(const float* partial, void* out, int ksplit, int
 // ---- gemm_sealed.hip ------------------------------------------------------------------------------------------------
 // The sealed twin of a packed weight array, for the decode shapes whose waves own 16 or 12 k-tiles (gate/up, the heads;
 // down_proj).  wseal_shape: the plan / shape is one the sealed kernels take, and kt_per_wave is its group size.
-enum { WSEAL_GU = 0, WSEAL_DOWN = 1, WSEAL_HEAD0 = 2, WSEAL_HEADS = 3, WSEAL_KINDS = 4 };
+// (the kinds: WSEAL_GU, WSEAL_DOWN, WSEAL_HEAD0, WSEAL_HEADS in shapes.h)
 bool wseal_shape(const GemmPlan& p, int K, int Npad, int epi);
 size_t wseal_bytes(int Npad, int K, int ktw);
 void launch_wseal(const void* Wp, void* Ws, int K, int ktw, int nt0, int ntiles, hipStream_t st);     // N-tiles nt0 .. nt0 + ntiles - 1

@@ -420,6 +420,13 @@ class Engine:
         capi.check(self.lib.mtts_debug_kv_pack_stats(self._h, o.ctypes.data))
         return dict(zip(("k_pages", "k_unsealed", "v_pages", "v_unsealed", "k_layers_on", "v_layers_on"), (int(x) for x in o)))
 
+    def step_plan(self, pages_bound):
+        """How the decode step the engine would run now at `pages_bound` KV pages chooses its kernels (csrc/stepplan.h:
+        describe) -> its lines, one per distinct launch group in issue order."""
+        buf = C.create_string_buffer(4096)
+        capi.check(self.lib.mtts_debug_step_plan(self._h, int(pages_bound), buf, len(buf)))
+        return buf.value.decode().splitlines()
+
     def wseal_stats(self):
         """Sealed weight streams -> {kind: dict(groups, unsealed, on)} for gate_up, down, head0, heads17 (groups of 16 or 12
         k-tiles x lanes; `unsealed` = a lane did not fit the 13-bit form, that wave reads its bf16 tiles; `on` = the decode

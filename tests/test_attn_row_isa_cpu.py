@@ -29,7 +29,7 @@ def asm(tmp_path_factory):
 
 
 def _row_waves():
-    src = open(os.path.join(CSRC, "attn.hip")).read()
+    src = open(os.path.join(CSRC, "shapes.h")).read()          # (single-sourced with the step planner)
     return int(re.search(r"^#define ROW_WAVES (\d+)", src, re.M).group(1))
 
 
