@@ -107,7 +107,8 @@ int32_t mtts_bind_weight(MttsEngine* e, const char* name, const void* dev_bf16,
  * straight into the engine's layout (csrc/adapter.hip); no row-major merged copy exists.  `name` must be one of the seven
  * projection weights of a layer (q/k/v/o_proj, gate/up/down_proj).  MTTS_EINVAL: any other name, a shape other than the
  * weight's, r outside 1..256, a pointer that is not 16-byte aligned.  MTTS_ESTATE: a run is open (the rule of
- * mtts_set_output_scores); the weights are then as they were.  Drops the captured step graphs, as mtts_bind_weight does.
+ * mtts_set_output_scores); the weights are then as they were.  Like mtts_bind_weight it writes the engine's arrays in
+ * place: captured step graphs hold addresses, not values, and stay valid.
  * Stream-ordered: the three tensors may be freed once `stream` has passed the call. */
 int32_t mtts_bind_weight_lora(MttsEngine* e, const char* name, const void* dev_base, int64_t rows, int64_t cols,
                               const float* dev_lora_a, const float* dev_lora_b, int32_t r, float scaling, void* stream);
@@ -124,7 +125,7 @@ int32_t mtts_bind_weight_lora(MttsEngine* e, const char* name, const void* dev_b
  * ([rows][cols], as mtts_bind_weight_lora names it): dev_lora_a fp32 [r][cols], dev_lora_b fp32 [rows][r], 16-byte
  * aligned, copied into engine-owned memory on `stream` (drained before the call returns); a pair loaded before for the
  * same matrix is replaced.  Matrices an adapter never loads are not targeted.  mtts_adapter_clear frees an adapter.
- * Both: MTTS_ESTATE while a run is open (the rule of mtts_bind_weight_lora), and the captured step graphs are dropped.
+ * Both: MTTS_ESTATE while a run is open (the rule of mtts_bind_weight_lora).
  * MTTS_EINVAL, with the offending value in mtts_last_error: an index outside the bank, a name that is not a projection
  * weight of a layer, a shape other than the weight's, r outside 1..MTTS_LORA_MAX_RANK, and an MTTS_DTYPE_F32 / _F16
  * engine (the bank exists on the bf16 engine only).  The engine takes no memory for any of this before the first
@@ -278,7 +279,7 @@ int32_t mtts_slot_submit(MttsEngine* e, int32_t slot, const int64_t* host_ids, i
  * static batch with that seed draws (mtts_slot_submit = row_id 0) */
 int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* host_ids, int32_t T, int32_t max_length, uint64_t seed,
                              int32_t row_id, void* stream);
-/* Philox row ids of the rows of the NEXT mtts_begin / mtts_generate (consumed by it; default 0..B-1): one rank's share of
+/* Philox row ids of the rows of the NEXT mtts_begin / mtts_generate (consumed by it, failures included; default 0..B-1): one rank's share of
  * a sharded batch draws what its rows would draw inside the whole batch (host_row_ids int32 [n], n = that call's B). */
 int32_t mtts_set_row_ids(MttsEngine* e, const int32_t* host_row_ids, int32_t n);
 /* Takes per prompt of the NEXT mtts_begin / mtts_generate (consumed by it, failures included; default 1): HF

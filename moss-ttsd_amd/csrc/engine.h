@@ -1,8 +1,14 @@
 // What engine.hip (engine object, C ABI of the product path) and hooks.hip (per-kernel test / bench entry points)
 // share: the engine's definition, error reporting, and the owner of device memory.  Only these two files include it.
 // The HIP-free host code sits apart, where a CPU test can include it: kvpool.h (the KV page pool; through launch.h),
-// staging.h (prompt staging; engine.hip alone) and stepplan.h (how a pass chooses its kernels; included here) -- besides
-// those includers only tests/host/pool_stage_main.cpp and tests/host/step_plan_main.cpp.
+// staging.h (prompt staging; engine.hip alone), stepplan.h (how a pass chooses its kernels) and runstate.h (the options a
+// run starts with, the addresses a captured step holds, the captured steps; both included here) -- besides those includers
+// only tests/host/pool_stage_main.cpp, tests/host/step_plan_main.cpp and tests/host/run_state_main.cpp.
+//
+// Device memory after mtts_engine_create: every mem.release, and every mem.get, targets either a member of StepBufs
+// (runstate.h; MttsEngine::bufs) -- which is part of what a captured step is found by, so no reallocation has to remember
+// the captured steps -- or a buffer whose address no launch of a decode step carries, and says so where it does: the
+// prefill staging, the sc_* scoring buffers, an adapter's matrices (a step finds those through the table in bufs.d_bank).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,7 +22,10 @@
 #include <vector>
 
 #include "launch.h"
+#include "runstate.h"
 #include "stepplan.h"
+
+static_assert(RUN_EINVAL == MTTS_EINVAL, "runstate.h reports with MTTS_EINVAL");
 
 // ---- errors -------------------------------------------------------------------
 #define MTTS_LOCAL __attribute__((visibility("hidden")))
@@ -118,24 +127,6 @@ static inline int alloc_scratch(DevBufs& m, SampleScratch& sc, int rows, int voc
     TRY(m.get(&sc.cand_n, (size_t)rows));
     return 0;
 }
-// output_scores scratch: only when asked for
-static inline int alloc_lp_scratch(DevBufs& m, SampleScratch& sc, int rows) {
-    if (sc.lp) return 0;
-    TRY(m.get(&sc.slice_sum, (size_t)rows * SAMP_NS));
-    TRY(m.get(&sc.lp, (size_t)rows * 8));
-    return 0;
-}
-// top_logprobs scratch (gen_topk.hip: GenTopkScratch): only when asked for, again when k outgrows it
-static inline int alloc_gen_topk_scratch(DevBufs& m, GenTopkScratch& sc, int rows, int k) {
-    if (sc.kcap >= k) return 0;
-    m.release(sc.cand); m.release(sc.smax); m.release(sc.ssum);
-    sc.kcap = 0;
-    TRY(m.get(&sc.cand, (size_t)rows * SAMP_NS * k));
-    TRY(m.get(&sc.smax, (size_t)rows * SAMP_NS));
-    TRY(m.get(&sc.ssum, (size_t)rows * SAMP_NS));
-    sc.kcap = k;
-    return 0;
-}
 
 // ---- the engine ------------------------------------------------------------------------------------------------
 struct Layer {
@@ -159,14 +150,12 @@ struct MttsEngine {
     void* head0 = nullptr;             // packed [V0_pad][H]
     void* heads17 = nullptr;           // packed [7*Vs_pad][H]
     void* final_norm = nullptr;
-    uint16_t *rope_cos = nullptr, *rope_sin = nullptr;
-    int rope_rows = 0;
     int emb_bound = 0, norm_bound = 0;
     const uint16_t** d_tables = nullptr;
     // plans
     GemmPlan p_qkv, p_o, p_gu, p_d, p_h0, p_h17;
     // workspaces
-    float* partial = nullptr;
+    // (the qkv / o_proj / down_proj split-K slabs `partial` are in bufs: the first adapter load widens them)
     float* partial2 = nullptr;          // small-batch path: o_proj / down_proj slabs (the qkv slabs stay in `partial`)
     void *x2 = nullptr, *act_rm = nullptr;   // small-batch path: second residual buffer (ping-pong), row-major SwiGLU output
     // how a pass chooses its kernels (stepplan.h): the switches of the environment as read at creation (attn_row and
@@ -197,8 +186,8 @@ struct MttsEngine {
     KvPool pool;
     std::vector<char> slot_live;        // host's view: the slot holds a dialogue that may still step
     int forced_draw = 0;
-    std::vector<int32_t> next_row_ids;  // Philox row ids of the next mtts_begin (mtts_set_row_ids); empty = 0..B-1
-    int next_takes = 1;                 // takes per prompt of the next mtts_begin / mtts_generate (mtts_set_takes)
+    PendingRun pending;                 // what the mtts_set_* calls left for the next run (runstate.h)
+    StepBufs bufs;                      // every address a decode step reads that can change after creation (runstate.h)
     int takes = 1;                      // of the current static run: row b*takes+j is take j of prompt b
     // ---- MTTS_DTYPE_F32 engine (f32path.hip): plain fp32 copies of everything, no packed layouts ----
     bool f32 = false;
@@ -207,7 +196,7 @@ struct MttsEngine {
     std::vector<LayerF32> lf;
     float* embf[8] = {nullptr};
     const float** d_tables_f = nullptr;
-    float *final_norm_f = nullptr, *rope_cos_f = nullptr, *rope_sin_f = nullptr;
+    float* final_norm_f = nullptr;
     float *kcache_f = nullptr, *vcache_f = nullptr;
     float *xf = nullptr, *xnf = nullptr, *qkvf = nullptr, *qbuf_f = nullptr, *attnf = nullptr, *yf = nullptr, *guf = nullptr,
           *actf = nullptr, *hlast_f = nullptr, *scores_f = nullptr;
@@ -217,29 +206,18 @@ struct MttsEngine {
     LoopState* d_ls = nullptr;
     LoopState* h_ls = nullptr;          // pinned mirror
     SeqState* h_seqs = nullptr;         // pinned mirror of d_seqs (mtts_sync_state)
-    int32_t *d_decisions = nullptr, *d_cur = nullptr, *d_gen = nullptr, *d_declog = nullptr, *d_forced = nullptr,
-            *d_tf = nullptr;
+    int32_t *d_decisions = nullptr, *d_cur = nullptr, *d_tf = nullptr;
     uint32_t* d_bitmaps = nullptr;
     int bm_words = 0;
     MttsSamplerCfg* d_scfg = nullptr;
-    SampleScratch sscr;
+    SampleScratch sscr;                 // (its slice_sum / lp stay null here: bufs holds them)
     int ch0_sampled = 0;
-    // output_scores: per-token log-probabilities [slot][gen_cap][8] fp32, laid out like d_gen; allocated on first use
-    float* d_lp = nullptr;
-    int lp_cap = 0;                     // gen_cap the buffer was allocated for
-    int scores_next = 0;                // mtts_set_output_scores: read by the next mtts_begin / mtts_generate / mtts_sched_open
+    // output_scores: per-token log-probabilities (bufs.d_lp, laid out like bufs.d_gen)
     int scores_on = 0;                  // of the current run
     bool run_open = false;              // a run has begun and has not been seen to end (mtts_set_output_scores)
-    // top_logprobs (gen_topk.hip): raw log-probability of every decision [slot][gen_cap][8] and the k most probable tokens
-    // [slot][gen_cap][8][k] (ids, log-probabilities); scratch and buffers exist only once a run asked for them
-    GenTopkScratch gtscr;
-    float* d_gt_logp = nullptr;
-    int32_t* d_gt_ids = nullptr;
-    float* d_gt_tlp = nullptr;
-    int gt_cap = 0, gt_k = 0;           // gen_cap and k the three buffers were allocated for
-    int topk_next = 0;                  // mtts_set_top_logprobs: read by the next mtts_begin / mtts_generate / mtts_sched_open
+    // top_logprobs (gen_topk.hip): raw log-probability of every decision and the k most probable tokens (bufs.d_gt_*)
     int topk_on = 0;                    // k of the current run (0: off)
-    // teacher-forced scoring (mtts_score; score.hip): allocated by the first call
+    // teacher-forced scoring (mtts_score; score.hip): allocated by the first call, grown by later ones; no decode step reads any of it
     int32_t* d_sc_labels = nullptr;     // [staged rows][8]: the label of the row's NEXT position, -100 = none
     float* d_sc_logp = nullptr;         // [staged rows][8]
     size_t sc_cap_rows = 0;
@@ -251,18 +229,13 @@ struct MttsEngine {
     size_t sc_top_cap = 0;              // elements of each
     uint32_t* sc_cand = nullptr;        // bf16 engine: every block's k candidate keys of MTTS_SCORE_TOPK_ROWS rows of one head launch
     // resident adapters, one per dialogue (mtts_adapter_load; multilora.hip): no device memory before the first load
-    std::vector<LoraEnt> bank;          // host copy of d_bank [MTTS_MAX_ADAPTERS][L * 7]; r == 0: the adapter has no pair for the matrix
-    LoraEnt* d_bank = nullptr;
+    std::vector<LoraEnt> bank;          // host copy of bufs.d_bank [MTTS_MAX_ADAPTERS][L * 7]; r == 0: the adapter has no pair for the matrix
     int bank_pairs[MTTS_MAX_ADAPTERS] = {0};     // matrix pairs each adapter holds (0: the adapter is empty)
-    int32_t* d_seq_adapter = nullptr;   // [MTTS_RCAP] adapter of the dialogue in each sequence slot (-1: none); kernels go RowMeta.seq -> here
+    // bufs.d_seq_adapter [MTTS_RCAP]: adapter of the dialogue in each sequence slot (-1: none); kernels go RowMeta.seq -> there
     std::vector<int32_t> seq_adapter = std::vector<int32_t>(MTTS_RCAP, -1);          // the host's copy
-    std::vector<int32_t> next_slot_adapter = std::vector<int32_t>(MTTS_RCAP, -1);    // mtts_set_slot_adapter, read by the slot's next submit
-    std::vector<int32_t> next_row_adapters;      // mtts_set_row_adapters, read by the next mtts_begin / mtts_generate
-    bool row_adapters_pending = false;
-    int32_t* d_pf_tokens = nullptr;     // prefill staging
+    int32_t* d_pf_tokens = nullptr;     // prefill staging: grows with the prompts; read by prefill passes, never by a decode step
     RowMeta* d_pf_meta = nullptr;
     size_t pf_cap_rows = 0;
-    int gen_cap = 0;
     // current run
     int B = 0, T = 0, base_length = 0, max_length = 0, max_steps = 0, steps_issued = 0;
     bool continuous = false;
@@ -271,9 +244,9 @@ struct MttsEngine {
     int max_real = 0;
     uint64_t seed = 0;
     bool began = false, has_forced = false;
-    // decode-step graphs: one captured step per (plan, KV page bound), replayed by mtts_step
-    struct StepGraph { StepPlan plan; int pages; hipGraphExec_t exec; };
-    std::vector<StepGraph> graphs;
+    // decode-step graphs: one captured step per (plan, KV page bound, bufs), replayed by mtts_step
+    struct DestroyExec { void operator()(hipGraphExec_t g) const { hipGraphExecDestroy(g); } };
+    StepGraphs<hipGraphExec_t, DestroyExec> graphs;
     hipStream_t cap_stream = nullptr;
     // sealed KV pages (attn.hip: kv_seal): every COMPLETE page also kept in a lossless 13-bit form the decode attention
     // reads instead of the bf16 page (MTTS_KV_PACK=0: off, no second pool)

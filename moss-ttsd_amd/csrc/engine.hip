@@ -78,7 +78,7 @@ static int forward_rows_f32(MttsEngine* e, const int32_t* d_tokens, const RowMet
         float* kc = e->kcache_f + e->layer_stride * n;
         float* vc = e->vcache_f + e->layer_stride * n;
         launch_f32_linear(l.wqkv, e->xnf, e->qkvf, R, e->qkv_rows, H, e->qkv_rows, h16, dec, st);
-        launch_f32_qkv_post(e->qkvf, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos_f, e->rope_sin_f, e->qbuf_f, kc, vc,
+        launch_f32_qkv_post(e->qkvf, e->qkv_rows, d_meta, l.qn, l.kn, e->bufs.rope_cos_f, e->bufs.rope_sin_f, e->qbuf_f, kc, vc,
                             e->d_page_table, e->max_pages, e->total_pages, R, nq, nkv, eps, h16, st);
         launch_f32_attn(e->qbuf_f, kc, vc, e->d_page_table, d_meta, e->scores_f, e->attnf, R, e->max_pages, e->total_pages, nq,
                         nkv, scale, Lmax, h16, st);
@@ -100,11 +100,6 @@ static int forward_rows_f32(MttsEngine* e, const int32_t* d_tokens, const RowMet
     }
     HIPCHK(hipGetLastError());
     return MTTS_OK;
-}
-
-static void drop_graphs(MttsEngine* e) {
-    for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
-    e->graphs.clear();
 }
 
 // the small-batch kernels' LDS holds this model's rows (StepCaps.small_fits)
@@ -230,7 +225,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     // activations hold a whole prefill pass (MTTS_PFCAP rows); split-K slabs: up to 8 of [MTTS_PFCAP][Npad] fp32
     size_t pmax = (size_t)8 * std::max(e->qkv_rows, round_up(H, 32));
     if (!e->f32) {
-        TRY(m.get(&e->partial, pmax * MTTS_PFCAP));
+        TRY(m.get(&e->bufs.partial, pmax * MTTS_PFCAP));
         TRY(m.get(&e->partial2, (size_t)8 * round_up(H, 32) * MTTS_PFCAP));
         TRY(m.get((uint16_t**)&e->x2, (size_t)MTTS_MAXR * H));
         TRY(m.get((uint16_t**)&e->act_rm, (size_t)MTTS_MAXR * I));
@@ -314,7 +309,7 @@ int32_t mtts_engine_destroy(MttsEngine* e) {
     if (!e) return MTTS_OK;
     hipSetDevice(e->device);
     hipDeviceSynchronize();
-    drop_graphs(e);
+    e->graphs.clear();
     if (e->cap_stream) hipStreamDestroy(e->cap_stream);
     for (int w = 0; w < PROF_N; ++w) for (auto& pr : e->ev[w]) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     e->mem.free_all();
@@ -410,7 +405,6 @@ static int resolve_weight(MttsEngine* e, const char* name_c, WeightSlot& w) {
 int32_t mtts_bind_weight(MttsEngine* e, const char* name_c, const void* src, int64_t rows, int64_t cols, void* stream) {
     if (!e || !name_c || !src) return fail(MTTS_EINVAL, "null argument");
     HIPCHK(hipSetDevice(e->device));
-    drop_graphs(e);
     hipStream_t st = S(stream);
     WeightSlot w;
     TRY(resolve_weight(e, name_c, w));
@@ -447,7 +441,6 @@ int32_t mtts_bind_weight_lora(MttsEngine* e, const char* name_c, const void* bas
     bool open = false;
     TRY(run_still_open(e, &open));
     if (open) return fail(MTTS_ESTATE, "weights cannot change while a run is open (the rule of mtts_set_output_scores)");
-    drop_graphs(e);
     hipStream_t st = S(stream);
     if (e->f32)
         launch_lora_rows_f32((const float*)base, lora_a, lora_b, r, scaling, w.f32_to + w.f32_row * w.cols, (int)w.rows, (int)w.cols,
@@ -484,7 +477,7 @@ static int adapter_id_check(MttsEngine* e, int id, const char* what, int at) {
     return MTTS_OK;
 }
 static int bank_upload(MttsEngine* e, size_t first, size_t n, hipStream_t st) {
-    HIPCHK(hipMemcpyAsync(e->d_bank + first, e->bank.data() + first, n * sizeof(LoraEnt), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->bufs.d_bank + first, e->bank.data() + first, n * sizeof(LoraEnt), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     return MTTS_OK;
 }
@@ -502,10 +495,9 @@ int32_t mtts_adapter_load(MttsEngine* e, int32_t adapter, const char* name_c, co
     if (rows != w.rows || cols != w.cols)
         return fail(MTTS_EINVAL, "%s: expected [%lld,%lld] got [%lld,%lld]", name_c, (long long)w.rows, (long long)w.cols, (long long)rows, (long long)cols);
     if (cols > LORA_MAX_K) return fail(MTTS_EINVAL, "%s: rows of %lld elements, the delta kernel stages at most %d", name_c, (long long)cols, LORA_MAX_K);
-    drop_graphs(e);
     hipStream_t st = S(stream);
     const size_t per = (size_t)e->L * 7;
-    if (!e->d_bank) {           // the first load: the bank's tables, the per-slot ids, and room for the extra slabs
+    if (!e->bufs.d_bank) {           // the first load: the bank's tables, the per-slot ids, and room for the extra slabs
         HIPCHK(hipDeviceSynchronize());
         // all three or none: a failure gives back what it took and leaves the engine as it was, so the load can be retried
         float* wider = nullptr;
@@ -516,13 +508,13 @@ int32_t mtts_adapter_load(MttsEngine* e, int32_t adapter, const char* name_c, co
         if (!rc) rc = e->mem.get(&tab, MTTS_MAX_ADAPTERS * per);
         if (!rc && hipMemset(ids, 0xff, MTTS_RCAP * sizeof(int32_t)) != hipSuccess) rc = fail(MTTS_EHIP, "mtts_adapter_load: hipMemset of the per-slot adapter ids failed");
         if (rc) { e->mem.release(wider); e->mem.release(ids); e->mem.release(tab); return rc; }
-        e->mem.release(e->partial);
-        e->partial = wider;
-        e->d_seq_adapter = ids;
+        e->mem.release(e->bufs.partial);
+        e->bufs.partial = wider;
+        e->bufs.d_seq_adapter = ids;
         e->bank.assign(MTTS_MAX_ADAPTERS * per, LoraEnt{nullptr, nullptr, 0, 0.f});
-        e->d_bank = tab;
+        e->bufs.d_bank = tab;
     }
-    float *a = nullptr, *b = nullptr;
+    float *a = nullptr, *b = nullptr;      // (no launch carries a pair's addresses: a step finds them through the table in bufs.d_bank)
     TRY(e->mem.get(&a, (size_t)r * cols, false));
     if (const int rc = e->mem.get(&b, (size_t)rows * r, false)) { e->mem.release(a); return rc; }
     if (hipMemcpyAsync(a, lora_a, (size_t)r * cols * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
@@ -545,8 +537,7 @@ int32_t mtts_adapter_clear(MttsEngine* e, int32_t adapter) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     HIPCHK(hipSetDevice(e->device));
     TRY(bank_check(e, adapter, "mtts_adapter_clear"));
-    drop_graphs(e);
-    if (!e->d_bank || !e->bank_pairs[adapter]) return MTTS_OK;
+    if (!e->bufs.d_bank || !e->bank_pairs[adapter]) return MTTS_OK;
     HIPCHK(hipDeviceSynchronize());
     const size_t per = (size_t)e->L * 7;
     for (size_t i = adapter * per; i < (adapter + 1) * per; ++i) {
@@ -561,8 +552,7 @@ int32_t mtts_adapter_clear(MttsEngine* e, int32_t adapter) {
 int32_t mtts_set_row_adapters(MttsEngine* e, const int32_t* host_ids, int32_t n) {
     if (!e || (n > 0 && !host_ids) || n < 0 || n > MTTS_RCAP) return fail(MTTS_EINVAL, "set_row_adapters: bad argument");
     if (e->f32) return fail(MTTS_EINVAL, "mtts_set_row_adapters: resident adapters exist on the bf16 engine only (this one is %s)", e->h16 ? "fp16" : "fp32");
-    e->next_row_adapters.assign(host_ids, host_ids + n);
-    e->row_adapters_pending = n > 0;
+    e->pending.set_row_adapters(host_ids, n);
     return MTTS_OK;
 }
 
@@ -571,23 +561,15 @@ int32_t mtts_set_slot_adapter(MttsEngine* e, int32_t slot, int32_t adapter) {
     if (e->f32) return fail(MTTS_EINVAL, "mtts_set_slot_adapter: resident adapters exist on the bf16 engine only (this one is %s)", e->h16 ? "fp16" : "fp32");
     if (slot < 0 || slot >= MTTS_RCAP) return fail(MTTS_EINVAL, "set_slot_adapter: slot %d out of range", slot);
     if (adapter < -1 || adapter >= MTTS_MAX_ADAPTERS) return fail(MTTS_EINVAL, "set_slot_adapter: adapter id %d outside -1..%d", adapter, MTTS_MAX_ADAPTERS - 1);
-    e->next_slot_adapter[slot] = adapter;
+    e->pending.set_slot_adapter(slot, adapter);
     return MTTS_OK;
 }
 // the adapter of the dialogue in `slot` from now on: the host's copy now, the device's on `st`
 static int set_seq_adapter(MttsEngine* e, int slot, int id, hipStream_t st) {
     e->seq_adapter[slot] = id;
-    if (e->d_seq_adapter) HIPCHK(hipMemcpyAsync(e->d_seq_adapter + slot, &e->seq_adapter[slot], sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (e->bufs.d_seq_adapter) HIPCHK(hipMemcpyAsync(e->bufs.d_seq_adapter + slot, &e->seq_adapter[slot], sizeof(int32_t), hipMemcpyHostToDevice, st));
     return MTTS_OK;
 }
-// the pending list of mtts_set_row_adapters, consumed
-static std::vector<int32_t> take_row_adapters(MttsEngine* e) {
-    std::vector<int32_t> v;
-    v.swap(e->next_row_adapters);
-    e->row_adapters_pending = false;
-    return v;
-}
-
 template <typename T>
 static int bind_rope_tables(MttsEngine* e, T*& c, T*& s, const void* cosb, const void* sinb, int rows, hipStream_t st) {
     e->mem.release(c);
@@ -596,16 +578,15 @@ static int bind_rope_tables(MttsEngine* e, T*& c, T*& s, const void* cosb, const
     TRY(e->mem.get(&s, (size_t)rows * 64, false));
     HIPCHK(hipMemcpyAsync(c, cosb, (size_t)rows * 64 * sizeof(T), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(s, sinb, (size_t)rows * 64 * sizeof(T), hipMemcpyDeviceToDevice, st));
-    e->rope_rows = rows;
+    e->bufs.rope_rows = rows;
     return MTTS_OK;
 }
 int32_t mtts_bind_rope(MttsEngine* e, const void* cosb, const void* sinb, int32_t rows, void* stream) {
     if (!e || !cosb || !sinb || rows < 1) return fail(MTTS_EINVAL, "bad rope table");
     HIPCHK(hipSetDevice(e->device));
-    drop_graphs(e);
     // fp32 engine: fp32 tables [rows][64], as Qwen3RotaryEmbedding leaves them before the cast to the model dtype
-    if (e->f32) return bind_rope_tables(e, e->rope_cos_f, e->rope_sin_f, cosb, sinb, rows, S(stream));
-    return bind_rope_tables(e, e->rope_cos, e->rope_sin, cosb, sinb, rows, S(stream));
+    if (e->f32) return bind_rope_tables(e, e->bufs.rope_cos_f, e->bufs.rope_sin_f, cosb, sinb, rows, S(stream));
+    return bind_rope_tables(e, e->bufs.rope_cos, e->bufs.rope_sin, cosb, sinb, rows, S(stream));
 }
 
 // Sealed weight streams: after a bind, count every kind's groups and those that did not seal (from the twins' dictionary
@@ -637,7 +618,7 @@ int32_t mtts_weights_ready(MttsEngine* e) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     if (e->emb_bound != 0xff) return fail(MTTS_ESTATE, "embedding tables missing (mask %x)", e->emb_bound);
     if (!e->norm_bound) return fail(MTTS_ESTATE, "final norm missing");
-    if (!e->rope_rows) return fail(MTTS_ESTATE, "rope table missing");
+    if (!e->bufs.rope_rows) return fail(MTTS_ESTATE, "rope table missing");
     for (int n = 0; n < e->L; ++n)
         if (e->layers[n].bound != 2047) return fail(MTTS_ESTATE, "layer %d incomplete (mask %x)", n, e->layers[n].bound);
     return wseal_policy(e);
@@ -676,7 +657,7 @@ static int attend_layer(MttsEngine* e, const StepPlan& plan, int n, const RowMet
     const float eps = e->cfg.rms_norm_eps, scale = 1.0f / sqrtf((float)MTTS_HD);
     uint16_t* kc = (uint16_t*)e->kcache + e->layer_stride * n;
     uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * n;
-    const QkvFuse fz{e->partial, ks_qkv, e->qkv_rows, (const uint16_t*)l.qn, (const uint16_t*)l.kn, e->rope_cos, e->rope_sin, eps};
+    const QkvFuse fz{e->bufs.partial, ks_qkv, e->qkv_rows, (const uint16_t*)l.qn, (const uint16_t*)l.kn, e->bufs.rope_cos, e->bufs.rope_sin, eps};
     const KvPack pk = layer_pack(e, plan, n);
     const KvPack* pkp = (pk.k || pk.v) ? &pk : nullptr;
     // one launch (the q/k/v epilogue is always inside), timed under the scores slot with the K + V bytes
@@ -694,7 +675,7 @@ static int attend_layer(MttsEngine* e, const StepPlan& plan, int n, const RowMet
     const AttnPhase* ph = form == ATTN_FORM_PREFILL_MFMA ? prefill_ph : decode_ph;
     const int nphases = plan.path == PATH_SMALL ? 2 : 3;
     if (!fused)
-        launch_qkv_post(e->partial, ks_qkv, e->qkv_rows, d_meta, l.qn, l.kn, e->rope_cos, e->rope_sin, e->qbuf,
+        launch_qkv_post(e->bufs.partial, ks_qkv, e->qkv_rows, d_meta, l.qn, l.kn, e->bufs.rope_cos, e->bufs.rope_sin, e->qbuf,
                         kc, vc, e->d_page_table, e->max_pages, e->total_pages, R, e->nq, e->nkv, eps, st);
     for (int i = 0; i < nphases; ++i) {
         hipEvent_t ev = nullptr;
@@ -734,7 +715,7 @@ static int forward_small(MttsEngine* e, const StepPlan& plan, const RowMeta* d_m
         Layer& l = e->layers[n];
         SmallPro pq = base;                            // input norm (+ the previous layer's down_proj slabs)
         pq.x_in = xa; pq.x_out = xb; pq.slabs = e->partial2; pq.ksplit = n ? e->p_d.ksplit : 0; pq.norm_w = (const uint16_t*)l.ln_in;
-        launch_gemv_small(EPI_PARTIAL, PRO_NORM, e->p_qkv, l.wqkv, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, pq, st);
+        launch_gemv_small(EPI_PARTIAL, PRO_NORM, e->p_qkv, l.wqkv, H, e->qkv_rows, e->qkv_rows, e->bufs.partial, nullptr, pq, st);
         TRY(attend_layer(e, plan, n, d_meta, R, pages_bound, e->p_qkv.ksplit, st, kv_tokens_hint));
         SmallPro po = base;                            // o_proj: the chunk partials of P.V are summed in its prologue
         po.opart = e->opart; po.meta = d_meta; po.nchunks_max = e->nchunks_max; po.nq = nq; po.pages_per_chunk = ATT_PB;
@@ -788,7 +769,7 @@ static int forward_rows(MttsEngine* e, const StepPlan& plan, const int32_t* d_to
     if (plan.path == PATH_F32) return forward_rows_f32(e, d_tokens, d_meta, plan.heads == 1 ? plan.B : R, plan.heads, st);
     launch_embed_norm(d_tokens, d_meta, e->d_tables, e->layers[0].ln_in, e->x, e->xn, R, H, eps, st);
     if (plan.path == PATH_SMALL) return forward_small(e, plan, d_meta, pages_bound, st, kv_tokens_hint);
-    if (lora && !e->d_bank) return fail(MTTS_ESTATE, "a pass with adapters on an engine without a bank");
+    if (lora && !e->bufs.d_bank) return fail(MTTS_ESTATE, "a pass with adapters on an engine without a bank");
     const int QD = nq * MTTS_HD, KD = nkv * MTTS_HD, EL = e->L * 7;
     const LoraJob j_qkv{3, e->qkv_rows, H, EL, {{0, QD, 1, 0}, {QD, KD, 1, 1}, {QD + KD, KD, 1, 2}}};
     const LoraJob j_o{1, Hp, QD, EL, {{0, H, 1, 3}}}, j_gu{2, 2 * I, H, EL, {{0, I, 2, 4}, {1, I, 2, 5}}}, j_d{1, Hp, I, EL, {{0, H, 1, 6}}};
@@ -802,14 +783,14 @@ static int forward_rows(MttsEngine* e, const StepPlan& plan, const int32_t* d_to
     // gate/up: the same plan with or without adapters (p_gu; one k-split of the tile GEMM), so slab 0 holds the sums
     // the fused epilogue would have rounded
     const int gu_epi = lora ? EPI_PARTIAL : EPI_SILU;
-    float* gu_slab = lora ? e->partial : nullptr;
+    float* gu_slab = lora ? e->bufs.partial : nullptr;
     for (int n = 0; n < e->L; ++n) {
         Layer& l = e->layers[n];
         // the adapters' delta of this layer's matrices in `job`, for the rows in `xp`, into slab `ks` of the partial buffer
         auto delta = [&](const LoraJob& job, const void* xp, int ks) {
-            launch_lora_delta(xp, d_meta, e->d_seq_adapter, e->d_bank + (size_t)n * 7, job, e->partial + (size_t)ks * MTTS_PFCAP * job.Npad, R, st);
+            launch_lora_delta(xp, d_meta, e->bufs.d_seq_adapter, e->bufs.d_bank + (size_t)n * 7, job, e->bufs.partial + (size_t)ks * MTTS_PFCAP * job.Npad, R, st);
         };
-        TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_qkv, false, 0, e->p_qkv, nullptr, l.wqkv, e->xn, H, e->qkv_rows, e->qkv_rows, e->partial, nullptr, st));
+        TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_qkv, false, 0, e->p_qkv, nullptr, l.wqkv, e->xn, H, e->qkv_rows, e->qkv_rows, e->bufs.partial, nullptr, st));
         if (lora) delta(j_qkv, e->xn, ks_qkv);
         TRY(attend_layer(e, plan, n, d_meta, R, pages_bound, ks_qkv + ex, st, kv_tokens_hint));
         if (plan.fold) {
@@ -819,20 +800,20 @@ static int forward_rows(MttsEngine* e, const StepPlan& plan, const int32_t* d_to
             launch_oproj_resid(l.wo, e->attn_p, e->x, e->xres_p, R, Hp, st);
             launch_gateup_norm(l.wgu, e->xres_p, l.ln_post, eps, e->act_p, 2 * I, st);
         } else {
-            TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_o, false, 0, e->p_o, nullptr, l.wo, e->attn_p, QD, Hp, Hp, e->partial, nullptr, st));
+            TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_o, false, 0, e->p_o, nullptr, l.wo, e->attn_p, QD, Hp, Hp, e->bufs.partial, nullptr, st));
             if (lora) delta(j_o, e->attn_p, ks_o);
-            launch_resid_norm(e->partial, ks_o + ex, Hp, e->x, l.ln_post, e->xn, nullptr, d_meta, R, H, eps, st);
+            launch_resid_norm(e->bufs.partial, ks_o + ex, Hp, e->x, l.ln_post, e->xn, nullptr, d_meta, R, H, eps, st);
             TRY(run_gemm(gu_epi, tiled, R, 1, plan.sealed[WSEAL_GU], 0, e->p_gu, l.wgu_s, l.wgu, e->xn, H, 2 * I, 2 * I, gu_slab, (uint16_t*)e->act_p, st));
         }
         if (lora) {
             delta(j_gu, e->xn, 1);
-            launch_swiglu_slabs(e->partial, e->partial + (size_t)MTTS_PFCAP * 2 * I, e->act_p, mb * 32, I, st);
+            launch_swiglu_slabs(e->bufs.partial, e->bufs.partial + (size_t)MTTS_PFCAP * 2 * I, e->act_p, mb * 32, I, st);
         }
-        TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_d, plan.sealed[WSEAL_DOWN], 0, e->p_d, l.wd_s, l.wd, e->act_p, I, Hp, Hp, e->partial, nullptr, st));
+        TRY(run_gemm(EPI_PARTIAL, tiled, R, ks_d, plan.sealed[WSEAL_DOWN], 0, e->p_d, l.wd_s, l.wd, e->act_p, I, Hp, Hp, e->bufs.partial, nullptr, st));
         if (lora) delta(j_d, e->act_p, ks_d);
         const bool lastl = (n == e->L - 1);
         const void* nw = lastl ? e->final_norm : e->layers[n + 1].ln_in;
-        launch_resid_norm(e->partial, ks_d + ex, Hp, e->x, nw, e->xn, lastl ? e->hlast : nullptr, d_meta, R, H, eps, st);
+        launch_resid_norm(e->bufs.partial, ks_d + ex, Hp, e->x, nw, e->xn, lastl ? e->hlast : nullptr, d_meta, R, H, eps, st);
     }
     seal_completed_pages(e, d_meta, R, st);
     if (plan.heads) {
@@ -864,69 +845,52 @@ static int prefill_staged(MttsEngine* e, size_t Mpad, int pages_bound, int last_
     return 0;
 }
 
-// generated-token storage [slot][gen_cap][8] (+ decision log and forced rows of the same shape)
-static int ensure_gen_storage(MttsEngine* e, int steps) {
-    if (steps <= e->gen_cap) return 0;
-    e->mem.release(e->d_gen); e->mem.release(e->d_declog); e->mem.release(e->d_forced);
-    drop_graphs(e);                      // captured steps hold the old pointers
-    e->gen_cap = steps;
-    const size_t n = (size_t)e->cfg.max_batch * steps * 8;
-    TRY(e->mem.get(&e->d_gen, n));
-    TRY(e->mem.get(&e->d_declog, n));
-    TRY(e->mem.get(&e->d_forced, n, false));
-    return 0;
-}
-
-// output_scores: the switch of the run that starts now; its buffer exists only once a run asked for it, follows gen_cap,
-// and starts as NaN (0xff bytes) in every slot
-static int start_scores(MttsEngine* e, hipStream_t st) {
-    e->scores_on = e->scores_next;
-    if (!e->scores_on) return 0;
-    if (!e->sscr.lp) {
-        drop_graphs(e);                  // (captured steps hold the scratch pointers by value)
-        TRY(alloc_lp_scratch(e->mem, e->sscr, e->cfg.max_batch));
+// The per-slot stores of the run that starts now, [slot][gen_cap][width] each (e->scores_on and e->topk_on are the run's):
+// generated tokens, decision log and forced rows always; output_scores and top_logprobs only once a run asked for them,
+// with the sampler's scratch for them.  A store that exists has the shape (bufs.gen_cap, bufs.gt_stride): when either changes,
+// what it shapes is released here and comes back when next wanted.  The optional ones start every run as NaN / -1 (0xff
+// bytes) in every slot, filled on `st` in the order below.
+static int start_outputs(MttsEngine* e, int steps, hipStream_t st) {
+    StepBufs& b = e->bufs;
+    DevBufs& m = e->mem;
+    const int k = e->topk_on, rows = e->cfg.max_batch;
+    const bool scores = e->scores_on != 0, grown = steps > b.gen_cap, restrided = k && k != b.gt_stride;
+    if (grown) b.gen_cap = steps;
+    if (restrided) b.gt_stride = k;
+    if (scores && !b.sscr_lp) {
+        TRY(m.get(&b.sscr_slice_sum, (size_t)rows * SAMP_NS));
+        TRY(m.get(&b.sscr_lp, (size_t)rows * 8));
     }
-    const size_t n = (size_t)e->cfg.max_batch * e->gen_cap * 8;
-    if (!e->d_lp || e->lp_cap != e->gen_cap) {
-        e->mem.release(e->d_lp);
-        drop_graphs(e);                  // captured steps hold the old pointer
-        TRY(e->mem.get(&e->d_lp, n, false));
-        e->lp_cap = e->gen_cap;
+    if (k > b.gt_scr_cap) {
+        m.release(b.gt_cand); m.release(b.gt_smax); m.release(b.gt_ssum);
+        b.gt_scr_cap = 0;
+        TRY(m.get(&b.gt_cand, (size_t)rows * SAMP_NS * k));
+        TRY(m.get(&b.gt_smax, (size_t)rows * SAMP_NS));
+        TRY(m.get(&b.gt_ssum, (size_t)rows * SAMP_NS));
+        b.gt_scr_cap = k;
     }
-    HIPCHK(hipMemsetAsync(e->d_lp, 0xff, n * sizeof(float), st));
-    return 0;
-}
-
-// top_logprobs: the k of the run that starts now (0: off, nothing below exists or is touched).  The scratch grows with k,
-// the three buffers follow (gen_cap, k) -- k is their innermost stride -- and start as NaN / -1 (0xff bytes) in every slot
-static int start_top_logprobs(MttsEngine* e, hipStream_t st) {
-    e->topk_on = e->topk_next;
-    const int k = e->topk_on;
-    if (!k) return 0;
-    if (e->gtscr.kcap < k) {
-        drop_graphs(e);                  // (captured steps hold the scratch pointers by value)
-        TRY(alloc_gen_topk_scratch(e->mem, e->gtscr, e->cfg.max_batch, k));
-    }
-    const size_t n = (size_t)e->cfg.max_batch * e->gen_cap * 8;
-    if (!e->d_gt_logp || e->gt_cap != e->gen_cap || e->gt_k != k) {
-        e->mem.release(e->d_gt_logp); e->mem.release(e->d_gt_ids); e->mem.release(e->d_gt_tlp);
-        drop_graphs(e);                  // captured steps hold the old pointers
-        e->gt_cap = e->gt_k = 0;
-        TRY(e->mem.get(&e->d_gt_logp, n, false));
-        TRY(e->mem.get(&e->d_gt_ids, n * k, false));
-        TRY(e->mem.get(&e->d_gt_tlp, n * k, false));
-        e->gt_cap = e->gen_cap; e->gt_k = k;
-    }
-    HIPCHK(hipMemsetAsync(e->d_gt_logp, 0xff, n * sizeof(float), st));
-    HIPCHK(hipMemsetAsync(e->d_gt_ids, 0xff, n * k * sizeof(int32_t), st));
-    HIPCHK(hipMemsetAsync(e->d_gt_tlp, 0xff, n * k * sizeof(float), st));
+    // one row per store: inner width 8 or 8 k, wanted by this run, zeroed when allocated, 0xff-filled when the run starts
+    const auto store = [&](auto*& p, bool per_k, bool wanted, bool zeroed, bool filled) -> int {
+        const size_t n = (size_t)rows * b.gen_cap * 8 * (per_k ? k : 1);
+        if (grown || (per_k && restrided)) m.release(p);
+        if (wanted && !p) TRY(m.get(&p, n, zeroed));
+        if (wanted && filled) HIPCHK(hipMemsetAsync(p, 0xff, n * sizeof(*p), st));
+        return 0;
+    };
+    TRY(store(b.d_gen, false, true, true, false));
+    TRY(store(b.d_declog, false, true, true, false));
+    TRY(store(b.d_forced, false, true, false, false));
+    TRY(store(b.d_lp, false, scores, false, true));
+    TRY(store(b.d_gt_logp, false, k > 0, false, true));
+    TRY(store(b.d_gt_ids, true, k > 0, false, true));
+    TRY(store(b.d_gt_tlp, true, k > 0, false, true));
     return 0;
 }
 
 // staged rows (staging.h) into the prefill staging, which grows to hold them.  on_stream: asynchronously on `st`, which
 // the caller drains before `sr` dies (mtts_begin, mtts_score); else synchronously (mtts_slot_submit)
 static int upload_staged(MttsEngine* e, const StagedRows& sr, bool on_stream, hipStream_t st) {
-    if (sr.Mpad > e->pf_cap_rows) {
+    if (sr.Mpad > e->pf_cap_rows) {       // (prefill passes read the staging, no decode step does)
         e->mem.release(e->d_pf_tokens); e->mem.release(e->d_pf_meta);
         e->pf_cap_rows = 0;
         TRY(e->mem.get(&e->d_pf_tokens, sr.Mpad * 8, false));
@@ -950,7 +914,7 @@ static const SeqState IDLE_SEQ{-1, 0, 0, 0, 0, 0, 0, 0, 0};
 static int reset_run_state(MttsEngine* e, const std::vector<SeqState>& seqs, bool continuous, const MttsSamplerCfg* sampler, hipStream_t st) {
     HIPCHK(hipMemcpyAsync(e->d_seqs, seqs.data(), seqs.size() * sizeof(SeqState), hipMemcpyHostToDevice, st));
     if (continuous) e->forced_draw = 0;
-    LoopState ls{0, 0, continuous ? 1 : 0, e->B, 0, e->gen_cap, e->forced_draw, e->f32 ? 1 : 0};
+    LoopState ls{0, 0, continuous ? 1 : 0, e->B, 0, e->bufs.gen_cap, e->forced_draw, e->f32 ? 1 : 0};
     e->continuous = continuous;
     e->join_step.assign(MTTS_RCAP, 0);
     HIPCHK(hipMemcpyAsync(e->d_ls, &ls, sizeof(ls), hipMemcpyHostToDevice, st));
@@ -996,23 +960,20 @@ static int launch_fork_job(MttsEngine* e, ForkJob& job, bool state_rows, hipStre
 
 // ---- begin: parse prompt, allocate pages, prefill --------------------------------------
 static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32_t B, int32_t T, int32_t max_length,
-                     const MttsSamplerCfg* sampler, uint64_t seed, int takes, const std::vector<int32_t>& row_adapters, void* stream) {
-    if (!e || !ids || !mask || !sampler) return fail(MTTS_EINVAL, "null argument");
+                     const MttsSamplerCfg* sampler, uint64_t seed, const RunOptions& opt, void* stream) {
+    if (!ids || !mask || !sampler) return fail(MTTS_EINVAL, "null argument");
     TRY(mtts_weights_ready(e));
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = S(stream);
     // one adapter id per prompt (mtts_set_row_adapters); none given: no row has one
-    if (!row_adapters.empty() && (int)row_adapters.size() != B)
-        return fail(MTTS_EINVAL, "mtts_set_row_adapters gave %d ids, the batch has %d prompts", (int)row_adapters.size(), B);
     bool lora = false;
-    for (size_t b = 0; b < row_adapters.size(); ++b) {
-        TRY(adapter_id_check(e, row_adapters[b], "row", (int)b));
-        lora |= row_adapters[b] >= 0;
+    for (size_t b = 0; b < opt.row_adapters.size(); ++b) {
+        TRY(adapter_id_check(e, opt.row_adapters[b], "row", (int)b));
+        lora |= opt.row_adapters[b] >= 0;
     }
     // takes: row b*takes+j is take j of prompt b; only the B prompts are prefilled (into rows b*takes), the other takes
     // share their complete prompt pages and get a copy of the rest (fork_kernel)
-    const int R = B * takes;
-    if (B < 1 || B > e->cfg.max_batch || R > e->cfg.max_batch) return fail(MTTS_EINVAL, "batch %d x %d takes exceeds max_batch %d", B, takes, e->cfg.max_batch);
+    const int takes = opt.takes, R = opt.rows();
     if (T < 8) return fail(MTTS_EINVAL, "T must be >= 8 (delay pattern adds 7 slots)");
     const int base = T - 7;
     if (max_length <= base) return fail(MTTS_EINVAL, "max_length %d leaves no room to generate (prompt slots %d)", max_length, base);
@@ -1057,16 +1018,15 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
         }
     }
     TRY(e->pool.flush(ship));
-    if (e->max_real + max_steps > e->rope_rows)
-        return fail(MTTS_EINVAL, "rope table has %d rows, need %d", e->rope_rows, e->max_real + max_steps);
+    if (e->max_real + max_steps > e->bufs.rope_rows)
+        return fail(MTTS_EINVAL, "rope table has %d rows, need %d", e->bufs.rope_rows, e->max_real + max_steps);
     // room for chained resurrections (linger_bound) as far as the page-table width and the RoPE table allow
     max_steps = std::max(max_steps, std::min(max_length - base + linger_bound(R),
-                                             std::min(e->max_pages * MTTS_PAGE, e->rope_rows) - e->max_real));
+                                             std::min(e->max_pages * MTTS_PAGE, e->bufs.rope_rows) - e->max_real));
     e->max_steps = max_steps;
     // generation buffers
-    TRY(ensure_gen_storage(e, max_steps));
-    TRY(start_scores(e, st));
-    TRY(start_top_logprobs(e, st));
+    e->scores_on = opt.output_scores; e->topk_on = opt.top_logprobs;
+    TRY(start_outputs(e, max_steps, st));
     StagedRows sr;
     TRY(stage_rows(seqs, e->V0, e->Vs, false, &sr));
     {
@@ -1080,17 +1040,13 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
             TRY(stage_tail(prompt + (size_t)base * 8, e->V0, e->Vs, " (delayed tail)", tf.data() + (size_t)rw * 7 * 8));
         }
         std::vector<SeqState> ss(MTTS_RCAP, IDLE_SEQ);
-        if (!e->next_row_ids.empty() && (int)e->next_row_ids.size() != R)
-            return fail(MTTS_EINVAL, "mtts_set_row_ids gave %d ids, the batch has %d rows", (int)e->next_row_ids.size(), R);
-        for (int b = 0; b < R; ++b)
-            ss[b] = SeqState{-1, 1, e->n_real[b], 0, base, max_length, e->next_row_ids.empty() ? b : e->next_row_ids[b], 1, seed};
-        e->next_row_ids.clear();
+        for (int b = 0; b < R; ++b) ss[b] = SeqState{-1, 1, e->n_real[b], 0, base, max_length, opt.row_id(b), 1, seed};
         TRY(upload_staged(e, sr, true, st));
         HIPCHK(hipMemcpyAsync(e->d_bitmaps, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(e->d_tf, tf.data(), tf.size() * 4, hipMemcpyHostToDevice, st));
         // the rows' adapters: a prompt's takes share its KV pages and so its adapter
-        for (int b = 0; b < MTTS_RCAP; ++b) e->seq_adapter[b] = (b < R && !row_adapters.empty()) ? row_adapters[b / takes] : -1;
-        if (e->d_seq_adapter) HIPCHK(hipMemcpyAsync(e->d_seq_adapter, e->seq_adapter.data(), MTTS_RCAP * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        for (int b = 0; b < MTTS_RCAP; ++b) e->seq_adapter[b] = b < R ? opt.row_adapter(b) : -1;
+        if (e->bufs.d_seq_adapter) HIPCHK(hipMemcpyAsync(e->bufs.d_seq_adapter, e->seq_adapter.data(), MTTS_RCAP * sizeof(int32_t), hipMemcpyHostToDevice, st));
         TRY(reset_run_state(e, ss, false, sampler, st));   // drains st: the host vectors above go out of scope
     }
     TRY(prefill_staged(e, sr.Mpad, pages_for(e->max_real), 2, lora, st));
@@ -1105,17 +1061,22 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
 int32_t mtts_set_takes(MttsEngine* e, int32_t n) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     if (n < 1 || n > MTTS_RCAP) return fail(MTTS_EINVAL, "takes must be 1..%d (got %d)", MTTS_RCAP, n);
-    e->next_takes = n;
+    e->pending.set_takes(n);
     return MTTS_OK;
+}
+// The options of the mtts_begin / mtts_generate that starts now: out of the engine first -- so the one-shot ones are
+// consumed whatever the call does next -- and then checked.
+static int take_options(MttsEngine* e, int B, bool forced, RunOptions* opt) {
+    *opt = e->pending.take(B);
+    return opt->check(e->cfg.max_batch, forced);
 }
 
 int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32_t B, int32_t T, int32_t max_length,
                    const MttsSamplerCfg* sampler, uint64_t seed, void* stream) {
     if (!e) return fail(MTTS_EINVAL, "null argument");
-    const int takes = e->next_takes;
-    e->next_takes = 1;                 // consumed by this call, whatever its outcome
-    const std::vector<int32_t> row_adapters = take_row_adapters(e);
-    return begin_run(e, ids, mask, B, T, max_length, sampler, seed, takes, row_adapters, stream);
+    RunOptions opt;
+    TRY(take_options(e, B, false, &opt));
+    return begin_run(e, ids, mask, B, T, max_length, sampler, seed, opt, stream);
 }
 
 // One decode step: sample from the previous logits, advance the per-dialogue state machine, run the stack.
@@ -1124,30 +1085,31 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
 // a dependent kernel costs ~1.5 us inside a graph against ~2.9 us launched on a stream (tools/latency_probe.hip).
 // The plan (decode_plan) says which launches; it is also what a captured step is found by.
 static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipStream_t st, int64_t kvtok) {
+    const StepBufs& b = e->bufs;
+    SampleScratch sscr = e->sscr;
+    sscr.slice_sum = b.sscr_slice_sum; sscr.lp = b.sscr_lp;
     launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
-                  e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, plan.B, e->sscr, plan.ch0_sampled,
+                  e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, plan.B, sscr, plan.ch0_sampled,
                   full_cap_for(e->V0), plan.scores_on, st);
     GenTopkOut gt;                       // top_logprobs: the raw distribution at the decisions just written, into this step's row
     if (plan.topk) {
-        gt = GenTopkOut{plan.topk, e->d_gt_logp, e->d_gt_ids, e->d_gt_tlp};
+        gt = GenTopkOut{plan.topk, b.d_gt_logp, b.d_gt_ids, b.d_gt_tlp};
         launch_gen_topk(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_scfg, e->d_ls, e->d_seqs, e->d_decisions, plan.B,
-                        e->gtscr, gt, st);
+                        GenTopkScratch{b.gt_cand, b.gt_smax, b.gt_ssum, b.gt_scr_cap}, gt, st);
     }
-    launch_update(e->d_decisions, e->d_declog, plan.forced ? e->d_forced : nullptr, e->d_tf, e->d_gen, e->d_cur,
+    launch_update(e->d_decisions, b.d_declog, plan.forced ? b.d_forced : nullptr, e->d_tf, b.d_gen, e->d_cur,
                   e->d_seqs, e->d_meta, e->d_bitmaps, e->bm_words, e->d_ls, e->cfg.eos_token_id,
                   e->cfg.speech_pad_token, e->cfg.speech_range_lo, e->cfg.speech_range_hi,
-                  plan.scores_on ? e->sscr.lp : nullptr, plan.scores_on ? e->d_lp : nullptr, gt, st);
+                  plan.scores_on ? b.sscr_lp : nullptr, plan.scores_on ? b.d_lp : nullptr, gt, st);
     return forward_rows(e, plan, e->d_cur, e->d_meta, pages_bound, st, kvtok);
 }
 
 static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     StepPlan plan = decode_plan(e, pages);
-    for (auto& g : e->graphs)
-        if (g.pages == pages && g.plan == plan) {
-            *out = g.exec;
-            return MTTS_OK;
-        }
-    if (e->graphs.size() >= 256) drop_graphs(e);
+    if (const hipGraphExec_t* hit = e->graphs.find(plan, pages, e->bufs)) {
+        *out = *hit;
+        return MTTS_OK;
+    }
     if (!e->cap_stream) HIPCHK(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
@@ -1159,7 +1121,7 @@ static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     HIPCHK(ie);
-    e->graphs.push_back({std::move(plan), pages, exec});
+    e->graphs.insert(std::move(plan), pages, e->bufs, exec);
     *out = exec;
     return MTTS_OK;
 }
@@ -1240,7 +1202,7 @@ template <typename Src, typename Dst>
 static int read_slots(MttsEngine* e, const Src* d_src, int slot0, int nslots, int steps, Dst* host, int w = 8) {
     std::vector<Src> tmp((size_t)std::max(steps, 1) * w);
     for (int b = 0; b < nslots; ++b) {
-        if (steps) HIPCHK(hipMemcpy(tmp.data(), d_src + (size_t)(slot0 + b) * e->gen_cap * w, (size_t)steps * w * sizeof(Src), hipMemcpyDeviceToHost));
+        if (steps) HIPCHK(hipMemcpy(tmp.data(), d_src + (size_t)(slot0 + b) * e->bufs.gen_cap * w, (size_t)steps * w * sizeof(Src), hipMemcpyDeviceToHost));
         for (int s = 0; s < steps; ++s)
             for (int c = 0; c < w; ++c) host[((size_t)s * nslots + b) * w + c] = tmp[(size_t)s * w + c];
     }
@@ -1287,7 +1249,7 @@ int32_t mtts_read_generated(MttsEngine* e, int64_t* host_gen, int32_t capacity_s
     if (!e || !e->began || !host_gen) return fail(MTTS_ESTATE, "nothing generated");
     HIPCHK(hipSetDevice(e->device));
     TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
-    return read_rows(e, e->d_gen, host_gen, capacity_steps, n_steps);
+    return read_rows(e, e->bufs.d_gen, host_gen, capacity_steps, n_steps);
 }
 
 // A run counts as open until the device says it has ended: every row finished / every slot empty.  -> *open.
@@ -1310,11 +1272,11 @@ static int run_still_open(MttsEngine* e, bool* open) {
 int32_t mtts_set_output_scores(MttsEngine* e, int32_t on) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     on = on ? 1 : 0;
-    if (on == e->scores_next) return MTTS_OK;
+    if (on == e->pending.output_scores) return MTTS_OK;
     bool open = false;
     TRY(run_still_open(e, &open));
     if (open) return fail(MTTS_ESTATE, "output_scores cannot change while a run is open (it is read when a run begins)");
-    e->scores_next = on;
+    e->pending.output_scores = on;
     return MTTS_OK;
 }
 
@@ -1324,17 +1286,17 @@ int32_t mtts_read_scores(MttsEngine* e, float* host_lp, int32_t capacity_steps, 
     if (!e->scores_on) return fail(MTTS_ESTATE, "the run was started with output_scores off (mtts_set_output_scores)");
     HIPCHK(hipSetDevice(e->device));
     TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
-    return read_rows(e, e->d_lp, host_lp, capacity_steps, n_steps);
+    return read_rows(e, e->bufs.d_lp, host_lp, capacity_steps, n_steps);
 }
 
 int32_t mtts_set_top_logprobs(MttsEngine* e, int32_t k) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     if (k < 0 || k > MTTS_SCORE_MAX_TOPK) return fail(MTTS_EINVAL, "top_logprobs must be 0 (off) or 1..%d (got %d)", MTTS_SCORE_MAX_TOPK, k);
-    if (k == e->topk_next) return MTTS_OK;
+    if (k == e->pending.top_logprobs) return MTTS_OK;
     bool open = false;
     TRY(run_still_open(e, &open));
     if (open) return fail(MTTS_ESTATE, "top_logprobs cannot change while a run is open (it is read when a run begins)");
-    e->topk_next = k;
+    e->pending.top_logprobs = k;
     return MTTS_OK;
 }
 
@@ -1345,9 +1307,9 @@ int32_t mtts_read_top_logprobs(MttsEngine* e, float* host_logp, int32_t* host_to
     if (!e->topk_on) return fail(MTTS_ESTATE, "the run was started with top_logprobs off (mtts_set_top_logprobs)");
     HIPCHK(hipSetDevice(e->device));
     TRY(mtts_sync_state(e, nullptr, nullptr, nullptr));
-    TRY(read_rows(e, e->d_gt_logp, host_logp, capacity_steps, n_steps));
-    TRY(read_rows(e, e->d_gt_ids, host_top_ids, capacity_steps, n_steps, 8 * e->topk_on));
-    return read_rows(e, e->d_gt_tlp, host_top_logp, capacity_steps, n_steps, 8 * e->topk_on);
+    TRY(read_rows(e, e->bufs.d_gt_logp, host_logp, capacity_steps, n_steps));
+    TRY(read_rows(e, e->bufs.d_gt_ids, host_top_ids, capacity_steps, n_steps, 8 * e->topk_on));
+    return read_rows(e, e->bufs.d_gt_tlp, host_top_logp, capacity_steps, n_steps, 8 * e->topk_on);
 }
 
 // ---- teacher-forced scoring (the labels branch of AsteroidTTSInstruct.forward, modeling_asteroid.py:382-410) ---------
@@ -1405,8 +1367,8 @@ static int32_t score_call(MttsEngine* e, const int64_t* ids, const uint8_t* mask
     hipStream_t st = S(stream);
     if (B < 1 || B > e->cfg.max_batch) return fail(MTTS_EINVAL, "batch %d outside 1..max_batch %d", B, e->cfg.max_batch);
     if (T < 1 || T > e->cfg.max_seq_len) return fail(MTTS_EINVAL, "T %d outside 1..max_seq_len %d", T, e->cfg.max_seq_len);
-    if (T > e->rope_rows) return fail(MTTS_EINVAL, "rope table has %d rows, need %d", e->rope_rows, T);
-    if (e->row_adapters_pending)
+    if (T > e->bufs.rope_rows) return fail(MTTS_EINVAL, "rope table has %d rows, need %d", e->bufs.rope_rows, T);
+    if (e->pending.has_row_adapters())
         return fail(MTTS_ESTATE, "mtts_score takes no per-row adapters and a mtts_set_row_adapters list is pending (it stays so): score an adapter merged, with mtts_bind_weight_lora");
     bool open = false;
     TRY(run_still_open(e, &open));
@@ -1436,7 +1398,7 @@ static int32_t score_call(MttsEngine* e, const int64_t* ids, const uint8_t* mask
     // pages: the need is checked against the pool before anything is launched
     if (need > (size_t)e->pool.free_count())
         return fail(MTTS_ENOMEM, "scoring needs %zu KV pages, the pool has %zu free (%d pages of %d tokens)", need, (size_t)e->pool.free_count(), e->total_pages, MTTS_PAGE);
-    if (Mpad > e->sc_cap_rows) {
+    if (Mpad > e->sc_cap_rows) {       // (the sc_* buffers below: read by scoring passes, never by a decode step)
         e->mem.release(e->d_sc_labels); e->mem.release(e->d_sc_logp);
         e->sc_cap_rows = 0;
         TRY(e->mem.get(&e->d_sc_labels, Mpad * 8, false));
@@ -1558,26 +1520,25 @@ int32_t mtts_generate(MttsEngine* e, const int64_t* ids, const uint8_t* mask, in
                       const MttsSamplerCfg* sampler, uint64_t seed, int64_t* out, int32_t out_capacity, int32_t* out_len,
                       const int64_t* forced, int32_t forced_len, int64_t* decisions, void* stream) {
     if (!e) return fail(MTTS_EINVAL, "null argument");
-    const int takes = e->next_takes;
-    e->next_takes = 1;                 // consumed by this call, whatever its outcome
-    const std::vector<int32_t> row_adapters = take_row_adapters(e);
+    RunOptions opt;
+    TRY(take_options(e, B, forced != nullptr, &opt));
     if (!out || !out_len) return fail(MTTS_EINVAL, "null output");
-    if (forced && takes > 1) return fail(MTTS_EINVAL, "forced replay (reference fixtures) has no takes: %d takes per prompt", takes);
-    TRY(begin_run(e, ids, mask, B, T, max_length, sampler, seed, takes, row_adapters, stream));
+    TRY(begin_run(e, ids, mask, B, T, max_length, sampler, seed, opt, stream));
     hipStream_t st = S(stream);
+    const int takes = opt.takes;
     const int base = e->base_length;
     const int R = e->B;
     if (forced) {
         if (!decisions) return fail(MTTS_EINVAL, "forced replay needs host_decisions");
-        std::vector<int32_t> f((size_t)e->cfg.max_batch * e->gen_cap * 8, -1);
+        std::vector<int32_t> f((size_t)e->cfg.max_batch * e->bufs.gen_cap * 8, -1);
         for (int s = 0; s < e->max_steps && base + s < forced_len; ++s)
             for (int b = 0; b < B; ++b)
                 for (int c = 0; c < 8; ++c) {
                     int64_t tk = forced[((size_t)b * forced_len + base + s) * 8 + c];
                     if (tk < 0 || tk >= (c == 0 ? e->V0 : e->Vs)) return fail(MTTS_EINVAL, "forced token %lld out of range on channel %d", (long long)tk, c);
-                    f[((size_t)b * e->gen_cap + s) * 8 + c] = (int32_t)tk;
+                    f[((size_t)b * e->bufs.gen_cap + s) * 8 + c] = (int32_t)tk;
                 }
-        HIPCHK(hipMemcpy(e->d_forced, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->bufs.d_forced, f.data(), f.size() * 4, hipMemcpyHostToDevice));
         e->has_forced = true;
         e->max_steps = std::min(e->max_steps, forced_len - base);
     }
@@ -1597,7 +1558,7 @@ int32_t mtts_generate(MttsEngine* e, const int64_t* ids, const uint8_t* mask, in
     if (total > out_capacity) return fail(MTTS_EINVAL, "out_capacity %d < %d", out_capacity, total);
     std::vector<int64_t> gen((size_t)std::max(steps, 1) * R * 8);
     int ns = 0;
-    TRY(read_rows(e, e->d_gen, gen.data(), steps, &ns));
+    TRY(read_rows(e, e->bufs.d_gen, gen.data(), steps, &ns));
     for (int b = 0; b < R; ++b) {
         const int p = b / takes;       // the row's prompt
         for (int t = 0; t < base; ++t)
@@ -1605,7 +1566,7 @@ int32_t mtts_generate(MttsEngine* e, const int64_t* ids, const uint8_t* mask, in
         for (int s = 0; s < steps; ++s)
             for (int c = 0; c < 8; ++c) out[((size_t)b * out_capacity + base + s) * 8 + c] = gen[((size_t)s * R + b) * 8 + c];
     }
-    if (decisions) TRY(read_rows(e, e->d_declog, decisions, steps, &ns));
+    if (decisions) TRY(read_rows(e, e->bufs.d_declog, decisions, steps, &ns));
     *out_len = total;
     e->run_open = false;               // (a forced replay may stop before every row has finished)
     return MTTS_OK;
@@ -1637,9 +1598,8 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     hipStream_t st = S(stream);
     if (B < 1 || B > e->cfg.max_batch) return fail(MTTS_EINVAL, "batch %d exceeds max_batch %d", B, e->cfg.max_batch);
     if (gen_cap < 8) return fail(MTTS_EINVAL, "gen_cap too small");
-    TRY(ensure_gen_storage(e, gen_cap));
-    TRY(start_scores(e, st));
-    TRY(start_top_logprobs(e, st));
+    e->scores_on = e->pending.output_scores; e->topk_on = e->pending.top_logprobs;      // the sticky switches only
+    TRY(start_outputs(e, gen_cap, st));
     e->B = B; e->steps_issued = 0; e->has_forced = false; e->continuous = true;
     e->max_steps = 1 << 30;
     e->n_real.assign(B, 0);
@@ -1649,7 +1609,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     std::fill(e->slot_live.begin(), e->slot_live.end(), 0);
     TRY(pack_policy_reset(e, st));
     std::fill(e->seq_adapter.begin(), e->seq_adapter.end(), -1);
-    if (e->d_seq_adapter) HIPCHK(hipMemsetAsync(e->d_seq_adapter, 0xff, MTTS_RCAP * sizeof(int32_t), st));
+    if (e->bufs.d_seq_adapter) HIPCHK(hipMemsetAsync(e->bufs.d_seq_adapter, 0xff, MTTS_RCAP * sizeof(int32_t), st));
     TRY(reset_run_state(e, std::vector<SeqState>(MTTS_RCAP, IDLE_SEQ), true, sampler, st));
     e->began = true;
     e->run_open = true;
@@ -1667,7 +1627,7 @@ int32_t mtts_slot_submit(MttsEngine* e, int32_t slot, const int64_t* ids, int32_
 // large one, draw exactly what its rows would draw inside the whole batch.
 int32_t mtts_set_row_ids(MttsEngine* e, const int32_t* host_row_ids, int32_t n) {
     if (!e || (n > 0 && !host_row_ids) || n < 0 || n > MTTS_RCAP) return fail(MTTS_EINVAL, "set_row_ids: bad argument");
-    e->next_row_ids.assign(host_row_ids, host_row_ids + n);
+    e->pending.set_row_ids(host_row_ids, n);
     return MTTS_OK;
 }
 
@@ -1677,16 +1637,15 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = S(stream);
     if (slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "slot %d out of range", slot);
-    const int adapter = e->next_slot_adapter[slot];
-    e->next_slot_adapter[slot] = -1;                  // mtts_set_slot_adapter: consumed by this call, whatever its outcome
+    const int adapter = e->pending.take_slot_adapter(slot);     // mtts_set_slot_adapter: consumed by this call, whatever its outcome
     TRY(adapter_id_check(e, adapter, "slot", slot));
     if (T < 8) return fail(MTTS_EINVAL, "T must be >= 8");
     const int base = T - 7, n = base;
     if (max_length <= base) return fail(MTTS_EINVAL, "max_length leaves no room to generate");
     const int max_new = max_length - base + FLUSH_STEPS;      // incl. a delay-pattern flush that starts at max_length
-    if (max_new > e->gen_cap) return fail(MTTS_EINVAL, "dialogue may run %d steps, slot storage holds %d", max_new, e->gen_cap);
+    if (max_new > e->bufs.gen_cap) return fail(MTTS_EINVAL, "dialogue may run %d steps, slot storage holds %d", max_new, e->bufs.gen_cap);
     if (pages_for(n + max_new) > e->max_pages) return fail(MTTS_ENOMEM, "dialogue needs more KV pages than a sequence may hold");
-    if (n + max_new > e->rope_rows) return fail(MTTS_EINVAL, "rope table too short");
+    if (n + max_new > e->bufs.rope_rows) return fail(MTTS_EINVAL, "rope table too short");
     HIPCHK(hipStreamSynchronize(st));
     {   // the slot must be empty
         SeqState cur;
@@ -1851,14 +1810,14 @@ int32_t mtts_set_forced_mode(MttsEngine* e, int32_t as_draw) {
 // generated rows of one slot: host_rows int64 [steps][8]
 int32_t mtts_slot_read(MttsEngine* e, int32_t slot, int64_t* host_rows, int32_t capacity_steps, int32_t* n_steps) {
     if (!e || !e->began || !host_rows || slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "bad argument");
-    return slot_read(e, e->d_gen, slot, host_rows, capacity_steps, n_steps);
+    return slot_read(e, e->bufs.d_gen, slot, host_rows, capacity_steps, n_steps);
 }
 
 // log-probabilities of one slot's generated rows: host_rows float [steps][8]
 int32_t mtts_slot_read_scores(MttsEngine* e, int32_t slot, float* host_rows, int32_t capacity_steps, int32_t* n_steps) {
     if (!e || !e->began || !host_rows || slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "bad argument");
     if (!e->scores_on) return fail(MTTS_ESTATE, "the run was started with output_scores off (mtts_set_output_scores)");
-    return slot_read(e, e->d_lp, slot, host_rows, capacity_steps, n_steps);
+    return slot_read(e, e->bufs.d_lp, slot, host_rows, capacity_steps, n_steps);
 }
 
 // the same of one slot's generated rows: host_logp float [steps][8], host_top_ids int32 / host_top_logp float [steps][8][k]
@@ -1866,9 +1825,9 @@ int32_t mtts_slot_read_top_logprobs(MttsEngine* e, int32_t slot, float* host_log
                                     int32_t capacity_steps, int32_t* n_steps) {
     if (!e || !e->began || !host_logp || !host_top_ids || !host_top_logp || slot < 0 || slot >= e->B) return fail(MTTS_EINVAL, "bad argument");
     if (!e->topk_on) return fail(MTTS_ESTATE, "the run was started with top_logprobs off (mtts_set_top_logprobs)");
-    TRY(slot_read(e, e->d_gt_logp, slot, host_logp, capacity_steps, n_steps));
-    TRY(slot_read(e, e->d_gt_ids, slot, host_top_ids, capacity_steps, n_steps, 8 * e->topk_on));
-    return slot_read(e, e->d_gt_tlp, slot, host_top_logp, capacity_steps, n_steps, 8 * e->topk_on);
+    TRY(slot_read(e, e->bufs.d_gt_logp, slot, host_logp, capacity_steps, n_steps));
+    TRY(slot_read(e, e->bufs.d_gt_ids, slot, host_top_ids, capacity_steps, n_steps, 8 * e->topk_on));
+    return slot_read(e, e->bufs.d_gt_tlp, slot, host_top_logp, capacity_steps, n_steps, 8 * e->topk_on);
 }
 
 // Frames first..first+n-1 of every sequence as codec codes int64 [8][B][n] on the device (delay pattern undone,
@@ -1878,7 +1837,7 @@ int32_t mtts_export_codes(MttsEngine* e, int32_t first, int32_t n, int64_t* dev_
     if (!e || !e->began || !dev_codes) return fail(MTTS_ESTATE, "nothing generated");
     if (first < 0 || n < 1 || first + n + 7 > e->steps_issued) return fail(MTTS_EINVAL, "frames %d..%d need %d issued steps, have %d", first, first + n - 1, first + n + 7, e->steps_issued);
     HIPCHK(hipSetDevice(e->device));
-    launch_export_codes(e->d_gen, dev_codes, e->B, first, n, e->cfg.speech_range_lo, e->cfg.speech_vocab_size - 2, e->gen_cap, S(stream));
+    launch_export_codes(e->bufs.d_gen, dev_codes, e->B, first, n, e->cfg.speech_range_lo, e->cfg.speech_vocab_size - 2, e->bufs.gen_cap, S(stream));
     HIPCHK(hipGetLastError());
     return MTTS_OK;
 }

@@ -388,7 +388,10 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
     HIPCHK(hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice));
     SampleScratch sc;
     TRY(alloc_scratch(hb, sc, rows, vocab));
-    if (dev_logp) TRY(alloc_lp_scratch(hb, sc, rows));
+    if (dev_logp) {                  // output_scores scratch
+        TRY(hb.get(&sc.slice_sum, (size_t)rows * SAMP_NS));
+        TRY(hb.get(&sc.lp, (size_t)rows * 8));
+    }
     launch_sample_single(logits, rows, vocab, (const uint32_t*)bitmap, (vocab + 31) / 32, d, mask_id, seed, step, channel, dec, err, sc,
                          full_cap_for(vocab), dev_logp ? 1 : 0, st);
     HIPCHK(hipGetLastError());
@@ -432,7 +435,10 @@ int32_t mtts_k_gen_topk(const void* dev_logits, int32_t is_f32, int32_t rows, in
     hipStream_t st = S(stream);
     DevBufs hb;
     GenTopkScratch sc;
-    TRY(alloc_gen_topk_scratch(hb, sc, rows, k));
+    TRY(hb.get(&sc.cand, (size_t)rows * SAMP_NS * k));
+    TRY(hb.get(&sc.smax, (size_t)rows * SAMP_NS));
+    TRY(hb.get(&sc.ssum, (size_t)rows * SAMP_NS));
+    sc.kcap = k;
     launch_gen_topk_single(dev_logits, is_f32 ? 1 : 0, rows, vocab, mask_id, dev_decisions, sc, GenTopkOut{k, dev_logp, dev_top_ids, dev_top_logp}, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
@@ -767,7 +773,7 @@ int32_t mtts_debug_set_kv_len(MttsEngine* e, int32_t kv_len) {
     if (e->f32) return fail(MTTS_EINVAL, "measurement hook of the bf16 engine");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipDeviceSynchronize());
-    const int cap = std::min(e->max_pages * MTTS_PAGE, e->rope_rows);          // positions the pages and the RoPE table hold
+    const int cap = std::min(e->max_pages * MTTS_PAGE, e->bufs.rope_rows);          // positions the pages and the RoPE table hold
     const int limit = cap - MTTS_PAGE;
     if (kv_len < 1 || kv_len > limit) return fail(MTTS_EINVAL, "kv_len %d outside 1..%d", kv_len, limit);
     e->max_steps = std::min(e->max_steps, e->steps_issued + cap - kv_len);   // stay inside the pages and the RoPE table
@@ -800,7 +806,7 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
     const StepPlan plan = decode_plan(e, pages_bound);      // the step's sealed reads per layer
     if (phase == ATTN_ROW) {
         if (attn_row_prepare()) return fail(MTTS_EINVAL, "attn_row_kernel: the dynamic LDS limit could not be raised");
-        const QkvFuse f0{e->partial, e->p_qkv.ksplit, e->qkv_rows, nullptr, nullptr, nullptr, nullptr, 0.f};
+        const QkvFuse f0{e->bufs.partial, e->p_qkv.ksplit, e->qkv_rows, nullptr, nullptr, nullptr, nullptr, 0.f};
         for (int n = 0; n < e->L; ++n) {
             const KvPack pk = layer_pack(e, plan, n);
             if (!attn_row_fits(e->nq / e->nkv, &f0, (pk.k || pk.v) ? &pk : nullptr, pages_bound))
@@ -815,8 +821,8 @@ int32_t mtts_k_attn_bench(MttsEngine* e, int32_t phase, int32_t iters, float* av
             uint16_t* kc = (uint16_t*)e->kcache + e->layer_stride * layer;
             uint16_t* vc = (uint16_t*)e->vcache + e->layer_stride * layer;
             // the product's decode launch: q/k/v epilogue fused (the slabs are whatever the last step left there)
-            const QkvFuse fz{e->partial, e->p_qkv.ksplit, e->qkv_rows, (const uint16_t*)e->layers[layer].qn,
-                             (const uint16_t*)e->layers[layer].kn, e->rope_cos, e->rope_sin, e->cfg.rms_norm_eps};
+            const QkvFuse fz{e->bufs.partial, e->p_qkv.ksplit, e->qkv_rows, (const uint16_t*)e->layers[layer].qn,
+                             (const uint16_t*)e->layers[layer].kn, e->bufs.rope_cos, e->bufs.rope_sin, e->cfg.rms_norm_eps};
             const KvPack pk = layer_pack(e, plan, layer);
             launch_attn(e->qbuf, kc, vc, e->d_page_table, e->d_meta, e->scores, e->stats, e->opart, e->attn_p, R, pages_bound,
                         e->max_pages, e->total_pages, e->nchunks_max, e->nq, e->nkv, scale, (phase == ATTN_ROW || e->B * pages_bound <= e->knobs.fuse_qkv_max) ? &fz : nullptr, (AttnPhase)phase, nullptr,

@@ -1,0 +1,138 @@
+// What a run is started with, and what a captured decode step holds on to.  Three small types, each of which keeps a rule
+// that engine.hip used to keep by hand:
+//   PendingRun / RunOptions   the settings of the mtts_set_* calls.  The one-shot ones leave the engine in one place
+//                             (take), before anything can fail, so "consumed by the next begin, failures included" holds
+//                             for every one of them; the sticky ones are copied.
+//   StepBufs                  every device address a decode step reads that can change after mtts_engine_create, with
+//                             whatever bounds the step's indexing into it.
+//   StepGraphs                the captured steps, found by (plan, KV page bound, StepBufs): a step captured with buffers
+//                             that have since been reallocated is never found again, and is destroyed by the next insert.
+// No HIP in here: engine.h includes it, and so does tests/host/run_state_main.cpp, which runs it on the CPU.
+#pragma once
+#include <cstring>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "stepplan.h"
+
+// defined by whoever includes this (engine.hip; the CPU test), as for kvpool.h
+__attribute__((visibility("hidden"), format(printf, 2, 3))) int fail(int code, const char* fmt, ...);
+static const int RUN_EINVAL = -1;       // MTTS_EINVAL of include/mtts.h (engine.h checks that it is)
+
+// ---- the options of one static run ----------------------------------------------------------------------------------
+struct RunOptions {
+    int B = 0;                          // prompts of the call
+    int takes = 1;                      // rows per prompt: row b*takes+j is take j of prompt b
+    std::vector<int32_t> row_ids;       // Philox row id per row; empty: 0..rows-1
+    std::vector<int32_t> row_adapters;  // adapter per PROMPT (its takes share its KV pages and so its adapter); empty: none
+    int output_scores = 0, top_logprobs = 0;
+    int rows() const { return B * takes; }
+    int row_id(int r) const { return row_ids.empty() ? r : row_ids[r]; }
+    int row_adapter(int r) const { return row_adapters.empty() ? -1 : row_adapters[r / takes]; }
+    // the sizes, before anything is indexed by them; forced: the call is a forced replay (mtts_generate with host_forced)
+    int check(int max_batch, bool forced) const {
+        if (forced && takes > 1) return fail(RUN_EINVAL, "forced replay (reference fixtures) has no takes: %d takes per prompt", takes);
+        if (!row_adapters.empty() && (int)row_adapters.size() != B)
+            return fail(RUN_EINVAL, "mtts_set_row_adapters gave %d ids, the batch has %d prompts", (int)row_adapters.size(), B);
+        if (B < 1 || B > max_batch || rows() > max_batch) return fail(RUN_EINVAL, "batch %d x %d takes exceeds max_batch %d", B, takes, max_batch);
+        if (!row_ids.empty() && (int)row_ids.size() != rows())
+            return fail(RUN_EINVAL, "mtts_set_row_ids gave %d ids, the batch has %d rows", (int)row_ids.size(), rows());
+        return 0;
+    }
+};
+
+// What the mtts_set_* calls leave for the next run.  They validate and store; nothing else in the engine reads these.
+class PendingRun {
+    int takes = 1;
+    std::vector<int32_t> row_ids, row_adapters;
+    std::vector<int32_t> slot_adapter = std::vector<int32_t>(MTTS_RCAP, -1);    // scheduler mode: of the slot's next submit
+public:
+    int output_scores = 0, top_logprobs = 0;        // sticky: every run reads them, none resets them
+    void set_takes(int n) { takes = n; }
+    void set_row_ids(const int32_t* ids, int n) { row_ids.assign(ids, ids + n); }
+    void set_row_adapters(const int32_t* ids, int n) { row_adapters.assign(ids, ids + n); }
+    void set_slot_adapter(int slot, int id) { slot_adapter[slot] = id; }
+    bool has_row_adapters() const { return !row_adapters.empty(); }
+    // mtts_begin / mtts_generate with B prompts: the one-shots move out and are back at their defaults, whatever the call
+    // does next (RunOptions::check included)
+    RunOptions take(int B) {
+        RunOptions o;
+        o.B = B; o.takes = takes; o.output_scores = output_scores; o.top_logprobs = top_logprobs;
+        o.row_ids.swap(row_ids);
+        o.row_adapters.swap(row_adapters);
+        takes = 1;
+        return o;
+    }
+    // mtts_slot_submit* into `slot`: the same for that slot's adapter
+    int take_slot_adapter(int slot) { return std::exchange(slot_adapter[slot], -1); }
+};
+
+// ---- the addresses a captured step holds ----------------------------------------------------------------------------
+// A step graph bakes in its launches' arguments.  Everything allocated by mtts_engine_create lives as long as the engine;
+// what is allocated or reallocated later and read by a decode step (step_body, forward_rows, forward_small, attend_layer,
+// forward_rows_f32 of engine.hip) is here, beside the sizes that bound the step's indexing into it -- an allocator may hand
+// the old address out again for another size.  Not here, though a step passes it: the run's seed.  launch_sample takes it
+// by value for the single-matrix test entry (sampler.hip: single_vocab > 0); a step's rows draw with SeqState.seed, which
+// lives in device memory, so a replayed step does not depend on the value it was captured with.
+struct LoraEnt;
+struct StepBufs {
+    int32_t *d_gen = nullptr, *d_declog = nullptr, *d_forced = nullptr;    // [slot][gen_cap][8]: tokens, decision log, forced rows
+    float* d_lp = nullptr;                  // output_scores [slot][gen_cap][8]; exists once a run asked for it
+    float *sscr_slice_sum = nullptr, *sscr_lp = nullptr;        // ... and the sampler's scratch for it (SampleScratch), sized by max_batch
+    float* d_gt_logp = nullptr;             // top_logprobs [slot][gen_cap][8], and [slot][gen_cap][8][gt_stride]:
+    int32_t* d_gt_ids = nullptr;
+    float* d_gt_tlp = nullptr;
+    unsigned long long* gt_cand = nullptr;  // ... and its scratch (GenTopkScratch), which holds gt_scr_cap candidates per slice
+    float* gt_smax = nullptr;
+    double* gt_ssum = nullptr;
+    uint16_t *rope_cos = nullptr, *rope_sin = nullptr;          // [rope_rows][64] (mtts_bind_rope): the bf16 engine's,
+    float *rope_cos_f = nullptr, *rope_sin_f = nullptr;         // the fp32 / fp16 engine's
+    float* partial = nullptr;               // split-K slabs: widened by the first mtts_adapter_load, with which the next two appear
+    LoraEnt* d_bank = nullptr;
+    int32_t* d_seq_adapter = nullptr;
+    int gen_cap = 0;                        // steps a slot's rows hold
+    int gt_stride = 0, gt_scr_cap = 0;      // innermost stride of d_gt_ids / d_gt_tlp; of gt_cand
+    int rope_rows = 0;
+    // every byte takes part (no padding: the assertion below), so a new member cannot be left out of the comparison
+    bool operator==(const StepBufs& o) const { return memcmp(this, &o, sizeof(StepBufs)) == 0; }
+    bool operator!=(const StepBufs& o) const { return !(*this == o); }
+};
+static_assert(std::has_unique_object_representations<StepBufs>::value, "StepBufs is compared (and swept by its test) bytewise: no padding");
+
+// ---- the captured steps ---------------------------------------------------------------------------------------------
+// Exec: the handle of a captured step (hipGraphExec_t; an int on the CPU); Destroy: what frees one.
+template <typename Exec, typename Destroy>
+class StepGraphs {
+    struct Entry { StepPlan plan; int pages; StepBufs bufs; Exec exec; };
+    std::vector<Entry> entries;
+    Destroy destroy;
+public:
+    enum { CAP = 256 };
+    explicit StepGraphs(Destroy d = Destroy()) : destroy(d) {}
+    StepGraphs(const StepGraphs&) = delete;
+    StepGraphs& operator=(const StepGraphs&) = delete;
+    ~StepGraphs() { clear(); }
+    size_t size() const { return entries.size(); }
+    const Exec* find(const StepPlan& plan, int pages, const StepBufs& bufs) const {
+        for (const Entry& g : entries)
+            if (g.pages == pages && g.bufs == bufs && g.plan == plan) return &g.exec;
+        return nullptr;
+    }
+    // Steps captured with other buffers hold addresses that are dead by now (the engine has one StepBufs at a time): they
+    // go first.  Then the cap: a run whose plans keep changing starts over instead of growing without bound.
+    void insert(StepPlan plan, int pages, const StepBufs& bufs, Exec exec) {
+        size_t keep = 0;
+        for (size_t i = 0; i < entries.size(); ++i) {
+            if (entries[i].bufs != bufs) destroy(entries[i].exec);
+            else { if (keep != i) entries[keep] = std::move(entries[i]); ++keep; }
+        }
+        entries.erase(entries.begin() + keep, entries.end());
+        if (entries.size() >= CAP) clear();
+        entries.push_back(Entry{std::move(plan), pages, bufs, exec});
+    }
+    void clear() {
+        for (Entry& g : entries) destroy(g.exec);
+        entries.clear();
+    }
+};

@@ -3,7 +3,8 @@
 // result says everything the engine branches on: forward_rows, forward_small and attend_layer (engine.hip) execute a
 // StepPlan and hold no policy of their own.  The plan of a decode step is also the key of its captured graph: two steps
 // replay the same graph exactly when their plans compare equal, so a path that joins the plan cannot be forgotten in the key.
-// No HIP in here: engine.h includes it, and so does tests/host/step_plan_main.cpp, which runs it on the CPU.
+// No HIP in here: engine.h includes it (and runstate.h, whose cache of captured steps holds plans), and so does
+// tests/host/step_plan_main.cpp, which runs it on the CPU.
 #pragma once
 #include <algorithm>
 #include <cstdio>
