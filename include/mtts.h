@@ -78,6 +78,21 @@ typedef struct MttsSamplerCfg {
     float repetition_penalty;
 } MttsSamplerCfg;
 
+/* The probability floors of one channel (mtts_set_sampler_floors): HF's MinPLogitsWarper, EpsilonLogitsWarper and
+ * EtaLogitsWarper.  They run in that order after repetition penalty, temperature, top-k and top-p, each on the
+ * survivors K of the one before it.  With e_i = exp(s_i - smax), tot = sum over K of e_i and p_i = e_i / tot:
+ *   min_p           floor = min_p * p_max, p_max = 1 / tot
+ *   epsilon_cutoff  floor = epsilon
+ *   eta_cutoff      floor = min(eta, sqrt(eta) * exp(-H)), H = -sum over K of p_i ln p_i
+ * Token i leaves iff p_i < floor and s_i < smax (HF's min_tokens_to_keep = 1: a token at the maximum never leaves).
+ * A field of 0 means "warper absent", as in MttsSamplerCfg.  A greedy channel applies none. */
+typedef struct MttsSamplerFloors {
+    float min_p;             /* 0..1 */
+    float epsilon_cutoff;    /* 0 <= . < 1 */
+    float eta_cutoff;        /* 0 <= . < 1 */
+    float sqrt_eta_cutoff;   /* sqrt(eta_cutoff) in fp32, computed by the caller as torch.sqrt of the fp32 scalar gives it */
+} MttsSamplerFloors;
+
 typedef struct MttsEngine MttsEngine;
 
 const char* mtts_last_error(void);
@@ -290,6 +305,15 @@ int32_t mtts_set_row_ids(MttsEngine* e, const int32_t* host_row_ids, int32_t n);
  * KV page) and copy the partially filled last one.  The tokens equal those of the repeat-interleaved batch.
  * MTTS_EINVAL: B*n > max_batch, or n > 1 with host_forced (the replay hook has no takes). */
 int32_t mtts_set_takes(MttsEngine* e, int32_t n);
+/* Probability floors of the NEXT run only (one-shot, like mtts_set_takes: consumed by the next mtts_begin, mtts_generate or
+ * mtts_sched_open, failures included; a run that does not ask for floors never inherits them): floors[c] is channel c's
+ * MttsSamplerFloors, applied where that run's sampler[c].do_sample is set.  NULL: none.  They act inside the sampler, on the
+ * kept set top-k / top-p leave: the draw rule (descending score, ties by higher id, the same Philox key) and every other
+ * output are as without them, lp of mtts_set_output_scores is the log-softmax over the final kept set, and
+ * mtts_set_top_logprobs, which describes the raw distribution, does not see them.  A run whose floors are all zero on its
+ * sampled channels launches what a run without floors launches.
+ * MTTS_EINVAL, naming the channel: min_p outside [0, 1], epsilon_cutoff or eta_cutoff outside [0, 1) (NaN included). */
+int32_t mtts_set_sampler_floors(MttsEngine* e, const MttsSamplerFloors floors[8] /* NULL: none */);
 /* Scheduler mode: start a take of the dialogue just submitted to src_slot in the empty dst_slot: same prompt (its
  * complete KV pages shared, the partially filled last one copied), drawing from (seed; step, row_id, channel).  The take's
  * tokens equal those of mtts_slot_submit_row(dst_slot, the same prompt, seed, row_id).  Stream-ordered on `stream`.
@@ -555,6 +579,12 @@ int32_t mtts_k_sample_scores(const void* dev_logits_bf16, int32_t rows, int32_t 
                              const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
                              int32_t* dev_tokens, float* dev_logp, void* stream);
+/* The same call with the channel's probability floors (mtts_set_sampler_floors; the same value checks).  floors NULL or
+ * all zero: the kernels without floors run, bit for bit mtts_k_sample_scores.  dev_logp may be NULL (tokens only). */
+int32_t mtts_k_sample_floors(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
+                             const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
+                             int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
+                             int32_t* dev_tokens, float* dev_logp, const MttsSamplerFloors* floors, void* stream);
 /* The kernels of mtts_set_top_logprobs on bare logits, launched as the engine launches them (the slice pass and the merge
  * when vocab > 4096, the single-block path otherwise): dev_logits [rows][vocab] bf16 bits, or fp32 when is_f32; mask_id
  * the one id at -inf (-1: none); dev_decisions int32 [rows].  dev_logp float [rows] = log_softmax(L)[decision],

@@ -210,6 +210,8 @@ struct MttsEngine {
     uint32_t* d_bitmaps = nullptr;
     int bm_words = 0;
     MttsSamplerCfg* d_scfg = nullptr;
+    MttsSamplerFloors* d_floors = nullptr;      // [8], allocated with the engine: a captured step may hold the address
+    int floors_on = 0;                  // of the current run: a sampled channel has a probability floor (mtts_set_sampler_floors)
     SampleScratch sscr;                 // (its slice_sum / lp stay null here: bufs holds them)
     int ch0_sampled = 0;
     // output_scores: per-token log-probabilities (bufs.d_lp, laid out like bufs.d_gen)
@@ -274,7 +276,8 @@ static inline bool rows_carry_adapters(const MttsEngine* e) {
 static inline StepState step_state(const MttsEngine* e, int heads, int R, int pages_bound, bool lora) {
     StepState s;
     s.heads = heads; s.B = e->B; s.R = R; s.pages_bound = pages_bound; s.lora = lora;
-    s.forced = e->has_forced; s.ch0_sampled = e->ch0_sampled != 0; s.scores_on = e->scores_on != 0; s.topk = e->topk_on;
+    s.forced = e->has_forced; s.ch0_sampled = e->ch0_sampled != 0; s.scores_on = e->scores_on != 0; s.floors_on = e->floors_on != 0;
+    s.topk = e->topk_on;
     for (int k = 0; k < WSEAL_KINDS; ++k) s.wseal_on[k] = e->wseal_on[k] != 0;
     if (e->kpack) s.pack_k_on = e->pack_k_on.data();
     if (e->vpack) s.pack_v_on = e->pack_v_on.data();

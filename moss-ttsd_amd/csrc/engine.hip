@@ -300,6 +300,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     e->bm_words = (e->V0 + 31) / 32;
     TRY(m.get(&e->d_bitmaps, (size_t)MTTS_RCAP * 8 * e->bm_words));
     TRY(m.get(&e->d_scfg, 8));
+    TRY(m.get(&e->d_floors, 8));
     TRY(alloc_scratch(m, e->sscr, c->max_batch, e->V0));
     *out = holder.release();
     return MTTS_OK;
@@ -909,9 +910,10 @@ static int upload_staged(MttsEngine* e, const StagedRows& sr, bool on_stream, hi
 }
 
 // A new run starts from `seqs` (MTTS_RCAP slots; the idle ones as IDLE_SEQ) with every decode row idle, the loop state at
-// step 0, the run's sampler settings and clean sampler scratch.  Returns with `st` drained.
+// step 0, the run's sampler settings (floors: per channel, or empty) and clean sampler scratch.  Returns with `st` drained.
 static const SeqState IDLE_SEQ{-1, 0, 0, 0, 0, 0, 0, 0, 0};
-static int reset_run_state(MttsEngine* e, const std::vector<SeqState>& seqs, bool continuous, const MttsSamplerCfg* sampler, hipStream_t st) {
+static int reset_run_state(MttsEngine* e, const std::vector<SeqState>& seqs, bool continuous, const MttsSamplerCfg* sampler,
+                           const std::vector<MttsSamplerFloors>& floors, hipStream_t st) {
     HIPCHK(hipMemcpyAsync(e->d_seqs, seqs.data(), seqs.size() * sizeof(SeqState), hipMemcpyHostToDevice, st));
     if (continuous) e->forced_draw = 0;
     LoopState ls{0, 0, continuous ? 1 : 0, e->B, 0, e->bufs.gen_cap, e->forced_draw, e->f32 ? 1 : 0};
@@ -923,6 +925,12 @@ static int reset_run_state(MttsEngine* e, const std::vector<SeqState>& seqs, boo
     HIPCHK(hipMemcpyAsync(e->d_meta, dm.data(), dm.size() * sizeof(RowMeta), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(e->d_scfg, sampler, 8 * sizeof(MttsSamplerCfg), hipMemcpyHostToDevice, st));
     e->ch0_sampled = sampler[0].do_sample ? 1 : 0;
+    // probability floors: on when a channel that samples has one (a greedy channel applies none); off, the step is the
+    // one a run without floors launches and nothing reads the table
+    e->floors_on = 0;
+    for (size_t c = 0; c < floors.size(); ++c)
+        if (sampler[c].do_sample && (floors[c].min_p > 0.f || floors[c].epsilon_cutoff > 0.f || floors[c].eta_cutoff > 0.f)) e->floors_on = 1;
+    if (e->floors_on) HIPCHK(hipMemcpyAsync(e->d_floors, floors.data(), 8 * sizeof(MttsSamplerFloors), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(e->sscr.hist, 0, (size_t)e->cfg.max_batch * 2048 * 4, st));
     HIPCHK(hipMemsetAsync(e->sscr.cand_n, 0, (size_t)e->cfg.max_batch * 4, st));
     HIPCHK(hipMemsetAsync(e->sscr.overflow, 0, (size_t)e->cfg.max_batch * 4, st));
@@ -1047,7 +1055,7 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
         // the rows' adapters: a prompt's takes share its KV pages and so its adapter
         for (int b = 0; b < MTTS_RCAP; ++b) e->seq_adapter[b] = b < R ? opt.row_adapter(b) : -1;
         if (e->bufs.d_seq_adapter) HIPCHK(hipMemcpyAsync(e->bufs.d_seq_adapter, e->seq_adapter.data(), MTTS_RCAP * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        TRY(reset_run_state(e, ss, false, sampler, st));   // drains st: the host vectors above go out of scope
+        TRY(reset_run_state(e, ss, false, sampler, opt.floors, st));   // drains st: the host vectors above go out of scope
     }
     TRY(prefill_staged(e, sr.Mpad, pages_for(e->max_real), 2, lora, st));
     // takes: the partially filled last prompt page of each source row into its takes' private pages, and the source
@@ -1063,6 +1071,10 @@ int32_t mtts_set_takes(MttsEngine* e, int32_t n) {
     if (n < 1 || n > MTTS_RCAP) return fail(MTTS_EINVAL, "takes must be 1..%d (got %d)", MTTS_RCAP, n);
     e->pending.set_takes(n);
     return MTTS_OK;
+}
+int32_t mtts_set_sampler_floors(MttsEngine* e, const MttsSamplerFloors* floors) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    return e->pending.set_floors(floors);
 }
 // The options of the mtts_begin / mtts_generate that starts now: out of the engine first -- so the one-shot ones are
 // consumed whatever the call does next -- and then checked.
@@ -1090,7 +1102,7 @@ static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipSt
     sscr.slice_sum = b.sscr_slice_sum; sscr.lp = b.sscr_lp;
     launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
                   e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, plan.B, sscr, plan.ch0_sampled,
-                  full_cap_for(e->V0), plan.scores_on, st);
+                  full_cap_for(e->V0), plan.scores_on, plan.floors_on ? e->d_floors : nullptr, st);
     GenTopkOut gt;                       // top_logprobs: the raw distribution at the decisions just written, into this step's row
     if (plan.topk) {
         gt = GenTopkOut{plan.topk, b.d_gt_logp, b.d_gt_ids, b.d_gt_tlp};
@@ -1592,7 +1604,9 @@ int32_t mtts_read_seq_state(MttsEngine* e, int32_t* host_nas, int32_t* host_unfi
 // while the others keep their state.  mtts_step() then advances every occupied slot by one frame; a dialogue that
 // finishes leaves the batch at once (no finished-row padding) and its slot can be refilled.
 int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSamplerCfg* sampler, void* stream) {
-    if (!e || !sampler) return fail(MTTS_EINVAL, "null argument");
+    if (!e) return fail(MTTS_EINVAL, "null argument");
+    const std::vector<MttsSamplerFloors> floors = e->pending.take_floors();     // the one-shot leaves first: consumed whatever follows
+    if (!sampler) return fail(MTTS_EINVAL, "null argument");
     TRY(mtts_weights_ready(e));
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = S(stream);
@@ -1610,7 +1624,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     TRY(pack_policy_reset(e, st));
     std::fill(e->seq_adapter.begin(), e->seq_adapter.end(), -1);
     if (e->bufs.d_seq_adapter) HIPCHK(hipMemsetAsync(e->bufs.d_seq_adapter, 0xff, MTTS_RCAP * sizeof(int32_t), st));
-    TRY(reset_run_state(e, std::vector<SeqState>(MTTS_RCAP, IDLE_SEQ), true, sampler, st));
+    TRY(reset_run_state(e, std::vector<SeqState>(MTTS_RCAP, IDLE_SEQ), true, sampler, floors, st));
     e->began = true;
     e->run_open = true;
     return MTTS_OK;

@@ -373,7 +373,8 @@ int32_t mtts_k_gemm_tile(int32_t epi, const void* dev_w, const void* dev_x, void
 }
 
 static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
-                    int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp, void* stream) {
+                    int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
+                    const MttsSamplerFloors* floors, void* stream) {
     if (!logits || !cfg || !dev_tokens || rows < 1 || vocab < 1 || channel < 0 || channel > 7) return fail(MTTS_EINVAL, "sample: bad argument");
     hipStream_t st = S(stream);
     MttsSamplerCfg h[8];
@@ -386,6 +387,18 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
     TRY(hb.get(&err, 1));
     TRY(hb.get(&dec, (size_t)rows * 8));
     HIPCHK(hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice));
+    // floors: checked like mtts_set_sampler_floors checks them; none, all zero or a greedy cfg: the kernels without floors
+    MttsSamplerFloors* dfl = nullptr;
+    if (floors) {
+        MttsSamplerFloors hf[8];
+        for (int i = 0; i < 8; ++i) hf[i] = *floors;
+        PendingRun chk;
+        TRY(chk.set_floors(hf));
+        if (cfg->do_sample && (floors->min_p > 0.f || floors->epsilon_cutoff > 0.f || floors->eta_cutoff > 0.f)) {
+            TRY(hb.get(&dfl, 8));
+            HIPCHK(hipMemcpy(dfl, hf, sizeof(hf), hipMemcpyHostToDevice));
+        }
+    }
     SampleScratch sc;
     TRY(alloc_scratch(hb, sc, rows, vocab));
     if (dev_logp) {                  // output_scores scratch
@@ -393,7 +406,7 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
         TRY(hb.get(&sc.lp, (size_t)rows * 8));
     }
     launch_sample_single(logits, rows, vocab, (const uint32_t*)bitmap, (vocab + 31) / 32, d, mask_id, seed, step, channel, dec, err, sc,
-                         full_cap_for(vocab), dev_logp ? 1 : 0, st);
+                         full_cap_for(vocab), dev_logp ? 1 : 0, dfl, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     std::vector<int32_t> hd((size_t)rows * 8);
@@ -415,14 +428,20 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
 
 int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                       int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, void* stream) {
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, nullptr, stream);
 }
 
 int32_t mtts_k_sample_scores(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
                              void* stream) {
     if (!dev_logp) return fail(MTTS_EINVAL, "sample: null dev_logp");
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, nullptr, stream);
+}
+
+int32_t mtts_k_sample_floors(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                             int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
+                             const MttsSamplerFloors* floors, void* stream) {
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, stream);
 }
 
 // The top_logprobs kernels of a decode step (gen_topk.hip) on bare logits, with a scratch of their own.

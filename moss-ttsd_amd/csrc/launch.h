@@ -146,10 +146,11 @@ struct SampleScratch {
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps,
                    int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed,
                    int32_t* decisions, int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap,
-                   int emit_lp, hipStream_t st);
+                   int emit_lp, const MttsSamplerFloors* floors /* device, 8 entries; null: no floors */, hipStream_t st);
 void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
                           const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
-                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp, hipStream_t st);
+                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp,
+                          const MttsSamplerFloors* floors8, hipStream_t st);
 // generate(top_logprobs=k): where a step's results go.  In the engine the per-slot buffers, laid out like gen: logp
 // [slot][gen_cap][8], ids / tlp [slot][gen_cap][8][k]; gen_topk_finish_kernel writes the step's row of every evaluated
 // dialogue, update_kernel<true> then puts NaN / -1 over the slots that are not model decisions, by the rule it applies

@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/mtts.h"       // MttsSamplerFloors (plain C, no HIP)
 #include "stepplan.h"
 
 // defined by whoever includes this (engine.hip; the CPU test), as for kvpool.h
@@ -26,6 +27,7 @@ struct RunOptions {
     int takes = 1;                      // rows per prompt: row b*takes+j is take j of prompt b
     std::vector<int32_t> row_ids;       // Philox row id per row; empty: 0..rows-1
     std::vector<int32_t> row_adapters;  // adapter per PROMPT (its takes share its KV pages and so its adapter); empty: none
+    std::vector<MttsSamplerFloors> floors;      // per channel (mtts_set_sampler_floors); empty: none
     int output_scores = 0, top_logprobs = 0;
     int rows() const { return B * takes; }
     int row_id(int r) const { return row_ids.empty() ? r : row_ids[r]; }
@@ -47,12 +49,25 @@ class PendingRun {
     int takes = 1;
     std::vector<int32_t> row_ids, row_adapters;
     std::vector<int32_t> slot_adapter = std::vector<int32_t>(MTTS_RCAP, -1);    // scheduler mode: of the slot's next submit
+    std::vector<MttsSamplerFloors> floors;
 public:
     int output_scores = 0, top_logprobs = 0;        // sticky: every run reads them, none resets them
     void set_takes(int n) { takes = n; }
     void set_row_ids(const int32_t* ids, int n) { row_ids.assign(ids, ids + n); }
     void set_row_adapters(const int32_t* ids, int n) { row_adapters.assign(ids, ids + n); }
     void set_slot_adapter(int slot, int id) { slot_adapter[slot] = id; }
+    // checked here, where every other size and value of a run's options is: the channel is named
+    int set_floors(const MttsSamplerFloors* f) {
+        floors.clear();
+        for (int c = 0; f && c < MTTS_CHANNELS; ++c) {
+            if (!(f[c].min_p >= 0.f && f[c].min_p <= 1.f)) return fail(RUN_EINVAL, "channel %d: min_p %g is outside [0, 1]", c, (double)f[c].min_p);
+            if (!(f[c].epsilon_cutoff >= 0.f && f[c].epsilon_cutoff < 1.f))
+                return fail(RUN_EINVAL, "channel %d: epsilon_cutoff %g is outside [0, 1)", c, (double)f[c].epsilon_cutoff);
+            if (!(f[c].eta_cutoff >= 0.f && f[c].eta_cutoff < 1.f)) return fail(RUN_EINVAL, "channel %d: eta_cutoff %g is outside [0, 1)", c, (double)f[c].eta_cutoff);
+        }
+        if (f) floors.assign(f, f + MTTS_CHANNELS);
+        return 0;
+    }
     bool has_row_adapters() const { return !row_adapters.empty(); }
     // mtts_begin / mtts_generate with B prompts: the one-shots move out and are back at their defaults, whatever the call
     // does next (RunOptions::check included)
@@ -61,9 +76,12 @@ public:
         o.B = B; o.takes = takes; o.output_scores = output_scores; o.top_logprobs = top_logprobs;
         o.row_ids.swap(row_ids);
         o.row_adapters.swap(row_adapters);
+        o.floors = take_floors();
         takes = 1;
         return o;
     }
+    // mtts_sched_open: a scheduler run takes no other one-shot
+    std::vector<MttsSamplerFloors> take_floors() { return std::exchange(floors, {}); }
     // mtts_slot_submit* into `slot`: the same for that slot's adapter
     int take_slot_adapter(int slot) { return std::exchange(slot_adapter[slot], -1); }
 };

@@ -272,10 +272,12 @@ __global__ __launch_bounds__(SAMP_T) void sample_collect_kernel(
 // Everything after the candidates are known: sort, HF top-k / top-p cuts, Philox draw.
 // val/idx: n candidate (score, id) pairs (LDS for the fast path, global memory for the full-vocabulary path),
 // capacity >= next_pow2(n).  NT threads.  Returns the chosen token in every thread; lp (may be null): thread 0's
-// receives log(softmax over the kept set)[pick].
-template <int NT>
+// receives log(softmax over the kept set)[pick].  FL: the probability floors `fl` (mtts.h: MttsSamplerFloors) cut the kept
+// set once more per active floor.
+template <int NT, bool FL>
 __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, int n, const MttsSamplerCfg& cfg, float smax,
-                             uint32_t step, uint32_t b, uint32_t c, uint64_t seed, double* shd, int* sh_i, float* lp) {
+                             uint32_t step, uint32_t b, uint32_t c, uint64_t seed, double* shd, int* sh_i, float* lp,
+                             const MttsSamplerFloors& fl) {
     const int tid = threadIdx.x;
     // bitonic sort of P = next_pow2(n) slots by (score asc, id asc); padding sorts last
     int P = 1;
@@ -328,6 +330,40 @@ __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, i
         (void)block_excl_scan<NT>((double)drop, shd, dtot);
         first_keep = f0 + (int)dtot;          // cum is monotone: the dropped ones are a prefix
     }
+    // probability floors (HF MinP / Epsilon / EtaLogitsWarper, in that order, each on the survivors of the last): a token
+    // leaves iff its share of the kept mass is below the floor and its score below the maximum.  Scores ascend, so the
+    // leavers are again a prefix of [first_keep, n)
+    if constexpr (FL) {
+        for (int w = 0; w < 3; ++w) {
+            const float fv = w == 0 ? fl.min_p : w == 1 ? fl.epsilon_cutoff : fl.eta_cutoff;
+            if (!(fv > 0.f)) continue;
+            const int mk = n - first_keep;
+            const int perf = (mk + NT - 1) / NT;
+            const int a0 = first_keep + tid * perf, a1 = min(n, a0 + perf);
+            double loc = 0.0, loc1 = 0.0;
+            for (int i = a0; i < a1; ++i) {
+                const double d = (double)(cval[i] - smax), e = (double)expf(cval[i] - smax);
+                loc += e;
+                loc1 += e * d;
+            }
+            double tot, tot1 = 0.0;
+            (void)block_excl_scan<NT>(loc, shd, tot);
+            if (w == 2) (void)block_excl_scan<NT>(loc1, shd, tot1);
+            // the floor as a mass: p_i < floor  <=>  e_i < floor * tot  (p_max = 1 / tot: the top token has e = 1)
+            double thr;
+            if (w == 0) thr = (double)fv;
+            else if (w == 1) thr = (double)fv * tot;
+            else {
+                const double H = log(tot) - tot1 / tot;       // -sum p ln p, p = e / tot, ln p = (s - smax) - ln tot
+                thr = fmin((double)fv, (double)fl.sqrt_eta_cutoff * exp(-H)) * tot;
+            }
+            int drop = 0;
+            for (int i = a0; i < a1; ++i) drop += ((double)expf(cval[i] - smax) < thr && cval[i] < smax) ? 1 : 0;
+            double dtot;
+            (void)block_excl_scan<NT>((double)drop, shd, dtot);
+            first_keep += (int)dtot;
+        }
+    }
     // draw: walk kept tokens from the top (position n-1 down to first_keep)
     const int nk = n - first_keep;
     const int perk = (nk + NT - 1) / NT;
@@ -355,12 +391,13 @@ __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, i
     return cidx[n - 1 - r];
 }
 
-template <bool LP>
+template <bool LP, bool FL>
 __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
     const uint16_t* __restrict__ logits0, const uint16_t* __restrict__ logits17, int V0, int Vs, int Vs_pad,
     const uint32_t* __restrict__ bitmaps, int bm_words, const MttsSamplerCfg* __restrict__ cfgs,
     const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs, uint64_t seed, int32_t* __restrict__ decisions,
-    int32_t* __restrict__ err, SampleScratch sc, int big_channel0, int single_vocab, int single_mask, int single_step, int single_channel) {
+    int32_t* __restrict__ err, SampleScratch sc, int big_channel0, int single_vocab, int single_mask, int single_step, int single_channel,
+    const MttsSamplerFloors* __restrict__ floors) {
     __shared__ float cval[SAMP_CAND];
     __shared__ int cidx[SAMP_CAND];
     __shared__ float shf[SAMP_T / 64];
@@ -465,8 +502,10 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
         return;
     }
     float lpv = 0.f;
-    const int pick = finish_sample<SAMP_T>(cval, cidx, n, cfg, smax, (uint32_t)x.step, x.row_id, (uint32_t)x.c,
-                                           single_vocab > 0 ? seed : x.seed, shd, sh_i, LP ? &lpv : nullptr);
+    MttsSamplerFloors fl{0.f, 0.f, 0.f, 0.f};
+    if constexpr (FL) fl = floors[x.c];
+    const int pick = finish_sample<SAMP_T, FL>(cval, cidx, n, cfg, smax, (uint32_t)x.step, x.row_id, (uint32_t)x.c,
+                                               single_vocab > 0 ? seed : x.seed, shd, sh_i, LP ? &lpv : nullptr, fl);
     if (tid == 0) {
         decisions[out_slot] = pick;
         if (LP) sc.lp[out_slot] = lpv;
@@ -496,32 +535,14 @@ struct NucShared {
     unsigned int out_cnt, grp_cnt;
     u64 out_mass, grp_mass;
 };
-// One digit pass over the row, restricted to the tokens of level-0 bin `binA` that are members of `z`.
-// level 1..3: key digits (higher digits == `prefix`); 4, 5: id digits (9 bits each) of the tokens whose key == `prefix`.
-__device__ void nuc_hist(NucShared& S, const uint32_t* __restrict__ keys, const uint16_t* __restrict__ bins, int V, const NucSel& z,
-                         float smax, int level, int binA, uint32_t prefix, int idhi) {
-    for (int i = threadIdx.x; i < NUC_BINS; i += SAMP_FT) { S.cnt[i] = 0; S.mass[i] = 0; }
-    __syncthreads();
-    // The bins are read 8 per 16-byte load, four loads in flight per thread (a load-test-loop pays one L2 round trip per
-    // token); almost every group holds no token of bin `binA` and leaves after one packed compare.
+// member(i) for every token i of level-0 bin `binA`, the row's tokens spread over the block's threads.
+// The bins are read 8 per 16-byte load, four loads in flight per thread (a load-test-loop pays one L2 round trip per
+// token); almost every group holds no token of bin `binA` and leaves after one packed compare.
+template <typename F>
+__device__ __forceinline__ void nuc_scan_bin(const uint16_t* __restrict__ bins, int V, int binA, F member) {
     const int G = (V + 7) >> 3;                           // (bins[V .. 8G) hold 0xffff: sample_full_kernel pads them)
     const u32x4_t* bv = (const u32x4_t*)bins;
     const uint32_t pat = (uint32_t)binA * 0x00010001u;
-    auto member = [&](int i) {
-        const uint32_t key = keys[i];
-        if (!nuc_in(z, key, i)) return;
-        int d;
-        if (level == 1) d = key >> 21;
-        else if (level == 2) { if ((key >> 21) != prefix) return; d = (key >> 10) & 2047; }
-        else if (level == 3) { if ((key >> 10) != prefix) return; d = key & 1023; }
-        else {
-            if (key != prefix) return;
-            if (level == 4) d = i >> 9;
-            else { if ((i >> 9) != idhi) return; d = i & 511; }
-        }
-        atomicAdd(&S.cnt[d], 1u);
-        if (level <= 3) atomicAdd(&S.mass[d], nuc_q(key, smax));
-    };
     for (int g0 = threadIdx.x; g0 < G; g0 += SAMP_FT * 4) {
         u32x4_t w[4];
 #pragma unroll
@@ -544,6 +565,30 @@ __device__ void nuc_hist(NucShared& S, const uint32_t* __restrict__ keys, const 
             }
         }
     }
+}
+
+// One digit pass over the row, restricted to the tokens of level-0 bin `binA` that are members of `z`.
+// level 1..3: key digits (higher digits == `prefix`); 4, 5: id digits (9 bits each) of the tokens whose key == `prefix`.
+__device__ void nuc_hist(NucShared& S, const uint32_t* __restrict__ keys, const uint16_t* __restrict__ bins, int V, const NucSel& z,
+                         float smax, int level, int binA, uint32_t prefix, int idhi) {
+    for (int i = threadIdx.x; i < NUC_BINS; i += SAMP_FT) { S.cnt[i] = 0; S.mass[i] = 0; }
+    __syncthreads();
+    auto member = [&](int i) {
+        const uint32_t key = keys[i];
+        if (!nuc_in(z, key, i)) return;
+        int d;
+        if (level == 1) d = key >> 21;
+        else if (level == 2) { if ((key >> 21) != prefix) return; d = (key >> 10) & 2047; }
+        else if (level == 3) { if ((key >> 10) != prefix) return; d = key & 1023; }
+        else {
+            if (key != prefix) return;
+            if (level == 4) d = i >> 9;
+            else { if ((i >> 9) != idhi) return; d = i & 511; }
+        }
+        atomicAdd(&S.cnt[d], 1u);
+        if (level <= 3) atomicAdd(&S.mass[d], nuc_q(key, smax));
+    };
+    nuc_scan_bin(bins, V, binA, member);
     __syncthreads();
 }
 
@@ -632,11 +677,74 @@ __device__ void nuc_drop_prefix(NucShared& S, int binA, unsigned int dc, u64 dm,
     __syncthreads();
 }
 
+// ---- probability floors (mtts.h: MttsSamplerFloors) on the full-vocabulary path.  A floor is a mass per token, so the
+// cut is a key threshold: the smallest key whose expf(score - smax) reaches `thr` (never above the maximum's own key,
+// which stays whatever the floor says); every member below it leaves.
+__device__ __forceinline__ uint32_t nuc_floor_key(double thr, float smax) {
+    uint32_t lo = 0x00800000u /* fkey(-FLT_MAX) */, hi = fkey(smax);
+    while (lo < hi) {                                       // smallest key in [lo, hi] that stays; hi always does
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((double)expf(unfkey(mid) - smax) < thr) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// The members of `z` below key `kthr` leave: z, n, tot and the level-0 histogram afterwards describe the survivors.
+__device__ void nuc_floor_cut(NucShared& S, const uint32_t* __restrict__ keys, const uint16_t* __restrict__ bins, int V, NucSel& z,
+                              float smax, uint32_t kthr, unsigned int& n, u64& tot) {
+    // bins ascend with the score: those below binA leave whole (a threshold under the binned window lies in bin 0)
+    const int binA = kthr < fkey(smax - 32.0f) ? 0 : nuc_bin(kthr, smax - 32.0f);
+    __syncthreads();
+    if (threadIdx.x == 0) { S.out_cnt = 0; S.out_mass = 0; S.grp_cnt = 0; S.grp_mass = 0; }
+    __syncthreads();
+    for (int i = threadIdx.x; i < binA; i += SAMP_FT)
+        if (S.cnt0[i]) { atomicAdd(&S.out_cnt, S.cnt0[i]); atomicAdd(&S.out_mass, S.mass0[i]); }
+    nuc_scan_bin(bins, V, binA, [&](int i) {
+        const uint32_t key = keys[i];
+        if (nuc_in(z, key, i) && key < kthr) { atomicAdd(&S.grp_cnt, 1u); atomicAdd(&S.grp_mass, nuc_q(key, smax)); }
+    });
+    __syncthreads();
+    const unsigned int c_bin = S.out_cnt, dc = c_bin + S.grp_cnt;
+    const u64 m_bin = S.out_mass, dm = m_bin + S.grp_mass;
+    if (dc == 0) return;                                    // (uniform: every thread read the same totals)
+    z.kmin = max(z.kmin, kthr);                             // (a top-p group that was partly dropped lies below kthr or stays as it is)
+    n -= dc;
+    tot -= dm;
+    nuc_drop_prefix(S, binA, dc, dm, c_bin, m_bin);
+}
+// sum over the members of exp(s - smax) * (s - smax), for the entropy of eta_cutoff: one pass over the row's keys, four
+// loads in flight; per-thread fp64 sums in index order, then lanes and waves in a fixed order (run-to-run identical)
+__device__ double nuc_entropy_sum(NucShared& S, const uint32_t* __restrict__ keys, int V, const NucSel& z, float smax) {
+    double loc = 0.0;
+    for (int i0 = threadIdx.x; i0 < V; i0 += SAMP_FT * 4) {
+        uint32_t k[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const int i = i0 + u * SAMP_FT; k[u] = i < V ? keys[i] : 0u; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = i0 + u * SAMP_FT;
+            if (i < V && nuc_in(z, k[u], i)) {
+                const float d = unfkey(k[u]) - smax;
+                loc += (double)expf(d) * (double)d;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) loc += __shfl_xor(loc, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) S.wm[threadIdx.x >> 6] = (u64)__double_as_longlong(loc);
+    __syncthreads();
+    double sum = 0.0;
+    for (int w = 0; w < SAMP_FT / 64; ++w) sum += __longlong_as_double((long long)S.wm[w]);
+    __syncthreads();
+    return sum;
+}
+
+template <bool FL>
 __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
     const uint16_t* __restrict__ logits0, int V0, const uint32_t* __restrict__ bitmaps, int bm_words,
     const MttsSamplerCfg* __restrict__ cfgs, const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs,
     uint64_t seed, int32_t* __restrict__ decisions, SampleScratch sc, int full_cap, int emit_lp, int single_vocab, int single_mask,
-    int single_step, int single_channel) {
+    int single_step, int single_channel, const MttsSamplerFloors* __restrict__ floors) {
     __shared__ NucShared S;
     __shared__ float shf[SAMP_FT / 64];
     __shared__ int shi[SAMP_FT / 64];
@@ -715,6 +823,20 @@ __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
                 n -= bc + t;
                 tot -= bm + (u64)t * q;
                 nuc_drop_prefix(S, binA, bc + t, bm + (u64)t * q, c_bin, m_bin);
+            }
+        }
+        // ---- probability floors (HF MinP / Epsilon / EtaLogitsWarper), each on the survivors of the stage before it
+        if constexpr (FL) {
+            const MttsSamplerFloors fl = floors[x.c];
+            // as a mass per token: p_i < floor  <=>  exp(s_i - smax) < floor * total  (p_max = 1 / total)
+            if (fl.min_p > 0.f) nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key((double)fl.min_p, smax), n, tot);
+            if (fl.epsilon_cutoff > 0.f)
+                nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key((double)fl.epsilon_cutoff * ((double)tot / NUC_SCALE), smax), n, tot);
+            if (fl.eta_cutoff > 0.f) {
+                const double t = (double)tot / NUC_SCALE;
+                const double H = log(t) - nuc_entropy_sum(S, keys, V, z, smax) / t;
+                const double eta = fmin((double)fl.eta_cutoff, (double)fl.sqrt_eta_cutoff * exp(-H));
+                nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key(eta * t, smax), n, tot);
             }
         }
         // ---- draw: walk the kept tokens from the top; the first whose running mass exceeds u * total
@@ -887,9 +1009,25 @@ __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __
 
 static SampleScratch g_dummy_scratch;
 // emit_lp (output_scores): the LP instantiations of the scan / final kernels; off, the step runs the plain ones.
+// floors (mtts_set_sampler_floors; device, 8 entries): the FL instantiations of the final / full kernels; null, the plain ones.
+template <bool LP, bool FL>
+static void launch_final(dim3 grid, hipStream_t st, const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad,
+                         const uint32_t* bitmaps, int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs,
+                         uint64_t seed, int32_t* decisions, int32_t* err, const SampleScratch& sc, int big0, int single_vocab,
+                         int single_mask, int single_step, int single_channel, const MttsSamplerFloors* floors) {
+    hipLaunchKernelGGL((sample_final_kernel<LP, FL>), grid, dim3(SAMP_T), 0, st, (const uint16_t*)logits0, (const uint16_t*)logits17,
+                       V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, err, sc, big0, single_vocab, single_mask,
+                       single_step, single_channel, floors);
+}
+#define LAUNCH_FINAL(...)                                                                                              \
+    do {                                                                                                               \
+        if (floors) { if (emit_lp) launch_final<true, true>(__VA_ARGS__); else launch_final<false, true>(__VA_ARGS__); } \
+        else { if (emit_lp) launch_final<true, false>(__VA_ARGS__); else launch_final<false, false>(__VA_ARGS__); }      \
+    } while (0)
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps, int bm_words,
                    const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed, int32_t* decisions,
-                   int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap, int emit_lp, hipStream_t st) {
+                   int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap, int emit_lp,
+                   const MttsSamplerFloors* floors, hipStream_t st) {
     const int big0 = V0 > SAMP_CAND ? 1 : 0;
     if (big0) {
         hipLaunchKernelGGL(emit_lp ? sample_scan_kernel<true> : sample_scan_kernel<false>, dim3(SAMP_NS, B), dim3(SAMP_T), 0, st,
@@ -898,16 +1036,17 @@ void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, in
             hipLaunchKernelGGL(sample_collect_kernel, dim3(SAMP_NS, B), dim3(SAMP_T), 0, st, (const uint16_t*)logits0, V0,
                                bitmaps, bm_words, cfgs, ls, seqs, sc, full_cap, 0, 0, 0, 0);
     }
-    hipLaunchKernelGGL(emit_lp ? sample_final_kernel<true> : sample_final_kernel<false>, dim3(8, B), dim3(SAMP_T), 0, st,
-                       (const uint16_t*)logits0, (const uint16_t*)logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed,
-                       decisions, err, sc, big0, 0, 0, 0, 0);
+    LAUNCH_FINAL(dim3(8, B), st, logits0, logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, err, sc, big0,
+                 0, 0, 0, 0, floors);
     if (big0 && ch0_sampled)
-        hipLaunchKernelGGL(sample_full_kernel, dim3(B), dim3(SAMP_FT), 0, st, (const uint16_t*)logits0, V0, bitmaps,
-                           bm_words, cfgs, ls, seqs, seed, decisions, sc, full_cap, emit_lp, 0, 0, 0, 0);
+        hipLaunchKernelGGL(floors ? sample_full_kernel<true> : sample_full_kernel<false>, dim3(B), dim3(SAMP_FT), 0, st,
+                           (const uint16_t*)logits0, V0, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, sc, full_cap, emit_lp,
+                           0, 0, 0, 0, floors);
 }
 void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
                           const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
-                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp, hipStream_t st) {
+                          int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp,
+                          const MttsSamplerFloors* floors, hipStream_t st) {
     if (vocab > SAMP_CAND) {
         hipLaunchKernelGGL(emit_lp ? sample_scan_kernel<true> : sample_scan_kernel<false>, dim3(SAMP_NS, rows), dim3(SAMP_T), 0, st,
                            (const uint16_t*)logits, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr,
@@ -915,14 +1054,14 @@ void launch_sample_single(const void* logits, int rows, int vocab, const uint32_
         hipLaunchKernelGGL(sample_collect_kernel, dim3(SAMP_NS, rows), dim3(SAMP_T), 0, st, (const uint16_t*)logits, vocab,
                            bitmap, bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, sc, full_cap, vocab, mask_id, step, channel);
     }
-    hipLaunchKernelGGL(emit_lp ? sample_final_kernel<true> : sample_final_kernel<false>, dim3(1, rows), dim3(SAMP_T), 0, st,
-                       (const uint16_t*)logits, (const uint16_t*)nullptr, vocab, vocab, vocab, bitmap, bm_words, cfgs8,
-                       (const LoopState*)nullptr, (const SeqState*)nullptr, seed, decisions, err, sc, 1, vocab, mask_id, step, channel);
+    LAUNCH_FINAL(dim3(1, rows), st, logits, nullptr, vocab, vocab, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr,
+                 (const SeqState*)nullptr, seed, decisions, err, sc, 1, vocab, mask_id, step, channel, floors);
     if (vocab > SAMP_CAND)
-        hipLaunchKernelGGL(sample_full_kernel, dim3(rows), dim3(SAMP_FT), 0, st, (const uint16_t*)logits, vocab, bitmap,
-                           bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, seed, decisions, sc, full_cap, emit_lp,
-                           vocab, mask_id, step, channel);
+        hipLaunchKernelGGL(floors ? sample_full_kernel<true> : sample_full_kernel<false>, dim3(rows), dim3(SAMP_FT), 0, st,
+                           (const uint16_t*)logits, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr,
+                           seed, decisions, sc, full_cap, emit_lp, vocab, mask_id, step, channel, floors);
 }
+#undef LAUNCH_FINAL
 void launch_update(const int32_t* decisions, int32_t* dec_log, const int32_t* forced, const int32_t* tf_tail,
                    int32_t* gen, int32_t* cur_tokens, SeqState* seqs, RowMeta* meta, uint32_t* bitmaps, int bm_words,
                    LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out, const GenTopkOut& gt,

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from mtts import adapters, synth, topk_spec
+from mtts import adapters, synth, topk_spec, warp_spec
 from mtts.engine import Engine
 
 _CFG_KEYS = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads",
@@ -65,6 +65,10 @@ class GenerationConfig:
         self.top_k = kw.get("top_k")
         self.top_p = kw.get("top_p")
         self.repetition_penalty = kw.get("repetition_penalty")
+        # HF's probability floors (MinP / Epsilon / EtaLogitsWarper), which _get_logits_processor puts behind top-p
+        self.min_p = kw.get("min_p")
+        self.epsilon_cutoff = kw.get("epsilon_cutoff", 0.0)
+        self.eta_cutoff = kw.get("eta_cutoff", 0.0)
         self.seed = kw.get("seed")
         self.num_return_sequences = kw.get("num_return_sequences", 1)
 
@@ -76,8 +80,13 @@ class GenerationConfig:
         with open(p) as f:
             return cls(**json.load(f))
 
-    def channel_settings(self, channels):
-        """-> (layers[8], do_samples[8]); the global-processor branch (:107-109) repeats one config."""
+    def channel_settings(self, channels, **floors):
+        """-> (layers[8], do_samples[8]); the global-processor branch (:107-109) repeats one config.
+        The probability floors min_p / epsilon_cutoff / eta_cutoff: in the global branch the top-level fields (or the
+        `floors` keywords, generate()'s overrides for one call) join the one dict under the conditions on which HF's
+        _get_logits_processor adds the warper: min_p is not None, 0 < epsilon_cutoff < 1, 0 < eta_cutoff < 1.  In the
+        per-channel branch they come from layers[i] -- this engine's extension of the four keys the reference reads
+        there -- and the top-level values are ignored, as that branch of the reference ignores every top-level warper."""
         if self.do_samples is not None:
             layers = list(self.layers or [])
             layers += [{}] * (channels - len(layers))
@@ -86,6 +95,10 @@ class GenerationConfig:
         if self.do_sample:
             one = dict(repetition_penalty=self.repetition_penalty, temperature=self.temperature,
                        top_k=self.top_k, top_p=self.top_p)
+            for k in warp_spec.FLOOR_KEYS:
+                v = floors[k] if floors.get(k) is not None else getattr(self, k)
+                if v is not None and (k == "min_p" or 0.0 < float(v) < 1.0):
+                    one[k] = v
         elif self.repetition_penalty not in (None, 1.0):
             one = dict(repetition_penalty=self.repetition_penalty)
         return [one] * channels, [self.do_sample] * channels
@@ -460,7 +473,7 @@ class AsteroidTTSInstruct:
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,
                  num_return_sequences=None, return_dict_in_generate=False, output_scores=False, adapter_names=None,
-                 top_logprobs=None, **kw):
+                 top_logprobs=None, min_p=None, epsilon_cutoff=None, eta_cutoff=None, **kw):
         """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
         num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
         repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages.
@@ -471,7 +484,15 @@ class AsteroidTTSInstruct:
         "__base__" or None for none; the prompt's takes run with it.  A row's tokens are those of the single-prompt call.
         top_logprobs=k (1..16, needs return_dict_in_generate=True): the output also carries `logprobs`, `top_ids` and
         `top_logprobs` (GenerateOutput), the model's own distribution at every decision, selected on the device in the
-        decode step; it changes no token and no transition score."""
+        decode step; it changes no token and no transition score.
+        min_p / epsilon_cutoff / eta_cutoff (HF's generate keywords): override generation_config's for this call in the
+        global branch; with generation_config.do_samples set the floors are per channel and belong in layers[i]."""
+        over = {k: v for k, v in (("min_p", min_p), ("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)) if v is not None}
+        for name, v in over.items():
+            warp_spec.check_floor(name, v, "generate(): ")
+        if over and self.generation_config.do_samples is not None:
+            raise ValueError(f"generate({', '.join(over)}=...) with generation_config.do_samples set: the per-channel branch reads its "
+                             "warpers from generation_config.layers[i]; put the floors there")
         k = 0
         if top_logprobs is not None:
             k = topk_spec.check_k(top_logprobs)
@@ -497,7 +518,9 @@ class AsteroidTTSInstruct:
         mnt = max_new_tokens if max_new_tokens is not None else gc.max_new_tokens
         if max_length is None:
             max_length = (T + mnt) if mnt is not None else gc.max_length
-        layers, do_samples = gc.channel_settings(C)
+        layers, do_samples = gc.channel_settings(C, **over)
+        for i, lc in enumerate(layers):
+            warp_spec.floors_of(lc, f"generation_config, channel {i}: ")       # a bad value: ValueError before the device is touched
         if n > 1 and not any(do_samples):
             # HF GenerationMixin: greedy search returns one sequence per prompt
             raise ValueError("Greedy methods (do_sample != True) without beam search do not support `num_return_sequences` "

@@ -22,6 +22,10 @@ class MttsSamplerCfg(C.Structure):
                 ("one_minus_top_p", C.c_float), ("temperature", C.c_float), ("repetition_penalty", C.c_float)]
 
 
+class MttsSamplerFloors(C.Structure):
+    _fields_ = [("min_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float), ("sqrt_eta_cutoff", C.c_float)]
+
+
 class MttsCodecConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "nq", "codebook_size", "rvq_dim", "quant_out_dim",
@@ -92,6 +96,7 @@ _SIGS = {
     "mtts_slot_submit_row": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p]),
     "mtts_set_row_ids": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mtts_set_takes": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "mtts_set_sampler_floors": (C.c_int32, [C.c_void_p, C.POINTER(MttsSamplerFloors)]),
     "mtts_slot_fork": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p]),
     "mtts_slot_states": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_slot_read": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
@@ -145,6 +150,9 @@ _SIGS = {
                                   C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mtts_k_sample_scores": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg),
                                          C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_k_sample_floors": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg),
+                                         C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.POINTER(MttsSamplerFloors), C.c_void_p]),
     "mtts_codec_last_error": (C.c_char_p, []),
     "mtts_codec_create": (C.c_int32, [C.POINTER(MttsCodecConfig), C.c_int32, C.POINTER(C.c_void_p)]),
     "mtts_codec_destroy": (C.c_int32, [C.c_void_p]),

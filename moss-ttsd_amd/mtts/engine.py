@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, warp_spec
 
 
 def sampler_cfgs(layers=None, do_samples=None):
@@ -26,6 +26,22 @@ def sampler_cfgs(layers=None, do_samples=None):
         rp = lc.get("repetition_penalty")
         s.repetition_penalty = float(rp) if rp is not None else 0.0
     return arr
+
+
+def sampler_floors(layers=None, do_samples=None):
+    """The probability floors of the same per-channel dicts -> MttsSamplerFloors[8], or None when no sampled channel sets
+    one (the run then launches what it launched before floors existed).  Keys `min_p`, `epsilon_cutoff`, `eta_cutoff`
+    (HF's MinP / Epsilon / EtaLogitsWarper; mtts/warp_spec.py states the rule): this engine's extension of the reference's
+    four per-channel keys.  None or 0 = absent; a greedy channel's are ignored, like its top_k / top_p.  ValueError, naming
+    the channel, for a value outside HF's range."""
+    arr, on = (capi.MttsSamplerFloors * 8)(), False
+    for i in range(8):
+        lc = (layers[i] if layers and i < len(layers) else {}) or {}
+        f = warp_spec.floors_of(lc, f"layers[{i}]: ")
+        if do_samples and do_samples[i]:
+            arr[i].min_p, arr[i].epsilon_cutoff, arr[i].eta_cutoff, arr[i].sqrt_eta_cutoff = f
+            on = on or any(v > 0.0 for v in f[:3])
+    return arr if on else None
 
 
 def rope_tables(head_dim, theta, rows, device, dtype=torch.bfloat16):
@@ -166,6 +182,10 @@ class Engine:
         capi.check(self.lib.mtts_set_takes(self._h, takes))
         return takes
 
+    def _set_floors(self, layers, do_samples):
+        """One-shot like takes: the floors of `layers` for the run that starts next, or none (mtts_set_sampler_floors)."""
+        capi.check(self.lib.mtts_set_sampler_floors(self._h, sampler_floors(layers, do_samples)))
+
     def set_output_scores(self, on):
         """Sticky engine switch, read when the next run begins (begin / generate / sched_open): per-token
         log-probabilities (include/mtts.h: mtts_set_output_scores).  MttsError(ESTATE) when it would change while rows of
@@ -208,6 +228,7 @@ class Engine:
         out = np.zeros((R, cap, 8), dtype=np.int64)
         out_len = C.c_int32(0)
         scfg = sampler_cfgs(layers, do_samples)
+        self._set_floors(layers, do_samples)
         self.set_output_scores(output_scores)
         self.set_top_logprobs(top_logprobs)
         self._set_row_ids(row_ids, R)       # Philox row id of each row (default: its position in this batch)
@@ -265,6 +286,7 @@ class Engine:
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
         self._B, self._T = B * int(takes), T
+        self._set_floors(layers, do_samples)
         self.set_output_scores(output_scores)
         self.set_top_logprobs(top_logprobs)
         self._set_row_ids(row_ids, B * int(takes))
@@ -323,6 +345,7 @@ class Engine:
     # ---- continuous batching ---------------------------------------------------------
     def sched_open(self, slots, gen_cap, layers=None, do_samples=None, output_scores=False, top_logprobs=0):
         self._B = int(slots)
+        self._set_floors(layers, do_samples)
         self.set_output_scores(output_scores)
         self.set_top_logprobs(top_logprobs)
         capi.check(self.lib.mtts_sched_open(self._h, int(slots), int(gen_cap), sampler_cfgs(layers, do_samples), None))
