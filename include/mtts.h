@@ -93,6 +93,23 @@ typedef struct MttsSamplerFloors {
     float sqrt_eta_cutoff;   /* sqrt(eta_cutoff) in fp32, computed by the caller as torch.sqrt of the fp32 scalar gives it */
 } MttsSamplerFloors;
 
+/* The hard bans of one channel (mtts_set_sampler_bans): HF's NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor
+ * and SuppressTokensLogitsProcessor.  All three only put tokens at -inf, and -inf survives penalty and temperature, so
+ * the order among the processors does not matter: a banned token has processed score -inf, everything else is as without
+ * bans.  They are processors, not warpers: a greedy channel applies them too.  With h the channel's history at decode step
+ * g (every left-padded prompt slot and every appended token: the stream the repetition penalty sees), the banned set is
+ *   no_repeat_ngram_size n   every h[j+n-1] with h[j : j+n-1] == h[len(h)-n+1 :], 0 <= j <= len(h)-n  (n = 1: all of h)
+ *   suppress                 every listed id inside the channel's vocabulary (others are ignored)
+ *   min_new_tokens m         eos_token_id while g < m + 7 (HF counts from the full prompt width, delay tail included)
+ * A field of 0 means "processor absent".  mtts/ban_spec.py states the same rule in numpy. */
+#define MTTS_NGRAM_MAX 16
+typedef struct MttsSamplerBans {
+    int32_t no_repeat_ngram_size;    /* 0..MTTS_NGRAM_MAX */
+    int32_t min_new_tokens;          /* >= 0 */
+    int32_t n_suppress;              /* entries of suppress */
+    const int32_t* suppress;         /* ids >= 0; read during the call only */
+} MttsSamplerBans;
+
 typedef struct MttsEngine MttsEngine;
 
 const char* mtts_last_error(void);
@@ -314,6 +331,21 @@ int32_t mtts_set_takes(MttsEngine* e, int32_t n);
  * sampled channels launches what a run without floors launches.
  * MTTS_EINVAL, naming the channel: min_p outside [0, 1], epsilon_cutoff or eta_cutoff outside [0, 1) (NaN included). */
 int32_t mtts_set_sampler_floors(MttsEngine* e, const MttsSamplerFloors floors[8] /* NULL: none */);
+/* Hard bans of the NEXT run only (one-shot like mtts_set_sampler_floors: consumed by the next mtts_begin, mtts_generate or
+ * mtts_sched_open, failures included): bans[c] is channel c's MttsSamplerBans, applied whether the channel samples or not.
+ * NULL: none.  A banned token has processed score -inf in every sampler kernel; lp of mtts_set_output_scores is the
+ * log-softmax over what survives, bans included, and mtts_set_top_logprobs, which describes the raw distribution, does not
+ * see them.  A row whose every token is banned gives token 0 with lp NaN, on greedy and sampled channels alike.  A run with
+ * a ban launches one more kernel per decode step, ahead of the sampler, which rewrites the per-(row, channel) ban words:
+ * the static part (suppress, eos while the step is below min_new_tokens + 7), then the followers of every earlier
+ * occurrence of the history's last n-1 tokens.  The history and ban buffers exist only once a run asked for them; a
+ * run without bans launches what it launched before and allocates nothing.  With an n-gram ban a prompt may have at most
+ * max_seq_len slots (padding included).
+ * MTTS_EINVAL, naming the channel: no_repeat_ngram_size outside [0, MTTS_NGRAM_MAX], min_new_tokens < 0, n_suppress < 0 or
+ * without a list, a negative id. */
+int32_t mtts_set_sampler_bans(MttsEngine* e, const MttsSamplerBans bans[8] /* NULL: none */);
+/* Launches of the ban kernel by this process so far (engine steps and mtts_k_ngram_ban). */
+int64_t mtts_debug_ban_launches(void);
 /* Scheduler mode: start a take of the dialogue just submitted to src_slot in the empty dst_slot: same prompt (its
  * complete KV pages shared, the partially filled last one copied), drawing from (seed; step, row_id, channel).  The take's
  * tokens equal those of mtts_slot_submit_row(dst_slot, the same prompt, seed, row_id).  Stream-ordered on `stream`.
@@ -585,6 +617,20 @@ int32_t mtts_k_sample_floors(const void* dev_logits_bf16, int32_t rows, int32_t 
                              const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
                              int32_t* dev_tokens, float* dev_logp, const MttsSamplerFloors* floors, void* stream);
+/* The same call with a ban bitmap (mtts_set_sampler_bans): dev_ban uint32 [rows][ceil(vocab / 32)], bit i of a row set =
+ * token i at -inf.  NULL: the plain call, bit for bit (an all-zero bitmap gives the same results). */
+int32_t mtts_k_sample_bans(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
+                           const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
+                           int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
+                           int32_t* dev_tokens, float* dev_logp, const MttsSamplerFloors* floors, const void* dev_ban,
+                           void* stream);
+/* The ban kernel of a decode step on bare histories, launched as the engine launches it (one block per row): dev_hist
+ * int32 [rows][cap], dev_lens int32 [rows] (each 0..cap), n = no_repeat_ngram_size (0..MTTS_NGRAM_MAX; 0: static bans
+ * only, no scan), host_static n_static ids (suppress; those outside [0, vocab) are ignored), eos_id banned when eos_on.
+ * dev_ban uint32 [rows][ceil(vocab / 32)] is overwritten: whatever it held before the call is gone, bits >= vocab are 0. */
+int32_t mtts_k_ngram_ban(const int32_t* dev_hist, const int32_t* dev_lens, int32_t rows, int32_t cap, int32_t n,
+                         const int32_t* host_static, int32_t n_static, int32_t vocab, int32_t eos_id, int32_t eos_on,
+                         void* dev_ban, void* stream);
 /* The kernels of mtts_set_top_logprobs on bare logits, launched as the engine launches them (the slice pass and the merge
  * when vocab > 4096, the single-block path otherwise): dev_logits [rows][vocab] bf16 bits, or fp32 when is_f32; mask_id
  * the one id at -inf (-1: none); dev_decisions int32 [rows].  dev_logp float [rows] = log_softmax(L)[decision],

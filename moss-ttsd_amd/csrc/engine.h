@@ -1,7 +1,7 @@
 // What engine.hip (engine object, C ABI of the product path) and hooks.hip (per-kernel test / bench entry points)
 // share: the engine's definition, error reporting, and the owner of device memory.  Only these two files include it.
 // The HIP-free host code sits apart, where a CPU test can include it: kvpool.h (the KV page pool; through launch.h),
-// staging.h (prompt staging; engine.hip alone), stepplan.h (how a pass chooses its kernels) and runstate.h (the options a
+// staging.h (prompt staging; engine.hip, and hooks.hip for the static ban bitmap), stepplan.h (how a pass chooses its kernels) and runstate.h (the options a
 // run starts with, the addresses a captured step holds, the captured steps; both included here) -- besides those includers
 // only tests/host/pool_stage_main.cpp, tests/host/step_plan_main.cpp and tests/host/run_state_main.cpp.
 //
@@ -212,7 +212,10 @@ struct MttsEngine {
     MttsSamplerCfg* d_scfg = nullptr;
     MttsSamplerFloors* d_floors = nullptr;      // [8], allocated with the engine: a captured step may hold the address
     int floors_on = 0;                  // of the current run: a sampled channel has a probability floor (mtts_set_sampler_floors)
-    SampleScratch sscr;                 // (its slice_sum / lp stay null here: bufs holds them)
+    BanCfg* d_bancfg = nullptr;         // [8], allocated with the engine like d_floors (launch.h: launch_ban)
+    int bans_on = 0;                    // of the current run: a channel has a hard ban (mtts_set_sampler_bans; the buffers are in bufs)
+    int ban_ngram_on = 0;               // ... an n-gram ban: submits stage the prompt's slots into bufs.d_hist
+    SampleScratch sscr;                 // (its slice_sum / lp / ban stay null here: bufs holds them)
     int ch0_sampled = 0;
     // output_scores: per-token log-probabilities (bufs.d_lp, laid out like bufs.d_gen)
     int scores_on = 0;                  // of the current run
@@ -277,6 +280,7 @@ static inline StepState step_state(const MttsEngine* e, int heads, int R, int pa
     StepState s;
     s.heads = heads; s.B = e->B; s.R = R; s.pages_bound = pages_bound; s.lora = lora;
     s.forced = e->has_forced; s.ch0_sampled = e->ch0_sampled != 0; s.scores_on = e->scores_on != 0; s.floors_on = e->floors_on != 0;
+    s.bans_on = e->bans_on != 0;
     s.topk = e->topk_on;
     for (int k = 0; k < WSEAL_KINDS; ++k) s.wseal_on[k] = e->wseal_on[k] != 0;
     if (e->kpack) s.pack_k_on = e->pack_k_on.data();

@@ -301,6 +301,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     TRY(m.get(&e->d_bitmaps, (size_t)MTTS_RCAP * 8 * e->bm_words));
     TRY(m.get(&e->d_scfg, 8));
     TRY(m.get(&e->d_floors, 8));
+    TRY(m.get(&e->d_bancfg, 8));
     TRY(alloc_scratch(m, e->sscr, c->max_batch, e->V0));
     *out = holder.release();
     return MTTS_OK;
@@ -888,6 +889,50 @@ static int start_outputs(MttsEngine* e, int steps, hipStream_t st) {
     return 0;
 }
 
+// The hard bans of the run that starts now (mtts_set_sampler_bans): the per-channel settings and static bitmaps go up, and
+// the buffers the ban kernel works on appear with the first run that asks -- the ban words and static bitmaps with any
+// ban, the prompt history with an n-gram ban.  They are members of bufs and keep their size, so nothing is released here.
+// A run without bans touches and allocates nothing.  Returns with `st` drained when it copied.
+static int start_bans(MttsEngine* e, const RunBans& bans, hipStream_t st) {
+    StepBufs& b = e->bufs;
+    e->bans_on = bans.any() ? 1 : 0;
+    e->ban_ngram_on = bans.ngram() ? 1 : 0;
+    if (!e->bans_on) return 0;
+    const int rows = e->cfg.max_batch, words = e->bm_words;
+    if (!b.d_ban) {
+        TRY(e->mem.get(&b.d_ban, (size_t)rows * 8 * words));
+        TRY(e->mem.get(&b.d_ban_static, (size_t)8 * words));
+        b.ban_words = words;
+    }
+    if (e->ban_ngram_on && !b.d_hist) {
+        TRY(e->mem.get(&b.d_hist, (size_t)rows * e->cfg.max_seq_len * 8));
+        b.hist_cap = e->cfg.max_seq_len;
+    }
+    BanCfg cfg[8];
+    std::vector<uint32_t> stat((size_t)8 * words, 0u);
+    for (int c = 0; c < 8; ++c) {
+        const ChannelBans& cb = bans.ch[c];
+        cfg[c] = BanCfg{cb.ngram, cb.min_new > 0 ? cb.min_new + 7 : 0};
+        stage_ban_static(cb.suppress.data(), (int)cb.suppress.size(), c == 0 ? e->V0 : e->Vs, words, stat.data() + (size_t)c * words);
+    }
+    HIPCHK(hipMemcpyAsync(e->d_bancfg, cfg, sizeof(cfg), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b.d_ban_static, stat.data(), stat.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+// the prompt slots [n][8] of the dialogue in `slot`, for the n-gram ban: into its row of bufs.d_hist.  on_stream: on `st`,
+// which the caller drains before `host` dies (mtts_begin); else synchronously (mtts_slot_submit)
+static int upload_history(MttsEngine* e, int slot, const int64_t* toks, int n, std::vector<int32_t>& host, bool on_stream, hipStream_t st) {
+    if (n > e->bufs.hist_cap)
+        return fail(MTTS_EINVAL, "no_repeat_ngram_size: the prompt has %d slots (padding included), the history holds max_seq_len = %d", n, e->bufs.hist_cap);
+    host.resize((size_t)n * 8);
+    stage_history(toks, n, host.data());
+    int32_t* dst = e->bufs.d_hist + (size_t)slot * e->bufs.hist_cap * 8;
+    if (on_stream) HIPCHK(hipMemcpyAsync(dst, host.data(), host.size() * 4, hipMemcpyHostToDevice, st));
+    else HIPCHK(hipMemcpy(dst, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
 // staged rows (staging.h) into the prefill staging, which grows to hold them.  on_stream: asynchronously on `st`, which
 // the caller drains before `sr` dies (mtts_begin, mtts_score); else synchronously (mtts_slot_submit)
 static int upload_staged(MttsEngine* e, const StagedRows& sr, bool on_stream, hipStream_t st) {
@@ -1035,6 +1080,9 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
     // generation buffers
     e->scores_on = opt.output_scores; e->topk_on = opt.top_logprobs;
     TRY(start_outputs(e, max_steps, st));
+    TRY(start_bans(e, opt.bans, st));
+    if (e->ban_ngram_on && base > e->bufs.hist_cap)
+        return fail(MTTS_EINVAL, "no_repeat_ngram_size: the prompt has %d slots (padding included), the history holds max_seq_len = %d", base, e->bufs.hist_cap);
     StagedRows sr;
     TRY(stage_rows(seqs, e->V0, e->Vs, false, &sr));
     {
@@ -1049,6 +1097,13 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
         }
         std::vector<SeqState> ss(MTTS_RCAP, IDLE_SEQ);
         for (int b = 0; b < R; ++b) ss[b] = SeqState{-1, 1, e->n_real[b], 0, base, max_length, opt.row_id(b), 1, seed};
+        // n-gram ban: every row's prompt slots, the stream the bitmap was built from (a prompt's takes start from the same)
+        std::vector<std::vector<int32_t>> hist(e->ban_ngram_on ? B : 0);
+        for (int rw = 0; e->ban_ngram_on && rw < R; ++rw) {
+            std::vector<int32_t>& hb = hist[rw / takes];
+            if (rw % takes == 0) TRY(upload_history(e, rw, ids + (size_t)(rw / takes) * T * 8, base, hb, true, st));
+            else HIPCHK(hipMemcpyAsync(e->bufs.d_hist + (size_t)rw * e->bufs.hist_cap * 8, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, st));
+        }
         TRY(upload_staged(e, sr, true, st));
         HIPCHK(hipMemcpyAsync(e->d_bitmaps, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(e->d_tf, tf.data(), tf.size() * 4, hipMemcpyHostToDevice, st));
@@ -1076,6 +1131,10 @@ int32_t mtts_set_sampler_floors(MttsEngine* e, const MttsSamplerFloors* floors) 
     if (!e) return fail(MTTS_EINVAL, "null engine");
     return e->pending.set_floors(floors);
 }
+int32_t mtts_set_sampler_bans(MttsEngine* e, const MttsSamplerBans* bans) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    return e->pending.set_bans(bans);
+}
 // The options of the mtts_begin / mtts_generate that starts now: out of the engine first -- so the one-shot ones are
 // consumed whatever the call does next -- and then checked.
 static int take_options(MttsEngine* e, int B, bool forced, RunOptions* opt) {
@@ -1100,6 +1159,11 @@ static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipSt
     const StepBufs& b = e->bufs;
     SampleScratch sscr = e->sscr;
     sscr.slice_sum = b.sscr_slice_sum; sscr.lp = b.sscr_lp;
+    if (plan.bans_on) {                  // this step's banned tokens, from the history as the last update_kernel left it
+        launch_ban(b.d_ban, b.d_ban_static, b.ban_words, e->d_bancfg, b.d_hist, b.hist_cap, b.d_gen, e->V0, e->Vs, e->cfg.eos_token_id,
+                   e->d_ls, e->d_seqs, plan.B, st);
+        sscr.ban = b.d_ban;
+    }
     launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
                   e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, plan.B, sscr, plan.ch0_sampled,
                   full_cap_for(e->V0), plan.scores_on, plan.floors_on ? e->d_floors : nullptr, st);
@@ -1605,7 +1669,8 @@ int32_t mtts_read_seq_state(MttsEngine* e, int32_t* host_nas, int32_t* host_unfi
 // finishes leaves the batch at once (no finished-row padding) and its slot can be refilled.
 int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSamplerCfg* sampler, void* stream) {
     if (!e) return fail(MTTS_EINVAL, "null argument");
-    const std::vector<MttsSamplerFloors> floors = e->pending.take_floors();     // the one-shot leaves first: consumed whatever follows
+    const std::vector<MttsSamplerFloors> floors = e->pending.take_floors();     // the one-shots leave first: consumed whatever follows
+    const RunBans bans = e->pending.take_bans();
     if (!sampler) return fail(MTTS_EINVAL, "null argument");
     TRY(mtts_weights_ready(e));
     HIPCHK(hipSetDevice(e->device));
@@ -1614,6 +1679,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     if (gen_cap < 8) return fail(MTTS_EINVAL, "gen_cap too small");
     e->scores_on = e->pending.output_scores; e->topk_on = e->pending.top_logprobs;      // the sticky switches only
     TRY(start_outputs(e, gen_cap, st));
+    TRY(start_bans(e, bans, st));
     e->B = B; e->steps_issued = 0; e->has_forced = false; e->continuous = true;
     e->max_steps = 1 << 30;
     e->n_real.assign(B, 0);
@@ -1679,6 +1745,8 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
     TRY(stage_rows({StageSeq{ids, n, slot, true, nullptr}}, e->V0, e->Vs, false, &sr));
     TRY(stage_tail(ids + (size_t)n * 8, e->V0, e->Vs, "", tf.data()));
     stage_bitmap(ids, n, e->bm_words, bm.data());
+    std::vector<int32_t> hist;
+    if (e->ban_ngram_on) TRY(upload_history(e, slot, ids, n, hist, false, st));
     TRY(upload_staged(e, sr, false, st));
     HIPCHK(hipMemcpy(e->d_bitmaps + (size_t)slot * 8 * e->bm_words, bm.data(), bm.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_tf + (size_t)slot * 7 * 8, tf.data(), tf.size() * 4, hipMemcpyHostToDevice));
@@ -1743,6 +1811,11 @@ int32_t mtts_slot_fork(MttsEngine* e, int32_t src, int32_t dst, uint64_t seed, i
     }
     if (!rc) rc = e->pool.flush(ship);
     if (!rc) rc = launch_fork_job(e, job, true, st);
+    if (!rc && e->ban_ngram_on) {                   // the take's own copy of the prompt history (n-gram ban); its generated part starts empty
+        const size_t row = (size_t)e->bufs.hist_cap * 8;
+        if (hipMemcpyAsync(e->bufs.d_hist + (size_t)dst * row, e->bufs.d_hist + (size_t)src * row, (size_t)e->h_seqs[src].base_length * 8 * 4,
+                           hipMemcpyDeviceToDevice, st) != hipSuccess) rc = fail(MTTS_EHIP, "fork: copying the prompt history failed");
+    }
     if (rc) { e->pool.release(dst); return rc; }    // the share is undone with the slot (counts, unshipped edits)
     SeqState ns = e->h_seqs[src];
     ns.row_id = row_id; ns.seed = seed;

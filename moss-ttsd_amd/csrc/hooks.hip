@@ -2,6 +2,7 @@
 // (mtts_k_*, mtts_debug_*: include/mtts.h).  None of them is on the product path.  A hook's device buffers live in a
 // DevBufs of its own: freed on every return path.
 #include "engine.h"
+#include "staging.h"        // stage_ban_static (mtts_k_ngram_ban)
 
 int32_t mtts_k_gemm_bf16(const void* w, const void* x, void* y, int32_t M, int32_t N, int32_t K, int32_t ksplit, void* stream) {
     if (!w || !x || !y || M < 1 || M > MTTS_PFCAP || K % 16 || N < 1) return fail(MTTS_EINVAL, "gemm: need 1<=M<=MTTS_PFCAP, K%%16==0");
@@ -374,7 +375,7 @@ int32_t mtts_k_gemm_tile(int32_t epi, const void* dev_w, const void* dev_x, void
 
 static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                     int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
-                    const MttsSamplerFloors* floors, void* stream) {
+                    const MttsSamplerFloors* floors, const void* ban, void* stream) {
     if (!logits || !cfg || !dev_tokens || rows < 1 || vocab < 1 || channel < 0 || channel > 7) return fail(MTTS_EINVAL, "sample: bad argument");
     hipStream_t st = S(stream);
     MttsSamplerCfg h[8];
@@ -401,6 +402,7 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
     }
     SampleScratch sc;
     TRY(alloc_scratch(hb, sc, rows, vocab));
+    sc.ban = (const uint32_t*)ban;   // [rows][ceil(vocab / 32)], or null: the same kernels, which then read no ban word
     if (dev_logp) {                  // output_scores scratch
         TRY(hb.get(&sc.slice_sum, (size_t)rows * SAMP_NS));
         TRY(hb.get(&sc.lp, (size_t)rows * 8));
@@ -428,21 +430,63 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
 
 int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                       int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, void* stream) {
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, nullptr, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, nullptr, nullptr, stream);
 }
 
 int32_t mtts_k_sample_scores(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
                              void* stream) {
     if (!dev_logp) return fail(MTTS_EINVAL, "sample: null dev_logp");
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, nullptr, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, nullptr, nullptr, stream);
 }
 
 int32_t mtts_k_sample_floors(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
                              const MttsSamplerFloors* floors, void* stream) {
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, nullptr, stream);
 }
+
+int32_t mtts_k_sample_bans(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                           int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
+                           const MttsSamplerFloors* floors, const void* dev_ban, void* stream) {
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, dev_ban, stream);
+}
+
+// The ban kernel of a decode step (sampler.hip: ban_kernel) on bare histories of one channel.
+int32_t mtts_k_ngram_ban(const int32_t* dev_hist, const int32_t* dev_lens, int32_t rows, int32_t cap, int32_t n,
+                         const int32_t* host_static, int32_t n_static, int32_t vocab, int32_t eos_id, int32_t eos_on,
+                         void* dev_ban, void* stream) {
+    if (!dev_lens || !dev_ban || rows < 1 || rows > MTTS_RCAP || cap < 0 || (cap > 0 && !dev_hist) || vocab < 1 || n_static < 0 ||
+        (n_static > 0 && !host_static))
+        return fail(MTTS_EINVAL, "ngram_ban: bad argument");
+    // the settings, checked like mtts_set_sampler_bans checks them
+    MttsSamplerBans hbans[8];
+    for (int i = 0; i < 8; ++i) hbans[i] = MttsSamplerBans{n, 0, n_static, host_static};
+    PendingRun chk;
+    TRY(chk.set_bans(hbans));
+    hipStream_t st = S(stream);
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int32_t> lens(rows);
+    HIPCHK(hipMemcpy(lens.data(), dev_lens, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < rows; ++r)
+        if (lens[r] < 0 || lens[r] > cap) return fail(MTTS_EINVAL, "ngram_ban: row %d has length %d, the histories hold %d", r, lens[r], cap);
+    const int words = (vocab + 31) / 32;
+    std::vector<uint32_t> stat(words);
+    stage_ban_static(host_static, n_static, vocab, words, stat.data());
+    const BanCfg hc{n, eos_on ? 1 : 0};
+    DevBufs hb;
+    BanCfg* dc = nullptr;
+    uint32_t* ds = nullptr;
+    TRY(hb.get(&dc, 1));
+    TRY(hb.get(&ds, (size_t)words));
+    HIPCHK(hipMemcpy(dc, &hc, sizeof(hc), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ds, stat.data(), stat.size() * 4, hipMemcpyHostToDevice));
+    launch_ban_single((uint32_t*)dev_ban, ds, dc, dev_hist, dev_lens, rows, cap, vocab, eos_id, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+int64_t mtts_debug_ban_launches(void) { return (int64_t)mtts_ban_launches(); }
 
 // The top_logprobs kernels of a decode step (gen_topk.hip) on bare logits, with a scratch of their own.
 int32_t mtts_k_gen_topk(const void* dev_logits, int32_t is_f32, int32_t rows, int32_t vocab, int32_t mask_id,

@@ -142,6 +142,9 @@ struct SampleScratch {
     // the next two exist only once output_scores was asked for (null otherwise; only the LP kernels touch them)
     float* slice_sum = nullptr;      // [rows][SAMP_NS] output_scores, greedy channel 0: sum of exp(s - slice_val) over the slice (its max IS slice_val)
     float* lp = nullptr;             // [rows][8] output_scores: log-probability of decisions[row][c], read by update_kernel
+    // not scratch, but it travels with it to every sampler kernel: this step's banned tokens (mtts_set_sampler_bans), laid out
+    // like the history bitmaps ([slot][8][bm_words]; the single-matrix entry: [rows][ceil(vocab / 32)]).  Null: no bans
+    const uint32_t* ban = nullptr;
 };
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps,
                    int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed,
@@ -151,6 +154,18 @@ void launch_sample_single(const void* logits, int rows, int vocab, const uint32_
                           const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
                           int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp,
                           const MttsSamplerFloors* floors8, hipStream_t st);
+// The ban kernel of a decode step (mtts_set_sampler_bans; sampler.hip: ban_kernel), one block per (row, channel) the
+// sampler evaluates: ban[row][c][words] = stat[c][words], plus eos while the row's step < cfgs[c].eos_below, plus -- where
+// cfgs[c].ngram = n > 0 -- the follower of every earlier occurrence of the history's last n-1 tokens.  The history of
+// (row, c) is hist[row][0 .. base_length)[c] followed by gen[row][0 .. step)[c].
+struct BanCfg { int32_t ngram, eos_below; };      // eos_below = min_new_tokens + 7, or 0
+void launch_ban(uint32_t* ban, const uint32_t* stat, int words, const BanCfg* cfgs, const int32_t* hist, int hist_cap,
+                const int32_t* gen, int V0, int Vs, int eos, const LoopState* ls, const SeqState* seqs, int B, hipStream_t st);
+// one channel on bare histories hist [rows][cap], lens [rows]: ban [rows][ceil(vocab / 32)]; cfg1: one device BanCfg
+// (eos_below != 0: eos banned); stat [ceil(vocab / 32)]
+void launch_ban_single(uint32_t* ban, const uint32_t* stat, const BanCfg* cfg1, const int32_t* hist, const int32_t* lens, int rows,
+                       int cap, int vocab, int eos, hipStream_t st);
+long long mtts_ban_launches();
 // generate(top_logprobs=k): where a step's results go.  In the engine the per-slot buffers, laid out like gen: logp
 // [slot][gen_cap][8], ids / tlp [slot][gen_cap][8][k]; gen_topk_finish_kernel writes the step's row of every evaluated
 // dialogue, update_kernel<true> then puts NaN / -1 over the slots that are not model decisions, by the rule it applies

@@ -14,12 +14,24 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/mtts.h"       // MttsSamplerFloors (plain C, no HIP)
+#include "../../include/mtts.h"       // MttsSamplerFloors, MttsSamplerBans (plain C, no HIP)
 #include "stepplan.h"
 
 // defined by whoever includes this (engine.hip; the CPU test), as for kvpool.h
 __attribute__((visibility("hidden"), format(printf, 2, 3))) int fail(int code, const char* fmt, ...);
 static const int RUN_EINVAL = -1;       // MTTS_EINVAL of include/mtts.h (engine.h checks that it is)
+
+// The hard bans of a run (mtts_set_sampler_bans), owned: the caller's suppress lists are copied when they are set.
+struct ChannelBans {
+    int ngram = 0, min_new = 0;         // no_repeat_ngram_size, min_new_tokens; 0: absent
+    std::vector<int32_t> suppress;
+    bool any() const { return ngram > 0 || min_new > 0 || !suppress.empty(); }
+};
+struct RunBans {
+    std::vector<ChannelBans> ch;        // per channel; empty: none
+    bool any() const { for (const ChannelBans& c : ch) if (c.any()) return true; return false; }
+    bool ngram() const { for (const ChannelBans& c : ch) if (c.ngram > 0) return true; return false; }
+};
 
 // ---- the options of one static run ----------------------------------------------------------------------------------
 struct RunOptions {
@@ -28,6 +40,7 @@ struct RunOptions {
     std::vector<int32_t> row_ids;       // Philox row id per row; empty: 0..rows-1
     std::vector<int32_t> row_adapters;  // adapter per PROMPT (its takes share its KV pages and so its adapter); empty: none
     std::vector<MttsSamplerFloors> floors;      // per channel (mtts_set_sampler_floors); empty: none
+    RunBans bans;                       // per channel (mtts_set_sampler_bans); empty: none
     int output_scores = 0, top_logprobs = 0;
     int rows() const { return B * takes; }
     int row_id(int r) const { return row_ids.empty() ? r : row_ids[r]; }
@@ -50,6 +63,7 @@ class PendingRun {
     std::vector<int32_t> row_ids, row_adapters;
     std::vector<int32_t> slot_adapter = std::vector<int32_t>(MTTS_RCAP, -1);    // scheduler mode: of the slot's next submit
     std::vector<MttsSamplerFloors> floors;
+    RunBans bans;
 public:
     int output_scores = 0, top_logprobs = 0;        // sticky: every run reads them, none resets them
     void set_takes(int n) { takes = n; }
@@ -68,6 +82,26 @@ public:
         if (f) floors.assign(f, f + MTTS_CHANNELS);
         return 0;
     }
+    // the same for the bans; a refused call leaves none behind
+    int set_bans(const MttsSamplerBans* b) {
+        bans.ch.clear();
+        if (!b) return 0;
+        std::vector<ChannelBans> ch(MTTS_CHANNELS);
+        for (int c = 0; c < MTTS_CHANNELS; ++c) {
+            if (b[c].no_repeat_ngram_size < 0 || b[c].no_repeat_ngram_size > MTTS_NGRAM_MAX)
+                return fail(RUN_EINVAL, "channel %d: no_repeat_ngram_size %d is outside [0, %d]", c, b[c].no_repeat_ngram_size, MTTS_NGRAM_MAX);
+            if (b[c].min_new_tokens < 0) return fail(RUN_EINVAL, "channel %d: min_new_tokens %d is negative", c, b[c].min_new_tokens);
+            if (b[c].n_suppress < 0 || (b[c].n_suppress > 0 && !b[c].suppress))
+                return fail(RUN_EINVAL, "channel %d: suppress_tokens: %d ids and %s list", c, b[c].n_suppress, b[c].suppress ? "a" : "no");
+            for (int i = 0; i < b[c].n_suppress; ++i)
+                if (b[c].suppress[i] < 0) return fail(RUN_EINVAL, "channel %d: suppress_tokens holds the negative id %d", c, b[c].suppress[i]);
+            ch[c].ngram = b[c].no_repeat_ngram_size;
+            ch[c].min_new = b[c].min_new_tokens;
+            if (b[c].n_suppress > 0) ch[c].suppress.assign(b[c].suppress, b[c].suppress + b[c].n_suppress);
+        }
+        bans.ch.swap(ch);
+        return 0;
+    }
     bool has_row_adapters() const { return !row_adapters.empty(); }
     // mtts_begin / mtts_generate with B prompts: the one-shots move out and are back at their defaults, whatever the call
     // does next (RunOptions::check included)
@@ -77,11 +111,13 @@ public:
         o.row_ids.swap(row_ids);
         o.row_adapters.swap(row_adapters);
         o.floors = take_floors();
+        o.bans = take_bans();
         takes = 1;
         return o;
     }
     // mtts_sched_open: a scheduler run takes no other one-shot
     std::vector<MttsSamplerFloors> take_floors() { return std::exchange(floors, {}); }
+    RunBans take_bans() { return std::exchange(bans, RunBans()); }
     // mtts_slot_submit* into `slot`: the same for that slot's adapter
     int take_slot_adapter(int slot) { return std::exchange(slot_adapter[slot], -1); }
 };
@@ -109,9 +145,14 @@ struct StepBufs {
     float* partial = nullptr;               // split-K slabs: widened by the first mtts_adapter_load, with which the next two appear
     LoraEnt* d_bank = nullptr;
     int32_t* d_seq_adapter = nullptr;
+    // hard bans (mtts_set_sampler_bans); all three exist once a run asked for a ban, d_hist once one asked for an n-gram ban
+    uint32_t* d_ban = nullptr;              // [slot][8][ban_words]: the step's banned tokens, rewritten by ban_kernel every step
+    uint32_t* d_ban_static = nullptr;       // [8][ban_words]: the run's suppress_tokens per channel
+    int32_t* d_hist = nullptr;              // [slot][hist_cap][8]: the prompt's slots, padding included (the generated ones are d_gen)
     int gen_cap = 0;                        // steps a slot's rows hold
     int gt_stride = 0, gt_scr_cap = 0;      // innermost stride of d_gt_ids / d_gt_tlp; of gt_cand
     int rope_rows = 0;
+    int hist_cap = 0, ban_words = 0;        // prompt slots a row of d_hist holds; words per (slot, channel) of d_ban
     // every byte takes part (no padding: the assertion below), so a new member cannot be left out of the comparison
     bool operator==(const StepBufs& o) const { return memcmp(this, &o, sizeof(StepBufs)) == 0; }
     bool operator!=(const StepBufs& o) const { return !(*this == o); }

@@ -9,6 +9,7 @@ struct LogitsPtr { const void* p; int f32; };     // one row of logits: bf16 bit
 struct SampleCtx {         // resolved per (row, channel)
     LogitsPtr lg;
     const uint32_t* bm;
+    const uint32_t* ban;   // this step's banned tokens, one bit each (mtts_set_sampler_bans); null: the run has none
     int V, mask_id, step, c;
     float penalty, temp;
     uint64_t seed;
@@ -19,12 +20,13 @@ __device__ __forceinline__ bool sample_ctx(SampleCtx& x, int b, int c_in, const 
                                            const uint16_t* logits17, int V0, int Vs, int Vs_pad,
                                            const uint32_t* bitmaps, int bm_words, const MttsSamplerCfg* cfgs,
                                            const LoopState* ls, const SeqState* seqs, int single_vocab, int single_mask,
-                                           int single_step, int single_channel) {
+                                           int single_step, int single_channel, const uint32_t* bans = nullptr) {
     if (single_vocab > 0) {            // unit-test entry: one logits matrix [rows][vocab]
         x.c = single_channel; x.step = single_step; x.V = single_vocab; x.mask_id = single_mask;
         x.seed = 0; x.row_id = (uint32_t)b;
         x.lg = LogitsPtr{logits0 + (size_t)b * x.V, 0};
         x.bm = bitmaps ? bitmaps + (size_t)b * bm_words : nullptr;
+        x.ban = bans ? bans + (size_t)b * ((x.V + 31) >> 5) : nullptr;       // unit-test entry: [rows][ceil(vocab / 32)]
     } else {
         if (ls->done) return false;
         const SeqState sq = seqs[b];
@@ -45,6 +47,7 @@ __device__ __forceinline__ bool sample_ctx(SampleCtx& x, int b, int c_in, const 
         if (x.c != 0 && x.step >= x.c) x.mask_id = 1024;
         if (x.c == 0 && x.step <= 6) x.mask_id = 152694;
         x.bm = bitmaps ? bitmaps + ((size_t)b * 8 + x.c) * bm_words : nullptr;
+        x.ban = bans ? bans + ((size_t)b * 8 + x.c) * bm_words : nullptr;    // laid out like the history bitmaps
     }
     const MttsSamplerCfg cfg = cfgs[x.c];
     x.penalty = (x.bm && cfg.repetition_penalty > 0.f) ? cfg.repetition_penalty : 0.f;

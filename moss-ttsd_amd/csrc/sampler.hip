@@ -39,13 +39,16 @@ __device__ __forceinline__ uint32_t fkey(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// Processed score of token i (everything except top-k / top-p, which act on the set).
-__device__ __forceinline__ float proc_score(LogitsPtr logits, int i, int mask_id,
-                                            const uint32_t* __restrict__ bitmap, float penalty, float temperature) {
-    if (i == mask_id) return -INFINITY;
-    float s = logits.f32 ? ((const float*)logits.p)[i] : bf2f(((const uint16_t*)logits.p)[i]);
-    if (penalty > 0.f && (bitmap[i >> 5] >> (i & 31)) & 1u) s = (s < 0.f) ? s * penalty : s / penalty;
-    if (temperature > 0.f) s = s / temperature;
+// Processed score of token i (everything except top-k / top-p, which act on the set).  A token banned this step
+// (x.ban: mtts_set_sampler_bans; null in a run without bans) is at -inf like the masked id, before penalty and temperature.
+// Every sampler pass reads scores through here, so a row whose every token is banned is a row of -inf to all of them:
+// the argmax merges keep the lowest id (0), no candidate is collected, and the kernels below give token 0 with lp NaN.
+__device__ __forceinline__ float proc_score(const SampleCtx& x, int i) {
+    if (i == x.mask_id) return -INFINITY;
+    if (x.ban && (x.ban[i >> 5] >> (i & 31)) & 1u) return -INFINITY;
+    float s = x.lg.f32 ? ((const float*)x.lg.p)[i] : bf2f(((const uint16_t*)x.lg.p)[i]);
+    if (x.penalty > 0.f && (x.bm[i >> 5] >> (i & 31)) & 1u) s = (s < 0.f) ? s * x.penalty : s / x.penalty;
+    if (x.temp > 0.f) s = s / x.temp;
     return s;
 }
 
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_scan_kernel(
     const int b = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel)) return;
+                    single_step, single_channel, sc.ban)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     const bool want_hist = cfg.do_sample && cfg.top_k > 0 && cfg.top_k < x.V;
     for (int i = tid; i < 2048; i += SAMP_T) hist[i] = 0;
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_scan_kernel(
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = i0 + tid; i < i1; i += SAMP_T) {
-        float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp);
+        float s = proc_score(x, i);
         argmax_merge(bv, bi, s, i);
         if (want_hist) atomicAdd(&hist[fkey(s) >> 21], 1u);
     }
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_scan_kernel(
         float loc = 0.f;
         if (bv > -INFINITY)
             for (int i = i0 + tid; i < i1; i += SAMP_T) {
-                const float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp);
+                const float s = proc_score(x, i);
                 if (s > -INFINITY) loc += expf(s - bv);
             }
         double tot;
@@ -178,7 +181,7 @@ __device__ __forceinline__ u64 nuc_q(uint32_t key, float smax) { return (u64)((d
 __device__ __forceinline__ void nuc_pass_a(const SampleCtx& x, float smax, float lo, uint32_t* __restrict__ keys,
                                            uint16_t* __restrict__ bins, unsigned int* cnt, u64* mass, int i0, int i1, int step) {
     for (int i = i0; i < i1; i += step) {
-        const float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp) + 0.0f;      // (-0 -> +0: one key per value)
+        const float s = proc_score(x, i) + 0.0f;      // (-0 -> +0: one key per value)
         const uint32_t key = fkey(s);
         keys[i] = key;
         if (s > -INFINITY) {
@@ -232,7 +235,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_collect_kernel(
     const int b = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel)) return;
+                    single_step, single_channel, sc.ban)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     if (!cfg.do_sample) return;
     // no top-k (every finite score is a candidate) or a top_k beyond the candidate buffer: nothing to collect, the row
@@ -260,7 +263,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_collect_kernel(
     const int per = (x.V + SAMP_NS - 1) / SAMP_NS;
     const int i0 = slice * per, i1 = min(x.V, i0 + per);
     for (int i = i0 + tid; i < i1; i += SAMP_T) {
-        float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp);
+        float s = proc_score(x, i);
         uint32_t key = fkey(s);
         if ((int)(key >> 21) >= b0 && key > ninf_key) {
             uint32_t slot = atomicAdd(&sc.cand_n[b], 1u);
@@ -410,7 +413,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
     const int b = blockIdx.y;
     SampleCtx x;
     if (!sample_ctx(x, b, blockIdx.x, logits0, logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, single_vocab,
-                    single_mask, single_step, single_channel)) return;
+                    single_mask, single_step, single_channel, sc.ban)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     const bool big = single_vocab > 0 ? (single_vocab > SAMP_CAND) : (x.c == 0 && big_channel0);
     const int out_slot = b * 8 + x.c;
@@ -441,7 +444,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
             for (int i = tid; i < 2048; i += SAMP_T) hist[i] = 0;
         __syncthreads();
         for (int i = tid; i < x.V; i += SAMP_T) {
-            float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp);
+            float s = proc_score(x, i);
             argmax_merge(bv, bi, s, i);
             if (prefilter) atomicAdd(&hist[fkey(s) >> 21], 1u);
             else if (cfg.do_sample && s > -INFINITY) {
@@ -454,7 +457,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
             const int b0 = topk_bin(hist, (uint32_t)cfg.top_k, wsum, &sh_i[2]);
             const uint32_t ninf_key = fkey(-INFINITY);
             for (int i = tid; i < x.V; i += SAMP_T) {
-                float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp);
+                float s = proc_score(x, i);
                 uint32_t key = fkey(s);
                 if ((int)(key >> 21) >= b0 && key > ninf_key) {
                     int slot = atomicAdd(&sh_i[0], 1);
@@ -470,7 +473,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
         if (tid == 0) decisions[out_slot] = amax;
         if (LP) {
             // greedy: lp = log_softmax over every finite processed score at the argmax = -log(sum exp(s - smax)).
-            // -inf scores add nothing; an all -inf row (cannot occur: the argmax is finite) gives NaN, no trap.
+            // -inf scores add nothing; an all -inf row (every token banned: smax = -inf, amax = 0) gives NaN, no trap.
             double tot = 0.0;
             if (big) {
                 if (tid == 0)                    // the row's 32 (slice max, slice sum) pairs, in slice order
@@ -482,7 +485,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
                 float loc = 0.f;
                 if (smax > -INFINITY)
                     for (int i = tid; i < x.V; i += SAMP_T) {
-                        const float s = proc_score(x.lg, i, x.mask_id, x.bm, x.penalty, x.temp);
+                        const float s = proc_score(x, i);
                         if (s > -INFINITY) loc += expf(s - smax);
                     }
                 (void)block_excl_scan<SAMP_T>((double)loc, shd, tot);
@@ -496,7 +499,8 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
             decisions[out_slot] = amax;
             if (n > SAMP_CAND && sc.overflow[b] == 0) sc.overflow[b] = 1;
             // channel 0 with too many candidates: the full-vocabulary kernel overwrites this.  n == 0 (every score -inf:
-            // cannot occur, the argmax is finite) on ANY channel: the NaN is final, nothing follows for channels 1-7
+            // every token of the row is banned, amax = 0) on ANY channel: token 0 and the NaN are final where nothing
+            // follows; the full-vocabulary kernel finds no member either (n == 0 there) and writes the same pair
             if (LP) sc.lp[out_slot] = __uint_as_float(0x7fc00000u);
         }
         return;
@@ -753,7 +757,7 @@ __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
     if (!flag) return;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel)) return;
+                    single_step, single_channel, sc.ban)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     uint16_t* bins = (uint16_t*)(sc.full_val + (size_t)b * full_cap);  // level-0 bin of every token (0xffff: -inf)
     uint32_t* keys = (uint32_t*)(sc.full_idx + (size_t)b * full_cap);  // order-preserving key of every processed score
@@ -787,7 +791,7 @@ __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
         for (int w = 0; w < SAMP_FT / 64; ++w) { n += S.wc[w]; tot += S.wm[w]; }
         __syncthreads();
     }
-    int pick = bi;
+    int pick = bi;          // n == 0 (every token banned: all keys are -inf's): the argmax of a row of -inf, token 0, lp NaN
     if (n > 0) {
         NucSel z{0u, 0u, 0};
         int binA; unsigned int c_bin; u64 m_bin;
@@ -1005,6 +1009,81 @@ __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __
         ls->step = ls->step + 1;
         if (!any_unfinished) ls->done = 1;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Hard bans (mtts_set_sampler_bans; launch.h: launch_ban).  One block per (row, channel) the sampler is about to evaluate
+// rewrites that pair's ban words: first the run's static bitmap of the channel (suppress_tokens) with eos while the
+// row's step is below min_new_tokens + 7 -- an overwrite, so it is also the per-step clear -- then, behind a barrier, HF's
+// NoRepeatNGram rule: the last n-1 tokens of the history are block-uniform (LDS); every thread tests a strided range of
+// window starts, leaves a window at its first unequal token, and ORs the follower of a matching one in.  OR is order-free,
+// so the words are the same bits run to run.  The history is the prompt's slots (hist, staged by the host) followed by
+// the row's generated tokens (gen, appended by update_kernel): the stream that sets bits in the repetition-penalty bitmap.
+// single_vocab > 0: the unit-test entry, hist [rows][hist_cap] of one channel with lengths single_lens.
+#define BAN_T 256
+__global__ __launch_bounds__(BAN_T) void ban_kernel(
+    uint32_t* __restrict__ ban, const uint32_t* __restrict__ stat, int words, const BanCfg* __restrict__ cfgs,
+    const int32_t* __restrict__ hist, int hist_cap, const int32_t* __restrict__ gen, int V0, int Vs, int eos,
+    const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs, const int32_t* __restrict__ single_lens, int single_vocab) {
+    __shared__ int32_t suf[MTTS_NGRAM_MAX];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int V, base, glen, hs;
+    const int32_t *hp, *gp;
+    const uint32_t* sp;
+    uint32_t* out;
+    BanCfg cfg;
+    bool eos_on;
+    if (single_vocab > 0) {
+        V = single_vocab; cfg = cfgs[0];
+        base = min(max(single_lens[b], 0), hist_cap); glen = 0; hs = 1;
+        hp = hist + (size_t)b * hist_cap; gp = nullptr;
+        out = ban + (size_t)b * ((V + 31) >> 5); sp = stat;
+        eos_on = cfg.eos_below != 0;
+    } else {
+        if (ls->done) return;
+        const SeqState sq = seqs[b];
+        if (!sq.active || !(sq.unfinished || sq.active == 2)) return;       // the rows sample_ctx evaluates
+        const int c = blockIdx.x;
+        V = c == 0 ? V0 : Vs; cfg = cfgs[c];
+        base = sq.base_length; glen = min(sq.step, ls->gen_cap); hs = 8;
+        if (base > hist_cap) cfg.ngram = 0;         // (the host refuses such a prompt: nothing past the row is ever read)
+        hp = hist + (size_t)b * hist_cap * 8 + c; gp = gen + (size_t)b * ls->gen_cap * 8 + c;
+        out = ban + ((size_t)b * 8 + c) * words; sp = stat + (size_t)c * words;
+        eos_on = sq.step < cfg.eos_below;
+    }
+    const int nw = (V + 31) >> 5;                   // (<= words; bits at and above V are never set)
+    for (int w = tid; w < nw; w += BAN_T) {
+        uint32_t v = sp[w];
+        if (eos_on && eos >= 0 && eos < V && (eos >> 5) == w) v |= 1u << (eos & 31);
+        out[w] = v;
+    }
+    const int n = cfg.ngram, len = base + glen;
+    if (n <= 0 || len < n) return;                  // (block-uniform)
+    const auto h = [&](int i) { return i < base ? hp[(size_t)i * hs] : gp[(size_t)(i - base) * hs]; };
+    if (tid < n - 1) suf[tid] = h(len - n + 1 + tid);
+    __syncthreads();                                // the static words are written, the suffix is in LDS
+    for (int j = tid; j <= len - n; j += BAN_T) {
+        int k = 0;
+        while (k < n - 1 && h(j + k) == suf[k]) ++k;
+        if (k == n - 1) {
+            const int t = h(j + n - 1);
+            if (t >= 0 && t < V) atomicOr(&out[t >> 5], 1u << (t & 31));
+        }
+    }
+}
+static long long g_ban_launches = 0;        // launches of ban_kernel (test hook: mtts_debug_ban_launches)
+long long mtts_ban_launches() { return g_ban_launches; }
+void launch_ban(uint32_t* ban, const uint32_t* stat, int words, const BanCfg* cfgs, const int32_t* hist, int hist_cap,
+                const int32_t* gen, int V0, int Vs, int eos, const LoopState* ls, const SeqState* seqs, int B, hipStream_t st) {
+    ++g_ban_launches;
+    hipLaunchKernelGGL(ban_kernel, dim3(8, B), dim3(BAN_T), 0, st, ban, stat, words, cfgs, hist, hist_cap, gen, V0, Vs, eos, ls, seqs,
+                       (const int32_t*)nullptr, 0);
+}
+void launch_ban_single(uint32_t* ban, const uint32_t* stat, const BanCfg* cfg1, const int32_t* hist, const int32_t* lens, int rows,
+                       int cap, int vocab, int eos, hipStream_t st) {
+    ++g_ban_launches;
+    hipLaunchKernelGGL(ban_kernel, dim3(1, rows), dim3(BAN_T), 0, st, ban, stat, (vocab + 31) >> 5, cfg1, hist, cap, (const int32_t*)nullptr,
+                       vocab, vocab, eos, (const LoopState*)nullptr, (const SeqState*)nullptr, lens, vocab);
 }
 
 static SampleScratch g_dummy_scratch;

@@ -86,6 +86,19 @@ static inline void stage_bitmap(const int64_t* toks, int n, int bm_words, uint32
             if (tk >= 0 && tk < (int64_t)bm_words * 32) bm[(size_t)c * bm_words + (tk >> 5)] |= 1u << (tk & 31);
         }
 }
+// history of one row for the n-gram ban (mtts_set_sampler_bans), hist [n][8], from the same `n` prompt slots: the token
+// stream the bitmap above is built from, in order.  Padded slots are not range-checked here either: a value no int32
+// token can equal is kept as -1 (it matches nothing a channel can emit and bans nothing).
+static inline void stage_history(const int64_t* toks, int n, int32_t* hist) {
+    for (size_t i = 0; i < (size_t)n * 8; ++i) hist[i] = (toks[i] >= 0 && toks[i] <= INT32_MAX) ? (int32_t)toks[i] : -1;
+}
+// the static bans of one channel, bm [words] (words * 32 >= V): the listed ids inside [0, V); the others are ignored, as
+// HF's isin(arange(V), ids) ignores them -- one list meets eight vocabularies
+static inline void stage_ban_static(const int32_t* ids, int n, int V, int words, uint32_t* bm) {
+    std::fill(bm, bm + words, 0u);
+    for (int i = 0; i < n; ++i)
+        if (ids[i] >= 0 && ids[i] < V) bm[ids[i] >> 5] |= 1u << (ids[i] & 31);
+}
 // teacher-forcing tail tf_inputs[:, base+s, :] for s = 0..6 (modeling_asteroid.py:143-145): `toks` = those 7 slots,
 // tf [7][8]; `note` ends the message of a token outside its vocabulary
 static inline int stage_tail(const int64_t* toks, int V0, int Vs, const char* note, int32_t* tf) {

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from mtts import adapters, synth, topk_spec, warp_spec
+from mtts import adapters, ban_spec, synth, topk_spec, warp_spec
 from mtts.engine import Engine
 
 _CFG_KEYS = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads",
@@ -69,6 +69,10 @@ class GenerationConfig:
         self.min_p = kw.get("min_p")
         self.epsilon_cutoff = kw.get("epsilon_cutoff", 0.0)
         self.eta_cutoff = kw.get("eta_cutoff", 0.0)
+        # HF's hard bans (NoRepeatNGram / SuppressTokens / MinNewTokensLength processors)
+        self.no_repeat_ngram_size = kw.get("no_repeat_ngram_size", 0)
+        self.suppress_tokens = kw.get("suppress_tokens")
+        self.min_new_tokens = kw.get("min_new_tokens")
         self.seed = kw.get("seed")
         self.num_return_sequences = kw.get("num_return_sequences", 1)
 
@@ -80,13 +84,18 @@ class GenerationConfig:
         with open(p) as f:
             return cls(**json.load(f))
 
-    def channel_settings(self, channels, **floors):
+    def channel_settings(self, channels, **over):
         """-> (layers[8], do_samples[8]); the global-processor branch (:107-109) repeats one config.
         The probability floors min_p / epsilon_cutoff / eta_cutoff: in the global branch the top-level fields (or the
         `floors` keywords, generate()'s overrides for one call) join the one dict under the conditions on which HF's
         _get_logits_processor adds the warper: min_p is not None, 0 < epsilon_cutoff < 1, 0 < eta_cutoff < 1.  In the
         per-channel branch they come from layers[i] -- this engine's extension of the four keys the reference reads
-        there -- and the top-level values are ignored, as that branch of the reference ignores every top-level warper."""
+        there -- and the top-level values are ignored, as that branch of the reference ignores every top-level warper.
+        The hard bans no_repeat_ngram_size / suppress_tokens / min_new_tokens travel the same way, with two differences:
+        they are processors, so in the global branch they join the dict whatever do_sample is (the reference's
+        `[logits_processor] * channels` applies them on all eight channels), and HF's conditions are n not None and > 0,
+        the list not None, m not None and > 0 with an eos_token_id.  A config that sets none gives the dicts it always gave.
+        min_length, begin_suppress_tokens, bad_words_ids and sequence_bias are not read."""
         if self.do_samples is not None:
             layers = list(self.layers or [])
             layers += [{}] * (channels - len(layers))
@@ -96,11 +105,20 @@ class GenerationConfig:
             one = dict(repetition_penalty=self.repetition_penalty, temperature=self.temperature,
                        top_k=self.top_k, top_p=self.top_p)
             for k in warp_spec.FLOOR_KEYS:
-                v = floors[k] if floors.get(k) is not None else getattr(self, k)
+                v = over[k] if over.get(k) is not None else getattr(self, k)
                 if v is not None and (k == "min_p" or 0.0 < float(v) < 1.0):
                     one[k] = v
         elif self.repetition_penalty not in (None, 1.0):
             one = dict(repetition_penalty=self.repetition_penalty)
+        ban = {k: (over[k] if over.get(k) is not None else getattr(self, k)) for k in ban_spec.BAN_KEYS}
+        # (HF skips a size or count <= 0; anything that is no integer goes on and is refused where the values are checked)
+        off = lambda v: v is None or (ban_spec.is_int(v) and v <= 0)
+        if not off(ban["no_repeat_ngram_size"]):
+            one["no_repeat_ngram_size"] = ban["no_repeat_ngram_size"]
+        if ban["suppress_tokens"] is not None:
+            one["suppress_tokens"] = ban["suppress_tokens"]
+        if not off(ban["min_new_tokens"]) and self.eos_token_id is not None:
+            one["min_new_tokens"] = ban["min_new_tokens"]
         return [one] * channels, [self.do_sample] * channels
 
 
@@ -473,7 +491,8 @@ class AsteroidTTSInstruct:
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,
                  num_return_sequences=None, return_dict_in_generate=False, output_scores=False, adapter_names=None,
-                 top_logprobs=None, min_p=None, epsilon_cutoff=None, eta_cutoff=None, **kw):
+                 top_logprobs=None, min_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None,
+                 suppress_tokens=None, min_new_tokens=None, **kw):
         """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
         num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
         repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages.
@@ -486,10 +505,17 @@ class AsteroidTTSInstruct:
         `top_logprobs` (GenerateOutput), the model's own distribution at every decision, selected on the device in the
         decode step; it changes no token and no transition score.
         min_p / epsilon_cutoff / eta_cutoff (HF's generate keywords): override generation_config's for this call in the
-        global branch; with generation_config.do_samples set the floors are per channel and belong in layers[i]."""
+        global branch; with generation_config.do_samples set the floors are per channel and belong in layers[i].
+        no_repeat_ngram_size / suppress_tokens / min_new_tokens (HF's generate keywords): the same for the hard bans, which
+        act on greedy and sampled channels alike (mtts/ban_spec.py); refused with do_samples set, like the floors."""
         over = {k: v for k, v in (("min_p", min_p), ("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)) if v is not None}
         for name, v in over.items():
             warp_spec.check_floor(name, v, "generate(): ")
+        bans = {k: v for k, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("suppress_tokens", suppress_tokens),
+                                  ("min_new_tokens", min_new_tokens)) if v is not None}
+        for name, v in bans.items():
+            ban_spec.check_ban(name, v, "generate(): ")
+        over.update(bans)
         if over and self.generation_config.do_samples is not None:
             raise ValueError(f"generate({', '.join(over)}=...) with generation_config.do_samples set: the per-channel branch reads its "
                              "warpers from generation_config.layers[i]; put the floors there")
@@ -521,6 +547,7 @@ class AsteroidTTSInstruct:
         layers, do_samples = gc.channel_settings(C, **over)
         for i, lc in enumerate(layers):
             warp_spec.floors_of(lc, f"generation_config, channel {i}: ")       # a bad value: ValueError before the device is touched
+            ban_spec.bans_of(lc, f"generation_config, channel {i}: ")
         if n > 1 and not any(do_samples):
             # HF GenerationMixin: greedy search returns one sequence per prompt
             raise ValueError("Greedy methods (do_sample != True) without beam search do not support `num_return_sequences` "

@@ -26,6 +26,11 @@ class MttsSamplerFloors(C.Structure):
     _fields_ = [("min_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float), ("sqrt_eta_cutoff", C.c_float)]
 
 
+class MttsSamplerBans(C.Structure):
+    _fields_ = [("no_repeat_ngram_size", C.c_int32), ("min_new_tokens", C.c_int32), ("n_suppress", C.c_int32),
+                ("suppress", C.POINTER(C.c_int32))]
+
+
 class MttsCodecConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "nq", "codebook_size", "rvq_dim", "quant_out_dim",
@@ -97,6 +102,8 @@ _SIGS = {
     "mtts_set_row_ids": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mtts_set_takes": (C.c_int32, [C.c_void_p, C.c_int32]),
     "mtts_set_sampler_floors": (C.c_int32, [C.c_void_p, C.POINTER(MttsSamplerFloors)]),
+    "mtts_set_sampler_bans": (C.c_int32, [C.c_void_p, C.POINTER(MttsSamplerBans)]),
+    "mtts_debug_ban_launches": (C.c_int64, []),
     "mtts_slot_fork": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p]),
     "mtts_slot_states": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_slot_read": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
@@ -153,6 +160,11 @@ _SIGS = {
     "mtts_k_sample_floors": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg),
                                          C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.POINTER(MttsSamplerFloors), C.c_void_p]),
+    "mtts_k_sample_bans": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg),
+                                       C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.POINTER(MttsSamplerFloors), C.c_void_p, C.c_void_p]),
+    "mtts_k_ngram_ban": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mtts_codec_last_error": (C.c_char_p, []),
     "mtts_codec_create": (C.c_int32, [C.POINTER(MttsCodecConfig), C.c_int32, C.POINTER(C.c_void_p)]),
     "mtts_codec_destroy": (C.c_int32, [C.c_void_p]),

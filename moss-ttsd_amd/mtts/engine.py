@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import capi, warp_spec
+from . import ban_spec, capi, warp_spec
 
 
 def sampler_cfgs(layers=None, do_samples=None):
@@ -41,6 +41,26 @@ def sampler_floors(layers=None, do_samples=None):
         if do_samples and do_samples[i]:
             arr[i].min_p, arr[i].epsilon_cutoff, arr[i].eta_cutoff, arr[i].sqrt_eta_cutoff = f
             on = on or any(v > 0.0 for v in f[:3])
+    return arr if on else None
+
+
+def sampler_bans(layers=None):
+    """The hard bans of the same per-channel dicts -> MttsSamplerBans[8], or None when no channel sets one (the run then
+    launches and allocates what it did before bans existed).  Keys `no_repeat_ngram_size` (1..16), `suppress_tokens` (a
+    list of ids >= 0; those outside the channel's vocabulary are ignored) and `min_new_tokens` (HF's NoRepeatNGram /
+    SuppressTokens / MinNewTokensLength processors; mtts/ban_spec.py states the rule).  None, 0 or [] = absent.  They are
+    processors, not warpers: a greedy channel applies them like a sampled one.  ValueError, naming the channel, for a bad
+    value.  The array keeps the id lists alive (`_keep`)."""
+    arr, on, keep = (capi.MttsSamplerBans * 8)(), False, []
+    for i in range(8):
+        lc = (layers[i] if layers and i < len(layers) else {}) or {}
+        n, m, sup = ban_spec.bans_of(lc, f"layers[{i}]: ")
+        ids = (C.c_int32 * max(len(sup), 1))(*sup)
+        keep.append(ids)
+        arr[i].no_repeat_ngram_size, arr[i].min_new_tokens, arr[i].n_suppress = n, m, len(sup)
+        arr[i].suppress = C.cast(ids, C.POINTER(C.c_int32))
+        on = on or n > 0 or m > 0 or len(sup) > 0
+    arr._keep = keep
     return arr if on else None
 
 
@@ -182,9 +202,12 @@ class Engine:
         capi.check(self.lib.mtts_set_takes(self._h, takes))
         return takes
 
-    def _set_floors(self, layers, do_samples):
-        """One-shot like takes: the floors of `layers` for the run that starts next, or none (mtts_set_sampler_floors)."""
-        capi.check(self.lib.mtts_set_sampler_floors(self._h, sampler_floors(layers, do_samples)))
+    def _set_floors_and_bans(self, layers, do_samples):
+        """One-shots like takes: the floors and the hard bans of `layers` for the run that starts next, or none
+        (mtts_set_sampler_floors, mtts_set_sampler_bans).  Both are marshalled first: a bad value leaves nothing pending."""
+        floors, bans = sampler_floors(layers, do_samples), sampler_bans(layers)
+        capi.check(self.lib.mtts_set_sampler_floors(self._h, floors))
+        capi.check(self.lib.mtts_set_sampler_bans(self._h, bans))
 
     def set_output_scores(self, on):
         """Sticky engine switch, read when the next run begins (begin / generate / sched_open): per-token
@@ -228,7 +251,7 @@ class Engine:
         out = np.zeros((R, cap, 8), dtype=np.int64)
         out_len = C.c_int32(0)
         scfg = sampler_cfgs(layers, do_samples)
-        self._set_floors(layers, do_samples)
+        self._set_floors_and_bans(layers, do_samples)
         self.set_output_scores(output_scores)
         self.set_top_logprobs(top_logprobs)
         self._set_row_ids(row_ids, R)       # Philox row id of each row (default: its position in this batch)
@@ -286,7 +309,7 @@ class Engine:
         ids, m = self._host_inputs(input_ids, attention_mask)
         B, T, _ = ids.shape
         self._B, self._T = B * int(takes), T
-        self._set_floors(layers, do_samples)
+        self._set_floors_and_bans(layers, do_samples)
         self.set_output_scores(output_scores)
         self.set_top_logprobs(top_logprobs)
         self._set_row_ids(row_ids, B * int(takes))
@@ -345,7 +368,7 @@ class Engine:
     # ---- continuous batching ---------------------------------------------------------
     def sched_open(self, slots, gen_cap, layers=None, do_samples=None, output_scores=False, top_logprobs=0):
         self._B = int(slots)
-        self._set_floors(layers, do_samples)
+        self._set_floors_and_bans(layers, do_samples)
         self.set_output_scores(output_scores)
         self.set_top_logprobs(top_logprobs)
         capi.check(self.lib.mtts_sched_open(self._h, int(slots), int(gen_cap), sampler_cfgs(layers, do_samples), None))
