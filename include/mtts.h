@@ -344,6 +344,19 @@ int32_t mtts_set_sampler_floors(MttsEngine* e, const MttsSamplerFloors floors[8]
  * MTTS_EINVAL, naming the channel: no_repeat_ngram_size outside [0, MTTS_NGRAM_MAX], min_new_tokens < 0, n_suppress < 0 or
  * without a list, a negative id. */
 int32_t mtts_set_sampler_bans(MttsEngine* e, const MttsSamplerBans bans[8] /* NULL: none */);
+/* typical_p of the NEXT run only (one-shot like mtts_set_sampler_floors: consumed by the next mtts_begin, mtts_generate or
+ * mtts_sched_open, failures included): typical_p[c] is channel c's mass for HF's TypicalLogitsWarper (locally typical
+ * sampling), applied where that run's sampler[c].do_sample is set.  It runs in HF's place, after min_p and before
+ * epsilon_cutoff.  Over the set K kept so far, with p = softmax over K, H = -sum p_i ln p_i and shift_i = |-ln p_i - H|:
+ * t* is the smallest shift whose tokens {shift_i <= t*} hold at least typical_p of the mass, and token i stays iff
+ * shift_i <= t*.  Tokens of equal score stay or leave together; the kept set is an interval in score order whose top need
+ * not be the row's maximum -- the one warper that can remove the most probable token.  epsilon_cutoff and eta_cutoff then
+ * never drop a token at the maximum of that interval, the draw walks it from its top down, and lp is the log-softmax over
+ * the final set.  0 and 1 mean "absent" (HF adds the warper for typical_p < 1); a run without a typical_p on a sampled
+ * channel launches what it launched before.  mtts/warp_spec.py states the rule in numpy.
+ * MTTS_EINVAL, naming the channel, and nothing is left pending: a typical_p that is neither 0 nor 1 nor strictly inside
+ * (0, 1), NaN included. */
+int32_t mtts_set_sampler_typical(MttsEngine* e, const float typical_p[8] /* NULL: none; 0 or 1: absent */);
 /* Launches of the ban kernel by this process so far (engine steps and mtts_k_ngram_ban). */
 int64_t mtts_debug_ban_launches(void);
 /* Scheduler mode: start a take of the dialogue just submitted to src_slot in the empty dst_slot: same prompt (its
@@ -624,6 +637,13 @@ int32_t mtts_k_sample_bans(const void* dev_logits_bf16, int32_t rows, int32_t vo
                            int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
                            int32_t* dev_tokens, float* dev_logp, const MttsSamplerFloors* floors, const void* dev_ban,
                            void* stream);
+/* The same call with the channel's typical_p (mtts_set_sampler_typical; the same value check).  0 or 1: bit for bit
+ * mtts_k_sample_bans, the same kernels. */
+int32_t mtts_k_sample_typical(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
+                              const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
+                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
+                              int32_t* dev_tokens, float* dev_logp, const MttsSamplerFloors* floors, const void* dev_ban,
+                              float typical_p, void* stream);
 /* The ban kernel of a decode step on bare histories, launched as the engine launches it (one block per row): dev_hist
  * int32 [rows][cap], dev_lens int32 [rows] (each 0..cap), n = no_repeat_ngram_size (0..MTTS_NGRAM_MAX; 0: static bans
  * only, no scan), host_static n_static ids (suppress; those outside [0, vocab) are ignored), eos_id banned when eos_on.

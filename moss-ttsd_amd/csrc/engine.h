@@ -212,6 +212,8 @@ struct MttsEngine {
     MttsSamplerCfg* d_scfg = nullptr;
     MttsSamplerFloors* d_floors = nullptr;      // [8], allocated with the engine: a captured step may hold the address
     int floors_on = 0;                  // of the current run: a sampled channel has a probability floor (mtts_set_sampler_floors)
+    float* d_typical = nullptr;         // [8] typical_p per channel (0: absent), allocated with the engine like d_floors
+    int typical_on = 0;                 // of the current run: a sampled channel has a typical_p (mtts_set_sampler_typical)
     BanCfg* d_bancfg = nullptr;         // [8], allocated with the engine like d_floors (launch.h: launch_ban)
     int bans_on = 0;                    // of the current run: a channel has a hard ban (mtts_set_sampler_bans; the buffers are in bufs)
     int ban_ngram_on = 0;               // ... an n-gram ban: submits stage the prompt's slots into bufs.d_hist
@@ -279,7 +281,7 @@ static inline bool rows_carry_adapters(const MttsEngine* e) {
 static inline StepState step_state(const MttsEngine* e, int heads, int R, int pages_bound, bool lora) {
     StepState s;
     s.heads = heads; s.B = e->B; s.R = R; s.pages_bound = pages_bound; s.lora = lora;
-    s.forced = e->has_forced; s.ch0_sampled = e->ch0_sampled != 0; s.scores_on = e->scores_on != 0; s.floors_on = e->floors_on != 0;
+    s.forced = e->has_forced; s.ch0_sampled = e->ch0_sampled != 0; s.scores_on = e->scores_on != 0; s.floors_on = e->floors_on != 0; s.typical_on = e->typical_on != 0;
     s.bans_on = e->bans_on != 0;
     s.topk = e->topk_on;
     for (int k = 0; k < WSEAL_KINDS; ++k) s.wseal_on[k] = e->wseal_on[k] != 0;

@@ -301,6 +301,7 @@ int32_t mtts_engine_create(const MttsConfig* c, int32_t device, MttsEngine** out
     TRY(m.get(&e->d_bitmaps, (size_t)MTTS_RCAP * 8 * e->bm_words));
     TRY(m.get(&e->d_scfg, 8));
     TRY(m.get(&e->d_floors, 8));
+    TRY(m.get(&e->d_typical, 8));
     TRY(m.get(&e->d_bancfg, 8));
     TRY(alloc_scratch(m, e->sscr, c->max_batch, e->V0));
     *out = holder.release();
@@ -955,10 +956,10 @@ static int upload_staged(MttsEngine* e, const StagedRows& sr, bool on_stream, hi
 }
 
 // A new run starts from `seqs` (MTTS_RCAP slots; the idle ones as IDLE_SEQ) with every decode row idle, the loop state at
-// step 0, the run's sampler settings (floors: per channel, or empty) and clean sampler scratch.  Returns with `st` drained.
+// step 0, the run's sampler settings (floors, typical: per channel, or empty) and clean sampler scratch.  Returns with `st` drained.
 static const SeqState IDLE_SEQ{-1, 0, 0, 0, 0, 0, 0, 0, 0};
 static int reset_run_state(MttsEngine* e, const std::vector<SeqState>& seqs, bool continuous, const MttsSamplerCfg* sampler,
-                           const std::vector<MttsSamplerFloors>& floors, hipStream_t st) {
+                           const std::vector<MttsSamplerFloors>& floors, const std::vector<float>& typical, hipStream_t st) {
     HIPCHK(hipMemcpyAsync(e->d_seqs, seqs.data(), seqs.size() * sizeof(SeqState), hipMemcpyHostToDevice, st));
     if (continuous) e->forced_draw = 0;
     LoopState ls{0, 0, continuous ? 1 : 0, e->B, 0, e->bufs.gen_cap, e->forced_draw, e->f32 ? 1 : 0};
@@ -975,7 +976,15 @@ static int reset_run_state(MttsEngine* e, const std::vector<SeqState>& seqs, boo
     e->floors_on = 0;
     for (size_t c = 0; c < floors.size(); ++c)
         if (sampler[c].do_sample && (floors[c].min_p > 0.f || floors[c].epsilon_cutoff > 0.f || floors[c].eta_cutoff > 0.f)) e->floors_on = 1;
-    if (e->floors_on) HIPCHK(hipMemcpyAsync(e->d_floors, floors.data(), 8 * sizeof(MttsSamplerFloors), hipMemcpyHostToDevice, st));
+    // typical_p: the same, per sampled channel; its kernels read both tables, so the floors go up (as zeros) with it
+    float typ[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    e->typical_on = 0;
+    for (size_t c = 0; c < typical.size(); ++c)
+        if (sampler[c].do_sample && typical[c] > 0.f) { typ[c] = typical[c]; e->typical_on = 1; }
+    MttsSamplerFloors fl[8] = {};
+    for (size_t c = 0; c < floors.size(); ++c) fl[c] = floors[c];
+    if (e->floors_on || e->typical_on) HIPCHK(hipMemcpyAsync(e->d_floors, fl, sizeof(fl), hipMemcpyHostToDevice, st));
+    if (e->typical_on) HIPCHK(hipMemcpyAsync(e->d_typical, typ, sizeof(typ), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(e->sscr.hist, 0, (size_t)e->cfg.max_batch * 2048 * 4, st));
     HIPCHK(hipMemsetAsync(e->sscr.cand_n, 0, (size_t)e->cfg.max_batch * 4, st));
     HIPCHK(hipMemsetAsync(e->sscr.overflow, 0, (size_t)e->cfg.max_batch * 4, st));
@@ -1110,7 +1119,7 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
         // the rows' adapters: a prompt's takes share its KV pages and so its adapter
         for (int b = 0; b < MTTS_RCAP; ++b) e->seq_adapter[b] = b < R ? opt.row_adapter(b) : -1;
         if (e->bufs.d_seq_adapter) HIPCHK(hipMemcpyAsync(e->bufs.d_seq_adapter, e->seq_adapter.data(), MTTS_RCAP * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        TRY(reset_run_state(e, ss, false, sampler, opt.floors, st));   // drains st: the host vectors above go out of scope
+        TRY(reset_run_state(e, ss, false, sampler, opt.floors, opt.typical, st));   // drains st: the host vectors above go out of scope
     }
     TRY(prefill_staged(e, sr.Mpad, pages_for(e->max_real), 2, lora, st));
     // takes: the partially filled last prompt page of each source row into its takes' private pages, and the source
@@ -1130,6 +1139,10 @@ int32_t mtts_set_takes(MttsEngine* e, int32_t n) {
 int32_t mtts_set_sampler_floors(MttsEngine* e, const MttsSamplerFloors* floors) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     return e->pending.set_floors(floors);
+}
+int32_t mtts_set_sampler_typical(MttsEngine* e, const float* typical_p) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    return e->pending.set_typical(typical_p);
 }
 int32_t mtts_set_sampler_bans(MttsEngine* e, const MttsSamplerBans* bans) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
@@ -1166,7 +1179,8 @@ static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipSt
     }
     launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
                   e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, plan.B, sscr, plan.ch0_sampled,
-                  full_cap_for(e->V0), plan.scores_on, plan.floors_on ? e->d_floors : nullptr, st);
+                  full_cap_for(e->V0), plan.scores_on, (plan.floors_on || plan.typical_on) ? e->d_floors : nullptr,
+                  plan.typical_on ? e->d_typical : nullptr, st);
     GenTopkOut gt;                       // top_logprobs: the raw distribution at the decisions just written, into this step's row
     if (plan.topk) {
         gt = GenTopkOut{plan.topk, b.d_gt_logp, b.d_gt_ids, b.d_gt_tlp};
@@ -1669,6 +1683,7 @@ int32_t mtts_read_seq_state(MttsEngine* e, int32_t* host_nas, int32_t* host_unfi
 // finishes leaves the batch at once (no finished-row padding) and its slot can be refilled.
 int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSamplerCfg* sampler, void* stream) {
     if (!e) return fail(MTTS_EINVAL, "null argument");
+    const std::vector<float> typical = e->pending.take_typical();
     const std::vector<MttsSamplerFloors> floors = e->pending.take_floors();     // the one-shots leave first: consumed whatever follows
     const RunBans bans = e->pending.take_bans();
     if (!sampler) return fail(MTTS_EINVAL, "null argument");
@@ -1690,7 +1705,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     TRY(pack_policy_reset(e, st));
     std::fill(e->seq_adapter.begin(), e->seq_adapter.end(), -1);
     if (e->bufs.d_seq_adapter) HIPCHK(hipMemsetAsync(e->bufs.d_seq_adapter, 0xff, MTTS_RCAP * sizeof(int32_t), st));
-    TRY(reset_run_state(e, std::vector<SeqState>(MTTS_RCAP, IDLE_SEQ), true, sampler, floors, st));
+    TRY(reset_run_state(e, std::vector<SeqState>(MTTS_RCAP, IDLE_SEQ), true, sampler, floors, typical, st));
     e->began = true;
     e->run_open = true;
     return MTTS_OK;

@@ -375,7 +375,7 @@ int32_t mtts_k_gemm_tile(int32_t epi, const void* dev_w, const void* dev_x, void
 
 static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                     int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
-                    const MttsSamplerFloors* floors, const void* ban, void* stream) {
+                    const MttsSamplerFloors* floors, const void* ban, float typical_p, void* stream) {
     if (!logits || !cfg || !dev_tokens || rows < 1 || vocab < 1 || channel < 0 || channel > 7) return fail(MTTS_EINVAL, "sample: bad argument");
     hipStream_t st = S(stream);
     MttsSamplerCfg h[8];
@@ -400,6 +400,18 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
             HIPCHK(hipMemcpy(dfl, hf, sizeof(hf), hipMemcpyHostToDevice));
         }
     }
+    // typical_p: checked like mtts_set_sampler_typical checks it; 0, 1 or a greedy cfg: the kernels without it
+    float* dty = nullptr;
+    {
+        float ht[8];
+        for (int i = 0; i < 8; ++i) ht[i] = typical_p;
+        PendingRun chk;
+        TRY(chk.set_typical(ht));
+        if (cfg->do_sample && typical_p > 0.f && typical_p < 1.f) {
+            TRY(hb.get(&dty, 8));
+            HIPCHK(hipMemcpy(dty, ht, sizeof(ht), hipMemcpyHostToDevice));
+        }
+    }
     SampleScratch sc;
     TRY(alloc_scratch(hb, sc, rows, vocab));
     sc.ban = (const uint32_t*)ban;   // [rows][ceil(vocab / 32)], or null: the same kernels, which then read no ban word
@@ -408,7 +420,7 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
         TRY(hb.get(&sc.lp, (size_t)rows * 8));
     }
     launch_sample_single(logits, rows, vocab, (const uint32_t*)bitmap, (vocab + 31) / 32, d, mask_id, seed, step, channel, dec, err, sc,
-                         full_cap_for(vocab), dev_logp ? 1 : 0, dfl, st);
+                         full_cap_for(vocab), dev_logp ? 1 : 0, dfl, dty, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     std::vector<int32_t> hd((size_t)rows * 8);
@@ -430,26 +442,32 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
 
 int32_t mtts_k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                       int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, void* stream) {
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, nullptr, nullptr, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, nullptr, nullptr, nullptr, 0.f, stream);
 }
 
 int32_t mtts_k_sample_scores(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
                              void* stream) {
     if (!dev_logp) return fail(MTTS_EINVAL, "sample: null dev_logp");
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, nullptr, nullptr, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, nullptr, nullptr, 0.f, stream);
 }
 
 int32_t mtts_k_sample_floors(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
                              const MttsSamplerFloors* floors, void* stream) {
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, nullptr, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, nullptr, 0.f, stream);
 }
 
 int32_t mtts_k_sample_bans(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                            int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
                            const MttsSamplerFloors* floors, const void* dev_ban, void* stream) {
-    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, dev_ban, stream);
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, dev_ban, 0.f, stream);
+}
+
+int32_t mtts_k_sample_typical(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                              int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
+                              const MttsSamplerFloors* floors, const void* dev_ban, float typical_p, void* stream) {
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, dev_ban, typical_p, stream);
 }
 
 // The ban kernel of a decode step (sampler.hip: ban_kernel) on bare histories of one channel.

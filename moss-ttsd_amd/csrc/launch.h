@@ -149,11 +149,12 @@ struct SampleScratch {
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps,
                    int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed,
                    int32_t* decisions, int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap,
-                   int emit_lp, const MttsSamplerFloors* floors /* device, 8 entries; null: no floors */, hipStream_t st);
+                   int emit_lp, const MttsSamplerFloors* floors /* device, 8 entries; null: no floors */,
+                   const float* typical /* device, 8 entries (0: absent); null: no typical_p */, hipStream_t st);
 void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
                           const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
                           int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp,
-                          const MttsSamplerFloors* floors8, hipStream_t st);
+                          const MttsSamplerFloors* floors8, const float* typical8, hipStream_t st);
 // The ban kernel of a decode step (mtts_set_sampler_bans; sampler.hip: ban_kernel), one block per (row, channel) the
 // sampler evaluates: ban[row][c][words] = stat[c][words], plus eos while the row's step < cfgs[c].eos_below, plus -- where
 // cfgs[c].ngram = n > 0 -- the follower of every earlier occurrence of the history's last n-1 tokens.  The history of

@@ -40,6 +40,7 @@ struct RunOptions {
     std::vector<int32_t> row_ids;       // Philox row id per row; empty: 0..rows-1
     std::vector<int32_t> row_adapters;  // adapter per PROMPT (its takes share its KV pages and so its adapter); empty: none
     std::vector<MttsSamplerFloors> floors;      // per channel (mtts_set_sampler_floors); empty: none
+    std::vector<float> typical;         // typical_p per channel (mtts_set_sampler_typical), 0: absent; empty: none
     RunBans bans;                       // per channel (mtts_set_sampler_bans); empty: none
     int output_scores = 0, top_logprobs = 0;
     int rows() const { return B * takes; }
@@ -63,6 +64,7 @@ class PendingRun {
     std::vector<int32_t> row_ids, row_adapters;
     std::vector<int32_t> slot_adapter = std::vector<int32_t>(MTTS_RCAP, -1);    // scheduler mode: of the slot's next submit
     std::vector<MttsSamplerFloors> floors;
+    std::vector<float> typical;
     RunBans bans;
 public:
     int output_scores = 0, top_logprobs = 0;        // sticky: every run reads them, none resets them
@@ -80,6 +82,20 @@ public:
             if (!(f[c].eta_cutoff >= 0.f && f[c].eta_cutoff < 1.f)) return fail(RUN_EINVAL, "channel %d: eta_cutoff %g is outside [0, 1)", c, (double)f[c].eta_cutoff);
         }
         if (f) floors.assign(f, f + MTTS_CHANNELS);
+        return 0;
+    }
+    // typical_p per channel: 0 or 1 mean "absent" (HF adds the warper for typical_p < 1) and are stored as 0; anything else
+    // lies strictly inside (0, 1), as HF's constructor demands.  A refused call leaves none behind
+    int set_typical(const float* t) {
+        typical.clear();
+        if (!t) return 0;
+        std::vector<float> v(MTTS_CHANNELS, 0.f);
+        for (int c = 0; c < MTTS_CHANNELS; ++c) {
+            if (t[c] == 0.f || t[c] == 1.f) continue;
+            if (!(t[c] > 0.f && t[c] < 1.f)) return fail(RUN_EINVAL, "channel %d: typical_p %g is outside (0, 1)", c, (double)t[c]);
+            v[c] = t[c];
+        }
+        typical.swap(v);
         return 0;
     }
     // the same for the bans; a refused call leaves none behind
@@ -111,12 +127,14 @@ public:
         o.row_ids.swap(row_ids);
         o.row_adapters.swap(row_adapters);
         o.floors = take_floors();
+        o.typical = take_typical();
         o.bans = take_bans();
         takes = 1;
         return o;
     }
     // mtts_sched_open: a scheduler run takes no other one-shot
     std::vector<MttsSamplerFloors> take_floors() { return std::exchange(floors, {}); }
+    std::vector<float> take_typical() { return std::exchange(typical, {}); }
     RunBans take_bans() { return std::exchange(bans, RunBans()); }
     // mtts_slot_submit* into `slot`: the same for that slot's adapter
     int take_slot_adapter(int slot) { return std::exchange(slot_adapter[slot], -1); }

@@ -164,10 +164,11 @@ struct NucSel {            // membership of the current candidate set, in (key, 
     uint32_t kmin;         // survivors of top-k: key >= kmin (and finite)
     uint32_t kp;           // kept by top-p: key > kp, or key == kp and id >= idp
     int idp;
+    uint32_t kmax = 0xffffffffu;       // typical_p, the one stage that can cut from the top: key <= kmax
 };
 __device__ __forceinline__ float unfkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 __device__ __forceinline__ bool nuc_in(const NucSel& z, uint32_t key, int id) {
-    return key > 0x007fffffu /* fkey(-inf) */ && key >= z.kmin && (key > z.kp || (key == z.kp && id >= z.idp));
+    return key > 0x007fffffu /* fkey(-inf) */ && key >= z.kmin && key <= z.kmax && (key > z.kp || (key == z.kp && id >= z.idp));
 }
 __device__ __forceinline__ int nuc_bin(uint32_t key, float lo) {
     const int b = (int)((unfkey(key) - lo) * ((float)(NUC_BINS - 1) / 32.0f));      // monotone in the score
@@ -272,15 +273,83 @@ __global__ __launch_bounds__(SAMP_T) void sample_collect_kernel(
     }
 }
 
+// ---- typical_p (HF TypicalLogitsWarper; mtts/warp_spec.py states the rule).  Over the kept set, with d_i = s_i - smax,
+// e_i = exp(d_i) and p_i = e_i / tot: the surprisal is ln tot - d_i and the entropy H = ln tot - sum p_i d_i, so
+// shift_i = |-ln p_i - H| = |d_i - dc| with dc = sum p_i d_i, the mean of d.  Both sampler paths take the shift as the
+// fp32 value below: a function of the score alone (tokens of equal score stay or leave together), falling to the
+// entropy crossing and rising after it as the score ascends, so "shift <= t" is an interval in score order.
+__device__ __forceinline__ uint32_t typ_shift_bits(float d, double dc) { return __float_as_uint((float)fabs((double)d - dc)); }
+
+// block-wide sum, the same bits in every thread; one barrier per call: consecutive calls alternate between the two rows of sh
+template <int NT>
+__device__ __forceinline__ double block_sum_alt(double v, double (*sh)[NT / 64], int it) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[it & 1][threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) s += sh[it & 1][w];
+    return s;
+}
+
+// In-block path: cval ascends over [first_keep, hi_keep).  t* = the smallest shift whose tokens {shift <= t*} hold typ of
+// the mass, found by bisection on the shift's bit pattern (non-negative floats order as their bits): every thread keeps
+// its run's (shift, e) in registers and a step costs one block sum.  The leavers are a prefix and a suffix of the range.
+template <int NT>
+__device__ void typical_cut(const float* __restrict__ cval, float smax, float typ, int& first_keep, int& hi_keep, double* shd) {
+    constexpr int TPT = SAMP_CAND / NT;         // tokens per thread at most
+    __shared__ double alt[2][NT / 64];
+    const int tid = threadIdx.x;
+    const int mk = hi_keep - first_keep;
+    const int perf = (mk + NT - 1) / NT;
+    const int a0 = first_keep + tid * perf, a1 = min(hi_keep, a0 + perf);
+    float dd[TPT], ee[TPT];
+    double loc = 0.0, loc1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < TPT; ++j) {
+        const bool on = j < perf && a0 + j < a1;
+        dd[j] = on ? cval[a0 + j] - smax : 0.f;
+        ee[j] = on ? expf(dd[j]) : 0.f;
+        loc += (double)ee[j];
+        loc1 += (double)ee[j] * (double)dd[j];
+    }
+    double tot, tot1;
+    (void)block_excl_scan<NT>(loc, shd, tot);
+    (void)block_excl_scan<NT>(loc1, shd, tot1);
+    const double dc = tot1 / tot, need = (double)typ * tot;
+    uint32_t sb[TPT];
+#pragma unroll
+    for (int j = 0; j < TPT; ++j) sb[j] = (j < perf && a0 + j < a1) ? typ_shift_bits(dd[j], dc) : 0xffffffffu;
+    uint32_t lo = 0u, hi = 0x7f800000u;         // (at +inf every token is in: the mass is tot >= need)
+    for (int it = 0; lo < hi; ++it) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        double m = 0.0;
+#pragma unroll
+        for (int j = 0; j < TPT; ++j) m += sb[j] <= mid ? (double)ee[j] : 0.0;
+        if (block_sum_alt<NT>(m, alt, it) >= need) hi = mid; else lo = mid + 1;
+    }
+    int below = 0, above = 0;
+#pragma unroll
+    for (int j = 0; j < TPT; ++j)
+        if (sb[j] != 0xffffffffu && sb[j] > lo) { if ((double)dd[j] < dc) ++below; else ++above; }
+    double nb, na;
+    (void)block_excl_scan<NT>((double)below, shd, nb);
+    (void)block_excl_scan<NT>((double)above, shd, na);
+    first_keep += (int)nb;
+    hi_keep -= (int)na;
+}
+
 // Everything after the candidates are known: sort, HF top-k / top-p cuts, Philox draw.
 // val/idx: n candidate (score, id) pairs (LDS for the fast path, global memory for the full-vocabulary path),
 // capacity >= next_pow2(n).  NT threads.  Returns the chosen token in every thread; lp (may be null): thread 0's
 // receives log(softmax over the kept set)[pick].  FL: the probability floors `fl` (mtts.h: MttsSamplerFloors) cut the kept
-// set once more per active floor.
-template <int NT, bool FL>
+// set once more per active floor.  TY: typical_p `typ` (0: absent) runs between min_p and epsilon_cutoff and may cut the kept
+// range from the top as well: [first_keep, hi_keep) from there on.
+template <int NT, bool FL, bool TY>
 __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, int n, const MttsSamplerCfg& cfg, float smax,
                              uint32_t step, uint32_t b, uint32_t c, uint64_t seed, double* shd, int* sh_i, float* lp,
-                             const MttsSamplerFloors& fl) {
+                             const MttsSamplerFloors& fl, float typ) {
     const int tid = threadIdx.x;
     // bitonic sort of P = next_pow2(n) slots by (score asc, id asc); padding sorts last
     int P = 1;
@@ -336,13 +405,21 @@ __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, i
     // probability floors (HF MinP / Epsilon / EtaLogitsWarper, in that order, each on the survivors of the last): a token
     // leaves iff its share of the kept mass is below the floor and its score below the maximum.  Scores ascend, so the
     // leavers are again a prefix of [first_keep, n)
+    int hi_keep = n;            // the kept range is [first_keep, hi_keep); only typical_p lowers its top, cval[hi_keep - 1]
+    float stop = smax;
     if constexpr (FL) {
         for (int w = 0; w < 3; ++w) {
+            if constexpr (TY) {
+                if (w == 1 && typ > 0.f) {
+                    typical_cut<NT>(cval, smax, typ, first_keep, hi_keep, shd);
+                    stop = cval[hi_keep - 1];
+                }
+            }
             const float fv = w == 0 ? fl.min_p : w == 1 ? fl.epsilon_cutoff : fl.eta_cutoff;
             if (!(fv > 0.f)) continue;
-            const int mk = n - first_keep;
+            const int mk = hi_keep - first_keep;
             const int perf = (mk + NT - 1) / NT;
-            const int a0 = first_keep + tid * perf, a1 = min(n, a0 + perf);
+            const int a0 = first_keep + tid * perf, a1 = min(hi_keep, a0 + perf);
             double loc = 0.0, loc1 = 0.0;
             for (int i = a0; i < a1; ++i) {
                 const double d = (double)(cval[i] - smax), e = (double)expf(cval[i] - smax);
@@ -361,16 +438,17 @@ __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, i
                 thr = fmin((double)fv, (double)fl.sqrt_eta_cutoff * exp(-H)) * tot;
             }
             int drop = 0;
-            for (int i = a0; i < a1; ++i) drop += ((double)expf(cval[i] - smax) < thr && cval[i] < smax) ? 1 : 0;
+            for (int i = a0; i < a1; ++i) drop += ((double)expf(cval[i] - smax) < thr && cval[i] < stop) ? 1 : 0;
             double dtot;
             (void)block_excl_scan<NT>((double)drop, shd, dtot);
             first_keep += (int)dtot;
         }
     }
-    // draw: walk kept tokens from the top (position n-1 down to first_keep)
-    const int nk = n - first_keep;
+    // draw: walk kept tokens from the top (position hi_keep-1 down to first_keep)
+    const int nk = hi_keep - first_keep;
     const int perk = (nk + NT - 1) / NT;
     const int r0 = tid * perk, r1 = min(nk, r0 + perk);    // ranks from the top
+    n = hi_keep;
     double loc = 0.0;
     for (int r = r0; r < r1; ++r) loc += (double)expf(cval[n - 1 - r] - smax);
     double tot;
@@ -394,13 +472,15 @@ __device__ int finish_sample(float* __restrict__ cval, int* __restrict__ cidx, i
     return cidx[n - 1 - r];
 }
 
-template <bool LP, bool FL>
-__global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
+// The body of sample_final_kernel<LP, FL> (TY false) and of sample_final_typ_kernel<LP> (TY: typical_p per channel in
+// `typical`, 0 = absent; `floors` may then be null).  A run without typical_p launches the kernels it launched before.
+template <bool LP, bool FL, bool TY>
+__device__ __forceinline__ void sample_final_body(
     const uint16_t* __restrict__ logits0, const uint16_t* __restrict__ logits17, int V0, int Vs, int Vs_pad,
     const uint32_t* __restrict__ bitmaps, int bm_words, const MttsSamplerCfg* __restrict__ cfgs,
     const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs, uint64_t seed, int32_t* __restrict__ decisions,
-    int32_t* __restrict__ err, SampleScratch sc, int big_channel0, int single_vocab, int single_mask, int single_step, int single_channel,
-    const MttsSamplerFloors* __restrict__ floors) {
+    int32_t* __restrict__ err, const SampleScratch& sc, int big_channel0, int single_vocab, int single_mask, int single_step, int single_channel,
+    const MttsSamplerFloors* __restrict__ floors, const float* __restrict__ typical) {
     __shared__ float cval[SAMP_CAND];
     __shared__ int cidx[SAMP_CAND];
     __shared__ float shf[SAMP_T / 64];
@@ -507,13 +587,36 @@ __global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
     }
     float lpv = 0.f;
     MttsSamplerFloors fl{0.f, 0.f, 0.f, 0.f};
-    if constexpr (FL) fl = floors[x.c];
-    const int pick = finish_sample<SAMP_T, FL>(cval, cidx, n, cfg, smax, (uint32_t)x.step, x.row_id, (uint32_t)x.c,
-                                               single_vocab > 0 ? seed : x.seed, shd, sh_i, LP ? &lpv : nullptr, fl);
+    if constexpr (FL) { if (!TY || floors) fl = floors[x.c]; }
+    float typ = 0.f;
+    if constexpr (TY) typ = typical[x.c];
+    const int pick = finish_sample<SAMP_T, FL, TY>(cval, cidx, n, cfg, smax, (uint32_t)x.step, x.row_id, (uint32_t)x.c,
+                                                   single_vocab > 0 ? seed : x.seed, shd, sh_i, LP ? &lpv : nullptr, fl, typ);
     if (tid == 0) {
         decisions[out_slot] = pick;
         if (LP) sc.lp[out_slot] = lpv;
     }
+}
+
+template <bool LP, bool FL>
+__global__ __launch_bounds__(SAMP_T) void sample_final_kernel(
+    const uint16_t* __restrict__ logits0, const uint16_t* __restrict__ logits17, int V0, int Vs, int Vs_pad,
+    const uint32_t* __restrict__ bitmaps, int bm_words, const MttsSamplerCfg* __restrict__ cfgs,
+    const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs, uint64_t seed, int32_t* __restrict__ decisions,
+    int32_t* __restrict__ err, SampleScratch sc, int big_channel0, int single_vocab, int single_mask, int single_step, int single_channel,
+    const MttsSamplerFloors* __restrict__ floors) {
+    sample_final_body<LP, FL, false>(logits0, logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, err, sc,
+                                     big_channel0, single_vocab, single_mask, single_step, single_channel, floors, nullptr);
+}
+template <bool LP>
+__global__ __launch_bounds__(SAMP_T) void sample_final_typ_kernel(
+    const uint16_t* __restrict__ logits0, const uint16_t* __restrict__ logits17, int V0, int Vs, int Vs_pad,
+    const uint32_t* __restrict__ bitmaps, int bm_words, const MttsSamplerCfg* __restrict__ cfgs,
+    const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs, uint64_t seed, int32_t* __restrict__ decisions,
+    int32_t* __restrict__ err, SampleScratch sc, int big_channel0, int single_vocab, int single_mask, int single_step, int single_channel,
+    const MttsSamplerFloors* __restrict__ floors, const float* __restrict__ typical) {
+    sample_final_body<LP, true, true>(logits0, logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, err, sc,
+                                      big_channel0, single_vocab, single_mask, single_step, single_channel, floors, typical);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -684,8 +787,9 @@ __device__ void nuc_drop_prefix(NucShared& S, int binA, unsigned int dc, u64 dm,
 // ---- probability floors (mtts.h: MttsSamplerFloors) on the full-vocabulary path.  A floor is a mass per token, so the
 // cut is a key threshold: the smallest key whose expf(score - smax) reaches `thr` (never above the maximum's own key,
 // which stays whatever the floor says); every member below it leaves.
-__device__ __forceinline__ uint32_t nuc_floor_key(double thr, float smax) {
-    uint32_t lo = 0x00800000u /* fkey(-FLT_MAX) */, hi = fkey(smax);
+// ktop: the key of the kept set's top, fkey(smax) until typical_p has cut from above.
+__device__ __forceinline__ uint32_t nuc_floor_key(double thr, float smax, uint32_t ktop) {
+    uint32_t lo = 0x00800000u /* fkey(-FLT_MAX) */, hi = ktop;
     while (lo < hi) {                                       // smallest key in [lo, hi] that stays; hi always does
         const uint32_t mid = lo + ((hi - lo) >> 1);
         if ((double)expf(unfkey(mid) - smax) < thr) lo = mid + 1; else hi = mid;
@@ -743,12 +847,137 @@ __device__ double nuc_entropy_sum(NucShared& S, const uint32_t* __restrict__ key
     return sum;
 }
 
-template <bool FL>
-__global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
+// ---- typical_p on the full-vocabulary path (typ_shift_bits above: the rule and the shift both paths use)
+// f(key, id) for every member of `z`, the row's keys spread over the block's threads, four loads in flight
+template <typename F>
+__device__ __forceinline__ void nuc_each_member(const uint32_t* __restrict__ keys, int V, const NucSel& z, F f) {
+    for (int i0 = threadIdx.x; i0 < V; i0 += SAMP_FT * 4) {
+        uint32_t k[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const int i = i0 + u * SAMP_FT; k[u] = i < V ? keys[i] : 0u; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = i0 + u * SAMP_FT;
+            if (i < V && nuc_in(z, k[u], i)) f(k[u], i);
+        }
+    }
+}
+// The members of `z` above key `kceil` leave: the mirror image of nuc_floor_cut.
+__device__ void nuc_ceil_cut(NucShared& S, const uint32_t* __restrict__ keys, const uint16_t* __restrict__ bins, int V, NucSel& z,
+                             float smax, uint32_t kceil, unsigned int& n, u64& tot) {
+    const int binB = kceil < fkey(smax - 32.0f) ? 0 : nuc_bin(kceil, smax - 32.0f);      // the bins above it leave whole
+    __syncthreads();
+    if (threadIdx.x == 0) { S.out_cnt = 0; S.out_mass = 0; S.grp_cnt = 0; S.grp_mass = 0; }
+    __syncthreads();
+    for (int i = binB + 1 + threadIdx.x; i < NUC_BINS; i += SAMP_FT)
+        if (S.cnt0[i]) { atomicAdd(&S.out_cnt, S.cnt0[i]); atomicAdd(&S.out_mass, S.mass0[i]); }
+    nuc_scan_bin(bins, V, binB, [&](int i) {
+        const uint32_t key = keys[i];
+        if (nuc_in(z, key, i) && key > kceil) { atomicAdd(&S.grp_cnt, 1u); atomicAdd(&S.grp_mass, nuc_q(key, smax)); }
+    });
+    __syncthreads();
+    const unsigned int gc = S.grp_cnt, dc = S.out_cnt + gc;
+    const u64 gm = S.grp_mass, dm = S.out_mass + gm;
+    z.kmax = min(z.kmax, kceil);
+    if (dc == 0) return;                                    // (uniform: every thread read the same totals)
+    n -= dc;
+    tot -= dm;
+    __syncthreads();
+    for (int i = binB + 1 + threadIdx.x; i < NUC_BINS; i += SAMP_FT) { S.cnt0[i] = 0; S.mass0[i] = 0; }
+    if (threadIdx.x == 0) { S.cnt0[binB] -= gc; S.mass0[binB] -= gm; }
+    __syncthreads();
+}
+// the largest key among the members: the top of the kept set once typical_p has cut from above
+__device__ uint32_t nuc_top_key(NucShared& S, const uint32_t* __restrict__ keys, int V, const NucSel& z) {
+    uint32_t m = 0;
+    nuc_each_member(keys, V, z, [&](uint32_t key, int) { m = max(m, key); });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) S.wc[threadIdx.x >> 6] = m;
+    __syncthreads();
+    uint32_t r = 0;
+    for (int w = 0; w < SAMP_FT / 64; ++w) r = max(r, S.wc[w]);
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ int typ_lin_bin(uint32_t sb) { return (int)fminf(__uint_as_float(sb) * 64.0f, (float)(NUC_BINS - 1)); }
+// t* is a selection by mass in ascending shift order, and the shift is a function of the key once dc is known: the count-
+// and-mass radix selection of this path on a derived key -- a linear binning of the shift (monotone in it, so the order by
+// (bin, shift bits) is the order by shift), then the three digits (11 | 11 | 10 bits) of the shift's bit pattern inside
+// the crossing bin.  Masses stay nuc_q of the SCORE key: exact integers, order-free.  One pass over the row's keys per
+// level and one for the mean.  The kept keys are then the interval [klo, khi] around the crossing, found without memory
+// traffic by bisection on the key; what lies below and above it leaves through nuc_floor_cut / nuc_ceil_cut.
+__device__ void nuc_typical_cut(NucShared& S, const uint32_t* __restrict__ keys, const uint16_t* __restrict__ bins, int V, NucSel& z,
+                                float smax, float typ, unsigned int& n, u64& tot) {
+    const double dc = nuc_entropy_sum(S, keys, V, z, smax) / ((double)tot / NUC_SCALE);
+    const double need = (double)typ * (double)tot;
+    auto reached = [need](unsigned int, u64 m) { return (double)m >= need; };
+    unsigned int bc = 0;
+    u64 bm = 0;
+    int binT = 0;
+    uint32_t prefix = 0, tb = 0x7f800000u;                  // (no crossing, which the exact masses rule out: everything stays)
+    for (int level = 0; level < 4; ++level) {
+        for (int i = threadIdx.x; i < NUC_BINS; i += SAMP_FT) { S.cnt[i] = 0; S.mass[i] = 0; }
+        __syncthreads();
+        nuc_each_member(keys, V, z, [&](uint32_t key, int) {
+            const uint32_t sb = typ_shift_bits(unfkey(key) - smax, dc);
+            int d = typ_lin_bin(sb);
+            if (level > 0) {
+                if (d != binT) return;
+                if (level == 1) d = sb >> 21;
+                else if (level == 2) { if ((sb >> 21) != prefix) return; d = (sb >> 10) & 2047; }
+                else { if ((sb >> 10) != prefix) return; d = sb & 1023; }
+            }
+            atomicAdd(&S.cnt[d], 1u);
+            atomicAdd(&S.mass[d], nuc_q(key, smax));
+        });
+        __syncthreads();
+        const int dg = nuc_cross(S, S.cnt, S.mass, true, bc, bm, reached);
+        if (dg < 0) break;                                  // (uniform)
+        if (level == 0) binT = dg;
+        else if (level == 1) prefix = (uint32_t)dg;
+        else if (level == 2) prefix = (prefix << 11) | (uint32_t)dg;
+        else tb = (prefix << 10) | (uint32_t)dg;
+    }
+    const uint32_t kbot = 0x00800000u /* fkey(-FLT_MAX) */, ktop = fkey(smax);
+    auto below = [&](uint32_t key) { return (double)(unfkey(key) - smax) <= dc; };
+    auto in = [&](uint32_t key) { return typ_shift_bits(unfkey(key) - smax, dc) <= tb; };
+    uint32_t lo = kbot, hi = ktop;                          // kc: the largest key at or below the crossing (kbot is)
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+        if (below(mid)) lo = mid; else hi = mid - 1;
+    }
+    const uint32_t kc = lo;
+    uint32_t klo = kc + 1, khi = kc;                        // the shift falls over [kbot, kc] and rises over (kc, ktop]
+    if (in(kc)) {
+        lo = kbot; hi = kc;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (in(mid)) hi = mid; else lo = mid + 1;
+        }
+        klo = lo;
+    }
+    if (kc < ktop && in(kc + 1)) {
+        lo = kc + 1; hi = ktop;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+            if (in(mid)) lo = mid; else hi = mid - 1;
+        }
+        khi = lo;
+    }
+    nuc_floor_cut(S, keys, bins, V, z, smax, klo, n, tot);
+    nuc_ceil_cut(S, keys, bins, V, z, smax, khi, n, tot);
+}
+
+// The body of sample_full_kernel<FL> (TY false) and of sample_full_typ_kernel (TY: typical_p per channel in `typical`,
+// 0 = absent; `floors` may then be null).
+template <bool FL, bool TY>
+__device__ __forceinline__ void sample_full_body(
     const uint16_t* __restrict__ logits0, int V0, const uint32_t* __restrict__ bitmaps, int bm_words,
     const MttsSamplerCfg* __restrict__ cfgs, const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs,
-    uint64_t seed, int32_t* __restrict__ decisions, SampleScratch sc, int full_cap, int emit_lp, int single_vocab, int single_mask,
-    int single_step, int single_channel, const MttsSamplerFloors* __restrict__ floors) {
+    uint64_t seed, int32_t* __restrict__ decisions, const SampleScratch& sc, int full_cap, int emit_lp, int single_vocab, int single_mask,
+    int single_step, int single_channel, const MttsSamplerFloors* __restrict__ floors, const float* __restrict__ typical) {
     __shared__ NucShared S;
     __shared__ float shf[SAMP_FT / 64];
     __shared__ int shi[SAMP_FT / 64];
@@ -831,16 +1060,26 @@ __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
         }
         // ---- probability floors (HF MinP / Epsilon / EtaLogitsWarper), each on the survivors of the stage before it
         if constexpr (FL) {
-            const MttsSamplerFloors fl = floors[x.c];
+            MttsSamplerFloors fl{0.f, 0.f, 0.f, 0.f};
+            if (!TY || floors) fl = floors[x.c];
+            uint32_t ktop = fkey(smax);
             // as a mass per token: p_i < floor  <=>  exp(s_i - smax) < floor * total  (p_max = 1 / total)
-            if (fl.min_p > 0.f) nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key((double)fl.min_p, smax), n, tot);
+            if (fl.min_p > 0.f) nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key((double)fl.min_p, smax, ktop), n, tot);
+            if constexpr (TY) {
+                const float typ = typical[x.c];
+                if (typ > 0.f) {
+                    nuc_typical_cut(S, keys, bins, V, z, smax, typ, n, tot);
+                    // the floors that follow never drop a token at the maximum of what is left
+                    if (fl.epsilon_cutoff > 0.f || fl.eta_cutoff > 0.f) ktop = nuc_top_key(S, keys, V, z);
+                }
+            }
             if (fl.epsilon_cutoff > 0.f)
-                nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key((double)fl.epsilon_cutoff * ((double)tot / NUC_SCALE), smax), n, tot);
+                nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key((double)fl.epsilon_cutoff * ((double)tot / NUC_SCALE), smax, ktop), n, tot);
             if (fl.eta_cutoff > 0.f) {
                 const double t = (double)tot / NUC_SCALE;
                 const double H = log(t) - nuc_entropy_sum(S, keys, V, z, smax) / t;
                 const double eta = fmin((double)fl.eta_cutoff, (double)fl.sqrt_eta_cutoff * exp(-H));
-                nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key(eta * t, smax), n, tot);
+                nuc_floor_cut(S, keys, bins, V, z, smax, nuc_floor_key(eta * t, smax, ktop), n, tot);
             }
         }
         // ---- draw: walk the kept tokens from the top; the first whose running mass exceeds u * total
@@ -870,6 +1109,23 @@ __global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
             sc.lp[b * 8 + x.c] = n > 0 ? (float)((double)(unfkey(keys[pick]) - smax) - log((double)tot / NUC_SCALE))
                                        : __uint_as_float(0x7fc00000u);
     }
+}
+template <bool FL>
+__global__ __launch_bounds__(SAMP_FT) void sample_full_kernel(
+    const uint16_t* __restrict__ logits0, int V0, const uint32_t* __restrict__ bitmaps, int bm_words,
+    const MttsSamplerCfg* __restrict__ cfgs, const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs,
+    uint64_t seed, int32_t* __restrict__ decisions, SampleScratch sc, int full_cap, int emit_lp, int single_vocab, int single_mask,
+    int single_step, int single_channel, const MttsSamplerFloors* __restrict__ floors) {
+    sample_full_body<FL, false>(logits0, V0, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, sc, full_cap, emit_lp, single_vocab,
+                                single_mask, single_step, single_channel, floors, nullptr);
+}
+__global__ __launch_bounds__(SAMP_FT) void sample_full_typ_kernel(
+    const uint16_t* __restrict__ logits0, int V0, const uint32_t* __restrict__ bitmaps, int bm_words,
+    const MttsSamplerCfg* __restrict__ cfgs, const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs,
+    uint64_t seed, int32_t* __restrict__ decisions, SampleScratch sc, int full_cap, int emit_lp, int single_vocab, int single_mask,
+    int single_step, int single_channel, const MttsSamplerFloors* __restrict__ floors, const float* __restrict__ typical) {
+    sample_full_body<true, true>(logits0, V0, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, sc, full_cap, emit_lp, single_vocab,
+                                 single_mask, single_step, single_channel, floors, typical);
 }
 
 // One block; thread b handles sequence slot b.  Restates modeling_asteroid.py:139-169 with a per-dialogue clock.
@@ -1089,11 +1345,19 @@ void launch_ban_single(uint32_t* ban, const uint32_t* stat, const BanCfg* cfg1, 
 static SampleScratch g_dummy_scratch;
 // emit_lp (output_scores): the LP instantiations of the scan / final kernels; off, the step runs the plain ones.
 // floors (mtts_set_sampler_floors; device, 8 entries): the FL instantiations of the final / full kernels; null, the plain ones.
+// typical (mtts_set_sampler_typical; device, 8 floats): the *_typ_kernel pair, which takes both tables (floors may be null
+// there); null, the launches above, as before typical_p existed.
 template <bool LP, bool FL>
 static void launch_final(dim3 grid, hipStream_t st, const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad,
                          const uint32_t* bitmaps, int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs,
                          uint64_t seed, int32_t* decisions, int32_t* err, const SampleScratch& sc, int big0, int single_vocab,
-                         int single_mask, int single_step, int single_channel, const MttsSamplerFloors* floors) {
+                         int single_mask, int single_step, int single_channel, const MttsSamplerFloors* floors, const float* typical) {
+    if (typical) {
+        hipLaunchKernelGGL((sample_final_typ_kernel<LP>), grid, dim3(SAMP_T), 0, st, (const uint16_t*)logits0, (const uint16_t*)logits17,
+                           V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, err, sc, big0, single_vocab, single_mask,
+                           single_step, single_channel, floors, typical);
+        return;
+    }
     hipLaunchKernelGGL((sample_final_kernel<LP, FL>), grid, dim3(SAMP_T), 0, st, (const uint16_t*)logits0, (const uint16_t*)logits17,
                        V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, err, sc, big0, single_vocab, single_mask,
                        single_step, single_channel, floors);
@@ -1106,7 +1370,7 @@ static void launch_final(dim3 grid, hipStream_t st, const void* logits0, const v
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps, int bm_words,
                    const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed, int32_t* decisions,
                    int32_t* err, int B, const SampleScratch& sc, int ch0_sampled, int full_cap, int emit_lp,
-                   const MttsSamplerFloors* floors, hipStream_t st) {
+                   const MttsSamplerFloors* floors, const float* typical, hipStream_t st) {
     const int big0 = V0 > SAMP_CAND ? 1 : 0;
     if (big0) {
         hipLaunchKernelGGL(emit_lp ? sample_scan_kernel<true> : sample_scan_kernel<false>, dim3(SAMP_NS, B), dim3(SAMP_T), 0, st,
@@ -1116,8 +1380,11 @@ void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, in
                                bitmaps, bm_words, cfgs, ls, seqs, sc, full_cap, 0, 0, 0, 0);
     }
     LAUNCH_FINAL(dim3(8, B), st, logits0, logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, err, sc, big0,
-                 0, 0, 0, 0, floors);
-    if (big0 && ch0_sampled)
+                 0, 0, 0, 0, floors, typical);
+    if (big0 && ch0_sampled && typical)
+        hipLaunchKernelGGL(sample_full_typ_kernel, dim3(B), dim3(SAMP_FT), 0, st, (const uint16_t*)logits0, V0, bitmaps, bm_words, cfgs,
+                           ls, seqs, seed, decisions, sc, full_cap, emit_lp, 0, 0, 0, 0, floors, typical);
+    else if (big0 && ch0_sampled)
         hipLaunchKernelGGL(floors ? sample_full_kernel<true> : sample_full_kernel<false>, dim3(B), dim3(SAMP_FT), 0, st,
                            (const uint16_t*)logits0, V0, bitmaps, bm_words, cfgs, ls, seqs, seed, decisions, sc, full_cap, emit_lp,
                            0, 0, 0, 0, floors);
@@ -1125,7 +1392,7 @@ void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, in
 void launch_sample_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words,
                           const MttsSamplerCfg* cfgs8, int mask_id, uint64_t seed, int step, int channel,
                           int32_t* decisions, int32_t* err, const SampleScratch& sc, int full_cap, int emit_lp,
-                          const MttsSamplerFloors* floors, hipStream_t st) {
+                          const MttsSamplerFloors* floors, const float* typical, hipStream_t st) {
     if (vocab > SAMP_CAND) {
         hipLaunchKernelGGL(emit_lp ? sample_scan_kernel<true> : sample_scan_kernel<false>, dim3(SAMP_NS, rows), dim3(SAMP_T), 0, st,
                            (const uint16_t*)logits, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr,
@@ -1134,8 +1401,12 @@ void launch_sample_single(const void* logits, int rows, int vocab, const uint32_
                            bitmap, bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, sc, full_cap, vocab, mask_id, step, channel);
     }
     LAUNCH_FINAL(dim3(1, rows), st, logits, nullptr, vocab, vocab, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr,
-                 (const SeqState*)nullptr, seed, decisions, err, sc, 1, vocab, mask_id, step, channel, floors);
-    if (vocab > SAMP_CAND)
+                 (const SeqState*)nullptr, seed, decisions, err, sc, 1, vocab, mask_id, step, channel, floors, typical);
+    if (vocab > SAMP_CAND && typical)
+        hipLaunchKernelGGL(sample_full_typ_kernel, dim3(rows), dim3(SAMP_FT), 0, st, (const uint16_t*)logits, vocab, bitmap, bm_words,
+                           cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, seed, decisions, sc, full_cap, emit_lp, vocab,
+                           mask_id, step, channel, floors, typical);
+    else if (vocab > SAMP_CAND)
         hipLaunchKernelGGL(floors ? sample_full_kernel<true> : sample_full_kernel<false>, dim3(rows), dim3(SAMP_FT), 0, st,
                            (const uint16_t*)logits, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr,
                            seed, decisions, sc, full_cap, emit_lp, vocab, mask_id, step, channel, floors);

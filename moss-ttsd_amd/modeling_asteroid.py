@@ -69,6 +69,8 @@ class GenerationConfig:
         self.min_p = kw.get("min_p")
         self.epsilon_cutoff = kw.get("epsilon_cutoff", 0.0)
         self.eta_cutoff = kw.get("eta_cutoff", 0.0)
+        # HF's TypicalLogitsWarper (locally typical sampling), between min_p and epsilon_cutoff; HF's default 1.0 = none
+        self.typical_p = kw.get("typical_p", 1.0)
         # HF's hard bans (NoRepeatNGram / SuppressTokens / MinNewTokensLength processors)
         self.no_repeat_ngram_size = kw.get("no_repeat_ngram_size", 0)
         self.suppress_tokens = kw.get("suppress_tokens")
@@ -91,6 +93,8 @@ class GenerationConfig:
         _get_logits_processor adds the warper: min_p is not None, 0 < epsilon_cutoff < 1, 0 < eta_cutoff < 1.  In the
         per-channel branch they come from layers[i] -- this engine's extension of the four keys the reference reads
         there -- and the top-level values are ignored, as that branch of the reference ignores every top-level warper.
+        typical_p travels with them: HF adds its warper when typical_p is not None and < 1.0, so 1.0 (HF's default) and None
+        leave the dict as it was.
         The hard bans no_repeat_ngram_size / suppress_tokens / min_new_tokens travel the same way, with two differences:
         they are processors, so in the global branch they join the dict whatever do_sample is (the reference's
         `[logits_processor] * channels` applies them on all eight channels), and HF's conditions are n not None and > 0,
@@ -108,6 +112,10 @@ class GenerationConfig:
                 v = over[k] if over.get(k) is not None else getattr(self, k)
                 if v is not None and (k == "min_p" or 0.0 < float(v) < 1.0):
                     one[k] = v
+            v = over["typical_p"] if over.get("typical_p") is not None else self.typical_p
+            # (anything that is not 1.0 goes on and is refused where the values are checked)
+            if v is not None and (isinstance(v, bool) or v != 1.0):
+                one["typical_p"] = v
         elif self.repetition_penalty not in (None, 1.0):
             one = dict(repetition_penalty=self.repetition_penalty)
         ban = {k: (over[k] if over.get(k) is not None else getattr(self, k)) for k in ban_spec.BAN_KEYS}
@@ -492,7 +500,7 @@ class AsteroidTTSInstruct:
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,
                  num_return_sequences=None, return_dict_in_generate=False, output_scores=False, adapter_names=None,
                  top_logprobs=None, min_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None,
-                 suppress_tokens=None, min_new_tokens=None, **kw):
+                 suppress_tokens=None, min_new_tokens=None, typical_p=None, **kw):
         """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
         num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
         repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages.
@@ -506,11 +514,15 @@ class AsteroidTTSInstruct:
         decode step; it changes no token and no transition score.
         min_p / epsilon_cutoff / eta_cutoff (HF's generate keywords): override generation_config's for this call in the
         global branch; with generation_config.do_samples set the floors are per channel and belong in layers[i].
+        typical_p (HF's generate keyword; mtts/warp_spec.py): the same; 1.0 runs without it.
         no_repeat_ngram_size / suppress_tokens / min_new_tokens (HF's generate keywords): the same for the hard bans, which
         act on greedy and sampled channels alike (mtts/ban_spec.py); refused with do_samples set, like the floors."""
         over = {k: v for k, v in (("min_p", min_p), ("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)) if v is not None}
         for name, v in over.items():
             warp_spec.check_floor(name, v, "generate(): ")
+        if typical_p is not None:
+            warp_spec.check_typical(typical_p, "generate(): ")
+            over["typical_p"] = typical_p
         bans = {k: v for k, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("suppress_tokens", suppress_tokens),
                                   ("min_new_tokens", min_new_tokens)) if v is not None}
         for name, v in bans.items():
@@ -547,6 +559,7 @@ class AsteroidTTSInstruct:
         layers, do_samples = gc.channel_settings(C, **over)
         for i, lc in enumerate(layers):
             warp_spec.floors_of(lc, f"generation_config, channel {i}: ")       # a bad value: ValueError before the device is touched
+            warp_spec.typical_of(lc, f"generation_config, channel {i}: ")
             ban_spec.bans_of(lc, f"generation_config, channel {i}: ")
         if n > 1 and not any(do_samples):
             # HF GenerationMixin: greedy search returns one sequence per prompt

@@ -103,6 +103,7 @@ _SIGS = {
     "mtts_set_takes": (C.c_int32, [C.c_void_p, C.c_int32]),
     "mtts_set_sampler_floors": (C.c_int32, [C.c_void_p, C.POINTER(MttsSamplerFloors)]),
     "mtts_set_sampler_bans": (C.c_int32, [C.c_void_p, C.POINTER(MttsSamplerBans)]),
+    "mtts_set_sampler_typical": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float)]),
     "mtts_debug_ban_launches": (C.c_int64, []),
     "mtts_slot_fork": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p]),
     "mtts_slot_states": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -163,6 +164,9 @@ _SIGS = {
     "mtts_k_sample_bans": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg),
                                        C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.POINTER(MttsSamplerFloors), C.c_void_p, C.c_void_p]),
+    "mtts_k_sample_typical": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg),
+                                          C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.POINTER(MttsSamplerFloors), C.c_void_p, C.c_float, C.c_void_p]),
     "mtts_k_ngram_ban": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mtts_codec_last_error": (C.c_char_p, []),

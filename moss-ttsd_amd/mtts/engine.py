@@ -44,6 +44,20 @@ def sampler_floors(layers=None, do_samples=None):
     return arr if on else None
 
 
+def sampler_typical(layers=None, do_samples=None):
+    """typical_p of the same per-channel dicts -> float[8], or None when no sampled channel sets one (the run then launches
+    what it launched before).  Key `typical_p` (HF's TypicalLogitsWarper; mtts/warp_spec.py states the rule).  None or 1.0 =
+    absent; a greedy channel's is ignored.  ValueError, naming the channel, for anything not strictly inside (0, 1)."""
+    arr, on = (C.c_float * 8)(), False
+    for i in range(8):
+        lc = (layers[i] if layers and i < len(layers) else {}) or {}
+        t = warp_spec.typical_of(lc, f"layers[{i}]: ")
+        if do_samples and do_samples[i]:
+            arr[i] = t
+            on = on or t > 0.0
+    return arr if on else None
+
+
 def sampler_bans(layers=None):
     """The hard bans of the same per-channel dicts -> MttsSamplerBans[8], or None when no channel sets one (the run then
     launches and allocates what it did before bans existed).  Keys `no_repeat_ngram_size` (1..16), `suppress_tokens` (a
@@ -204,9 +218,11 @@ class Engine:
 
     def _set_floors_and_bans(self, layers, do_samples):
         """One-shots like takes: the floors and the hard bans of `layers` for the run that starts next, or none
-        (mtts_set_sampler_floors, mtts_set_sampler_bans).  Both are marshalled first: a bad value leaves nothing pending."""
-        floors, bans = sampler_floors(layers, do_samples), sampler_bans(layers)
+        (mtts_set_sampler_floors, mtts_set_sampler_typical, mtts_set_sampler_bans).  All are marshalled first: a bad value
+        leaves nothing pending."""
+        floors, typical, bans = sampler_floors(layers, do_samples), sampler_typical(layers, do_samples), sampler_bans(layers)
         capi.check(self.lib.mtts_set_sampler_floors(self._h, floors))
+        capi.check(self.lib.mtts_set_sampler_typical(self._h, typical))
         capi.check(self.lib.mtts_set_sampler_bans(self._h, bans))
 
     def set_output_scores(self, on):
