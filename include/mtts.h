@@ -708,6 +708,66 @@ int32_t mtts_k_gemm_f32(const float* dev_a, const float* dev_w, const float* dev
 int32_t mtts_k_gemm_planes_bench(int32_t M, int32_t N, int32_t K, int32_t flags, int32_t tile_code, int32_t iters,
                                  float* avg_us, int32_t* code_used);
 
+/* ---- unit test: the codec's kernels, one launch function of the engine each -------------------------------------
+ * All buffers are caller-owned device memory unless named host_*; scratch is allocated and freed inside; every entry
+ * returns after the stream is idle.  "Planes" are bf16 hi / lo planes in MFMA-fragment order (element (r, k) of a
+ * matrix with rows of K elements at ((r/32) 32 K + ((k/16) 64 + r%32 + 32 ((k%16)/8)) 8 + k%8); hi plane first, the lo
+ * plane pad32(rows) * K elements further, pad32(r) = r rounded up to 32).
+ *
+ * Attention of one transformer layer, head dim 64: qkv f32 [B][T][3 d], d = 64 heads; host_lens int32 [B], each 0 .. T.
+ * mode 0: S = q k^T / 8 (exact f32), masked softmax, P V in three launches; 1: the fused kernel; 2: K / V packed once,
+ * then the fused kernel on the planes.  A valid query (t < len) attends to keys < len, a padded one uniformly to all T.
+ * att: f32 [B][T][d], or with planes != 0 (modes 1, 2) planes of B T rows x d, in a buffer of pad32(B T) d floats. */
+int32_t mtts_k_codec_attn(const float* dev_qkv, const int32_t* host_lens, float* dev_att, int32_t B, int32_t T, int32_t heads,
+                          int32_t mode, int32_t planes, void* stream);
+/* The pre-split bf16x3 GEMM (gemm_b3t_kernel) through the engine's argument builder: rows row0 .. row0 + M - 1 of
+ * C = epi(A W^T).  A f32 [R][K] and W f32 [N][K] are split and packed here, R = plane_rows, or M when plane_rows = 0
+ * (then row0 = 0).  flags: 1 GELU | 2 * gamma | 4 + residual | 8 plane output, one of 0, 4, 6, 9, with gamma / res null
+ * exactly when their flag is clear; epilogue order + bias (may be null), GELU, * gamma, + res.  C and res: f32 [R][ldc];
+ * with flag 8 C holds planes of R rows x N.  Needs K % 64 = 0, N % 4 = 0, row0 % 32 = 0, plane_rows >= row0 + M,
+ * ldc % 4 = 0, ldc >= N, and for plane output ldc = N, N % 16 = 0.  tile: 0 = the production choice, else NA NB U OCC
+ * as decimal digits; nt_out: nontemporal stores of the GELU planes, as MTTS_CODEC_NT_OUT. */
+int32_t mtts_k_codec_gemm_planes(const float* dev_a, const float* dev_w, const float* dev_bias, const float* dev_gamma,
+                                 const float* dev_res, float* dev_c, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t flags,
+                                 int32_t tile, int32_t row0, int32_t plane_rows, int32_t nt_out, void* stream);
+/* The fused Vocos pointwise pair: h[M][512] += gamma * (W2 GELU(W1 xn + b1) + b2), xn f32 [M][512], W1 [4096][512],
+ * W2 [512][4096]; xn and both weights are split and packed here (W2 in the kernel's permuted K order). */
+int32_t mtts_k_codec_vocos_pw(const float* dev_xn, const float* dev_w1, const float* dev_b1, const float* dev_w2,
+                              const float* dev_b2, const float* dev_gamma, float* dev_h, int32_t M, void* stream);
+/* layernorm_kernel: y[r][0..C) = LN(x[r]) w + b over C <= 1024 channels, row stride ldy >= C.  host_lens (may be null):
+ * int32 [rows / T]; row r with r % T >= lens[r / T] is written as zeros.  planes != 0: planes of rows x C instead of
+ * fp32 (ldy = C, C % 16 = 0), in a buffer of pad32(rows) C floats. */
+int32_t mtts_k_codec_layernorm(const float* dev_x, const float* dev_w, const float* dev_b, float* dev_y, int32_t rows, int32_t C,
+                               float eps, const int32_t* host_lens, int32_t T, int32_t ldy, int32_t planes, void* stream);
+/* layernorm_wide_kernel: one block per row, any C; y f32 [rows][C]. */
+int32_t mtts_k_codec_layernorm_wide(const float* dev_x, const float* dev_w, const float* dev_b, float* dev_y, int32_t rows,
+                                    int32_t C, float eps, void* stream);
+/* Depthwise Conv1d(k = 7, pad 3) per window + bias + LayerNorm: h f32 [B][T][C], dw [7][C].  kernel: 0 = the kernel
+ * for any C <= 1024, 4 / 8 = the C = 512 kernel with that many rows per wave.  y: f32 [B T][C], or with planes != 0
+ * planes of B T rows x C (C % 16 = 0) in a buffer of pad32(B T) C floats. */
+int32_t mtts_k_codec_dwconv_ln(const float* dev_h, const float* dev_dw, const float* dev_dwb, const float* dev_lw,
+                               const float* dev_lb, float* dev_y, int32_t B, int32_t T, int32_t C, float eps, int32_t kernel,
+                               int32_t planes, void* stream);
+/* softmax_mask_kernel in place on S f32 [B][heads][T][ldT], ldT % 16 = 0, ldT >= T: masking as mtts_k_codec_attn,
+ * columns T .. ldT - 1 are written as zeros.  The kernel takes its loop branch when ldT > 2048. */
+int32_t mtts_k_codec_softmax_mask(float* dev_s, const int32_t* host_lens, int32_t B, int32_t heads, int32_t T, int32_t ldT,
+                                  void* stream);
+/* One RVQ stage of the encoder: per row (b, t) with t < lens[b], code = argmin_j (|r|^2 - 2 dot[row][j]) + cc[j], first
+ * index on ties, and residual[row] -= cb[code]; other rows keep their residual and get the code of dot = |r|^2 = 0.
+ * dot f32 [B T][K], cb [K][D], cc [K], residual [B T][D] (in / out), codes int64 [B T] (out). */
+int32_t mtts_k_codec_vq_argmin_update(const float* dev_dot, const float* dev_cb, const float* dev_cc, float* dev_residual,
+                                      int64_t* dev_codes, const int32_t* host_lens, int32_t B, int32_t T, int32_t K, int32_t D,
+                                      void* stream);
+/* The exact-f32 GEMM in its general form: for z < batch, zo = z / batch_inner, zi = z % batch_inner,
+ * C_z[m][n] = ((sum_k A_z[m][k] W_z[..]) + bias[n]) * scale -> GELU(erf) if act -> * gamma[n] -> + res[m' ][n], with
+ * W_z[n][k] (b_kn = 0) or W_z[k][n] (b_kn = 1), m' = m % res_rows (res_rows = 0: m), X_z = X + zo s_o + zi s_i and
+ * host strides = {sAo, sAi, sWo, sWi, sCo, sCi}.  bias, gamma, res may be null.  lda, ldw and the A / W strides must be
+ * multiples of 4 (16-byte loads). */
+int32_t mtts_k_codec_gemm_f32_ex(const float* dev_a, const float* dev_w, float* dev_c, const float* dev_bias,
+                                 const float* dev_gamma, const float* dev_res, int32_t M, int32_t N, int32_t K, int32_t b_kn,
+                                 int64_t lda, int64_t ldw, int64_t ldc, int64_t ldres, int32_t res_rows, int32_t act, float scale,
+                                 int32_t batch, int32_t batch_inner, const int64_t* host_strides, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

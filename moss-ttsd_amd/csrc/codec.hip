@@ -1005,6 +1005,55 @@ __global__ __launch_bounds__(256) void vq_argmin_update_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------
+// Launch code of the row kernels and of the three-launch attention: one copy, called by the engine below and by the
+// unit-test entries at the end of this file.
+// ------------------------------------------------------------------------------------
+static void launch_layernorm(hipStream_t st, const float* x, const float* w, const float* b, float* y, int rows, int C, float eps,
+                             const int* lens, int T, long ldy, uint16_t* ylo = nullptr) {
+    hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, w, b, y, rows, C, eps, lens, T, ldy, ylo);
+}
+static void launch_layernorm_wide(hipStream_t st, const float* x, const float* w, const float* b, float* y, int rows, int C, float eps) {
+    hipLaunchKernelGGL(layernorm_wide_kernel, dim3(rows), dim3(256), 0, st, x, w, b, y, C, eps);
+}
+static void launch_softmax_mask(hipStream_t st, float* S, const int* d_lens, int B, int heads, int T, int ldT) {
+    hipLaunchKernelGGL(softmax_mask_kernel, dim3((unsigned)(((long)B * heads * T + 3) / 4)), dim3(256), 0, st, S, d_lens, heads, T,
+                       ldT, (long)B * heads * T);
+}
+// depthwise conv + LayerNorm of a Vocos block.  wide512: the C = 512 kernel, `dw_rows` rows per wave (4, else 8);
+// ylo != null: fragment-packed hi / lo planes (hi plane at y) instead of fp32
+static void launch_dwconv_ln(hipStream_t st, bool wide512, int dw_rows, const float* h, const float* dw, const float* dwb,
+                             const float* lw, const float* lb, float* y, int B, int T, int C, float eps, uint16_t* ylo) {
+    const int rows = B * T;
+    if (wide512)
+        if (dw_rows == 4)
+            hipLaunchKernelGGL(dwconv_ln512_kernel<4>, dim3((rows + 15) / 16), dim3(256), 0, st, h, dw, dwb, lw, lb, y, B, T, eps, ylo);
+        else
+            hipLaunchKernelGGL(dwconv_ln512_kernel<8>, dim3((rows + 31) / 32), dim3(256), 0, st, h, dw, dwb, lw, lb, y, B, T, eps, ylo);
+    else
+        hipLaunchKernelGGL(dwconv_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, h, dw, dwb, lw, lb, y, B, T, C, eps, ylo);
+}
+static void launch_vq_argmin_update(hipStream_t st, const float* dot, const float* cb, const float* cc, float* residual,
+                                    int64_t* codes, const int* d_lens, int rows, int T, int K, int D) {
+    hipLaunchKernelGGL(vq_argmin_update_kernel, dim3(rows), dim3(256), 0, st, dot, cb, cc, residual, codes, d_lens, T, K, D);
+}
+// Attention of one layer in three launches on qkv [B][T][3d] (exact f32): S[b,h] = (q k^T) * hd^-0.5 (the reference scales
+// q before the product, modules.py:131) into `scores` [B][heads][T][ldT], masked softmax in place, O[b,:,h] = P[b,h] V[b,:,h]
+static void launch_attn3(hipStream_t st, const float* qkv, float* scores, float* att, const int* d_lens, int B, int T, int d,
+                         int heads) {
+    const int hd = d / heads, ldT = (T + 15) / 16 * 16;
+    gemm_f32(st, false, qkv, qkv + d, scores, T, T, hd, 3 * d, 3 * d, ldT, nullptr, 0, nullptr, nullptr, 0, 0,
+             1.0f / sqrtf((float)hd), B * heads, heads, (long)T * 3 * d, hd, (long)T * 3 * d, hd, (long)heads * T * ldT,
+             (long)T * ldT);
+    launch_softmax_mask(st, scores, d_lens, B, heads, T, ldT);
+    gemm_f32(st, true, scores, qkv + 2 * d, att, T, hd, T, ldT, 3 * d, d, nullptr, 0, nullptr, nullptr, 0, 0, 1.f,
+             B * heads, heads, (long)heads * T * ldT, (long)T * ldT, (long)T * 3 * d, hd, (long)T * d, hd);
+}
+static void launch_split_pack_w(hipStream_t st, const float* w, uint16_t* hi, uint16_t* lo, int N, int K) {
+    const long n = (long)N * K;
+    hipLaunchKernelGGL(split_pack_w_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, hi, lo, N, K);
+}
+
+// ------------------------------------------------------------------------------------
 // Host object
 // ------------------------------------------------------------------------------------
 static thread_local char g_cerr[512] = "";
@@ -1195,8 +1244,7 @@ static int weight_planes(MttsCodec* k, hipStream_t st, const float* W, int N, in
     const long wn = pad32(N) * (long)K;
     CHK(hipMalloc((void**)&wp, (size_t)wn * 4));
     CHK(hipMemsetAsync(wp, 0, (size_t)wn * 4, st));
-    const long n = (long)N * K;
-    hipLaunchKernelGGL(split_pack_w_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W, wp, wp + wn, N, K);
+    launch_split_pack_w(st, W, wp, wp + wn, N, K);
     CHK(hipStreamSynchronize(st));           // once per weight: later calls may come in on another stream
     k->wplanes[W] = wp;
     *out = wp;
@@ -1228,28 +1276,36 @@ static bool fused_pw_pays(long rows, long setting) {
 }
 // `row0` / `plane_rows`: rows row0 .. row0 + M - 1 of operands whose planes were laid out for `plane_rows` rows (row0 a
 // multiple of 32: a whole number of fragment tiles; 0 / 0 = all of them): the part of a Vocos call the fused kernel leaves.
-static int gemm_planes(MttsCodec* k, hipStream_t st, const float* a_planes, long a_rows, const float* W, float* C, int M, int N,
-                       int K, long lda, long ldc, const float* bias, int act, const float* gamma, const float* res, long ldres,
-                       bool c_planes, long c_rows, long row0 = 0, long plane_rows = 0) {
-    (void)a_rows; (void)c_rows; (void)lda;
+// The launch on operands that are all planes already (`wp`: the weight's hi plane, lo plane pad32(N) * K further): checks,
+// the operand / row0 / plane_rows addresses, the tile choice (tile 0 = b3t_choose) and the nontemporal-store choice.
+static int gemm_planes_launch(hipStream_t st, const float* a_planes, const uint16_t* wp, float* C, int M, int N, int K, long ldc,
+                              const float* bias, int act, const float* gamma, const float* res, long ldres, bool c_planes,
+                              long row0, long plane_rows, int nt_out, int tile) {
     if (!plane_rows) plane_rows = M;
     if (row0 % 32) return cfail(MTTS_EINVAL, "gemm_planes: row0 must be a multiple of 32");
     if (N % 4) return cfail(MTTS_EINVAL, "gemm_planes: N must be a multiple of 4");
     const int combo = (act == 1) | (gamma ? 2 : 0) | (res ? 4 : 0) | (c_planes ? 8 : 0);          // the kernel's epilogues
     if (combo != 0 && combo != 4 && combo != 6 && combo != 9) return cfail(MTTS_EINVAL, "gemm_planes: no epilogue for flag combination %d", combo);
-    uint16_t* wp = nullptr;
     const long wn = pad32(N) * (long)K;                      // elements per weight plane
-    TRYC(weight_planes(k, st, W, N, K, &wp));
     // activation planes: hi plane first, lo plane pad32(M) rows further (both in fragment order, K = row length)
     const uint16_t* ah = (const uint16_t*)a_planes + row0 * K;
     uint16_t* ch = c_planes ? (uint16_t*)C + row0 * ldc : nullptr;
     GemmF32Args g{nullptr, nullptr, c_planes ? C : C + row0 * ldc, bias, gamma, res ? res + row0 * ldres : nullptr, M, N, K, (long)K, (long)K, ldc, ldres,
                   0, 1.f, act, 1, 0, 0, 0, 0, 0, 0,
                   ah, ah + pad32(plane_rows) * K, wp, wp + wn, ch, c_planes ? ch + pad32(plane_rows) * ldc : nullptr};
-    int code = k->tile ? k->tile : b3t_choose(M, N, K, act);
-    if (k->nt_out && combo == 9) g.batch_inner = 2;
+    int code = tile ? tile : b3t_choose(M, N, K, act);
+    if (nt_out && combo == 9) g.batch_inner = 2;
     TRYC(b3t_launch(st, g, code));
     return 0;
+}
+static int gemm_planes(MttsCodec* k, hipStream_t st, const float* a_planes, long a_rows, const float* W, float* C, int M, int N,
+                       int K, long lda, long ldc, const float* bias, int act, const float* gamma, const float* res, long ldres,
+                       bool c_planes, long c_rows, long row0 = 0, long plane_rows = 0) {
+    (void)a_rows; (void)c_rows; (void)lda;
+    uint16_t* wp = nullptr;
+    TRYC(weight_planes(k, st, W, N, K, &wp));
+    return gemm_planes_launch(st, a_planes, wp, C, M, N, K, ldc, bias, act, gamma, res, ldres, c_planes, row0, plane_rows, k->nt_out,
+                              k->tile);
 }
 
 static int ensure_workspace(MttsCodec* k, int B, int T) {
@@ -1639,26 +1695,25 @@ __global__ __launch_bounds__(256, 2) void codec_attn_packed_kernel(const float* 
 }
 
 // fused attention of one layer: K / V packed once into the (otherwise unused) score buffer, then the packed kernel
-static void launch_codec_attn(MttsCodec* k, hipStream_t st, const float* qkv, float* att, const int* d_lens, int B, int T, int d,
-                              int heads, uint16_t* att_lo) {
+static void launch_codec_attn(hipStream_t st, bool packed, float* scratch, const float* qkv, float* att, const int* d_lens, int B,
+                              int T, int d, int heads, uint16_t* att_lo) {
     const float scale = 1.0f / sqrtf(64.f);
-    if (!k->attn_packed) {
+    if (!packed) {
         hipLaunchKernelGGL(codec_attn_kernel, dim3((T + 127) / 128, heads, B), dim3(256), 0, st, qkv, att, d_lens, T, d, scale, att_lo);
         return;
     }
     const int tiles = (T + 31) / 32;
     const size_t plane = (size_t)B * heads * tiles * 2048;               // 4 planes x 2 B <= B heads T ldT x 4 B of k->scores
-    hipLaunchKernelGGL(attn_pack_kv_kernel, dim3(tiles, heads, B), dim3(64), 0, st, qkv, (uint16_t*)k->scores, plane, T, d, tiles);
+    hipLaunchKernelGGL(attn_pack_kv_kernel, dim3(tiles, heads, B), dim3(64), 0, st, qkv, (uint16_t*)scratch, plane, T, d, tiles);
     const int nqb = (T + 127) / 128, groups = B * heads;
     hipLaunchKernelGGL(codec_attn_packed_kernel, dim3((unsigned)(((groups + 7) / 8) * 8 * nqb)), dim3(256), 0, st, qkv,
-                       (const uint16_t*)k->scores, plane, tiles, att, d_lens, T, d, scale, att_lo, heads, nqb, groups);
+                       (const uint16_t*)scratch, plane, tiles, att, d_lens, T, d, scale, att_lo, heads, nqb, groups);
 }
 
 // One pre-LN transformer layer (OmniWhisperTransformerLayer, modules.py:187-205) on x [B*T][d].
 static int transformer_layer(MttsCodec* k, hipStream_t st, const std::string& p, float* x, float* tmp, float* qkv, float* att,
                              int B, int T, int d, int heads, int ffn, const int* d_lens) {
     const int rows = B * T, hd = d / heads;
-    const int ldT = (T + 15) / 16 * 16;
     NEED(ln1w, p + "ln1.w", d); NEED(ln1b, p + "ln1.b", d);
     NEED(wqkv, p + "qkv.w", (size_t)3 * d * d); NEED(bqkv, p + "qkv.b", 3 * d);
     NEED(wo, p + "o.w", (size_t)d * d); NEED(bo, p + "o.b", d);
@@ -1669,41 +1724,33 @@ static int transformer_layer(MttsCodec* k, hipStream_t st, const std::string& p,
         // decode direction, pre-split operands: every activation that only feeds a GEMM is written as bf16 hi / lo planes
         // by its producer (same buffers: hi plane first, lo plane `rows` rows further), weights are split once
         uint16_t* tlo = (uint16_t*)tmp + pad32(rows) * d;
-        hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, ln1w, ln1b, tmp, rows, d, 1e-5f,
+        launch_layernorm(st, x, ln1w, ln1b, tmp, rows, d, 1e-5f,
                            (const int*)nullptr, T, (long)d, tlo);
         TRYC(gemm_planes(k, st, tmp, rows, wqkv, qkv, rows, 3 * d, d, d, 3 * d, bqkv, 0, nullptr, nullptr, 0, false, 0));
-        launch_codec_attn(k, st, qkv, att, d_lens, B, T, d, heads, (uint16_t*)att + pad32(rows) * d);
+        launch_codec_attn(st, k->attn_packed, k->scores, qkv, att, d_lens, B, T, d, heads, (uint16_t*)att + pad32(rows) * d);
         TRYC(gemm_planes(k, st, att, rows, wo, x, rows, d, d, d, d, bo, 0, nullptr, x, d, false, 0));      // x += out_proj(att)
-        hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, ln2w, ln2b, tmp, rows, d, 1e-5f,
+        launch_layernorm(st, x, ln2w, ln2b, tmp, rows, d, 1e-5f,
                            (const int*)nullptr, T, (long)d, tlo);
         TRYC(gemm_planes(k, st, tmp, rows, w1, k->big, rows, ffn, d, d, ffn, b1, 1, nullptr, nullptr, 0, true, rows));
         TRYC(gemm_planes(k, st, k->big, rows, w2, x, rows, d, ffn, ffn, d, b2, 0, nullptr, x, d, false, 0));  // x += fc2(gelu(fc1))
         return 0;
     }
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, ln1w, ln1b, tmp, rows, d, 1e-5f,
+    launch_layernorm(st, x, ln1w, ln1b, tmp, rows, d, 1e-5f,
                        (const int*)nullptr, T, (long)d);
     gemm_f32(st, false, tmp, wqkv, qkv, rows, 3 * d, d, d, d, 3 * d, bqkv);
     if (g_gemm_split && hd == 64) {
         // decode direction: one fused launch, the score matrix stays on chip
-        launch_codec_attn(k, st, qkv, att, d_lens, B, T, d, heads, nullptr);
+        launch_codec_attn(st, k->attn_packed, k->scores, qkv, att, d_lens, B, T, d, heads, nullptr);
         gemm_f32(st, false, att, wo, x, rows, d, d, d, d, d, bo, 0, nullptr, x, d);          // x += out_proj(att)
-        hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, ln2w, ln2b, tmp, rows, d, 1e-5f,
+        launch_layernorm(st, x, ln2w, ln2b, tmp, rows, d, 1e-5f,
                            (const int*)nullptr, T, (long)d);
         gemm_f32(st, false, tmp, w1, k->big, rows, ffn, d, d, d, ffn, b1, 1);
         gemm_f32(st, false, k->big, w2, x, rows, d, ffn, ffn, ffn, d, b2, 0, nullptr, x, d);  // x += fc2(gelu(fc1))
         return 0;
     }
-    // S[b,h] = (q k^T) * hd^-0.5   (the reference scales q before the product, modules.py:131)
-    gemm_f32(st, false, qkv, qkv + d, k->scores, T, T, hd, 3 * d, 3 * d, ldT, nullptr, 0, nullptr, nullptr, 0, 0,
-             1.0f / sqrtf((float)hd), B * heads, heads, (long)T * 3 * d, hd, (long)T * 3 * d, hd, (long)heads * T * ldT,
-             (long)T * ldT);
-    hipLaunchKernelGGL(softmax_mask_kernel, dim3((unsigned)(((long)B * heads * T + 3) / 4)), dim3(256), 0, st, k->scores,
-                       d_lens, heads, T, ldT, (long)B * heads * T);
-    // O[b,:,h] = P[b,h] V[b,:,h]
-    gemm_f32(st, true, k->scores, qkv + 2 * d, att, T, hd, T, ldT, 3 * d, d, nullptr, 0, nullptr, nullptr, 0, 0, 1.f,
-             B * heads, heads, (long)heads * T * ldT, (long)T * ldT, (long)T * 3 * d, hd, (long)T * d, hd);
+    launch_attn3(st, qkv, k->scores, att, d_lens, B, T, d, heads);
     gemm_f32(st, false, att, wo, x, rows, d, d, d, d, d, bo, 0, nullptr, x, d);          // x += out_proj(att)
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, ln2w, ln2b, tmp, rows, d, 1e-5f,
+    launch_layernorm(st, x, ln2w, ln2b, tmp, rows, d, 1e-5f,
                        (const int*)nullptr, T, (long)d);
     gemm_f32(st, false, tmp, w1, k->big, rows, ffn, d, d, d, ffn, b1, 1);
     gemm_f32(st, false, k->big, w2, x, rows, d, ffn, ffn, ffn, d, b2, 0, nullptr, x, d);  // x += fc2(gelu(fc1))
@@ -1795,7 +1842,7 @@ static int detokenize_async(MttsCodec* k, const int64_t* dev_codes, const int32_
     }
     NEED(aln_w, "adapter.ln.w", da); NEED(aln_b, "adapter.ln.b", da);
     NEED(ao_w, "adapter.out.w", (size_t)Q * da); NEED(ao_b, "adapter.out.b", Q);
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, A, aln_w, aln_b, Cc, rows, da, 1e-5f,
+    launch_layernorm(st, A, aln_w, aln_b, Cc, rows, da, 1e-5f,
                        (const int*)k->d_lens, T, (long)da);
     gemm_f32(st, false, Cc, ao_w, Bb, rows, Q, da, da, da, Q, ao_b);
     // C3: upsample ConvTranspose1d(k = s = up): GEMM to [rows][up*dd] == token-major [rows*up][dd]
@@ -1812,7 +1859,7 @@ static int detokenize_async(MttsCodec* k, const int64_t* dev_codes, const int32_
         if (r) return r;
     }
     NEED(dln_w, "dec.ln.w", dd); NEED(dln_b, "dec.ln.b", dd);
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows4 + 3) / 4), dim3(256), 0, st, A, dln_w, dln_b, Cc, rows4, dd, 1e-5f,
+    launch_layernorm(st, A, dln_w, dln_b, Cc, rows4, dd, 1e-5f,
                        (const int*)k->d_lens4, T4, (long)dd);
     NEED(dc1_w, "dec.deconv1.w", (size_t)3 * dd * dd); NEED(dc1_b, "dec.deconv1.b", dd);
     NEED(dc2_w, "dec.deconv2.w", (size_t)3 * c.mel_bins * dd); NEED(dc2_b, "dec.deconv2.b", c.mel_bins);
@@ -1827,7 +1874,7 @@ static int detokenize_async(MttsCodec* k, const int64_t* dev_codes, const int32_
     NEED(vn_w, "voc.norm.w", vd); NEED(vn_b, "voc.norm.b", vd);
     hipLaunchKernelGGL(im2col7_kernel, dim3(T8, B), dim3(256), 0, st, Cc, Bb, T8, mel);
     gemm_f32(st, false, Bb, ve_w, D, rows8, vd, 7 * mel, 7 * mel, 7 * mel, vd, ve_b);
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows8 + 3) / 4), dim3(256), 0, st, D, vn_w, vn_b, A, rows8, vd, 1e-6f,
+    launch_layernorm(st, D, vn_w, vn_b, A, rows8, vd, 1e-6f,
                        (const int*)nullptr, T8, (long)vd);
     for (int n = 0; n < c.voc_layers; ++n) {
         const std::string p = "voc.blocks." + std::to_string(n) + ".";
@@ -1837,16 +1884,7 @@ static int detokenize_async(MttsCodec* k, const int64_t* dev_codes, const int32_
         NEED(p2_w, p + "pw2.w", (size_t)vd * vi); NEED(p2_b, p + "pw2.b", vd);
         NEED(gam, p + "gamma", vd);
         if (planes_ok(k, vd, vd) && planes_ok(k, vi, vi)) {
-            if (vd == 512)
-                if (k->dw_rows == 4)
-                    hipLaunchKernelGGL(dwconv_ln512_kernel<4>, dim3((rows8 + 15) / 16), dim3(256), 0, st, A, dw_w, dw_b, ln_w, ln_b, Cc, B, T8,
-                                       1e-6f, (uint16_t*)Cc + pad32(rows8) * vd);
-                else
-                    hipLaunchKernelGGL(dwconv_ln512_kernel<8>, dim3((rows8 + 31) / 32), dim3(256), 0, st, A, dw_w, dw_b, ln_w, ln_b, Cc, B, T8,
-                                       1e-6f, (uint16_t*)Cc + pad32(rows8) * vd);
-            else
-                hipLaunchKernelGGL(dwconv_ln_kernel, dim3((rows8 + 3) / 4), dim3(256), 0, st, A, dw_w, dw_b, ln_w, ln_b, Cc, B, T8,
-                                   vd, 1e-6f, (uint16_t*)Cc + pad32(rows8) * vd);
+            launch_dwconv_ln(st, vd == 512, k->dw_rows, A, dw_w, dw_b, ln_w, ln_b, Cc, B, T8, vd, 1e-6f, (uint16_t*)Cc + pad32(rows8) * vd);
             if (vd == 512 && vi == 4096 && k->fused_pw_rows != 0) {
                 // pw1 -> GELU -> pw2 in one launch: the 4096-wide intermediate stays on the CU.  Either the whole call, or
                 // (auto) its full rounds of 256 blocks with the last, partial round left to the two launches below.
@@ -1869,13 +1907,12 @@ static int detokenize_async(MttsCodec* k, const int64_t* dev_codes, const int32_
             TRYC(gemm_planes(k, st, k->big, rows8, p2_w, A, rows8, vd, vi, vi, vd, p2_b, 0, gam, A, vd, false, 0));   // h += gamma * pw2(..)
             continue;
         }
-        hipLaunchKernelGGL(dwconv_ln_kernel, dim3((rows8 + 3) / 4), dim3(256), 0, st, A, dw_w, dw_b, ln_w, ln_b, Cc, B, T8,
-                           vd, 1e-6f);
+        launch_dwconv_ln(st, false, k->dw_rows, A, dw_w, dw_b, ln_w, ln_b, Cc, B, T8, vd, 1e-6f, nullptr);
         gemm_f32(st, false, Cc, p1_w, k->big, rows8, vi, vd, vd, vd, vi, p1_b, 1);
         gemm_f32(st, false, k->big, p2_w, A, rows8, vd, vi, vi, vi, vd, p2_b, 0, gam, A, vd);   // h += gamma * pw2(..)
     }
     NEED(fl_w, "voc.final_ln.w", vd); NEED(fl_b, "voc.final_ln.b", vd);
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows8 + 3) / 4), dim3(256), 0, st, A, fl_w, fl_b, Cc, rows8, vd, 1e-6f,
+    launch_layernorm(st, A, fl_w, fl_b, Cc, rows8, vd, 1e-6f,
                        (const int*)nullptr, T8, (long)vd);
     // C6: ISTFT head
     const int nfft = c.n_fft, nb = nfft / 2 + 1, ldsp = (2 * nb + 15) / 16 * 16;
@@ -1961,7 +1998,7 @@ extern "C" int32_t mtts_codec_tokenize(MttsCodec* k, const float* dev_wav, const
         int r = run_audio_encoder(k, st, "sem.", B, A, Bb, Cc, D);
         if (r) return r;
         NEED(lw, "sem.ln.w", d); NEED(lb, "sem.ln.b", d);
-        hipLaunchKernelGGL(layernorm_kernel, dim3((rows2 + 3) / 4), dim3(256), 0, st, A, lw, lb, Cc, rows2, d, 1e-5f,
+        launch_layernorm(st, A, lw, lb, Cc, rows2, d, 1e-5f,
                            (const int*)k->d_lens2, T2, (long)d);
         hipLaunchKernelGGL(add_pe_kernel, dim3((unsigned)(((long)rows2 * d + 255) / 256)), dim3(256), 0, st, Cc, pe,
                            (long)rows2 * d, T2, d);
@@ -1971,7 +2008,7 @@ extern "C" int32_t mtts_codec_tokenize(MttsCodec* k, const float* dev_wav, const
             if (r) return r;
         }
         NEED(aw, "semad.ln.w", d); NEED(ab, "semad.ln.b", d);
-        hipLaunchKernelGGL(layernorm_kernel, dim3((rows2 + 3) / 4), dim3(256), 0, st, Cc, aw, ab, E, rows2, d, 1e-5f,
+        launch_layernorm(st, Cc, aw, ab, E, rows2, d, 1e-5f,
                            (const int*)k->d_lens2, T2, (long)2 * d);
     }
     // acoustic encoder -> E[:, d:2d]
@@ -1979,7 +2016,7 @@ extern "C" int32_t mtts_codec_tokenize(MttsCodec* k, const float* dev_wav, const
         int r = run_audio_encoder(k, st, "aco.", B, A, Bb, Cc, D);
         if (r) return r;
         NEED(lw, "aco.ln.w", d); NEED(lb, "aco.ln.b", d);
-        hipLaunchKernelGGL(layernorm_kernel, dim3((rows2 + 3) / 4), dim3(256), 0, st, A, lw, lb, E + d, rows2, d, 1e-5f,
+        launch_layernorm(st, A, lw, lb, E + d, rows2, d, 1e-5f,
                            (const int*)k->d_lens2, T2, (long)2 * d);
     }
     // pre_rvq_adapter
@@ -1992,7 +2029,7 @@ extern "C" int32_t mtts_codec_tokenize(MttsCodec* k, const float* dev_wav, const
             if (r) return r;
         }
         NEED(lw, "prervq.ln.w", d); NEED(lb, "prervq.ln.b", d);
-        hipLaunchKernelGGL(layernorm_kernel, dim3((rows2 + 3) / 4), dim3(256), 0, st, A, lw, lb, Cc, rows2, d, 1e-5f,
+        launch_layernorm(st, A, lw, lb, Cc, rows2, d, 1e-5f,
                            (const int*)k->d_lens2, T2, (long)d);
     }
     // ResidualDownConv (modules.py:452-477): rows of P consecutive frames
@@ -2005,7 +2042,7 @@ extern "C" int32_t mtts_codec_tokenize(MttsCodec* k, const float* dev_wav, const
         hipLaunchKernelGGL(silu_mul_kernel, dim3((unsigned)(((long)rows4 * di + 255) / 256)), dim3(256), 0, st, A, Bb,
                            (long)rows4 * di);
         gemm_f32(st, false, A, dw, D, rows4, di, di, di, di, di, nullptr, 0, nullptr, Cc, di);
-        hipLaunchKernelGGL(layernorm_wide_kernel, dim3(rows4), dim3(256), 0, st, D, lw, lb, A, di, 1e-5f);
+        launch_layernorm_wide(st, D, lw, lb, A, rows4, di, 1e-5f);
     }
     // ResidualVQ.forward, eval branch
     {
@@ -2016,8 +2053,7 @@ extern "C" int32_t mtts_codec_tokenize(MttsCodec* k, const float* dev_wav, const
             NEED(cb, "rvq.codebook." + std::to_string(q), (size_t)K * R);
             NEED(cc, "rvq.cc." + std::to_string(q), K);
             gemm_f32(st, false, Bb, cb, Cc, rows4, K, R, R, R, K);
-            hipLaunchKernelGGL(vq_argmin_update_kernel, dim3(rows4), dim3(256), 0, st, Cc, cb, cc, Bb,
-                               dev_codes + (long)q * rows4, (const int*)k->d_lens4, Tc, K, R);
+            launch_vq_argmin_update(st, Cc, cb, cc, Bb, dev_codes + (long)q * rows4, (const int*)k->d_lens4, rows4, Tc, K, R);
         }
     }
     CHK(hipGetLastError());
@@ -2047,8 +2083,8 @@ extern "C" int32_t mtts_k_gemm_planes_bench(int32_t M, int32_t N, int32_t K, int
     CHK(hipMemset(ap, 0, (size_t)Mp * K * 4)); CHK(hipMemset(wp, 0, (size_t)Np * K * 4));
     auto fill = [&](float* p, long n, unsigned seed, float sc) { hipLaunchKernelGGL(fill_lcg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, p, n, seed, sc); };
     fill(a32, (long)M * K, 1u, 1.0f); fill(w32, (long)N * K, 2u, 0.05f); fill(vecs, 2L * N, 3u, 1.0f); fill(res, (long)M * N, 4u, 1.0f);
-    hipLaunchKernelGGL(split_pack_w_kernel, dim3((unsigned)(((long)M * K + 255) / 256)), dim3(256), 0, nullptr, a32, ap, ap + Mp * K, M, K);
-    hipLaunchKernelGGL(split_pack_w_kernel, dim3((unsigned)(((long)N * K + 255) / 256)), dim3(256), 0, nullptr, w32, wp, wp + Np * K, N, K);
+    launch_split_pack_w(nullptr, a32, ap, ap + Mp * K, M, K);
+    launch_split_pack_w(nullptr, w32, wp, wp + Np * K, N, K);
     const bool planes = flags & 8;
     GemmF32Args g{nullptr, nullptr, c, vecs, (flags & 2) ? vecs + N : nullptr, (flags & 4) ? res : nullptr, M, N, K, (long)K, (long)K, (long)N,
                   (long)N, 0, 1.f, flags & 1, 1, 0, 0, 0, 0, 0, 0, ap, ap + Mp * K, wp, wp + Np * K,
@@ -2080,5 +2116,172 @@ extern "C" int32_t mtts_k_gemm_f32(const float* A, const float* W, const float* 
     gemm_f32((hipStream_t)stream, false, A, W, C, M, N, K, K, K, N, bias, act & 0xff);
     g_gemm_split = 0;
     CHK(hipGetLastError());
+    return MTTS_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Unit-test entries (mtts.h: mtts_k_codec_*): one launch function of the engine each, on caller-owned device buffers.
+// Scratch is allocated and freed here; every entry synchronises the stream before it returns.
+// ------------------------------------------------------------------------------------
+struct KScratch {                       // device allocations of one entry, freed on every return path
+    std::vector<void*> p;
+    ~KScratch() { for (void* q : p) hipFree(q); }
+    int get(void** out, size_t bytes) {
+        CHK(hipMalloc(out, bytes ? bytes : 4));
+        p.push_back(*out);
+        return 0;
+    }
+};
+static int k_lens(KScratch& s, const int32_t* host_lens, int B, int T, int** out) {
+    for (int b = 0; b < B; ++b)
+        if (host_lens[b] < 0 || host_lens[b] > T) return cfail(MTTS_EINVAL, "length %d out of range", host_lens[b]);
+    TRYC(s.get((void**)out, (size_t)B * 4));
+    CHK(hipMemcpy(*out, host_lens, (size_t)B * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+// fp32 [R][K] -> zeroed fragment-packed planes (hi plane, lo plane pad32(R) * K elements further)
+static int k_planes(KScratch& s, hipStream_t st, const float* x, int R, int K, uint16_t** out) {
+    const size_t n = (size_t)pad32(R) * K;
+    TRYC(s.get((void**)out, n * 4));
+    CHK(hipMemsetAsync(*out, 0, n * 4, st));
+    launch_split_pack_w(st, x, *out, *out + n, R, K);
+    return 0;
+}
+
+extern "C" int32_t mtts_k_codec_attn(const float* qkv, const int32_t* host_lens, float* att, int32_t B, int32_t T, int32_t heads,
+                                     int32_t mode, int32_t planes, void* stream) {
+    if (!qkv || !host_lens || !att || B < 1 || T < 1 || heads < 1) return cfail(MTTS_EINVAL, "codec_attn: bad argument");
+    if (mode < 0 || mode > 2) return cfail(MTTS_EINVAL, "codec_attn: mode %d (0 three launches, 1 fused, 2 fused on packed K / V)", mode);
+    if (planes && mode == 0) return cfail(MTTS_EINVAL, "codec_attn: the three-launch form writes fp32 only");
+    hipStream_t st = (hipStream_t)stream;
+    KScratch s;
+    int* d_lens = nullptr;
+    TRYC(k_lens(s, host_lens, B, T, &d_lens));
+    const int d = heads * 64;
+    const size_t ldT = ((size_t)T + 15) / 16 * 16;
+    const size_t n_sc = std::max((size_t)B * heads * T * ldT, (size_t)B * heads * (((size_t)T + 31) / 32) * 4096);   // as ensure_workspace
+    float* scratch = nullptr;
+    TRYC(s.get((void**)&scratch, n_sc * 4));
+    g_gemm_split = 0;
+    if (mode == 0) launch_attn3(st, qkv, scratch, att, d_lens, B, T, d, heads);
+    else launch_codec_attn(st, mode == 2, scratch, qkv, att, d_lens, B, T, d, heads, planes ? (uint16_t*)att + pad32((long)B * T) * d : nullptr);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+extern "C" int32_t mtts_k_codec_gemm_planes(const float* A, const float* W, const float* bias, const float* gamma, const float* res,
+                                            float* C, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t flags, int32_t tile,
+                                            int32_t row0, int32_t plane_rows, int32_t nt_out, void* stream) {
+    if (!A || !W || !C || M < 1 || N < 1 || K < 64 || K % 64) return cfail(MTTS_EINVAL, "codec_gemm_planes: bad argument (K must be a multiple of 64)");
+    if (row0 < 0 || (plane_rows ? plane_rows < row0 + M : row0 != 0)) return cfail(MTTS_EINVAL, "codec_gemm_planes: rows %d .. %d outside the planes", row0, row0 + M);
+    if (ldc < N || ldc % 4) return cfail(MTTS_EINVAL, "codec_gemm_planes: ldc must be a multiple of 4, at least N");
+    if ((flags & 8) && (ldc != N || N % 16)) return cfail(MTTS_EINVAL, "codec_gemm_planes: plane output needs ldc = N, a multiple of 16");
+    if (((flags & 2) != 0) != (gamma != nullptr) || ((flags & 4) != 0) != (res != nullptr)) return cfail(MTTS_EINVAL, "codec_gemm_planes: flags and pointers disagree");
+    hipStream_t st = (hipStream_t)stream;
+    KScratch s;
+    uint16_t *ap = nullptr, *wp = nullptr;
+    TRYC(k_planes(s, st, A, plane_rows ? plane_rows : M, K, &ap));
+    TRYC(k_planes(s, st, W, N, K, &wp));
+    TRYC(gemm_planes_launch(st, (const float*)ap, wp, C, M, N, K, ldc, bias, flags & 1, gamma, res, ldc, (flags & 8) != 0, row0, plane_rows,
+                            nt_out, tile));
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+extern "C" int32_t mtts_k_codec_vocos_pw(const float* xn, const float* W1, const float* b1, const float* W2, const float* b2,
+                                         const float* gamma, float* h, int32_t M, void* stream) {
+    if (!xn || !W1 || !b1 || !W2 || !b2 || !gamma || !h || M < 1) return cfail(MTTS_EINVAL, "codec_vocos_pw: bad argument");
+    const int vd = 512, vi = 4096;
+    hipStream_t st = (hipStream_t)stream;
+    KScratch s;
+    uint16_t *xp = nullptr, *w1p = nullptr, *w2p = nullptr;
+    TRYC(k_planes(s, st, xn, M, vd, &xp));
+    TRYC(k_planes(s, st, W1, vi, vd, &w1p));
+    TRYC(s.get((void**)&w2p, (size_t)vd * vi * 4));
+    launch_split_pack_w2perm(st, W2, w2p, w2p + (long)vd * vi);
+    launch_vocos_pw_fused(st, xp, pad32(M) * (long)vd, w1p, b1, w2p, (long)vd * vi, b2, gamma, h, M);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+extern "C" int32_t mtts_k_codec_layernorm(const float* x, const float* w, const float* b, float* y, int32_t rows, int32_t C, float eps,
+                                          const int32_t* host_lens, int32_t T, int32_t ldy, int32_t planes, void* stream) {
+    if (!x || !w || !b || !y || rows < 1 || C < 1 || C > 1024 || T < 1 || ldy < C) return cfail(MTTS_EINVAL, "codec_layernorm: bad argument (C <= 1024, ldy >= C)");
+    if (host_lens && rows % T) return cfail(MTTS_EINVAL, "codec_layernorm: rows must be whole windows of T when lens are given");
+    if (planes && (ldy != C || C % 16)) return cfail(MTTS_EINVAL, "codec_layernorm: plane output needs ldy = C, a multiple of 16");
+    hipStream_t st = (hipStream_t)stream;
+    KScratch s;
+    int* d_lens = nullptr;
+    if (host_lens) TRYC(k_lens(s, host_lens, rows / T, T, &d_lens));
+    launch_layernorm(st, x, w, b, y, rows, C, eps, d_lens, T, (long)ldy, planes ? (uint16_t*)y + pad32(rows) * (long)ldy : nullptr);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
+extern "C" int32_t mtts_k_codec_layernorm_wide(const float* x, const float* w, const float* b, float* y, int32_t rows, int32_t C,
+                                               float eps, void* stream) {
+    if (!x || !w || !b || !y || rows < 1 || C < 1) return cfail(MTTS_EINVAL, "codec_layernorm_wide: bad argument");
+    launch_layernorm_wide((hipStream_t)stream, x, w, b, y, rows, C, eps);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize((hipStream_t)stream));
+    return MTTS_OK;
+}
+
+extern "C" int32_t mtts_k_codec_dwconv_ln(const float* h, const float* dw, const float* dwb, const float* lw, const float* lb, float* y,
+                                          int32_t B, int32_t T, int32_t C, float eps, int32_t kernel, int32_t planes, void* stream) {
+    if (!h || !dw || !dwb || !lw || !lb || !y || B < 1 || T < 1 || C < 1 || C > 1024) return cfail(MTTS_EINVAL, "codec_dwconv_ln: bad argument");
+    if (kernel != 0 && kernel != 4 && kernel != 8) return cfail(MTTS_EINVAL, "codec_dwconv_ln: kernel %d (0 any width, 4 / 8 rows per wave at C = 512)", kernel);
+    if (kernel && C != 512) return cfail(MTTS_EINVAL, "codec_dwconv_ln: the %d-row kernel is for C = 512", kernel);
+    if (planes && C % 16) return cfail(MTTS_EINVAL, "codec_dwconv_ln: plane output needs C to be a multiple of 16");
+    launch_dwconv_ln((hipStream_t)stream, kernel != 0, kernel, h, dw, dwb, lw, lb, y, B, T, C, eps,
+                     planes ? (uint16_t*)y + pad32((long)B * T) * C : nullptr);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize((hipStream_t)stream));
+    return MTTS_OK;
+}
+
+extern "C" int32_t mtts_k_codec_softmax_mask(float* S, const int32_t* host_lens, int32_t B, int32_t heads, int32_t T, int32_t ldT,
+                                             void* stream) {
+    if (!S || !host_lens || B < 1 || heads < 1 || T < 1 || ldT < T || ldT % 16) return cfail(MTTS_EINVAL, "codec_softmax_mask: bad argument (ldT a multiple of 16, at least T)");
+    KScratch s;
+    int* d_lens = nullptr;
+    TRYC(k_lens(s, host_lens, B, T, &d_lens));
+    launch_softmax_mask((hipStream_t)stream, S, d_lens, B, heads, T, ldT);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize((hipStream_t)stream));
+    return MTTS_OK;
+}
+
+extern "C" int32_t mtts_k_codec_vq_argmin_update(const float* dot, const float* cb, const float* cc, float* residual, int64_t* codes,
+                                                 const int32_t* host_lens, int32_t B, int32_t T, int32_t K, int32_t D, void* stream) {
+    if (!dot || !cb || !cc || !residual || !codes || !host_lens || B < 1 || T < 1 || K < 1 || D < 1) return cfail(MTTS_EINVAL, "codec_vq_argmin_update: bad argument");
+    KScratch s;
+    int* d_lens = nullptr;
+    TRYC(k_lens(s, host_lens, B, T, &d_lens));
+    launch_vq_argmin_update((hipStream_t)stream, dot, cb, cc, residual, codes, d_lens, B * T, T, K, D);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize((hipStream_t)stream));
+    return MTTS_OK;
+}
+
+extern "C" int32_t mtts_k_codec_gemm_f32_ex(const float* A, const float* W, float* C, const float* bias, const float* gamma,
+                                            const float* res, int32_t M, int32_t N, int32_t K, int32_t b_kn, int64_t lda, int64_t ldw,
+                                            int64_t ldc, int64_t ldres, int32_t res_rows, int32_t act, float scale, int32_t batch,
+                                            int32_t batch_inner, const int64_t* strides, void* stream) {
+    if (!A || !W || !C || !strides || M < 1 || N < 1 || K < 1 || batch < 1 || batch_inner < 1 || res_rows < 0 || (act != 0 && act != 1))
+        return cfail(MTTS_EINVAL, "codec_gemm_f32_ex: bad argument");
+    // the kernel's 16-byte loads: k (and n of [K][N] weights) advance in fours from the row start
+    if (lda % 4 || ldw % 4 || strides[0] % 4 || strides[1] % 4 || strides[2] % 4 || strides[3] % 4)
+        return cfail(MTTS_EINVAL, "codec_gemm_f32_ex: lda, ldw and the A / W strides must be multiples of 4");
+    if (lda < K || ldw < (b_kn ? N : K) || ldc < N || (res && ldres < N)) return cfail(MTTS_EINVAL, "codec_gemm_f32_ex: a leading dimension is shorter than its row");
+    g_gemm_split = 0;
+    gemm_f32((hipStream_t)stream, b_kn != 0, A, W, C, M, N, K, lda, ldw, ldc, bias, act, gamma, res, ldres, res_rows, scale, batch,
+             batch_inner, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize((hipStream_t)stream));
     return MTTS_OK;
 }

@@ -181,6 +181,18 @@ _SIGS = {
                                     C.c_int32, C.c_void_p]),
     "mtts_k_gemm_planes_bench": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "mtts_k_codec_attn": (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p]),
+    "mtts_k_codec_gemm_planes": (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] * 9 + [C.c_void_p]),
+    "mtts_k_codec_vocos_pw": (C.c_int32, [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]),
+    "mtts_k_codec_layernorm": (C.c_int32, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_float, C.c_void_p] + [C.c_int32] * 3 +
+                               [C.c_void_p]),
+    "mtts_k_codec_layernorm_wide": (C.c_int32, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "mtts_k_codec_dwconv_ln": (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
+    "mtts_k_codec_softmax_mask": (C.c_int32, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
+    "mtts_k_codec_vq_argmin_update": (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p]),
+    "mtts_k_codec_gemm_f32_ex": (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_int64] * 4 + [C.c_int32, C.c_int32, C.c_float,
+                                                                                                   C.c_int32, C.c_int32, C.c_void_p,
+                                                                                                   C.c_void_p]),
 }
 
 

@@ -186,3 +186,58 @@ def test_gemm_planes_bench_hook_runs_every_variant():
             assert lib.mtts_k_gemm_planes_bench(1000, 768, 256, flags, code, 2, C.byref(us), C.byref(used)) == 0
             assert us.value > 0 and (code == 0 or used.value == code)
     assert lib.mtts_k_gemm_planes_bench(1000, 768, 256, 3, 0, 2, C.byref(us), C.byref(used)) != 0
+
+
+_VARIANT_LENGTHS = (13, 131, 375)
+
+
+def _variant_setup():
+    cfg = synth_codec.reduced(dec_layers=1, voc_layers=2)
+    w = synth_codec.synth_weights(cfg, 77)
+    rng = np.random.default_rng(78)
+    codes = [rng.integers(0, 1024, (8, n)) for n in _VARIANT_LENGTHS]
+    return cfg, w, codes
+
+
+def _variant_decode(cfg, w, codes):
+    from mtts.codec import CodecEngine
+    eng = CodecEngine(cfg)
+    eng.bind_state_dict(w)
+    out = [x.cpu().numpy() for x in eng.decode_each([torch.from_numpy(c) for c in codes])]
+    eng.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def variant_baseline():
+    """The default engine's waveforms and the oracle's, once for all switches."""
+    cfg, w, codes = _variant_setup()
+    orc = co.CodecOracle(cfg, w)
+    return _variant_decode(cfg, w, codes), [orc.decode([c])[0] for c in codes]
+
+
+@pytest.mark.parametrize("switch,value,bit_identical", [("MTTS_CODEC_ATTN_PACKED", "0", False), ("MTTS_CODEC_PLANES", "0", False),
+                                                        ("MTTS_CODEC_DW_ROWS", "8", True), ("MTTS_CODEC_NT_OUT", "0", True),
+                                                        ("MTTS_CODEC_XCD", "0", False)])
+def test_codec_variant_switches_through_the_whole_decoder(monkeypatch, variant_baseline, switch, value, bit_identical):
+    """The paths behind the engine's switches that no other test takes: codec_attn_kernel (ATTN_PACKED=0), fp32 activations
+    between the kernels (PLANES=0), dwconv_ln512_kernel<8> (DW_ROWS=8), plain stores of the GELU planes (NT_OUT=0) and the
+    row-major block -> tile order (XCD=0).  Each stays within the waveform bar of the oracle and within 1e-5 RMS of the
+    default engine ("same arithmetic, different order"); rows per wave and the store kind must not change a bit."""
+    from mtts.codec import CodecEngine
+    cfg, w, codes = _variant_setup()
+    base, want = variant_baseline
+    monkeypatch.setenv(switch, value)
+    try:
+        got = _variant_decode(cfg, w, codes)
+    finally:
+        if switch == "MTTS_CODEC_XCD":            # the switch writes a __constant__ that outlives the engine: put the default back
+            monkeypatch.setenv(switch, "1")
+            CodecEngine(cfg).close()
+    for g, b, o, n in zip(got, base, want, _VARIANT_LENGTHS):
+        assert g.shape == b.shape == o.shape == (n * 1920,)
+        e = g.astype(np.float64) - o.astype(np.float64)
+        assert np.sqrt(np.mean(e ** 2)) <= RMS_TOL, (switch, n)
+        assert np.sqrt(np.mean((g.astype(np.float64) - b) ** 2)) <= 1e-5, (switch, n)
+        if bit_identical:
+            assert np.array_equal(g, b), (switch, n)
