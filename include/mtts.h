@@ -110,6 +110,41 @@ typedef struct MttsSamplerBans {
     const int32_t* suppress;         /* ids >= 0; read during the call only */
 } MttsSamplerBans;
 
+/* The sequence rules and step-conditioned bans of one channel (mtts_set_sampler_bias): HF's SequenceBiasLogitsProcessor,
+ * NoBadWordsLogitsProcessor, MinLengthLogitsProcessor and SuppressTokensAtBeginLogitsProcessor.  With h the channel's history
+ * at decode step g as MttsSamplerBans defines it, len(h) = base + g:
+ *   rule (t_1..t_L, beta)   L = 1: token t_1 always carries beta.  L > 1: t_L carries beta at a step where len(h) >= L and
+ *                           the last L-1 tokens of h are t_1..t_{L-1} (HF skips a rule longer than its context, so a
+ *                           history of exactly L-1 tokens does not fire it).  A token's term is an fp32 chain: its single-token
+ *                           beta (0 without one), then the beta of every matching longer rule in the order of rule_len,
+ *                           each addition in fp32.  The processed score is penalty(raw + term) / temperature: one fp32
+ *                           addition on the fp32 value of the raw logit, behind the two hard-coded masks (-inf stays
+ *                           -inf) and in front of the repetition penalty, HF's order.  beta = -inf (bad_words_ids): a
+ *                           matching rule bans t_L this step, with everything MttsSamplerBans says about a banned token.
+ *                           A rule with an id outside the channel's vocabulary is ignored on that channel.
+ *   min_length m            eos_token_id is banned while len(h) < m.
+ *   begin_suppress          the listed ids inside the vocabulary are banned at the one step with len(h) = base + 7: HF's
+ *                           begin_index is the full prompt width, delay tail included.
+ * A field of 0 means "processor absent".  mtts/bias_spec.py states the same rule in numpy. */
+#define MTTS_BIAS_RULES_MAX 64       /* rules per channel */
+#define MTTS_BIAS_RULE_LEN_MAX 16    /* tokens per rule */
+typedef struct MttsSamplerBias {
+    int32_t n_rules;                 /* 0..MTTS_BIAS_RULES_MAX */
+    int32_t min_length;              /* >= 0 */
+    int32_t n_begin_suppress;        /* entries of begin_suppress */
+    const int32_t* rule_len;         /* [n_rules], each 1..MTTS_BIAS_RULE_LEN_MAX; read during the call only, like the next three */
+    const int32_t* rule_ids;         /* the rules' ids one rule after another, sum(rule_len) entries, each >= 0 */
+    const float* rule_bias;          /* [n_rules]: beta; -inf is a ban, +inf and NaN are refused */
+    const int32_t* begin_suppress;   /* ids >= 0 */
+} MttsSamplerBias;
+/* The terms of one (row, channel) pair at one step, as the rule kernel leaves them for the sampler: the n tokens that carry
+ * a finite term this step, ascending by id, each with its chain's sum. */
+typedef struct MttsBiasTable {
+    int32_t n;
+    int32_t ids[MTTS_BIAS_RULES_MAX];
+    float term[MTTS_BIAS_RULES_MAX];
+} MttsBiasTable;
+
 typedef struct MttsEngine MttsEngine;
 
 const char* mtts_last_error(void);
@@ -359,6 +394,25 @@ int32_t mtts_set_sampler_bans(MttsEngine* e, const MttsSamplerBans bans[8] /* NU
 int32_t mtts_set_sampler_typical(MttsEngine* e, const float typical_p[8] /* NULL: none; 0 or 1: absent */);
 /* Launches of the ban kernel by this process so far (engine steps and mtts_k_ngram_ban). */
 int64_t mtts_debug_ban_launches(void);
+/* Sequence rules, min_length and begin_suppress_tokens of the NEXT run only (one-shot like mtts_set_sampler_bans: consumed by
+ * the next mtts_begin, mtts_generate or mtts_sched_open, failures included): bias[c] is channel c's MttsSamplerBias, applied
+ * whether the channel samples or not.  NULL: none.  The lists are copied during the call.  lp of mtts_set_output_scores is
+ * the log-softmax over the final kept set of the biased, processed scores; mtts_set_top_logprobs, which describes the raw
+ * distribution, sees neither term nor ban.  A run with a rule launches one more kernel per decode step, behind the ban kernel
+ * and ahead of the sampler: one block per (row, channel), whose first wave tests every rule's prefix against the tail of
+ * the history, ORs the last token of each matching -inf rule into the pair's ban words, and -- in a run with a finite beta --
+ * rewrites the pair's bias words (a bitmap in the ban words' layout, from the channel's single-token rules) and its
+ * MttsBiasTable, from which the sampler's score function adds the term of a token whose bit is set.  No float atomics: the
+ * chain is summed in rule order by one lane per token, so words and tables are the same bits run to run and under graph
+ * replay.  A -inf rule, min_length or begin_suppress turn the ban path on (eos under min_length and the begin list are
+ * step-conditioned static bans of the ban kernel).  Rules longer than one token need the prompt history of the n-gram
+ * ban: a prompt may then have at most max_seq_len slots (padding included).  Every buffer exists only once a run asked for
+ * it; a run that sets none of this launches and allocates what it did before.
+ * MTTS_EINVAL, naming the channel, and nothing is left pending: n_rules outside [0, MTTS_BIAS_RULES_MAX], a rule length
+ * outside [1, MTTS_BIAS_RULE_LEN_MAX], a negative id, a beta that is NaN or +inf, min_length < 0, a count without its list. */
+int32_t mtts_set_sampler_bias(MttsEngine* e, const MttsSamplerBias bias[8] /* NULL: none */);
+/* Launches of the rule kernel by this process so far (engine steps and mtts_k_seq_bias). */
+int64_t mtts_debug_bias_launches(void);
 /* Scheduler mode: start a take of the dialogue just submitted to src_slot in the empty dst_slot: same prompt (its
  * complete KV pages shared, the partially filled last one copied), drawing from (seed; step, row_id, channel).  The take's
  * tokens equal those of mtts_slot_submit_row(dst_slot, the same prompt, seed, row_id).  Stream-ordered on `stream`.
@@ -651,6 +705,22 @@ int32_t mtts_k_sample_typical(const void* dev_logits_bf16, int32_t rows, int32_t
 int32_t mtts_k_ngram_ban(const int32_t* dev_hist, const int32_t* dev_lens, int32_t rows, int32_t cap, int32_t n,
                          const int32_t* host_static, int32_t n_static, int32_t vocab, int32_t eos_id, int32_t eos_on,
                          void* dev_ban, void* stream);
+/* The rule kernel of a decode step (mtts_set_sampler_bias) on bare histories of one channel, launched as the engine launches
+ * it (one block per row): dev_hist / dev_lens as for mtts_k_ngram_ban, host_rules ONE channel's settings (its rules only;
+ * the same value checks; rules with an id outside [0, vocab) are ignored).  dev_ban uint32 [rows][ceil(vocab / 32)] keeps
+ * what it holds and gains the last token of every matching -inf rule (NULL: allowed when no rule is -inf).  dev_bias_words,
+ * the same shape, and dev_bias_tab [rows] are overwritten: whatever they held is gone (both NULL: the -inf rules only). */
+int32_t mtts_k_seq_bias(const int32_t* dev_hist, const int32_t* dev_lens, int32_t rows, int32_t cap,
+                        const MttsSamplerBias* host_rules, int32_t vocab, void* dev_ban, void* dev_bias_words,
+                        MttsBiasTable* dev_bias_tab, void* stream);
+/* mtts_k_sample_typical with the bias inputs the rule kernel leaves: dev_bias_words uint32 [rows][ceil(vocab / 32)], bit i of
+ * a row set = token i carries the term dev_bias_tab[row] lists for it.  Both NULL: mtts_k_sample_typical bit for bit, the
+ * same kernels reading no bias word. */
+int32_t mtts_k_sample_bias(const void* dev_logits_bf16, int32_t rows, int32_t vocab,
+                           const void* dev_history_bitmap, const MttsSamplerCfg* cfg,
+                           int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
+                           int32_t* dev_tokens, float* dev_logp, const MttsSamplerFloors* floors, const void* dev_ban,
+                           float typical_p, const void* dev_bias_words, const MttsBiasTable* dev_bias_tab, void* stream);
 /* The kernels of mtts_set_top_logprobs on bare logits, launched as the engine launches them (the slice pass and the merge
  * when vocab > 4096, the single-block path otherwise): dev_logits [rows][vocab] bf16 bits, or fp32 when is_f32; mask_id
  * the one id at -inf (-1: none); dev_decisions int32 [rows].  dev_logp float [rows] = log_softmax(L)[decision],

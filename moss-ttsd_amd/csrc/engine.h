@@ -217,6 +217,9 @@ struct MttsEngine {
     BanCfg* d_bancfg = nullptr;         // [8], allocated with the engine like d_floors (launch.h: launch_ban)
     int bans_on = 0;                    // of the current run: a channel has a hard ban (mtts_set_sampler_bans; the buffers are in bufs)
     int ban_ngram_on = 0;               // ... an n-gram ban: submits stage the prompt's slots into bufs.d_hist
+    int ban_begin_on = 0;               // ... begin_suppress_tokens (mtts_set_sampler_bias): bufs.d_ban_begin appears
+    int bias_on = 0, bias_terms = 0;    // of the current run: a channel has a sequence rule / a finite one (mtts_set_sampler_bias)
+    int hist_on = 0;                    // ban_ngram_on, or a rule longer than one token: the prompt history is staged
     SampleScratch sscr;                 // (its slice_sum / lp / ban stay null here: bufs holds them)
     int ch0_sampled = 0;
     // output_scores: per-token log-probabilities (bufs.d_lp, laid out like bufs.d_gen)
@@ -282,7 +285,7 @@ static inline StepState step_state(const MttsEngine* e, int heads, int R, int pa
     StepState s;
     s.heads = heads; s.B = e->B; s.R = R; s.pages_bound = pages_bound; s.lora = lora;
     s.forced = e->has_forced; s.ch0_sampled = e->ch0_sampled != 0; s.scores_on = e->scores_on != 0; s.floors_on = e->floors_on != 0; s.typical_on = e->typical_on != 0;
-    s.bans_on = e->bans_on != 0;
+    s.bans_on = e->bans_on != 0; s.bias_on = e->bias_on != 0; s.bias_terms = e->bias_terms != 0;
     s.topk = e->topk_on;
     for (int k = 0; k < WSEAL_KINDS; ++k) s.wseal_on[k] = e->wseal_on[k] != 0;
     if (e->kpack) s.pack_k_on = e->pack_k_on.data();

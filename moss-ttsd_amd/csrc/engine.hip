@@ -894,38 +894,76 @@ static int start_outputs(MttsEngine* e, int steps, hipStream_t st) {
 // the buffers the ban kernel works on appear with the first run that asks -- the ban words and static bitmaps with any
 // ban, the prompt history with an n-gram ban.  They are members of bufs and keep their size, so nothing is released here.
 // A run without bans touches and allocates nothing.  Returns with `st` drained when it copied.
-static int start_bans(MttsEngine* e, const RunBans& bans, hipStream_t st) {
+// The same for mtts_set_sampler_bias, which shares the ban path: a -inf rule, min_length or begin_suppress_tokens turn it on
+// (min_length travels in BanCfg, the begin list in a second static bitmap), a rule longer than one token needs the prompt
+// history.  The flattened rules appear with the first run that has a rule; the bias words, their static part and the
+// tables with the first that has a finite one.
+static int start_bans(MttsEngine* e, const RunBans& bans, const RunBias& bias, hipStream_t st) {
     StepBufs& b = e->bufs;
-    e->bans_on = bans.any() ? 1 : 0;
+    e->bans_on = (bans.any() || bias.bans()) ? 1 : 0;
     e->ban_ngram_on = bans.ngram() ? 1 : 0;
-    if (!e->bans_on) return 0;
+    e->ban_begin_on = bias.begin() ? 1 : 0;
+    e->bias_on = bias.rules() ? 1 : 0;
+    e->bias_terms = bias.finite() ? 1 : 0;
+    e->hist_on = (e->ban_ngram_on || bias.history()) ? 1 : 0;
+    if (!e->bans_on && !e->bias_on) return 0;
     const int rows = e->cfg.max_batch, words = e->bm_words;
-    if (!b.d_ban) {
+    if (e->bans_on && !b.d_ban) {
         TRY(e->mem.get(&b.d_ban, (size_t)rows * 8 * words));
         TRY(e->mem.get(&b.d_ban_static, (size_t)8 * words));
-        b.ban_words = words;
     }
-    if (e->ban_ngram_on && !b.d_hist) {
+    if (e->ban_begin_on && !b.d_ban_begin) TRY(e->mem.get(&b.d_ban_begin, (size_t)8 * words));
+    if (e->bias_on && !b.d_bias_rules) TRY(e->mem.get(&b.d_bias_rules, 8));
+    if (e->bias_terms && !b.d_bias_w) {
+        TRY(e->mem.get(&b.d_bias_w, (size_t)rows * 8 * words));
+        TRY(e->mem.get(&b.d_bias_static, (size_t)8 * words));
+        TRY(e->mem.get(&b.d_bias_tab, (size_t)rows * 8));
+    }
+    b.ban_words = words;
+    if (e->hist_on && !b.d_hist) {
         TRY(e->mem.get(&b.d_hist, (size_t)rows * e->cfg.max_seq_len * 8));
         b.hist_cap = e->cfg.max_seq_len;
     }
-    BanCfg cfg[8];
-    std::vector<uint32_t> stat((size_t)8 * words, 0u);
-    for (int c = 0; c < 8; ++c) {
-        const ChannelBans& cb = bans.ch[c];
-        cfg[c] = BanCfg{cb.ngram, cb.min_new > 0 ? cb.min_new + 7 : 0};
-        stage_ban_static(cb.suppress.data(), (int)cb.suppress.size(), c == 0 ? e->V0 : e->Vs, words, stat.data() + (size_t)c * words);
+    const ChannelBans no_bans;
+    const ChannelBias no_bias;
+    if (e->bans_on) {
+        BanCfg cfg[8];
+        // (once the begin bitmap exists every run with bans restages it, empty included: a captured step holds its address)
+        const bool has_begin = b.d_ban_begin != nullptr;
+        std::vector<uint32_t> stat((size_t)8 * words, 0u), begin(has_begin ? (size_t)8 * words : 0, 0u);
+        for (int c = 0; c < 8; ++c) {
+            const ChannelBans& cb = bans.ch.empty() ? no_bans : bans.ch[c];
+            const ChannelBias& ci = bias.ch.empty() ? no_bias : bias.ch[c];
+            const int V = c == 0 ? e->V0 : e->Vs;
+            cfg[c] = BanCfg{cb.ngram, cb.min_new > 0 ? cb.min_new + 7 : 0, ci.min_length};
+            stage_ban_static(cb.suppress.data(), (int)cb.suppress.size(), V, words, stat.data() + (size_t)c * words);
+            if (has_begin) stage_ban_static(ci.begin.data(), (int)ci.begin.size(), V, words, begin.data() + (size_t)c * words);
+        }
+        HIPCHK(hipMemcpyAsync(e->d_bancfg, cfg, sizeof(cfg), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b.d_ban_static, stat.data(), stat.size() * 4, hipMemcpyHostToDevice, st));
+        if (has_begin) HIPCHK(hipMemcpyAsync(b.d_ban_begin, begin.data(), begin.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
-    HIPCHK(hipMemcpyAsync(e->d_bancfg, cfg, sizeof(cfg), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b.d_ban_static, stat.data(), stat.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (e->bias_on) {
+        std::vector<BiasRules> rules(8);
+        std::vector<uint32_t> stat(e->bias_terms ? (size_t)8 * words : 0, 0u);
+        for (int c = 0; c < 8; ++c) {
+            const ChannelBias& ci = bias.ch[c];
+            stage_bias_rules(ci.len.data(), ci.ids.data(), ci.beta.data(), (int)ci.len.size(), c == 0 ? e->V0 : e->Vs, words, &rules[c],
+                             e->bias_terms ? stat.data() + (size_t)c * words : nullptr);
+        }
+        HIPCHK(hipMemcpyAsync(b.d_bias_rules, rules.data(), rules.size() * sizeof(BiasRules), hipMemcpyHostToDevice, st));
+        if (e->bias_terms) HIPCHK(hipMemcpyAsync(b.d_bias_static, stat.data(), stat.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
     return 0;
 }
-// the prompt slots [n][8] of the dialogue in `slot`, for the n-gram ban: into its row of bufs.d_hist.  on_stream: on `st`,
+static const char* hist_user(const MttsEngine* e) { return e->ban_ngram_on ? "no_repeat_ngram_size" : "sequence_bias / bad_words_ids"; }
+// the prompt slots [n][8] of the dialogue in `slot`, for the n-gram ban and the rules longer than one token: into its row of bufs.d_hist.  on_stream: on `st`,
 // which the caller drains before `host` dies (mtts_begin); else synchronously (mtts_slot_submit)
 static int upload_history(MttsEngine* e, int slot, const int64_t* toks, int n, std::vector<int32_t>& host, bool on_stream, hipStream_t st) {
     if (n > e->bufs.hist_cap)
-        return fail(MTTS_EINVAL, "no_repeat_ngram_size: the prompt has %d slots (padding included), the history holds max_seq_len = %d", n, e->bufs.hist_cap);
+        return fail(MTTS_EINVAL, "%s: the prompt has %d slots (padding included), the history holds max_seq_len = %d", hist_user(e), n, e->bufs.hist_cap);
     host.resize((size_t)n * 8);
     stage_history(toks, n, host.data());
     int32_t* dst = e->bufs.d_hist + (size_t)slot * e->bufs.hist_cap * 8;
@@ -1089,9 +1127,9 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
     // generation buffers
     e->scores_on = opt.output_scores; e->topk_on = opt.top_logprobs;
     TRY(start_outputs(e, max_steps, st));
-    TRY(start_bans(e, opt.bans, st));
-    if (e->ban_ngram_on && base > e->bufs.hist_cap)
-        return fail(MTTS_EINVAL, "no_repeat_ngram_size: the prompt has %d slots (padding included), the history holds max_seq_len = %d", base, e->bufs.hist_cap);
+    TRY(start_bans(e, opt.bans, opt.bias, st));
+    if (e->hist_on && base > e->bufs.hist_cap)
+        return fail(MTTS_EINVAL, "%s: the prompt has %d slots (padding included), the history holds max_seq_len = %d", hist_user(e), base, e->bufs.hist_cap);
     StagedRows sr;
     TRY(stage_rows(seqs, e->V0, e->Vs, false, &sr));
     {
@@ -1107,8 +1145,8 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
         std::vector<SeqState> ss(MTTS_RCAP, IDLE_SEQ);
         for (int b = 0; b < R; ++b) ss[b] = SeqState{-1, 1, e->n_real[b], 0, base, max_length, opt.row_id(b), 1, seed};
         // n-gram ban: every row's prompt slots, the stream the bitmap was built from (a prompt's takes start from the same)
-        std::vector<std::vector<int32_t>> hist(e->ban_ngram_on ? B : 0);
-        for (int rw = 0; e->ban_ngram_on && rw < R; ++rw) {
+        std::vector<std::vector<int32_t>> hist(e->hist_on ? B : 0);
+        for (int rw = 0; e->hist_on && rw < R; ++rw) {
             std::vector<int32_t>& hb = hist[rw / takes];
             if (rw % takes == 0) TRY(upload_history(e, rw, ids + (size_t)(rw / takes) * T * 8, base, hb, true, st));
             else HIPCHK(hipMemcpyAsync(e->bufs.d_hist + (size_t)rw * e->bufs.hist_cap * 8, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, st));
@@ -1148,6 +1186,10 @@ int32_t mtts_set_sampler_bans(MttsEngine* e, const MttsSamplerBans* bans) {
     if (!e) return fail(MTTS_EINVAL, "null engine");
     return e->pending.set_bans(bans);
 }
+int32_t mtts_set_sampler_bias(MttsEngine* e, const MttsSamplerBias* bias) {
+    if (!e) return fail(MTTS_EINVAL, "null engine");
+    return e->pending.set_bias(bias);
+}
 // The options of the mtts_begin / mtts_generate that starts now: out of the engine first -- so the one-shot ones are
 // consumed whatever the call does next -- and then checked.
 static int take_options(MttsEngine* e, int B, bool forced, RunOptions* opt) {
@@ -1173,9 +1215,14 @@ static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipSt
     SampleScratch sscr = e->sscr;
     sscr.slice_sum = b.sscr_slice_sum; sscr.lp = b.sscr_lp;
     if (plan.bans_on) {                  // this step's banned tokens, from the history as the last update_kernel left it
-        launch_ban(b.d_ban, b.d_ban_static, b.ban_words, e->d_bancfg, b.d_hist, b.hist_cap, b.d_gen, e->V0, e->Vs, e->cfg.eos_token_id,
+        launch_ban(b.d_ban, b.d_ban_static, b.d_ban_begin, b.ban_words, e->d_bancfg, b.d_hist, b.hist_cap, b.d_gen, e->V0, e->Vs, e->cfg.eos_token_id,
                    e->d_ls, e->d_seqs, plan.B, st);
         sscr.ban = b.d_ban;
+    }
+    if (plan.bias_on) {                  // the rules against the same history: -inf hits into the ban words, finite ones into words and tables
+        launch_bias(plan.bans_on ? b.d_ban : nullptr, plan.bias_terms ? b.d_bias_w : nullptr, b.d_bias_static, plan.bias_terms ? b.d_bias_tab : nullptr,
+                    b.ban_words, b.d_bias_rules, b.d_hist, b.hist_cap, b.d_gen, e->V0, e->Vs, e->d_ls, e->d_seqs, plan.B, st);
+        if (plan.bias_terms) { sscr.bias_w = b.d_bias_w; sscr.bias_t = b.d_bias_tab; }
     }
     launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
                   e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, plan.B, sscr, plan.ch0_sampled,
@@ -1686,6 +1733,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     const std::vector<float> typical = e->pending.take_typical();
     const std::vector<MttsSamplerFloors> floors = e->pending.take_floors();     // the one-shots leave first: consumed whatever follows
     const RunBans bans = e->pending.take_bans();
+    const RunBias bias = e->pending.take_bias();
     if (!sampler) return fail(MTTS_EINVAL, "null argument");
     TRY(mtts_weights_ready(e));
     HIPCHK(hipSetDevice(e->device));
@@ -1694,7 +1742,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     if (gen_cap < 8) return fail(MTTS_EINVAL, "gen_cap too small");
     e->scores_on = e->pending.output_scores; e->topk_on = e->pending.top_logprobs;      // the sticky switches only
     TRY(start_outputs(e, gen_cap, st));
-    TRY(start_bans(e, bans, st));
+    TRY(start_bans(e, bans, bias, st));
     e->B = B; e->steps_issued = 0; e->has_forced = false; e->continuous = true;
     e->max_steps = 1 << 30;
     e->n_real.assign(B, 0);
@@ -1761,7 +1809,7 @@ int32_t mtts_slot_submit_row(MttsEngine* e, int32_t slot, const int64_t* ids, in
     TRY(stage_tail(ids + (size_t)n * 8, e->V0, e->Vs, "", tf.data()));
     stage_bitmap(ids, n, e->bm_words, bm.data());
     std::vector<int32_t> hist;
-    if (e->ban_ngram_on) TRY(upload_history(e, slot, ids, n, hist, false, st));
+    if (e->hist_on) TRY(upload_history(e, slot, ids, n, hist, false, st));
     TRY(upload_staged(e, sr, false, st));
     HIPCHK(hipMemcpy(e->d_bitmaps + (size_t)slot * 8 * e->bm_words, bm.data(), bm.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_tf + (size_t)slot * 7 * 8, tf.data(), tf.size() * 4, hipMemcpyHostToDevice));
@@ -1826,7 +1874,7 @@ int32_t mtts_slot_fork(MttsEngine* e, int32_t src, int32_t dst, uint64_t seed, i
     }
     if (!rc) rc = e->pool.flush(ship);
     if (!rc) rc = launch_fork_job(e, job, true, st);
-    if (!rc && e->ban_ngram_on) {                   // the take's own copy of the prompt history (n-gram ban); its generated part starts empty
+    if (!rc && e->hist_on) {                        // the take's own copy of the prompt history (n-gram ban, rules); its generated part starts empty
         const size_t row = (size_t)e->bufs.hist_cap * 8;
         if (hipMemcpyAsync(e->bufs.d_hist + (size_t)dst * row, e->bufs.d_hist + (size_t)src * row, (size_t)e->h_seqs[src].base_length * 8 * 4,
                            hipMemcpyDeviceToDevice, st) != hipSuccess) rc = fail(MTTS_EHIP, "fork: copying the prompt history failed");

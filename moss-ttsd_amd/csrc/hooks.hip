@@ -375,7 +375,9 @@ int32_t mtts_k_gemm_tile(int32_t epi, const void* dev_w, const void* dev_x, void
 
 static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
                     int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
-                    const MttsSamplerFloors* floors, const void* ban, float typical_p, void* stream) {
+                    const MttsSamplerFloors* floors, const void* ban, float typical_p, void* stream, const void* bias_w = nullptr,
+                    const MttsBiasTable* bias_t = nullptr) {
+    if ((bias_w == nullptr) != (bias_t == nullptr)) return fail(MTTS_EINVAL, "sample: bias words and bias tables come together");
     if (!logits || !cfg || !dev_tokens || rows < 1 || vocab < 1 || channel < 0 || channel > 7) return fail(MTTS_EINVAL, "sample: bad argument");
     hipStream_t st = S(stream);
     MttsSamplerCfg h[8];
@@ -415,6 +417,7 @@ static int k_sample(const void* logits, int32_t rows, int32_t vocab, const void*
     SampleScratch sc;
     TRY(alloc_scratch(hb, sc, rows, vocab));
     sc.ban = (const uint32_t*)ban;   // [rows][ceil(vocab / 32)], or null: the same kernels, which then read no ban word
+    sc.bias_w = (const uint32_t*)bias_w; sc.bias_t = bias_t;    // the same for the additive terms: [rows][ceil(vocab / 32)], [rows]
     if (dev_logp) {                  // output_scores scratch
         TRY(hb.get(&sc.slice_sum, (size_t)rows * SAMP_NS));
         TRY(hb.get(&sc.lp, (size_t)rows * 8));
@@ -470,6 +473,14 @@ int32_t mtts_k_sample_typical(const void* logits, int32_t rows, int32_t vocab, c
     return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, dev_ban, typical_p, stream);
 }
 
+int32_t mtts_k_sample_bias(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                           int32_t mask_id, uint64_t seed, int32_t step, int32_t channel, int32_t* dev_tokens, float* dev_logp,
+                           const MttsSamplerFloors* floors, const void* dev_ban, float typical_p, const void* dev_bias_words,
+                           const MttsBiasTable* dev_bias_tab, void* stream) {
+    return k_sample(logits, rows, vocab, bitmap, cfg, mask_id, seed, step, channel, dev_tokens, dev_logp, floors, dev_ban, typical_p, stream,
+                    dev_bias_words, dev_bias_tab);
+}
+
 // The ban kernel of a decode step (sampler.hip: ban_kernel) on bare histories of one channel.
 int32_t mtts_k_ngram_ban(const int32_t* dev_hist, const int32_t* dev_lens, int32_t rows, int32_t cap, int32_t n,
                          const int32_t* host_static, int32_t n_static, int32_t vocab, int32_t eos_id, int32_t eos_on,
@@ -505,6 +516,47 @@ int32_t mtts_k_ngram_ban(const int32_t* dev_hist, const int32_t* dev_lens, int32
     return MTTS_OK;
 }
 int64_t mtts_debug_ban_launches(void) { return (int64_t)mtts_ban_launches(); }
+
+// The rule kernel of a decode step (sampler.hip: bias_kernel) on bare histories of one channel.
+int32_t mtts_k_seq_bias(const int32_t* dev_hist, const int32_t* dev_lens, int32_t rows, int32_t cap, const MttsSamplerBias* host_rules,
+                        int32_t vocab, void* dev_ban, void* dev_bias_words, MttsBiasTable* dev_bias_tab, void* stream) {
+    if (!dev_lens || !host_rules || rows < 1 || rows > MTTS_RCAP || cap < 0 || (cap > 0 && !dev_hist) || vocab < 1 ||
+        (dev_bias_words == nullptr) != (dev_bias_tab == nullptr))
+        return fail(MTTS_EINVAL, "seq_bias: bad argument");
+    // the settings, checked like mtts_set_sampler_bias checks them
+    MttsSamplerBias hb8[8];
+    for (int i = 0; i < 8; ++i) hb8[i] = *host_rules;
+    PendingRun chk;
+    TRY(chk.set_bias(hb8));
+    const RunBias rb = chk.take_bias();
+    const ChannelBias& cb = rb.ch[0];
+    bool ninf = false, fin = false;
+    for (float v : cb.beta) { ninf = ninf || !(v > -INFINITY); fin = fin || v > -INFINITY; }
+    if (ninf && !dev_ban) return fail(MTTS_EINVAL, "seq_bias: a -inf rule and no ban words");
+    if (fin && !dev_bias_words) return fail(MTTS_EINVAL, "seq_bias: a finite rule and no bias words");
+    hipStream_t st = S(stream);
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int32_t> lens(rows);
+    HIPCHK(hipMemcpy(lens.data(), dev_lens, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < rows; ++r)
+        if (lens[r] < 0 || lens[r] > cap) return fail(MTTS_EINVAL, "seq_bias: row %d has length %d, the histories hold %d", r, lens[r], cap);
+    const int words = (vocab + 31) / 32;
+    BiasRules hr;
+    std::vector<uint32_t> stat(words);
+    stage_bias_rules(cb.len.data(), cb.ids.data(), cb.beta.data(), (int)cb.len.size(), vocab, words, &hr, stat.data());
+    DevBufs hb;
+    BiasRules* dr = nullptr;
+    uint32_t* ds = nullptr;
+    TRY(hb.get(&dr, 1));
+    TRY(hb.get(&ds, (size_t)words));
+    HIPCHK(hipMemcpy(dr, &hr, sizeof(hr), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ds, stat.data(), stat.size() * 4, hipMemcpyHostToDevice));
+    launch_bias_single((uint32_t*)dev_ban, (uint32_t*)dev_bias_words, ds, dev_bias_tab, dr, dev_hist, dev_lens, rows, cap, vocab, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+int64_t mtts_debug_bias_launches(void) { return (int64_t)mtts_bias_launches(); }
 
 // The top_logprobs kernels of a decode step (gen_topk.hip) on bare logits, with a scratch of their own.
 int32_t mtts_k_gen_topk(const void* dev_logits, int32_t is_f32, int32_t rows, int32_t vocab, int32_t mask_id,

@@ -145,6 +145,11 @@ struct SampleScratch {
     // not scratch, but it travels with it to every sampler kernel: this step's banned tokens (mtts_set_sampler_bans), laid out
     // like the history bitmaps ([slot][8][bm_words]; the single-matrix entry: [rows][ceil(vocab / 32)]).  Null: no bans
     const uint32_t* ban = nullptr;
+    // the same for this step's additive terms (mtts_set_sampler_bias): bias_w one bit per token that carries a term, in the
+    // ban words' layout; bias_t the (id, term) table of each pair ([slot][8]; the single-matrix entry: [rows]).  Both null:
+    // no finite rule
+    const uint32_t* bias_w = nullptr;
+    const MttsBiasTable* bias_t = nullptr;
 };
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps,
                    int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed,
@@ -159,14 +164,28 @@ void launch_sample_single(const void* logits, int rows, int vocab, const uint32_
 // sampler evaluates: ban[row][c][words] = stat[c][words], plus eos while the row's step < cfgs[c].eos_below, plus -- where
 // cfgs[c].ngram = n > 0 -- the follower of every earlier occurrence of the history's last n-1 tokens.  The history of
 // (row, c) is hist[row][0 .. base_length)[c] followed by gen[row][0 .. step)[c].
-struct BanCfg { int32_t ngram, eos_below; };      // eos_below = min_new_tokens + 7, or 0
-void launch_ban(uint32_t* ban, const uint32_t* stat, int words, const BanCfg* cfgs, const int32_t* hist, int hist_cap,
+// min_length (mtts_set_sampler_bias) rides along: eos is also banned while base_length + step < cfgs[c].min_length, and
+// begin ([8][words], or null) is a second static bitmap ORed in at the one step == 7, HF's begin_index.
+struct BanCfg { int32_t ngram, eos_below, min_length; };      // eos_below = min_new_tokens + 7, or 0; min_length or 0
+void launch_ban(uint32_t* ban, const uint32_t* stat, const uint32_t* begin, int words, const BanCfg* cfgs, const int32_t* hist, int hist_cap,
                 const int32_t* gen, int V0, int Vs, int eos, const LoopState* ls, const SeqState* seqs, int B, hipStream_t st);
 // one channel on bare histories hist [rows][cap], lens [rows]: ban [rows][ceil(vocab / 32)]; cfg1: one device BanCfg
 // (eos_below != 0: eos banned); stat [ceil(vocab / 32)]
 void launch_ban_single(uint32_t* ban, const uint32_t* stat, const BanCfg* cfg1, const int32_t* hist, const int32_t* lens, int rows,
                        int cap, int vocab, int eos, hipStream_t st);
 long long mtts_ban_launches();
+// The rule kernel of a decode step (mtts_set_sampler_bias; sampler.hip: bias_kernel), behind launch_ban and ahead of the
+// sampler, one block per (row, channel) the sampler evaluates: rules[c] against the tail of the pair's history (hist /
+// gen as for launch_ban; hist may be null when no rule is longer than one token).  The last token of every matching -inf
+// rule is ORed into ban (null: the run has no -inf rule).  bias_w / tabs (both null: the run has no finite rule):
+// bias_w[row][c][words] = bias_stat[c][words] plus the bit of every finite hit, tabs[row][c] the pair's (id, term) table.
+void launch_bias(uint32_t* ban, uint32_t* bias_w, const uint32_t* bias_stat, MttsBiasTable* tabs, int words, const BiasRules* rules,
+                 const int32_t* hist, int hist_cap, const int32_t* gen, int V0, int Vs, const LoopState* ls, const SeqState* seqs,
+                 int B, hipStream_t st);
+// one channel on bare histories: rules1 one device BiasRules, bias_stat [ceil(vocab / 32)]; ban / bias_w [rows][ceil(vocab / 32)], tabs [rows]
+void launch_bias_single(uint32_t* ban, uint32_t* bias_w, const uint32_t* bias_stat, MttsBiasTable* tabs, const BiasRules* rules1,
+                        const int32_t* hist, const int32_t* lens, int rows, int cap, int vocab, hipStream_t st);
+long long mtts_bias_launches();
 // generate(top_logprobs=k): where a step's results go.  In the engine the per-slot buffers, laid out like gen: logp
 // [slot][gen_cap][8], ids / tlp [slot][gen_cap][8][k]; gen_topk_finish_kernel writes the step's row of every evaluated
 // dialogue, update_kernel<true> then puts NaN / -1 over the slots that are not model decisions, by the rule it applies

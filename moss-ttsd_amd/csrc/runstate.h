@@ -9,12 +9,13 @@
 //                             that have since been reallocated is never found again, and is destroyed by the next insert.
 // No HIP in here: engine.h includes it, and so does tests/host/run_state_main.cpp, which runs it on the CPU.
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 #include <utility>
 #include <vector>
 
-#include "../../include/mtts.h"       // MttsSamplerFloors, MttsSamplerBans (plain C, no HIP)
+#include "../../include/mtts.h"       // MttsSamplerFloors, MttsSamplerBans, MttsSamplerBias (plain C, no HIP)
 #include "stepplan.h"
 
 // defined by whoever includes this (engine.hip; the CPU test), as for kvpool.h
@@ -33,6 +34,30 @@ struct RunBans {
     bool ngram() const { for (const ChannelBans& c : ch) if (c.ngram > 0) return true; return false; }
 };
 
+// The sequence rules and step-conditioned bans of a run (mtts_set_sampler_bias), owned like the bans.
+struct ChannelBias {
+    std::vector<int32_t> len, ids;      // rule r: the next len[r] entries of ids
+    std::vector<float> beta;            // -inf: a ban (bad_words_ids)
+    int min_length = 0;                 // 0: absent
+    std::vector<int32_t> begin;         // begin_suppress_tokens
+    bool any() const { return !len.empty() || min_length > 0 || !begin.empty(); }
+};
+struct RunBias {
+    std::vector<ChannelBias> ch;        // per channel; empty: none
+    bool any() const { for (const ChannelBias& c : ch) if (c.any()) return true; return false; }
+    bool rules() const { for (const ChannelBias& c : ch) if (!c.len.empty()) return true; return false; }          // the rule kernel runs
+    bool finite() const { for (const ChannelBias& c : ch) for (float v : c.beta) if (v > -INFINITY) return true; return false; }   // the sampler adds terms
+    bool bans() const {                 // the ban path is on: a -inf rule, min_length, begin_suppress_tokens
+        for (const ChannelBias& c : ch) {
+            if (c.min_length > 0 || !c.begin.empty()) return true;
+            for (float v : c.beta) if (!(v > -INFINITY)) return true;
+        }
+        return false;
+    }
+    bool begin() const { for (const ChannelBias& c : ch) if (!c.begin.empty()) return true; return false; }
+    bool history() const { for (const ChannelBias& c : ch) for (int32_t l : c.len) if (l > 1) return true; return false; }    // a rule reads the history
+};
+
 // ---- the options of one static run ----------------------------------------------------------------------------------
 struct RunOptions {
     int B = 0;                          // prompts of the call
@@ -42,6 +67,7 @@ struct RunOptions {
     std::vector<MttsSamplerFloors> floors;      // per channel (mtts_set_sampler_floors); empty: none
     std::vector<float> typical;         // typical_p per channel (mtts_set_sampler_typical), 0: absent; empty: none
     RunBans bans;                       // per channel (mtts_set_sampler_bans); empty: none
+    RunBias bias;                       // per channel (mtts_set_sampler_bias); empty: none
     int output_scores = 0, top_logprobs = 0;
     int rows() const { return B * takes; }
     int row_id(int r) const { return row_ids.empty() ? r : row_ids[r]; }
@@ -66,6 +92,7 @@ class PendingRun {
     std::vector<MttsSamplerFloors> floors;
     std::vector<float> typical;
     RunBans bans;
+    RunBias bias;
 public:
     int output_scores = 0, top_logprobs = 0;        // sticky: every run reads them, none resets them
     void set_takes(int n) { takes = n; }
@@ -118,6 +145,41 @@ public:
         bans.ch.swap(ch);
         return 0;
     }
+    // the same for the sequence rules, min_length and begin_suppress_tokens; a refused call leaves none behind
+    int set_bias(const MttsSamplerBias* b) {
+        bias.ch.clear();
+        if (!b) return 0;
+        std::vector<ChannelBias> ch(MTTS_CHANNELS);
+        for (int c = 0; c < MTTS_CHANNELS; ++c) {
+            const MttsSamplerBias& s = b[c];
+            if (s.n_rules < 0 || s.n_rules > MTTS_BIAS_RULES_MAX)
+                return fail(RUN_EINVAL, "channel %d: %d sequence_bias / bad_words_ids rules, at most %d", c, s.n_rules, MTTS_BIAS_RULES_MAX);
+            if (s.n_rules > 0 && (!s.rule_len || !s.rule_ids || !s.rule_bias)) return fail(RUN_EINVAL, "channel %d: %d rules and a list missing", c, s.n_rules);
+            if (s.min_length < 0) return fail(RUN_EINVAL, "channel %d: min_length %d is negative", c, s.min_length);
+            if (s.n_begin_suppress < 0 || (s.n_begin_suppress > 0 && !s.begin_suppress))
+                return fail(RUN_EINVAL, "channel %d: begin_suppress_tokens: %d ids and %s list", c, s.n_begin_suppress, s.begin_suppress ? "a" : "no");
+            size_t total = 0;
+            for (int r = 0; r < s.n_rules; ++r) {
+                if (s.rule_len[r] < 1 || s.rule_len[r] > MTTS_BIAS_RULE_LEN_MAX)
+                    return fail(RUN_EINVAL, "channel %d: rule %d has %d tokens, a rule has 1 to %d", c, r, s.rule_len[r], MTTS_BIAS_RULE_LEN_MAX);
+                if (!(s.rule_bias[r] < INFINITY)) return fail(RUN_EINVAL, "channel %d: rule %d has the bias %g (NaN and +inf are refused)", c, r, (double)s.rule_bias[r]);
+                for (int k = 0; k < s.rule_len[r]; ++k)
+                    if (s.rule_ids[total + k] < 0) return fail(RUN_EINVAL, "channel %d: rule %d holds the negative id %d", c, r, s.rule_ids[total + k]);
+                total += (size_t)s.rule_len[r];
+            }
+            for (int i = 0; i < s.n_begin_suppress; ++i)
+                if (s.begin_suppress[i] < 0) return fail(RUN_EINVAL, "channel %d: begin_suppress_tokens holds the negative id %d", c, s.begin_suppress[i]);
+            if (s.n_rules > 0) {
+                ch[c].len.assign(s.rule_len, s.rule_len + s.n_rules);
+                ch[c].beta.assign(s.rule_bias, s.rule_bias + s.n_rules);
+                ch[c].ids.assign(s.rule_ids, s.rule_ids + total);
+            }
+            ch[c].min_length = s.min_length;
+            if (s.n_begin_suppress > 0) ch[c].begin.assign(s.begin_suppress, s.begin_suppress + s.n_begin_suppress);
+        }
+        bias.ch.swap(ch);
+        return 0;
+    }
     bool has_row_adapters() const { return !row_adapters.empty(); }
     // mtts_begin / mtts_generate with B prompts: the one-shots move out and are back at their defaults, whatever the call
     // does next (RunOptions::check included)
@@ -129,6 +191,7 @@ public:
         o.floors = take_floors();
         o.typical = take_typical();
         o.bans = take_bans();
+        o.bias = take_bias();
         takes = 1;
         return o;
     }
@@ -136,6 +199,7 @@ public:
     std::vector<MttsSamplerFloors> take_floors() { return std::exchange(floors, {}); }
     std::vector<float> take_typical() { return std::exchange(typical, {}); }
     RunBans take_bans() { return std::exchange(bans, RunBans()); }
+    RunBias take_bias() { return std::exchange(bias, RunBias()); }
     // mtts_slot_submit* into `slot`: the same for that slot's adapter
     int take_slot_adapter(int slot) { return std::exchange(slot_adapter[slot], -1); }
 };
@@ -167,6 +231,12 @@ struct StepBufs {
     uint32_t* d_ban = nullptr;              // [slot][8][ban_words]: the step's banned tokens, rewritten by ban_kernel every step
     uint32_t* d_ban_static = nullptr;       // [8][ban_words]: the run's suppress_tokens per channel
     int32_t* d_hist = nullptr;              // [slot][hist_cap][8]: the prompt's slots, padding included (the generated ones are d_gen)
+    // sequence rules (mtts_set_sampler_bias); each exists once a run asked for what it serves
+    uint32_t* d_ban_begin = nullptr;        // [8][ban_words]: begin_suppress_tokens per channel, ORed in by ban_kernel at its one step
+    BiasRules* d_bias_rules = nullptr;      // [8]: the run's rules per channel, flattened (any rule)
+    uint32_t* d_bias_w = nullptr;           // [slot][8][ban_words]: the step's tokens with a term, rewritten by bias_kernel every step (a finite rule)
+    uint32_t* d_bias_static = nullptr;      // [8][ban_words]: the single-token finite rules per channel
+    MttsBiasTable* d_bias_tab = nullptr;    // [slot][8]: the step's (id, term) tables
     int gen_cap = 0;                        // steps a slot's rows hold
     int gt_stride = 0, gt_scr_cap = 0;      // innermost stride of d_gt_ids / d_gt_tlp; of gt_cand
     int rope_rows = 0;

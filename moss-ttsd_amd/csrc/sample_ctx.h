@@ -10,6 +10,8 @@ struct SampleCtx {         // resolved per (row, channel)
     LogitsPtr lg;
     const uint32_t* bm;
     const uint32_t* ban;   // this step's banned tokens, one bit each (mtts_set_sampler_bans); null: the run has none
+    const uint32_t* bias_w;        // this step's tokens with an additive term, one bit each (mtts_set_sampler_bias); null: none
+    const MttsBiasTable* bias_t;   // ... and their terms, ascending by id
     int V, mask_id, step, c;
     float penalty, temp;
     uint64_t seed;
@@ -20,13 +22,16 @@ __device__ __forceinline__ bool sample_ctx(SampleCtx& x, int b, int c_in, const 
                                            const uint16_t* logits17, int V0, int Vs, int Vs_pad,
                                            const uint32_t* bitmaps, int bm_words, const MttsSamplerCfg* cfgs,
                                            const LoopState* ls, const SeqState* seqs, int single_vocab, int single_mask,
-                                           int single_step, int single_channel, const uint32_t* bans = nullptr) {
+                                           int single_step, int single_channel, const uint32_t* bans = nullptr,
+                                           const uint32_t* bias_w = nullptr, const MttsBiasTable* bias_t = nullptr) {
     if (single_vocab > 0) {            // unit-test entry: one logits matrix [rows][vocab]
         x.c = single_channel; x.step = single_step; x.V = single_vocab; x.mask_id = single_mask;
         x.seed = 0; x.row_id = (uint32_t)b;
         x.lg = LogitsPtr{logits0 + (size_t)b * x.V, 0};
         x.bm = bitmaps ? bitmaps + (size_t)b * bm_words : nullptr;
         x.ban = bans ? bans + (size_t)b * ((x.V + 31) >> 5) : nullptr;       // unit-test entry: [rows][ceil(vocab / 32)]
+        x.bias_w = bias_w ? bias_w + (size_t)b * ((x.V + 31) >> 5) : nullptr;
+        x.bias_t = bias_w ? bias_t + b : nullptr;
     } else {
         if (ls->done) return false;
         const SeqState sq = seqs[b];
@@ -48,6 +53,8 @@ __device__ __forceinline__ bool sample_ctx(SampleCtx& x, int b, int c_in, const 
         if (x.c == 0 && x.step <= 6) x.mask_id = 152694;
         x.bm = bitmaps ? bitmaps + ((size_t)b * 8 + x.c) * bm_words : nullptr;
         x.ban = bans ? bans + ((size_t)b * 8 + x.c) * bm_words : nullptr;    // laid out like the history bitmaps
+        x.bias_w = bias_w ? bias_w + ((size_t)b * 8 + x.c) * bm_words : nullptr;
+        x.bias_t = bias_w ? bias_t + ((size_t)b * 8 + x.c) : nullptr;
     }
     const MttsSamplerCfg cfg = cfgs[x.c];
     x.penalty = (x.bm && cfg.repetition_penalty > 0.f) ? cfg.repetition_penalty : 0.f;

@@ -43,10 +43,22 @@ __device__ __forceinline__ uint32_t fkey(float f) {
 // (x.ban: mtts_set_sampler_bans; null in a run without bans) is at -inf like the masked id, before penalty and temperature.
 // Every sampler pass reads scores through here, so a row whose every token is banned is a row of -inf to all of them:
 // the argmax merges keep the lowest id (0), no candidate is collected, and the kernels below give token 0 with lp NaN.
+// A token whose bit is set in x.bias_w (mtts_set_sampler_bias; null in a run without finite rules) carries an additive term
+// this step: one fp32 addition on the fp32 value of the raw logit, behind the masks and in front of the penalty, which
+// therefore sees the sign of raw + term (HF's order: SequenceBias, then RepetitionPenalty).  The stored logits stay raw.
+__device__ __forceinline__ float bias_term(const MttsBiasTable* __restrict__ t, int i) {
+    int lo = 0, hi = min(t->n, MTTS_BIAS_RULES_MAX);
+    while (lo < hi) {                   // the first entry with ids[k] >= i
+        const int mid = (lo + hi) >> 1;
+        if (t->ids[mid] < i) lo = mid + 1; else hi = mid;
+    }
+    return (lo < MTTS_BIAS_RULES_MAX && lo < t->n && t->ids[lo] == i) ? t->term[lo] : 0.f;
+}
 __device__ __forceinline__ float proc_score(const SampleCtx& x, int i) {
     if (i == x.mask_id) return -INFINITY;
     if (x.ban && (x.ban[i >> 5] >> (i & 31)) & 1u) return -INFINITY;
     float s = x.lg.f32 ? ((const float*)x.lg.p)[i] : bf2f(((const uint16_t*)x.lg.p)[i]);
+    if (x.bias_w && (x.bias_w[i >> 5] >> (i & 31)) & 1u) s = s + bias_term(x.bias_t, i);
     if (x.penalty > 0.f && (x.bm[i >> 5] >> (i & 31)) & 1u) s = (s < 0.f) ? s * x.penalty : s / x.penalty;
     if (x.temp > 0.f) s = s / x.temp;
     return s;
@@ -121,7 +133,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_scan_kernel(
     const int b = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel, sc.ban)) return;
+                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     const bool want_hist = cfg.do_sample && cfg.top_k > 0 && cfg.top_k < x.V;
     for (int i = tid; i < 2048; i += SAMP_T) hist[i] = 0;
@@ -236,7 +248,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_collect_kernel(
     const int b = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel, sc.ban)) return;
+                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     if (!cfg.do_sample) return;
     // no top-k (every finite score is a candidate) or a top_k beyond the candidate buffer: nothing to collect, the row
@@ -493,7 +505,7 @@ __device__ __forceinline__ void sample_final_body(
     const int b = blockIdx.y;
     SampleCtx x;
     if (!sample_ctx(x, b, blockIdx.x, logits0, logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, single_vocab,
-                    single_mask, single_step, single_channel, sc.ban)) return;
+                    single_mask, single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     const bool big = single_vocab > 0 ? (single_vocab > SAMP_CAND) : (x.c == 0 && big_channel0);
     const int out_slot = b * 8 + x.c;
@@ -986,7 +998,7 @@ __device__ __forceinline__ void sample_full_body(
     if (!flag) return;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel, sc.ban)) return;
+                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     uint16_t* bins = (uint16_t*)(sc.full_val + (size_t)b * full_cap);  // level-0 bin of every token (0xffff: -inf)
     uint32_t* keys = (uint32_t*)(sc.full_idx + (size_t)b * full_cap);  // order-preserving key of every processed score
@@ -1278,10 +1290,11 @@ __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __
 // single_vocab > 0: the unit-test entry, hist [rows][hist_cap] of one channel with lengths single_lens.
 #define BAN_T 256
 __global__ __launch_bounds__(BAN_T) void ban_kernel(
-    uint32_t* __restrict__ ban, const uint32_t* __restrict__ stat, int words, const BanCfg* __restrict__ cfgs,
-    const int32_t* __restrict__ hist, int hist_cap, const int32_t* __restrict__ gen, int V0, int Vs, int eos,
+    uint32_t* __restrict__ ban, const uint32_t* __restrict__ stat, const uint32_t* __restrict__ begin, int words,
+    const BanCfg* __restrict__ cfgs, const int32_t* __restrict__ hist, int hist_cap, const int32_t* __restrict__ gen, int V0, int Vs, int eos,
     const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs, const int32_t* __restrict__ single_lens, int single_vocab) {
     __shared__ int32_t suf[MTTS_NGRAM_MAX];
+    const uint32_t* bp = nullptr;       // begin_suppress_tokens of the channel, at its one step
     const int b = blockIdx.y, tid = threadIdx.x;
     int V, base, glen, hs;
     const int32_t *hp, *gp;
@@ -1305,11 +1318,13 @@ __global__ __launch_bounds__(BAN_T) void ban_kernel(
         if (base > hist_cap) cfg.ngram = 0;         // (the host refuses such a prompt: nothing past the row is ever read)
         hp = hist + (size_t)b * hist_cap * 8 + c; gp = gen + (size_t)b * ls->gen_cap * 8 + c;
         out = ban + ((size_t)b * 8 + c) * words; sp = stat + (size_t)c * words;
-        eos_on = sq.step < cfg.eos_below;
+        eos_on = sq.step < cfg.eos_below || base + sq.step < cfg.min_length;         // min_new_tokens; min_length against len(h)
+        if (begin && sq.step == 7) bp = begin + (size_t)c * words;                  // len(h) == base + 7, HF's begin_index
     }
     const int nw = (V + 31) >> 5;                   // (<= words; bits at and above V are never set)
     for (int w = tid; w < nw; w += BAN_T) {
         uint32_t v = sp[w];
+        if (bp) v |= bp[w];
         if (eos_on && eos >= 0 && eos < V && (eos >> 5) == w) v |= 1u << (eos & 31);
         out[w] = v;
     }
@@ -1329,17 +1344,129 @@ __global__ __launch_bounds__(BAN_T) void ban_kernel(
 }
 static long long g_ban_launches = 0;        // launches of ban_kernel (test hook: mtts_debug_ban_launches)
 long long mtts_ban_launches() { return g_ban_launches; }
-void launch_ban(uint32_t* ban, const uint32_t* stat, int words, const BanCfg* cfgs, const int32_t* hist, int hist_cap,
+void launch_ban(uint32_t* ban, const uint32_t* stat, const uint32_t* begin, int words, const BanCfg* cfgs, const int32_t* hist, int hist_cap,
                 const int32_t* gen, int V0, int Vs, int eos, const LoopState* ls, const SeqState* seqs, int B, hipStream_t st) {
     ++g_ban_launches;
-    hipLaunchKernelGGL(ban_kernel, dim3(8, B), dim3(BAN_T), 0, st, ban, stat, words, cfgs, hist, hist_cap, gen, V0, Vs, eos, ls, seqs,
+    hipLaunchKernelGGL(ban_kernel, dim3(8, B), dim3(BAN_T), 0, st, ban, stat, begin, words, cfgs, hist, hist_cap, gen, V0, Vs, eos, ls, seqs,
                        (const int32_t*)nullptr, 0);
 }
 void launch_ban_single(uint32_t* ban, const uint32_t* stat, const BanCfg* cfg1, const int32_t* hist, const int32_t* lens, int rows,
                        int cap, int vocab, int eos, hipStream_t st) {
     ++g_ban_launches;
-    hipLaunchKernelGGL(ban_kernel, dim3(1, rows), dim3(BAN_T), 0, st, ban, stat, (vocab + 31) >> 5, cfg1, hist, cap, (const int32_t*)nullptr,
-                       vocab, vocab, eos, (const LoopState*)nullptr, (const SeqState*)nullptr, lens, vocab);
+    hipLaunchKernelGGL(ban_kernel, dim3(1, rows), dim3(BAN_T), 0, st, ban, stat, (const uint32_t*)nullptr, (vocab + 31) >> 5, cfg1, hist, cap,
+                       (const int32_t*)nullptr, vocab, vocab, eos, (const LoopState*)nullptr, (const SeqState*)nullptr, lens, vocab);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Sequence rules (mtts_set_sampler_bias; launch.h: launch_bias), behind ban_kernel in the step graph.  One block per (row,
+// channel) the sampler is about to evaluate.  All threads rewrite the pair's bias words from the channel's static words
+// (the single-token finite rules, staged by the host) -- an overwrite, so it is also the per-step clear.  Meanwhile lane
+// r of the first wave tests rule r: a rule of L > 1 tokens matches when the history holds L tokens (HF skips a rule longer
+// than its context) and its last L-1 are the rule's prefix; one of a single token always; the history is indexed as in ban_kernel.  Behind the barrier the same wave ORs the last
+// token of every matching -inf rule into the pair's ban words, the bit of every finite hit into its bias words, and builds
+// the table: the first hit of a token (in rule order) is its leader, which sums the token's chain -- its own beta, then
+// the beta of every later hit of the token, one fp32 addition each, the order in which the host laid the rules out -- and
+// writes (id, term) at the rank of its id among the leaders.  One lane per token, a fixed order, no float atomics: words
+// and table are the same bits run to run.  OR into the ban words is order-free.
+// single_vocab > 0: the unit-test entry, hist [rows][hist_cap] of one channel with lengths single_lens.
+#define BIAS_T 256
+static_assert(BIAS_RULES == 64 && BIAS_RULES == MTTS_BIAS_RULES_MAX && BIAS_RULE_LEN == MTTS_BIAS_RULE_LEN_MAX, "one rule per lane of a wave");
+__global__ __launch_bounds__(BIAS_T) void bias_kernel(
+    uint32_t* __restrict__ ban, uint32_t* __restrict__ bias_w, const uint32_t* __restrict__ bias_stat, MttsBiasTable* __restrict__ tabs,
+    int words, const BiasRules* __restrict__ rules, const int32_t* __restrict__ hist, int hist_cap, const int32_t* __restrict__ gen,
+    int V0, int Vs, const LoopState* __restrict__ ls, const SeqState* __restrict__ seqs, const int32_t* __restrict__ single_lens,
+    int single_vocab) {
+    __shared__ int32_t s_tok[BIAS_RULES];
+    __shared__ float s_beta[BIAS_RULES];
+    __shared__ int32_t s_hit[BIAS_RULES];           // 0: no hit, 1: a finite one, 2: a ban
+    __shared__ int32_t s_lead[BIAS_RULES];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int V, base, glen, hs;
+    const int32_t *hp, *gp;
+    const uint32_t* sp;
+    uint32_t *banw, *outw;
+    MttsBiasTable* tab;
+    const BiasRules* R;
+    if (single_vocab > 0) {
+        V = single_vocab; R = rules;
+        base = min(max(single_lens[b], 0), hist_cap); glen = 0; hs = 1;
+        hp = hist + (size_t)b * hist_cap; gp = nullptr;
+        const size_t row = (size_t)b * ((V + 31) >> 5);
+        banw = ban ? ban + row : nullptr; outw = bias_w ? bias_w + row : nullptr; sp = bias_stat;
+        tab = tabs ? tabs + b : nullptr;
+    } else {
+        if (ls->done) return;
+        const SeqState sq = seqs[b];
+        if (!sq.active || !(sq.unfinished || sq.active == 2)) return;       // the rows sample_ctx evaluates
+        const int c = blockIdx.x;
+        V = c == 0 ? V0 : Vs; R = rules + c;
+        base = sq.base_length; glen = min(sq.step, ls->gen_cap); hs = 8;
+        hp = hist ? hist + (size_t)b * hist_cap * 8 + c : nullptr; gp = gen + (size_t)b * ls->gen_cap * 8 + c;
+        if (base > hist_cap) hp = nullptr;          // (the host refuses such a prompt: nothing past the row is ever read)
+        const size_t pair = (size_t)b * 8 + c;
+        banw = ban ? ban + pair * words : nullptr; outw = bias_w ? bias_w + pair * words : nullptr;
+        sp = bias_stat ? bias_stat + (size_t)c * words : nullptr;
+        tab = tabs ? tabs + pair : nullptr;
+    }
+    const int nw = (V + 31) >> 5;                   // (<= words; bits at and above V are never set)
+    if (outw)
+        for (int w = tid; w < nw; w += BIAS_T) outw[w] = sp ? sp[w] : 0u;
+    const int len = base + glen, nr = min(max(R->n, 0), BIAS_RULES);
+    int tok = -1, hit = 0;
+    float beta = 0.f;
+    if (tid < BIAS_RULES) {
+        if (tid < nr) {
+            const int L = min(max(R->len[tid], 1), BIAS_RULE_LEN);
+            tok = R->ids[tid][L - 1]; beta = R->beta[tid];
+            bool m = tok >= 0 && tok < V && (L == 1 || (len >= L && (hp || len - (L - 1) >= base)));
+            for (int k = 0; m && k < L - 1; ++k) {
+                const int i = len - (L - 1) + k;
+                m = (i < base ? hp[(size_t)i * hs] : gp[(size_t)(i - base) * hs]) == R->ids[tid][k];
+            }
+            if (m) hit = beta == -INFINITY ? 2 : 1;
+        }
+        s_tok[tid] = tok; s_beta[tid] = beta; s_hit[tid] = hit;
+    }
+    __syncthreads();                                // the static words are written, the hits are in LDS
+    bool lead = false;
+    if (tid < BIAS_RULES) {
+        if (hit == 2 && banw) atomicOr(&banw[tok >> 5], 1u << (tok & 31));
+        if (hit == 1 && outw) {
+            atomicOr(&outw[tok >> 5], 1u << (tok & 31));
+            lead = true;
+            for (int r = 0; r < tid; ++r) lead = lead && !(s_hit[r] == 1 && s_tok[r] == tok);
+        }
+        s_lead[tid] = lead ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid < BIAS_RULES && tab) {
+        if (lead) {
+            float term = beta;
+            int rank = 0;
+            for (int r = 0; r < nr; ++r) {
+                if (r > tid && s_hit[r] == 1 && s_tok[r] == tok) term = term + s_beta[r];
+                rank += (s_lead[r] && s_tok[r] < tok) ? 1 : 0;
+            }
+            tab->ids[rank] = tok; tab->term[rank] = term;
+        }
+        const int n = __popcll(__ballot(lead));
+        if (tid == 0) tab->n = n;
+    }
+}
+static long long g_bias_launches = 0;       // launches of bias_kernel (test hook: mtts_debug_bias_launches)
+long long mtts_bias_launches() { return g_bias_launches; }
+void launch_bias(uint32_t* ban, uint32_t* bias_w, const uint32_t* bias_stat, MttsBiasTable* tabs, int words, const BiasRules* rules,
+                 const int32_t* hist, int hist_cap, const int32_t* gen, int V0, int Vs, const LoopState* ls, const SeqState* seqs,
+                 int B, hipStream_t st) {
+    ++g_bias_launches;
+    hipLaunchKernelGGL(bias_kernel, dim3(8, B), dim3(BIAS_T), 0, st, ban, bias_w, bias_stat, tabs, words, rules, hist, hist_cap, gen, V0, Vs,
+                       ls, seqs, (const int32_t*)nullptr, 0);
+}
+void launch_bias_single(uint32_t* ban, uint32_t* bias_w, const uint32_t* bias_stat, MttsBiasTable* tabs, const BiasRules* rules1,
+                        const int32_t* hist, const int32_t* lens, int rows, int cap, int vocab, hipStream_t st) {
+    ++g_bias_launches;
+    hipLaunchKernelGGL(bias_kernel, dim3(1, rows), dim3(BIAS_T), 0, st, ban, bias_w, bias_stat, tabs, (vocab + 31) >> 5, rules1, hist, cap,
+                       (const int32_t*)nullptr, vocab, vocab, (const LoopState*)nullptr, (const SeqState*)nullptr, lens, vocab);
 }
 
 static SampleScratch g_dummy_scratch;

@@ -19,6 +19,18 @@ struct RowMeta {
     int32_t pad;
 };
 
+// One channel's sequence rules (mtts_set_sampler_bias) as the rule kernel reads them (sampler.hip: bias_kernel), flattened
+// by the host (staging.h: stage_bias_rules): the single-token rules first, then the longer ones in the caller's order, so
+// a token's fp32 chain is the rules' order.  Rule r is ids[r][0 .. len[r]), its last id the token that carries beta[r].
+#define BIAS_RULES 64         // MTTS_BIAS_RULES_MAX of include/mtts.h (sampler.hip checks that it is)
+#define BIAS_RULE_LEN 16      // MTTS_BIAS_RULE_LEN_MAX
+struct BiasRules {
+    int32_t n;
+    int32_t len[BIAS_RULES];
+    float beta[BIAS_RULES];
+    int32_t ids[BIAS_RULES][BIAS_RULE_LEN];
+};
+
 // The weight kinds that also exist as a sealed twin (gemm_sealed.hip)
 enum { WSEAL_GU = 0, WSEAL_DOWN = 1, WSEAL_HEAD0 = 2, WSEAL_HEADS = 3, WSEAL_KINDS = 4 };
 

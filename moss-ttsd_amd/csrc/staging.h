@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "kvpool.h"          // fail(), MTTS_EINVAL; shapes.h: RowMeta, MTTS_MAXR, MTTS_RCAP
@@ -98,6 +99,31 @@ static inline void stage_ban_static(const int32_t* ids, int n, int V, int words,
     std::fill(bm, bm + words, 0u);
     for (int i = 0; i < n; ++i)
         if (ids[i] >= 0 && ids[i] < V) bm[ids[i] >> 5] |= 1u << (ids[i] & 31);
+}
+// the sequence rules of one channel (mtts_set_sampler_bias) as the rule kernel reads them: n rules, rule r = the next len[r]
+// entries of ids with beta[r].  A rule with an id outside [0, V) is dropped -- it can never match or land on this channel,
+// and one list meets eight vocabularies.  The single-token rules go first and the longer ones follow in the caller's order:
+// a token's chain starts from its single-token value, as HF's starts from length_1_bias.  bias_stat [words] (null: not
+// wanted): the bits of the single-token finite rules, the static part of the bias words.  The caller has checked the
+// counts and lengths (PendingRun::set_bias); -> the rules kept
+static inline int stage_bias_rules(const int32_t* len, const int32_t* ids, const float* beta, int n, int V, int words, BiasRules* out,
+                                   uint32_t* bias_stat) {
+    *out = BiasRules();
+    if (bias_stat) std::fill(bias_stat, bias_stat + words, 0u);
+    for (int pass = 0; pass < 2; ++pass) {          // 0: the single-token rules, 1: the others
+        const int32_t* p = ids;
+        for (int r = 0; r < n; p += len[r], ++r) {
+            if ((len[r] == 1) != (pass == 0) || out->n >= BIAS_RULES || len[r] < 1 || len[r] > BIAS_RULE_LEN) continue;
+            bool inside = true;
+            for (int k = 0; k < len[r]; ++k) inside = inside && p[k] >= 0 && p[k] < V;
+            if (!inside) continue;
+            const int o = out->n++;
+            out->len[o] = len[r]; out->beta[o] = beta[r];
+            std::copy(p, p + len[r], out->ids[o]);
+            if (bias_stat && len[r] == 1 && beta[r] > -INFINITY) bias_stat[p[0] >> 5] |= 1u << (p[0] & 31);
+        }
+    }
+    return out->n;
 }
 // teacher-forcing tail tf_inputs[:, base+s, :] for s = 0..6 (modeling_asteroid.py:143-145): `toks` = those 7 slots,
 // tf [7][8]; `note` ends the message of a token outside its vocabulary

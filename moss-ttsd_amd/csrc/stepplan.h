@@ -79,7 +79,10 @@ struct StepState {
     bool forced = false, ch0_sampled = false, scores_on = false;     // the sampler's variants (decode)
     bool floors_on = false;         // a sampled channel of the run has a probability floor (mtts_set_sampler_floors)
     bool typical_on = false;        // a sampled channel of the run has a typical_p (mtts_set_sampler_typical)
-    bool bans_on = false;           // a channel of the run has a hard ban (mtts_set_sampler_bans): ban_kernel runs ahead of the sampler
+    bool bans_on = false;           // a channel of the run has a hard ban (mtts_set_sampler_bans, or a -inf rule, min_length or
+                                    // begin_suppress_tokens of mtts_set_sampler_bias): ban_kernel runs ahead of the sampler
+    bool bias_on = false;           // a channel has a sequence rule (mtts_set_sampler_bias): bias_kernel runs behind ban_kernel
+    bool bias_terms = false;        // ... a finite one: the sampler reads the bias words and tables
     int topk = 0;
     bool wseal_on[WSEAL_KINDS] = {false, false, false, false};       // the weight policy: the kind's decode GEMMs read the twin
     const char* pack_k_on = nullptr;    // [L] the KV read policy per layer; null: the engine keeps no sealed pages
@@ -106,14 +109,14 @@ struct StepPlan {
     bool sealed[WSEAL_KINDS] = {false, false, false, false};        // the GEMM reads the sealed twin
     bool head_persistent = false;   // ... the heads through the persistent kernel
     std::vector<LayerPlan> layers;  // empty on the F32 path
-    bool forced = false, ch0_sampled = false, scores_on = false, floors_on = false, typical_on = false, bans_on = false;
+    bool forced = false, ch0_sampled = false, scores_on = false, floors_on = false, typical_on = false, bans_on = false, bias_on = false, bias_terms = false;
     int topk = 0;
     int gemm_form[GEMM_KINDS] = {0, 0, 0, 0, 0, 0, 0};              // for describe(): a function of the fields above and the caps
     bool operator==(const StepPlan& o) const {
         return path == o.path && heads == o.heads && B == o.B && R == o.R && mb == o.mb && hmb == o.hmb && tiled == o.tiled &&
                lora == o.lora && fold == o.fold && std::equal(sealed, sealed + WSEAL_KINDS, o.sealed) &&
                head_persistent == o.head_persistent && layers == o.layers && forced == o.forced && ch0_sampled == o.ch0_sampled &&
-               scores_on == o.scores_on && floors_on == o.floors_on && typical_on == o.typical_on && bans_on == o.bans_on && topk == o.topk && std::equal(gemm_form, gemm_form + GEMM_KINDS, o.gemm_form);
+               scores_on == o.scores_on && floors_on == o.floors_on && typical_on == o.typical_on && bans_on == o.bans_on && bias_on == o.bias_on && bias_terms == o.bias_terms && topk == o.topk && std::equal(gemm_form, gemm_form + GEMM_KINDS, o.gemm_form);
     }
     bool operator!=(const StepPlan& o) const { return !(*this == o); }
 };
@@ -127,7 +130,7 @@ static inline StepPlan plan_step(const StepKnobs& k, const StepCaps& c, const St
     StepPlan p;
     const bool decode = s.heads == 1;
     p.heads = s.heads; p.B = s.B; p.R = s.R;
-    if (decode) { p.forced = s.forced; p.ch0_sampled = s.ch0_sampled; p.scores_on = s.scores_on; p.floors_on = s.floors_on; p.typical_on = s.typical_on; p.bans_on = s.bans_on; p.topk = s.topk; }
+    if (decode) { p.forced = s.forced; p.ch0_sampled = s.ch0_sampled; p.scores_on = s.scores_on; p.floors_on = s.floors_on; p.typical_on = s.typical_on; p.bans_on = s.bans_on; p.bias_on = s.bias_on; p.bias_terms = s.bias_on && s.bias_terms; p.topk = s.topk; }
     if (c.f32) { p.path = PATH_F32; return p; }
     // decode steps of a few dialogues: six launches per layer whose prologues redo the small kernels' work.  The small path
     // has no slabs for an adapter's delta; its arithmetic is the general path's, so nothing depends on which one runs
@@ -185,8 +188,8 @@ static inline std::string describe(const StepPlan& p) {
     snprintf(buf, sizeof(buf), "pass: %s B=%d R=%d heads=%d layers=%d\n", paths[p.path], p.B, p.R, p.heads, (int)p.layers.size());
     std::string out = buf;
     if (p.heads == 1) {
-        snprintf(buf, sizeof(buf), "sample:%s%s%s%s%s%s topk=%d\n", p.ch0_sampled ? " ch0_sampled" : " ch0_greedy", p.scores_on ? " scores" : "",
-                 p.floors_on ? " floors" : "", p.typical_on ? " typical" : "", p.bans_on ? " bans" : "", p.forced ? " forced" : "", p.topk);
+        snprintf(buf, sizeof(buf), "sample:%s%s%s%s%s%s%s topk=%d\n", p.ch0_sampled ? " ch0_sampled" : " ch0_greedy", p.scores_on ? " scores" : "",
+                 p.floors_on ? " floors" : "", p.typical_on ? " typical" : "", p.bans_on ? " bans" : "", p.bias_terms ? " bias" : p.bias_on ? " rules" : "", p.forced ? " forced" : "", p.topk);
         out += buf;
     }
     if (p.path == PATH_F32) return out;

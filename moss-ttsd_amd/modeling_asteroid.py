@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from mtts import adapters, ban_spec, synth, topk_spec, warp_spec
+from mtts import adapters, ban_spec, bias_spec, synth, topk_spec, warp_spec
 from mtts.engine import Engine
 
 _CFG_KEYS = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads",
@@ -75,6 +75,11 @@ class GenerationConfig:
         self.no_repeat_ngram_size = kw.get("no_repeat_ngram_size", 0)
         self.suppress_tokens = kw.get("suppress_tokens")
         self.min_new_tokens = kw.get("min_new_tokens")
+        # HF's SequenceBias / NoBadWords / MinLength / SuppressTokensAtBegin processors (mtts/bias_spec.py)
+        self.sequence_bias = kw.get("sequence_bias")
+        self.bad_words_ids = kw.get("bad_words_ids")
+        self.min_length = kw.get("min_length", 0)
+        self.begin_suppress_tokens = kw.get("begin_suppress_tokens")
         self.seed = kw.get("seed")
         self.num_return_sequences = kw.get("num_return_sequences", 1)
 
@@ -99,7 +104,10 @@ class GenerationConfig:
         they are processors, so in the global branch they join the dict whatever do_sample is (the reference's
         `[logits_processor] * channels` applies them on all eight channels), and HF's conditions are n not None and > 0,
         the list not None, m not None and > 0 with an eos_token_id.  A config that sets none gives the dicts it always gave.
-        min_length, begin_suppress_tokens, bad_words_ids and sequence_bias are not read."""
+        sequence_bias / bad_words_ids / min_length / begin_suppress_tokens (mtts/bias_spec.py) are processors too and travel
+        like the bans.  HF's conditions: sequence_bias, bad_words_ids and begin_suppress_tokens not None, min_length not None
+        and > 0 with an eos_token_id.  The lists of bad_words_ids equal to [eos_token_id] are dropped where the values are
+        marshalled (mtts.engine.sampler_bias).  Forced BOS / EOS, prefix constraints, guidance and top_h are not read."""
         if self.do_samples is not None:
             layers = list(self.layers or [])
             layers += [{}] * (channels - len(layers))
@@ -127,6 +135,12 @@ class GenerationConfig:
             one["suppress_tokens"] = ban["suppress_tokens"]
         if not off(ban["min_new_tokens"]) and self.eos_token_id is not None:
             one["min_new_tokens"] = ban["min_new_tokens"]
+        bias = {k: (over[k] if over.get(k) is not None else getattr(self, k)) for k in bias_spec.BIAS_KEYS}
+        for k in ("sequence_bias", "bad_words_ids", "begin_suppress_tokens"):
+            if bias[k] is not None:
+                one[k] = bias[k]
+        if not off(bias["min_length"]) and self.eos_token_id is not None:
+            one["min_length"] = bias["min_length"]
         return [one] * channels, [self.do_sample] * channels
 
 
@@ -500,7 +514,8 @@ class AsteroidTTSInstruct:
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=None, max_length=None, seed=None,
                  num_return_sequences=None, return_dict_in_generate=False, output_scores=False, adapter_names=None,
                  top_logprobs=None, min_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None,
-                 suppress_tokens=None, min_new_tokens=None, typical_p=None, **kw):
+                 suppress_tokens=None, min_new_tokens=None, typical_p=None, sequence_bias=None, bad_words_ids=None,
+                 min_length=None, begin_suppress_tokens=None, **kw):
         """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
         num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
         repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages.
@@ -516,7 +531,10 @@ class AsteroidTTSInstruct:
         global branch; with generation_config.do_samples set the floors are per channel and belong in layers[i].
         typical_p (HF's generate keyword; mtts/warp_spec.py): the same; 1.0 runs without it.
         no_repeat_ngram_size / suppress_tokens / min_new_tokens (HF's generate keywords): the same for the hard bans, which
-        act on greedy and sampled channels alike (mtts/ban_spec.py); refused with do_samples set, like the floors."""
+        act on greedy and sampled channels alike (mtts/ban_spec.py); refused with do_samples set, like the floors.
+        sequence_bias / bad_words_ids / min_length / begin_suppress_tokens (HF's generate keywords; mtts/bias_spec.py): the
+        same again -- an additive fp32 term on a token, always or behind a token sequence; multi-token bans; EOS kept out
+        while the channel is shorter than min_length; ids banned at the first free step.  Refused with do_samples set."""
         over = {k: v for k, v in (("min_p", min_p), ("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)) if v is not None}
         for name, v in over.items():
             warp_spec.check_floor(name, v, "generate(): ")
@@ -528,9 +546,14 @@ class AsteroidTTSInstruct:
         for name, v in bans.items():
             ban_spec.check_ban(name, v, "generate(): ")
         over.update(bans)
+        bias = {k: v for k, v in (("sequence_bias", sequence_bias), ("bad_words_ids", bad_words_ids), ("min_length", min_length),
+                                  ("begin_suppress_tokens", begin_suppress_tokens)) if v is not None}
+        for name, v in bias.items():
+            bias_spec.check_bias(name, v, "generate(): ")
+        over.update(bias)
         if over and self.generation_config.do_samples is not None:
             raise ValueError(f"generate({', '.join(over)}=...) with generation_config.do_samples set: the per-channel branch reads its "
-                             "warpers from generation_config.layers[i]; put the floors there")
+                             "warpers and processors from generation_config.layers[i]; put the floors there")
         k = 0
         if top_logprobs is not None:
             k = topk_spec.check_k(top_logprobs)
@@ -561,6 +584,7 @@ class AsteroidTTSInstruct:
             warp_spec.floors_of(lc, f"generation_config, channel {i}: ")       # a bad value: ValueError before the device is touched
             warp_spec.typical_of(lc, f"generation_config, channel {i}: ")
             ban_spec.bans_of(lc, f"generation_config, channel {i}: ")
+            bias_spec.bias_of(lc, f"generation_config, channel {i}: ")
         if n > 1 and not any(do_samples):
             # HF GenerationMixin: greedy search returns one sequence per prompt
             raise ValueError("Greedy methods (do_sample != True) without beam search do not support `num_return_sequences` "

@@ -31,6 +31,16 @@ class MttsSamplerBans(C.Structure):
                 ("suppress", C.POINTER(C.c_int32))]
 
 
+class MttsSamplerBias(C.Structure):
+    _fields_ = [("n_rules", C.c_int32), ("min_length", C.c_int32), ("n_begin_suppress", C.c_int32),
+                ("rule_len", C.POINTER(C.c_int32)), ("rule_ids", C.POINTER(C.c_int32)), ("rule_bias", C.POINTER(C.c_float)),
+                ("begin_suppress", C.POINTER(C.c_int32))]
+
+
+class MttsBiasTable(C.Structure):
+    _fields_ = [("n", C.c_int32), ("ids", C.c_int32 * 64), ("term", C.c_float * 64)]
+
+
 class MttsCodecConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "nq", "codebook_size", "rvq_dim", "quant_out_dim",
@@ -105,6 +115,8 @@ _SIGS = {
     "mtts_set_sampler_bans": (C.c_int32, [C.c_void_p, C.POINTER(MttsSamplerBans)]),
     "mtts_set_sampler_typical": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float)]),
     "mtts_debug_ban_launches": (C.c_int64, []),
+    "mtts_set_sampler_bias": (C.c_int32, [C.c_void_p, C.POINTER(MttsSamplerBias)]),
+    "mtts_debug_bias_launches": (C.c_int64, []),
     "mtts_slot_fork": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p]),
     "mtts_slot_states": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_slot_read": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
@@ -167,6 +179,11 @@ _SIGS = {
     "mtts_k_sample_typical": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg),
                                           C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.POINTER(MttsSamplerFloors), C.c_void_p, C.c_float, C.c_void_p]),
+    "mtts_k_sample_bias": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg),
+                                       C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.POINTER(MttsSamplerFloors), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_k_seq_bias": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MttsSamplerBias), C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_k_ngram_ban": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mtts_codec_last_error": (C.c_char_p, []),

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import ban_spec, capi, warp_spec
+from . import ban_spec, bias_spec, capi, warp_spec
 
 
 def sampler_cfgs(layers=None, do_samples=None):
@@ -74,6 +74,33 @@ def sampler_bans(layers=None):
         arr[i].no_repeat_ngram_size, arr[i].min_new_tokens, arr[i].n_suppress = n, m, len(sup)
         arr[i].suppress = C.cast(ids, C.POINTER(C.c_int32))
         on = on or n > 0 or m > 0 or len(sup) > 0
+    arr._keep = keep
+    return arr if on else None
+
+
+def sampler_bias(layers=None, eos_token_id=None):
+    """The sequence rules and step-conditioned bans of the same per-channel dicts -> MttsSamplerBias[8], or None when no
+    channel sets one (the run then launches and allocates what it did before they existed).  Keys `sequence_bias` (HF's dict
+    or list form), `bad_words_ids` (lists equal to [eos_token_id] are dropped, as HF drops them), `min_length` and
+    `begin_suppress_tokens` (HF's SequenceBias / NoBadWords / MinLength / SuppressTokensAtBegin processors; mtts/bias_spec.py
+    states the rule).  None, 0, {} or [] = absent.  Processors, not warpers: a greedy channel applies them like a sampled
+    one.  ValueError, naming the channel, for a bad value.  The array keeps its lists alive (`_keep`)."""
+    arr, on, keep = (capi.MttsSamplerBias * 8)(), False, []
+    for i in range(8):
+        lc = (layers[i] if layers and i < len(layers) else {}) or {}
+        rules, m, begin = bias_spec.bias_of(lc, f"layers[{i}]: ", eos_token_id)
+        flat = [t for ids, _ in rules for t in ids]
+        lens = (C.c_int32 * max(len(rules), 1))(*[len(ids) for ids, _ in rules])
+        ids = (C.c_int32 * max(len(flat), 1))(*flat)
+        beta = (C.c_float * max(len(rules), 1))(*[b for _, b in rules])
+        beg = (C.c_int32 * max(len(begin), 1))(*begin)
+        keep.append((lens, ids, beta, beg))
+        arr[i].n_rules, arr[i].min_length, arr[i].n_begin_suppress = len(rules), m, len(begin)
+        arr[i].rule_len = C.cast(lens, C.POINTER(C.c_int32))
+        arr[i].rule_ids = C.cast(ids, C.POINTER(C.c_int32))
+        arr[i].rule_bias = C.cast(beta, C.POINTER(C.c_float))
+        arr[i].begin_suppress = C.cast(beg, C.POINTER(C.c_int32))
+        on = on or bool(rules) or m > 0 or bool(begin)
     arr._keep = keep
     return arr if on else None
 
@@ -218,12 +245,14 @@ class Engine:
 
     def _set_floors_and_bans(self, layers, do_samples):
         """One-shots like takes: the floors and the hard bans of `layers` for the run that starts next, or none
-        (mtts_set_sampler_floors, mtts_set_sampler_typical, mtts_set_sampler_bans).  All are marshalled first: a bad value
-        leaves nothing pending."""
+        (mtts_set_sampler_floors, mtts_set_sampler_typical, mtts_set_sampler_bans, mtts_set_sampler_bias).  All are
+        marshalled first: a bad value leaves nothing pending."""
         floors, typical, bans = sampler_floors(layers, do_samples), sampler_typical(layers, do_samples), sampler_bans(layers)
+        bias = sampler_bias(layers, self.cfg.get("eos_token_id"))
         capi.check(self.lib.mtts_set_sampler_floors(self._h, floors))
         capi.check(self.lib.mtts_set_sampler_typical(self._h, typical))
         capi.check(self.lib.mtts_set_sampler_bans(self._h, bans))
+        capi.check(self.lib.mtts_set_sampler_bias(self._h, bias))
 
     def set_output_scores(self, on):
         """Sticky engine switch, read when the next run begins (begin / generate / sched_open): per-token
