@@ -247,6 +247,29 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* host_input_ids, const uint8_t* 
 int32_t mtts_step(MttsEngine* e, int32_t n_steps, void* stream);   /* n x (sample+update, forward); async */
 int32_t mtts_sync_state(MttsEngine* e, int32_t* steps_done, int32_t* all_finished, void* stream);
 int32_t mtts_read_generated(MttsEngine* e, int64_t* host_gen, int32_t capacity_steps, int32_t* n_steps);
+/* ---- the split step: the caller's per-step hooks (HF generate(logits_processor=, stopping_criteria=, streamer=); reference
+ * modeling_asteroid.py:109,129,161-168) ----
+ * One decode step of a run started with mtts_begin, in halves with the caller in between; all calls are stream-ordered on
+ * `stream` and return without waiting.  They replace one mtts_step(e, 1) and may alternate with mtts_step between steps.
+ * mtts_step_begin: everything in front of the sampler.  For every (row, channel) the sampler would evaluate this step the
+ * processed scores in front of the warpers are written as fp32: the two hard-coded masks, the bans and sequence rules of
+ * the run (-inf / an added term) and the repetition penalty; no temperature.  dev_scores0: [rows of the run][vocab_size
+ * padded to 32], channel 0; dev_scores17: [rows][7][speech_vocab_size padded to 32], channels 1..7; both device memory of
+ * the caller, 16-byte aligned, alive until mtts_step_finish returns.  Pad columns get -inf; rows the sampler skips
+ * (finished rows that cannot come back) are left untouched and never read.
+ * mtts_step_sample: the sampler on those buffers as the caller left them -- temperature, top-k, top-p, min_p, typical_p and
+ * the cutoffs, argmax or the Philox draw, output_scores as the log-softmax over the kept set; top_logprobs still reads the
+ * raw logits -- then the state machine.  A row of -inf gives token 0 with a NaN score.  dev_tokens (device int64
+ * [rows][8], or NULL): the tokens the step appended, padding and flushes included.
+ * mtts_step_finish: host_stop (one byte per row, or NULL) is the caller's stopping criteria for the rows as they stand
+ * after this step's tokens: a stopped row is finished (reference :166-168; a row inside its EOS flush finishes the flush
+ * first) and emits (eos, speech_pad x 7) from the next step on; then the KV page bookkeeping and the forward pass.  Called
+ * right after mtts_step_begin it runs mtts_step_sample itself.
+ * MTTS_ESTATE: no run, a scheduler run (mtts_sched_open), a call out of order, no step left; mtts_step refuses while a
+ * split step is in flight.  A run that never calls these launches, allocates and captures what it always did. */
+int32_t mtts_step_begin(MttsEngine* e, float* dev_scores0, float* dev_scores17, void* stream);
+int32_t mtts_step_sample(MttsEngine* e, int64_t* dev_tokens, void* stream);
+int32_t mtts_step_finish(MttsEngine* e, const uint8_t* host_stop, void* stream);
 /* ---- output_scores: per-token log-probabilities (HF generate(output_scores=True) reduced to what
  * compute_transition_scores(sequences, scores, normalize_logits=True) returns: one float per decision) ----
  * lp[g][r][c] = log_softmax(S)[d]: S = the channel's processed score row of step g (hard-coded masks, repetition penalty,
@@ -721,6 +744,14 @@ int32_t mtts_k_sample_bias(const void* dev_logits_bf16, int32_t rows, int32_t vo
                            int32_t mask_id, uint64_t seed, int32_t step, int32_t channel,
                            int32_t* dev_tokens, float* dev_logp, const MttsSamplerFloors* floors, const void* dev_ban,
                            float typical_p, const void* dev_bias_words, const MttsBiasTable* dev_bias_tab, void* stream);
+/* scores_materialize_kernel of the split step (mtts_step_begin) on one logits matrix, launched as the engine launches it
+ * (one block per row): dev_scores float [rows][vocab padded to 32] receives, per token, what mtts_k_sample_bias would sample
+ * from in front of the temperature -- mask_id, dev_ban and the terms at their places, the repetition penalty of `cfg`
+ * where the history bitmap has the token's bit -- and -inf in the pad columns.  dev_ban, dev_bias_words / dev_bias_tab as
+ * above, each NULL for none; dev_history_bitmap may be NULL (no penalty). */
+int32_t mtts_k_scores_materialize(const void* dev_logits_bf16, int32_t rows, int32_t vocab, const void* dev_history_bitmap,
+                                  const MttsSamplerCfg* cfg, int32_t mask_id, int32_t step, int32_t channel, const void* dev_ban,
+                                  const void* dev_bias_words, const MttsBiasTable* dev_bias_tab, float* dev_scores, void* stream);
 /* The kernels of mtts_set_top_logprobs on bare logits, launched as the engine launches them (the slice pass and the merge
  * when vocab > 4096, the single-block path otherwise): dev_logits [rows][vocab] bf16 bits, or fp32 when is_f32; mask_id
  * the one id at -inf (-1: none); dev_decisions int32 [rows].  dev_logp float [rows] = log_softmax(L)[decision],

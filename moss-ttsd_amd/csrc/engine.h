@@ -254,6 +254,9 @@ struct MttsEngine {
     int max_real = 0;
     uint64_t seed = 0;
     bool began = false, has_forced = false;
+    // the split step (mtts_step_begin / mtts_step_sample / mtts_step_finish): which half comes next, and what the halves share
+    int split_phase = 0;                // 0: between steps; 1: mtts_step_begin has run; 2: mtts_step_sample has run
+    float *split_scores0 = nullptr, *split_scores17 = nullptr;     // the caller's score rows of the step in flight
     // decode-step graphs: one captured step per (plan, KV page bound, bufs), replayed by mtts_step
     struct DestroyExec { void operator()(hipGraphExec_t g) const { hipGraphExecDestroy(g); } };
     StepGraphs<hipGraphExec_t, DestroyExec> graphs;
@@ -281,20 +284,21 @@ static inline bool rows_carry_adapters(const MttsEngine* e) {
 }
 // What plan_step is asked about a pass of R rows: the run's options and the two read policies as they stand now.  The
 // only place that gathers one.
-static inline StepState step_state(const MttsEngine* e, int heads, int R, int pages_bound, bool lora) {
+static inline StepState step_state(const MttsEngine* e, int heads, int R, int pages_bound, bool lora, bool split = false) {
     StepState s;
     s.heads = heads; s.B = e->B; s.R = R; s.pages_bound = pages_bound; s.lora = lora;
     s.forced = e->has_forced; s.ch0_sampled = e->ch0_sampled != 0; s.scores_on = e->scores_on != 0; s.floors_on = e->floors_on != 0; s.typical_on = e->typical_on != 0;
     s.bans_on = e->bans_on != 0; s.bias_on = e->bias_on != 0; s.bias_terms = e->bias_terms != 0;
-    s.topk = e->topk_on;
+    s.topk = e->topk_on; s.split = split;
     for (int k = 0; k < WSEAL_KINDS; ++k) s.wseal_on[k] = e->wseal_on[k] != 0;
     if (e->kpack) s.pack_k_on = e->pack_k_on.data();
     if (e->vpack) s.pack_v_on = e->pack_v_on.data();
     return s;
 }
 // the plan of the decode step the engine would run now at this page bound
-static inline StepPlan decode_plan(const MttsEngine* e, int pages_bound) {
-    return plan_step(e->knobs, e->caps, step_state(e, 1, round_up(e->B, 32), pages_bound, rows_carry_adapters(e)));
+// (split: the step issued in halves, mtts_step_begin / mtts_step_finish)
+static inline StepPlan decode_plan(const MttsEngine* e, int pages_bound, bool split = false) {
+    return plan_step(e->knobs, e->caps, step_state(e, 1, round_up(e->B, 32), pages_bound, rows_carry_adapters(e), split));
 }
 
 // layer n's sealed pools, each null where the plan says bf16 pages

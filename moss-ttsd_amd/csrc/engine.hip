@@ -1081,7 +1081,7 @@ static int begin_run(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int
     // (`unfinished | needs_additional_steps > 0`, modeling_asteroid.py:165-168)
     int max_steps = max_length - base + LINGER_STEPS;          // the least the engine must have room for; widened below
     e->B = R; e->T = T; e->base_length = base; e->max_length = max_length; e->takes = takes;
-    e->seed = seed; e->steps_issued = 0; e->has_forced = false;
+    e->seed = seed; e->steps_issued = 0; e->has_forced = false; e->split_phase = 0;
     e->n_real.assign(R, 0);
     e->max_real = 0;
     std::vector<StageSeq> seqs(B);     // prompt b: its real tokens, into row b*takes; the last one's logits start the run
@@ -1210,7 +1210,9 @@ int32_t mtts_begin(MttsEngine* e, const int64_t* ids, const uint8_t* mask, int32
 // launches repeat until the KV page bound grows: they are captured once per bound into a hipGraph and replayed --
 // a dependent kernel costs ~1.5 us inside a graph against ~2.9 us launched on a stream (tools/latency_probe.hip).
 // The plan (decode_plan) says which launches; it is also what a captured step is found by.
-static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipStream_t st, int64_t kvtok) {
+// The three parts below are what the split step (mtts_step_begin / mtts_step_sample / mtts_step_finish) issues one by one.
+// step_front: this step's ban words and rule tables; -> the sampler's scratch with what they wrote
+static SampleScratch step_front(MttsEngine* e, const StepPlan& plan, hipStream_t st) {
     const StepBufs& b = e->bufs;
     SampleScratch sscr = e->sscr;
     sscr.slice_sum = b.sscr_slice_sum; sscr.lp = b.sscr_lp;
@@ -1224,7 +1226,13 @@ static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipSt
                     b.ban_words, b.d_bias_rules, b.d_hist, b.hist_cap, b.d_gen, e->V0, e->Vs, e->d_ls, e->d_seqs, plan.B, st);
         if (plan.bias_terms) { sscr.bias_w = b.d_bias_w; sscr.bias_t = b.d_bias_tab; }
     }
-    launch_sample(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
+    return sscr;
+}
+// step_decide: the sampler on score rows l0 / l17 (the heads' logits; the split step: the caller's fp32 rows, sscr.ext), then
+// top_logprobs on the heads' logits and the state machine
+static void step_decide(MttsEngine* e, const StepPlan& plan, const SampleScratch& sscr, const void* l0, const void* l17, hipStream_t st) {
+    const StepBufs& b = e->bufs;
+    launch_sample(l0, l17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls,
                   e->d_seqs, e->seed, e->d_decisions, &e->d_ls->error, plan.B, sscr, plan.ch0_sampled,
                   full_cap_for(e->V0), plan.scores_on, (plan.floors_on || plan.typical_on) ? e->d_floors : nullptr,
                   plan.typical_on ? e->d_typical : nullptr, st);
@@ -1238,6 +1246,10 @@ static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipSt
                   e->d_seqs, e->d_meta, e->d_bitmaps, e->bm_words, e->d_ls, e->cfg.eos_token_id,
                   e->cfg.speech_pad_token, e->cfg.speech_range_lo, e->cfg.speech_range_hi,
                   plan.scores_on ? b.sscr_lp : nullptr, plan.scores_on ? b.d_lp : nullptr, gt, st);
+}
+static int step_body(MttsEngine* e, const StepPlan& plan, int pages_bound, hipStream_t st, int64_t kvtok) {
+    const SampleScratch sscr = step_front(e, plan, st);
+    step_decide(e, plan, sscr, e->logits0, e->logits17, st);
     return forward_rows(e, plan, e->d_cur, e->d_meta, pages_bound, st, kvtok);
 }
 
@@ -1263,22 +1275,28 @@ static int step_graph(MttsEngine* e, int pages, hipGraphExec_t* out) {
     return MTTS_OK;
 }
 
+// The step about to be issued appends one token per live dialogue at position n_real + steps_issued: take its page if that
+// crosses a page boundary (the host's view of "live" lags the device by at most one poll: a dialogue that has just
+// finished may get one page it never writes, returned with the others).  -> the step's KV page bound
+static int step_pages(MttsEngine* e, hipStream_t st, int* pages_bound) {
+    int len_bound = 1;
+    const auto ship = ship_on(e, st);
+    for (int b = 0; b < e->B; ++b) {
+        if (!e->slot_live[b]) continue;
+        const int len = e->n_real[b] + e->steps_issued + 1;
+        len_bound = std::max(len_bound, len);
+        TRY(e->pool.grow(b, pages_for(len), ship));
+    }
+    TRY(e->pool.flush(ship));
+    *pages_bound = pages_for(len_bound);
+    return MTTS_OK;
+}
+
 static int issue_steps(MttsEngine* e, int n, hipStream_t st) {
     for (int i = 0; i < n; ++i) {
         if (e->steps_issued >= e->max_steps) break;
-        // this step appends one token per live dialogue at position n_real + steps_issued: take its page if that
-        // crosses a page boundary (the host's view of "live" lags the device by at most one poll: a dialogue that
-        // has just finished may get one page it never writes, returned with the others)
-        int len_bound = 1;
-        const auto ship = ship_on(e, st);
-        for (int b = 0; b < e->B; ++b) {
-            if (!e->slot_live[b]) continue;
-            const int len = e->n_real[b] + e->steps_issued + 1;
-            len_bound = std::max(len_bound, len);
-            TRY(e->pool.grow(b, pages_for(len), ship));
-        }
-        TRY(e->pool.flush(ship));
-        const int pages_bound = pages_for(len_bound);
+        int pages_bound = 0;
+        TRY(step_pages(e, st, &pages_bound));
         if (e->knobs.use_graphs && !e->prof) {
             // the attention grids are sized by the page bound: round it up to a whole pass-B chunk so that one
             // graph serves ATT_PB pages (512 steps); blocks past a row's last page exit at once
@@ -1301,8 +1319,72 @@ static int issue_steps(MttsEngine* e, int n, hipStream_t st) {
 
 int32_t mtts_step(MttsEngine* e, int32_t n_steps, void* stream) {
     if (!e || !e->began) return fail(MTTS_ESTATE, "mtts_begin has not run");
+    if (e->split_phase) return fail(MTTS_ESTATE, "mtts_step in the middle of a split step: mtts_step_finish first");
     HIPCHK(hipSetDevice(e->device));
     return issue_steps(e, n_steps, S(stream));
+}
+
+// ---- the split step: generate(logits_processor=, stopping_criteria=, streamer=) ------------------------------------------
+// One decode step in up to three calls with the caller in between (include/mtts.h).  The launches are those of step_body,
+// in its order, on the caller's stream: a split step is never captured, and its plan carries `split`, so it is never taken
+// for a captured unsplit step either.
+static int split_check(MttsEngine* e, const char* who) {
+    if (!e || !e->began) return fail(MTTS_ESTATE, "%s: mtts_begin has not run", who);
+    if (e->continuous) return fail(MTTS_ESTATE, "%s: the scheduler's steps are not split (mtts_sched_open is running)", who);
+    return MTTS_OK;
+}
+int32_t mtts_step_begin(MttsEngine* e, float* dev_scores0, float* dev_scores17, void* stream) {
+    TRY(split_check(e, "mtts_step_begin"));
+    if (e->split_phase) return fail(MTTS_ESTATE, "mtts_step_begin: a split step is in flight, mtts_step_finish first");
+    if (!dev_scores0 || !dev_scores17 || ((uintptr_t)dev_scores0 & 15) || ((uintptr_t)dev_scores17 & 15))
+        return fail(MTTS_EINVAL, "mtts_step_begin: the score buffers are null or not 16-byte aligned");
+    if (e->steps_issued >= e->max_steps) return fail(MTTS_ESTATE, "mtts_step_begin: the run has no step left (%d issued)", e->steps_issued);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = S(stream);
+    const StepPlan plan = decode_plan(e, 1, true);      // (the page bound plays no part in front of the forward pass)
+    const SampleScratch sscr = step_front(e, plan, st);
+    launch_scores_materialize(e->logits0, e->logits17, e->V0, e->Vs, e->Vs_pad, e->d_bitmaps, e->bm_words, e->d_scfg, e->d_ls, e->d_seqs,
+                              plan.B, sscr, dev_scores0, dev_scores17, st);
+    HIPCHK(hipGetLastError());
+    e->split_scores0 = dev_scores0; e->split_scores17 = dev_scores17;
+    e->split_phase = 1;
+    return MTTS_OK;
+}
+int32_t mtts_step_sample(MttsEngine* e, int64_t* dev_tokens, void* stream) {
+    TRY(split_check(e, "mtts_step_sample"));
+    if (e->split_phase != 1) return fail(MTTS_ESTATE, "mtts_step_sample: mtts_step_begin has not run for this step");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = S(stream);
+    const StepPlan plan = decode_plan(e, 1, true);
+    SampleScratch sscr = e->sscr;       // no ban words, no terms: the rows carry them
+    sscr.slice_sum = e->bufs.sscr_slice_sum; sscr.lp = e->bufs.sscr_lp;
+    sscr.ext = 1;
+    step_decide(e, plan, sscr, e->split_scores0, e->split_scores17, st);
+    if (dev_tokens) launch_step_tokens(e->d_cur, dev_tokens, e->d_ls, st);
+    HIPCHK(hipGetLastError());
+    e->split_phase = 2;
+    return MTTS_OK;
+}
+int32_t mtts_step_finish(MttsEngine* e, const uint8_t* host_stop, void* stream) {
+    TRY(split_check(e, "mtts_step_finish"));
+    if (!e->split_phase) return fail(MTTS_ESTATE, "mtts_step_finish: mtts_step_begin has not run for this step");
+    if (e->split_phase == 1) TRY(mtts_step_sample(e, nullptr, stream));
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = S(stream);
+    if (host_stop) {
+        StopMask m;                     // (travels as a kernel argument: no copy to order, no buffer to keep)
+        memset(m.row, 0, sizeof(m.row));
+        memcpy(m.row, host_stop, (size_t)e->B);
+        launch_stop_rows(m, e->d_seqs, e->d_meta, e->d_ls, st);
+    }
+    int pages_bound = 0;
+    TRY(step_pages(e, st, &pages_bound));
+    int64_t kvtok = 0;
+    for (int b = 0; b < e->B; ++b) if (e->slot_live[b]) kvtok += e->n_real[b] + e->steps_issued + 1;
+    TRY(forward_rows(e, decode_plan(e, pages_bound, true), e->d_cur, e->d_meta, pages_bound, st, kvtok));
+    e->steps_issued++;
+    e->split_phase = 0;
+    return MTTS_OK;
 }
 
 int32_t mtts_sync_state(MttsEngine* e, int32_t* steps_done, int32_t* all_finished, void* stream) {
@@ -1743,7 +1825,7 @@ int32_t mtts_sched_open(MttsEngine* e, int32_t B, int32_t gen_cap, const MttsSam
     e->scores_on = e->pending.output_scores; e->topk_on = e->pending.top_logprobs;      // the sticky switches only
     TRY(start_outputs(e, gen_cap, st));
     TRY(start_bans(e, bans, bias, st));
-    e->B = B; e->steps_issued = 0; e->has_forced = false; e->continuous = true;
+    e->B = B; e->steps_issued = 0; e->has_forced = false; e->continuous = true; e->split_phase = 0;
     e->max_steps = 1 << 30;
     e->n_real.assign(B, 0);
     e->max_real = 0;

@@ -481,6 +481,30 @@ int32_t mtts_k_sample_bias(const void* logits, int32_t rows, int32_t vocab, cons
                     dev_bias_words, dev_bias_tab);
 }
 
+// scores_materialize_kernel of the split step (sampler.hip) on one logits matrix.
+int32_t mtts_k_scores_materialize(const void* logits, int32_t rows, int32_t vocab, const void* bitmap, const MttsSamplerCfg* cfg,
+                                  int32_t mask_id, int32_t step, int32_t channel, const void* dev_ban, const void* dev_bias_words,
+                                  const MttsBiasTable* dev_bias_tab, float* dev_scores, void* stream) {
+    if (!logits || !cfg || !dev_scores || rows < 1 || rows > MTTS_RCAP || vocab < 1 || channel < 0 || channel > 7 || mask_id >= vocab)
+        return fail(MTTS_EINVAL, "scores_materialize: bad argument");
+    if ((dev_bias_words == nullptr) != (dev_bias_tab == nullptr)) return fail(MTTS_EINVAL, "scores_materialize: bias words and bias tables come together");
+    if ((uintptr_t)dev_scores & 15) return fail(MTTS_EINVAL, "scores_materialize: dev_scores is not 16-byte aligned");
+    hipStream_t st = S(stream);
+    MttsSamplerCfg h[8];
+    for (int i = 0; i < 8; ++i) h[i] = *cfg;
+    DevBufs hb;
+    MttsSamplerCfg* d = nullptr;
+    TRY(hb.get(&d, 8));
+    HIPCHK(hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice));
+    SampleScratch sc;
+    sc.ban = (const uint32_t*)dev_ban;
+    sc.bias_w = (const uint32_t*)dev_bias_words; sc.bias_t = dev_bias_tab;
+    launch_scores_materialize_single(logits, rows, vocab, (const uint32_t*)bitmap, (vocab + 31) / 32, d, mask_id, step, channel, sc, dev_scores, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return MTTS_OK;
+}
+
 // The ban kernel of a decode step (sampler.hip: ban_kernel) on bare histories of one channel.
 int32_t mtts_k_ngram_ban(const int32_t* dev_hist, const int32_t* dev_lens, int32_t rows, int32_t cap, int32_t n,
                          const int32_t* host_static, int32_t n_static, int32_t vocab, int32_t eos_id, int32_t eos_on,

@@ -150,6 +150,9 @@ struct SampleScratch {
     // no finite rule
     const uint32_t* bias_w = nullptr;
     const MttsBiasTable* bias_t = nullptr;
+    // externally scored rows (the split step: mtts_step_begin / mtts_step_finish): the logits pointers the sampler kernels get
+    // are fp32 rows in the logits' layout that already carry masks, bans, terms and penalty (sample_ctx.h)
+    int ext = 0;
 };
 void launch_sample(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps,
                    int bm_words, const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, uint64_t seed,
@@ -200,6 +203,25 @@ void launch_update(const int32_t* decisions, int32_t* dec_log, const int32_t* fo
                    int32_t* gen, int32_t* cur_tokens, SeqState* seqs, RowMeta* meta, uint32_t* bitmaps, int bm_words,
                    LoopState* ls, int eos, int spad, int sp_lo, int sp_hi, const float* lp_in, float* lp_out,
                    const GenTopkOut& gt, hipStream_t st);
+// The split step (mtts_step_begin / mtts_step_sample / mtts_step_finish; sampler.hip).
+// launch_scores_materialize: one block per (row, channel) the sampler would evaluate this step writes that pair's processed
+// scores in front of the warpers -- proc_score without the temperature: masks, bans (sc.ban), terms (sc.bias_w / sc.bias_t),
+// repetition penalty -- as fp32 into out0 [B][V0 padded to 32] / out17 [B][7][Vs_pad]; the pad columns get -inf, rows the
+// sampler skips are left untouched.  The sampler then runs on those buffers with sc.ext = 1.
+void launch_scores_materialize(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps, int bm_words,
+                               const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, int B, const SampleScratch& sc,
+                               float* out0, float* out17, hipStream_t st);
+// one logits matrix [rows][vocab] of bf16 bits -> out [rows][vocab padded to 32] (sc.ban / sc.bias_w / sc.bias_t: per row)
+void launch_scores_materialize_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words, const MttsSamplerCfg* cfgs8,
+                                      int mask_id, int step, int channel, const SampleScratch& sc, float* out, hipStream_t st);
+// tokens [B][8] int64 = the tokens update_kernel appended this step (cur_tokens); rows at and above ls->B are left alone
+void launch_step_tokens(const int32_t* cur_tokens, int64_t* tokens, const LoopState* ls, hipStream_t st);
+// The caller's stopping criteria (reference modeling_asteroid.py:166-168), behind update_kernel: a row whose byte of stop
+// is set and that is unfinished outside an EOS flush (needs_additional_steps <= 0) becomes a finished row -- it emits
+// (eos, speech_pad x 7) from the next step on and, in a static batch, is still evaluated like a row max_length finished
+// (active == 2: the reference may resurrect it for a flush); a row inside its flush stays unfinished.  ls->done is recomputed.
+struct StopMask { uint8_t row[MTTS_RCAP]; };      // one byte per sequence slot, passed by value
+void launch_stop_rows(const StopMask& stop, SeqState* seqs, RowMeta* meta, LoopState* ls, hipStream_t st);
 void launch_export_codes(const int32_t* gen, int64_t* codes, int B, int first, int n, int speech_offset, int clamp_hi,
                          int cap, hipStream_t st);
 

@@ -23,11 +23,11 @@ __device__ __forceinline__ bool sample_ctx(SampleCtx& x, int b, int c_in, const 
                                            const uint32_t* bitmaps, int bm_words, const MttsSamplerCfg* cfgs,
                                            const LoopState* ls, const SeqState* seqs, int single_vocab, int single_mask,
                                            int single_step, int single_channel, const uint32_t* bans = nullptr,
-                                           const uint32_t* bias_w = nullptr, const MttsBiasTable* bias_t = nullptr) {
+                                           const uint32_t* bias_w = nullptr, const MttsBiasTable* bias_t = nullptr, int ext = 0) {
     if (single_vocab > 0) {            // unit-test entry: one logits matrix [rows][vocab]
         x.c = single_channel; x.step = single_step; x.V = single_vocab; x.mask_id = single_mask;
         x.seed = 0; x.row_id = (uint32_t)b;
-        x.lg = LogitsPtr{logits0 + (size_t)b * x.V, 0};
+        x.lg = ext ? LogitsPtr{(const float*)logits0 + (size_t)b * x.V, 1} : LogitsPtr{logits0 + (size_t)b * x.V, 0};
         x.bm = bitmaps ? bitmaps + (size_t)b * bm_words : nullptr;
         x.ban = bans ? bans + (size_t)b * ((x.V + 31) >> 5) : nullptr;       // unit-test entry: [rows][ceil(vocab / 32)]
         x.bias_w = bias_w ? bias_w + (size_t)b * ((x.V + 31) >> 5) : nullptr;
@@ -45,7 +45,8 @@ __device__ __forceinline__ bool sample_ctx(SampleCtx& x, int b, int c_in, const 
             // channel-0 rows are padded to a multiple of 32 tokens (aligned rows: the head GEMM stores 8 bytes per lane)
             const size_t off = (x.c == 0) ? (size_t)b * ((V0 + 31) & ~31) : ((size_t)b * 7 + (x.c - 1)) * Vs_pad;
             const char* base = (const char*)((x.c == 0) ? logits0 : logits17);
-            x.lg = LogitsPtr{base + off * (ls->logits_f32 ? 4 : 2), ls->logits_f32};
+            const int f32 = ext ? 1 : ls->logits_f32;
+            x.lg = LogitsPtr{base + off * (f32 ? 4 : 2), f32};
         }
         // modeling_asteroid.py:124-128 (hard-coded ids 1024 / 152694 as in the reference)
         x.mask_id = -1;
@@ -59,5 +60,9 @@ __device__ __forceinline__ bool sample_ctx(SampleCtx& x, int b, int c_in, const 
     const MttsSamplerCfg cfg = cfgs[x.c];
     x.penalty = (x.bm && cfg.repetition_penalty > 0.f) ? cfg.repetition_penalty : 0.f;
     x.temp = cfg.temperature;
+    // externally scored rows (mtts_step_begin / mtts_step_finish): logits0 / logits17 are the caller's fp32 buffers in the
+    // layout above, holding what scores_materialize_kernel wrote and the caller's processors left -- the masks, the bans,
+    // the terms and the penalty are in them already; the temperature and everything behind it are still to come
+    if (ext) { x.mask_id = -1; x.ban = nullptr; x.bias_w = nullptr; x.bias_t = nullptr; x.penalty = 0.f; }
     return true;
 }

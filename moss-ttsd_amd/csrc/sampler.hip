@@ -133,7 +133,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_scan_kernel(
     const int b = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
+                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t, sc.ext)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     const bool want_hist = cfg.do_sample && cfg.top_k > 0 && cfg.top_k < x.V;
     for (int i = tid; i < 2048; i += SAMP_T) hist[i] = 0;
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_collect_kernel(
     const int b = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
+                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t, sc.ext)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     if (!cfg.do_sample) return;
     // no top-k (every finite score is a candidate) or a top_k beyond the candidate buffer: nothing to collect, the row
@@ -505,7 +505,7 @@ __device__ __forceinline__ void sample_final_body(
     const int b = blockIdx.y;
     SampleCtx x;
     if (!sample_ctx(x, b, blockIdx.x, logits0, logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, single_vocab,
-                    single_mask, single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
+                    single_mask, single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t, sc.ext)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     const bool big = single_vocab > 0 ? (single_vocab > SAMP_CAND) : (x.c == 0 && big_channel0);
     const int out_slot = b * 8 + x.c;
@@ -998,7 +998,7 @@ __device__ __forceinline__ void sample_full_body(
     if (!flag) return;
     SampleCtx x;
     if (!sample_ctx(x, b, 0, logits0, nullptr, V0, 0, 0, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
-                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
+                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t, sc.ext)) return;
     const MttsSamplerCfg cfg = cfgs[x.c];
     uint16_t* bins = (uint16_t*)(sc.full_val + (size_t)b * full_cap);  // level-0 bin of every token (0xffff: -inf)
     uint32_t* keys = (uint32_t*)(sc.full_idx + (size_t)b * full_cap);  // order-preserving key of every processed score
@@ -1277,6 +1277,95 @@ __global__ void update_kernel(const int32_t* __restrict__ decisions, int32_t* __
         ls->step = ls->step + 1;
         if (!any_unfinished) ls->done = 1;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The split step (mtts_step_begin / mtts_step_sample / mtts_step_finish): generate(logits_processor=, stopping_criteria=,
+// streamer=).  The step pauses between the heads and the sampler: scores_materialize_kernel hands the caller the rows HF's
+// built-in processors leave (reference modeling_asteroid.py:123-129 up to the caller's own list), the sampler kernels above
+// then run on what the caller made of them (SampleScratch::ext), step_tokens_kernel shows the appended tokens, and
+// stop_rows_kernel applies the caller's stopping criteria (:166-168).
+//
+// scores_materialize_kernel: grid (8, B) (the unit-test entry: (1, rows)), the gate of the sampler (sample_ctx).  The value
+// of token i is proc_score with x.temp = 0 -- the function every sampler pass reads through, so the row cannot drift from
+// what the unsplit step samples from; the sampler's only operation left on it is the division by the temperature, on the
+// same fp32 value.  Four tokens per thread and store: 16-byte vector stores, no atomics; the row's pad columns get -inf.
+#define MAT_T 256
+__global__ __launch_bounds__(MAT_T) void scores_materialize_kernel(
+    const uint16_t* __restrict__ logits0, const uint16_t* __restrict__ logits17, int V0, int Vs, int Vs_pad,
+    const uint32_t* __restrict__ bitmaps, int bm_words, const MttsSamplerCfg* __restrict__ cfgs, const LoopState* __restrict__ ls,
+    const SeqState* __restrict__ seqs, SampleScratch sc, float* __restrict__ out0, float* __restrict__ out17, int single_vocab,
+    int single_mask, int single_step, int single_channel) {
+    const int b = blockIdx.y, tid = threadIdx.x;
+    SampleCtx x;
+    if (!sample_ctx(x, b, blockIdx.x, logits0, logits17, V0, Vs, Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, single_vocab, single_mask,
+                    single_step, single_channel, sc.ban, sc.bias_w, sc.bias_t)) return;
+    x.temp = 0.f;
+    float* out;
+    int ld;                            // the row's length with its padding: a multiple of 32, so every 16-byte store stays inside
+    if (single_vocab > 0) { ld = (x.V + 31) & ~31; out = out0 + (size_t)b * ld; }
+    else if (x.c == 0) { ld = (V0 + 31) & ~31; out = out0 + (size_t)b * ld; }
+    else { ld = Vs_pad; out = out17 + ((size_t)b * 7 + (x.c - 1)) * Vs_pad; }
+    for (int i = tid * 4; i < ld; i += MAT_T * 4) {
+        f32x4_t v;
+        v.x = i < x.V ? proc_score(x, i) : -INFINITY;
+        v.y = i + 1 < x.V ? proc_score(x, i + 1) : -INFINITY;
+        v.z = i + 2 < x.V ? proc_score(x, i + 2) : -INFINITY;
+        v.w = i + 3 < x.V ? proc_score(x, i + 3) : -INFINITY;
+        *(f32x4_t*)(out + i) = v;
+    }
+}
+void launch_scores_materialize(const void* logits0, const void* logits17, int V0, int Vs, int Vs_pad, const uint32_t* bitmaps, int bm_words,
+                               const MttsSamplerCfg* cfgs, const LoopState* ls, const SeqState* seqs, int B, const SampleScratch& sc,
+                               float* out0, float* out17, hipStream_t st) {
+    hipLaunchKernelGGL(scores_materialize_kernel, dim3(8, B), dim3(MAT_T), 0, st, (const uint16_t*)logits0, (const uint16_t*)logits17, V0, Vs,
+                       Vs_pad, bitmaps, bm_words, cfgs, ls, seqs, sc, out0, out17, 0, 0, 0, 0);
+}
+void launch_scores_materialize_single(const void* logits, int rows, int vocab, const uint32_t* bitmap, int bm_words, const MttsSamplerCfg* cfgs8,
+                                      int mask_id, int step, int channel, const SampleScratch& sc, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(scores_materialize_kernel, dim3(1, rows), dim3(MAT_T), 0, st, (const uint16_t*)logits, (const uint16_t*)nullptr, vocab,
+                       vocab, vocab, bitmap, bm_words, cfgs8, (const LoopState*)nullptr, (const SeqState*)nullptr, sc, out, (float*)nullptr,
+                       vocab, mask_id, step, channel);
+}
+
+// One block; thread b handles sequence slot b: the tokens update_kernel has just appended, widened for a LongTensor.
+__global__ void step_tokens_kernel(const int32_t* __restrict__ cur_tokens, int64_t* __restrict__ tokens, const LoopState* __restrict__ ls) {
+    const int b = threadIdx.x;
+    if (b >= ls->B) return;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) tokens[b * 8 + c] = (int64_t)cur_tokens[b * 8 + c];
+}
+void launch_step_tokens(const int32_t* cur_tokens, int64_t* tokens, const LoopState* ls, hipStream_t st) {
+    hipLaunchKernelGGL(step_tokens_kernel, dim3(1), dim3(MTTS_RCAP), 0, st, cur_tokens, tokens, ls);
+}
+
+// One block; thread b handles sequence slot b, behind update_kernel of the same step.  Reference modeling_asteroid.py:166-168:
+// unfinished &= ~stop, then a row with needs_additional_steps > 0 stays unfinished.  update_kernel has applied the built-in
+// criteria (max_length, EOS, the end of a flush) already, so what is left is to finish the rows the caller stopped: like a
+// row max_length finished, a static batch keeps evaluating it (active == 2; its needs_additional_steps is < 0 here, since a
+// row with 0 is finished and one with > 0 is exempt), the scheduler frees its slot.
+__global__ void stop_rows_kernel(const StopMask stop, SeqState* __restrict__ seqs, RowMeta* __restrict__ meta,
+                                 LoopState* __restrict__ ls) {
+    __shared__ int any_unfinished;
+    if (ls->done) return;
+    const int b = threadIdx.x, B = ls->B;
+    if (b == 0) any_unfinished = 0;
+    __syncthreads();
+    if (b < B) {
+        SeqState s = seqs[b];
+        if (s.active && s.unfinished && stop.row[b] && s.nas <= 0) {
+            s.unfinished = 0;
+            s.active = ls->continuous ? 0 : 2;
+            meta[b].seq = s.active == 2 ? b : -1;
+            seqs[b] = s;
+        }
+        if (s.active && s.unfinished) atomicOr(&any_unfinished, 1);
+    }
+    __syncthreads();
+    if (b == 0 && !any_unfinished) ls->done = 1;
+}
+void launch_stop_rows(const StopMask& stop, SeqState* seqs, RowMeta* meta, LoopState* ls, hipStream_t st) {
+    hipLaunchKernelGGL(stop_rows_kernel, dim3(1), dim3(MTTS_RCAP), 0, st, stop, seqs, meta, ls);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

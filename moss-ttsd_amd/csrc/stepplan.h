@@ -84,6 +84,8 @@ struct StepState {
     bool bias_on = false;           // a channel has a sequence rule (mtts_set_sampler_bias): bias_kernel runs behind ban_kernel
     bool bias_terms = false;        // ... a finite one: the sampler reads the bias words and tables
     int topk = 0;
+    bool split = false;             // the step is issued in halves with the caller in between (mtts_step_begin / mtts_step_finish):
+                                    // the sampler reads the caller's fp32 score rows
     bool wseal_on[WSEAL_KINDS] = {false, false, false, false};       // the weight policy: the kind's decode GEMMs read the twin
     const char* pack_k_on = nullptr;    // [L] the KV read policy per layer; null: the engine keeps no sealed pages
     const char* pack_v_on = nullptr;
@@ -111,12 +113,13 @@ struct StepPlan {
     std::vector<LayerPlan> layers;  // empty on the F32 path
     bool forced = false, ch0_sampled = false, scores_on = false, floors_on = false, typical_on = false, bans_on = false, bias_on = false, bias_terms = false;
     int topk = 0;
+    bool split = false;             // issued in halves (mtts_step_begin / mtts_step_finish): never the unsplit step's captured graph
     int gemm_form[GEMM_KINDS] = {0, 0, 0, 0, 0, 0, 0};              // for describe(): a function of the fields above and the caps
     bool operator==(const StepPlan& o) const {
         return path == o.path && heads == o.heads && B == o.B && R == o.R && mb == o.mb && hmb == o.hmb && tiled == o.tiled &&
                lora == o.lora && fold == o.fold && std::equal(sealed, sealed + WSEAL_KINDS, o.sealed) &&
                head_persistent == o.head_persistent && layers == o.layers && forced == o.forced && ch0_sampled == o.ch0_sampled &&
-               scores_on == o.scores_on && floors_on == o.floors_on && typical_on == o.typical_on && bans_on == o.bans_on && bias_on == o.bias_on && bias_terms == o.bias_terms && topk == o.topk && std::equal(gemm_form, gemm_form + GEMM_KINDS, o.gemm_form);
+               scores_on == o.scores_on && floors_on == o.floors_on && typical_on == o.typical_on && bans_on == o.bans_on && bias_on == o.bias_on && bias_terms == o.bias_terms && topk == o.topk && split == o.split && std::equal(gemm_form, gemm_form + GEMM_KINDS, o.gemm_form);
     }
     bool operator!=(const StepPlan& o) const { return !(*this == o); }
 };
@@ -130,7 +133,7 @@ static inline StepPlan plan_step(const StepKnobs& k, const StepCaps& c, const St
     StepPlan p;
     const bool decode = s.heads == 1;
     p.heads = s.heads; p.B = s.B; p.R = s.R;
-    if (decode) { p.forced = s.forced; p.ch0_sampled = s.ch0_sampled; p.scores_on = s.scores_on; p.floors_on = s.floors_on; p.typical_on = s.typical_on; p.bans_on = s.bans_on; p.bias_on = s.bias_on; p.bias_terms = s.bias_on && s.bias_terms; p.topk = s.topk; }
+    if (decode) { p.forced = s.forced; p.ch0_sampled = s.ch0_sampled; p.scores_on = s.scores_on; p.floors_on = s.floors_on; p.typical_on = s.typical_on; p.bans_on = s.bans_on; p.bias_on = s.bias_on; p.bias_terms = s.bias_on && s.bias_terms; p.topk = s.topk; p.split = s.split; }
     if (c.f32) { p.path = PATH_F32; return p; }
     // decode steps of a few dialogues: six launches per layer whose prologues redo the small kernels' work.  The small path
     // has no slabs for an adapter's delta; its arithmetic is the general path's, so nothing depends on which one runs
@@ -188,8 +191,8 @@ static inline std::string describe(const StepPlan& p) {
     snprintf(buf, sizeof(buf), "pass: %s B=%d R=%d heads=%d layers=%d\n", paths[p.path], p.B, p.R, p.heads, (int)p.layers.size());
     std::string out = buf;
     if (p.heads == 1) {
-        snprintf(buf, sizeof(buf), "sample:%s%s%s%s%s%s%s topk=%d\n", p.ch0_sampled ? " ch0_sampled" : " ch0_greedy", p.scores_on ? " scores" : "",
-                 p.floors_on ? " floors" : "", p.typical_on ? " typical" : "", p.bans_on ? " bans" : "", p.bias_terms ? " bias" : p.bias_on ? " rules" : "", p.forced ? " forced" : "", p.topk);
+        snprintf(buf, sizeof(buf), "sample:%s%s%s%s%s%s%s topk=%d%s\n", p.ch0_sampled ? " ch0_sampled" : " ch0_greedy", p.scores_on ? " scores" : "",
+                 p.floors_on ? " floors" : "", p.typical_on ? " typical" : "", p.bans_on ? " bans" : "", p.bias_terms ? " bias" : p.bias_on ? " rules" : "", p.forced ? " forced" : "", p.topk, p.split ? " split" : "");
         out += buf;
     }
     if (p.path == PATH_F32) return out;

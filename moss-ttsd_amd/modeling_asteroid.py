@@ -515,7 +515,7 @@ class AsteroidTTSInstruct:
                  num_return_sequences=None, return_dict_in_generate=False, output_scores=False, adapter_names=None,
                  top_logprobs=None, min_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None,
                  suppress_tokens=None, min_new_tokens=None, typical_p=None, sequence_bias=None, bad_words_ids=None,
-                 min_length=None, begin_suppress_tokens=None, **kw):
+                 min_length=None, begin_suppress_tokens=None, logits_processor=None, stopping_criteria=None, streamer=None, **kw):
         """LongTensor[B,T,8], mask[B,T] -> LongTensor[B*n, T-7+G, 8] (generation_utils.py:406-409), n =
         num_return_sequences (keyword, else generation_config; HF: row b*n+j is take j of prompt b, as generate on the
         repeat-interleaved batch returns it).  The n takes of a prompt share its prefill and its complete KV pages.
@@ -534,7 +534,17 @@ class AsteroidTTSInstruct:
         act on greedy and sampled channels alike (mtts/ban_spec.py); refused with do_samples set, like the floors.
         sequence_bias / bad_words_ids / min_length / begin_suppress_tokens (HF's generate keywords; mtts/bias_spec.py): the
         same again -- an additive fp32 term on a token, always or behind a token sequence; multi-token bans; EOS kept out
-        while the channel is shorter than min_length; ids banned at the first free step.  Refused with do_samples set."""
+        while the channel is shorter than min_length; ids banned at the first free step.  Refused with do_samples set.
+        logits_processor / stopping_criteria / streamer (HF's generate keywords; the reference's _sample takes all three,
+        modeling_asteroid.py:53-61): any of them runs the call as a host loop over the engine's split step (_generate_hooked),
+        one round trip per step and no captured step graph.  Every processor is called as processor(input_ids[..., c],
+        scores_c) on each of the eight channels, behind the built-in processors and in front of the temperature and the
+        warpers -- HF's order; every criterion as criterion(input_ids[..., 0], None) after the step's tokens are appended;
+        the streamer gets the prompt, then next_tokens[:, 0].cpu() per step, then end().  Refused: logits_processor with
+        do_samples set (the reference's per-channel branch ignores the caller's list), more rows than MAX_ENGINE_BATCH, an
+        entry that is not callable, a streamer without put / end."""
+        processors, criteria = self._check_hooks(logits_processor, stopping_criteria, streamer)
+        hooked = bool(processors or criteria or streamer is not None)
         over = {k: v for k, v in (("min_p", min_p), ("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)) if v is not None}
         for name, v in over.items():
             warp_spec.check_floor(name, v, "generate(): ")
@@ -589,6 +599,9 @@ class AsteroidTTSInstruct:
             # HF GenerationMixin: greedy search returns one sequence per prompt
             raise ValueError("Greedy methods (do_sample != True) without beam search do not support `num_return_sequences` "
                              f"different than 1 (got {n}).")
+        if hooked and B * n > self.MAX_ENGINE_BATCH:
+            raise ValueError(f"generate(logits_processor / stopping_criteria / streamer) with {B * n} rows: the hooks run on one static batch "
+                             f"of at most {self.MAX_ENGINE_BATCH} rows (more go through the continuous batcher, whose steps are not split)")
         seed = self._next_seed(seed)
         ids = input_ids.detach().cpu().numpy()
         msk = attention_mask.detach().cpu().numpy()
@@ -600,7 +613,11 @@ class AsteroidTTSInstruct:
         # room for the reference's finished-row flushes past max_length: 14 steps at least, the whole chain
         # (6 * B + 8, include/mtts.h: mtts_generate) where that is cheap
         eng = self._get_engine(R, int(max_length) + 6 * min(R, self.MAX_ENGINE_BATCH) + 8)
-        if R <= self.MAX_ENGINE_BATCH:
+        if hooked:
+            out, lp, top = self._generate_hooked(eng, ids, msk, int(max_length), layers, do_samples, seed,
+                                                 [r * n + j for r in rows for j in range(n)], n, want_lp, row_adapters, k,
+                                                 processors, criteria, streamer, input_ids)
+        elif R <= self.MAX_ENGINE_BATCH:
             # one static batch, the reference's semantics: finished rows emit (eos, 1024 x 7) until the batch ends
             out = eng.generate(ids, msk, int(max_length), layers=layers, do_samples=do_samples, seed=seed,
                                row_ids=[r * n + j for r in rows for j in range(n)], takes=n, output_scores=want_lp,
@@ -619,6 +636,86 @@ class AsteroidTTSInstruct:
             go.logprobs, go.top_logprobs = torch.from_numpy(top[0]).to(dev), torch.from_numpy(top[2]).to(dev)
             go.top_ids = torch.from_numpy(top[1].astype(np.int64)).to(dev)
         return go
+
+    def _check_hooks(self, logits_processor, stopping_criteria, streamer):
+        """generate()'s three hooks -> (processors, criteria) as lists; ValueError before any engine work.  None and an empty
+        list are the same: nothing to call."""
+        processors = [] if logits_processor is None else (list(logits_processor) if isinstance(logits_processor, (list, tuple)) or
+                                                          not callable(logits_processor) else [logits_processor])
+        criteria = [] if stopping_criteria is None else (list(stopping_criteria) if isinstance(stopping_criteria, (list, tuple)) or
+                                                         not callable(stopping_criteria) else [stopping_criteria])
+        for i, p in enumerate(processors):
+            if not callable(p):
+                raise ValueError(f"logits_processor[{i}] ({type(p).__name__}) is not callable: a processor is called as "
+                                 "processor(input_ids, scores) -> scores")
+        for i, c in enumerate(criteria):
+            if not callable(c):
+                raise ValueError(f"stopping_criteria[{i}] ({type(c).__name__}) is not callable: a criterion is called as "
+                                 "criterion(input_ids, scores) -> bool per row")
+        if streamer is not None and not (callable(getattr(streamer, "put", None)) and callable(getattr(streamer, "end", None))):
+            raise ValueError(f"streamer ({type(streamer).__name__}) needs put(tokens) and end(), as transformers' BaseStreamer has them")
+        if processors and self.generation_config.do_samples is not None:
+            raise ValueError("generate(logits_processor=...) with generation_config.do_samples set: the reference's per-channel branch "
+                             "builds its processors from generation_config.layers[i] and ignores the caller's list "
+                             "(modeling_asteroid.py:95-106); unset do_samples to run the global branch")
+        return processors, criteria
+
+    def _generate_hooked(self, eng, ids, msk, max_length, layers, do_samples, seed, row_ids, takes, output_scores, row_adapters,
+                         top_logprobs, processors, criteria, streamer, input_ids):
+        """generate() with the caller's hooks: the reference's loop (modeling_asteroid.py:110-185) on the host, one split engine
+        step per turn (mtts.engine.Engine.step_begin / step_sample / step_finish).  `input_ids` of the hooks is the reference's:
+        the [rows, cur_len, 8] history on the device, left pads included, grown by each step's tokens.
+        -> (sequences, lp or None, top or None) as Engine.generate returns them."""
+        B, T, C = ids.shape
+        base, R = T - 7, B * takes
+        eng.begin(ids, msk, max_length, layers=layers, do_samples=do_samples, seed=seed, row_ids=row_ids, takes=takes,
+                  output_scores=output_scores, row_adapters=row_adapters, top_logprobs=top_logprobs)
+        try:
+            if streamer is not None:
+                streamer.put(input_ids.cpu() if torch.is_tensor(input_ids) else torch.from_numpy(ids))     # HF: the prompt first
+            hist, cur, steps, done = None, base, 0, False
+            while not done:
+                s0, s17, _ = eng.step_begin(want_rows=False)
+                if hist is None:                   # one buffer for the whole run; the hooks see views of its first cur slots
+                    hist = torch.zeros((R, base + 64, C), dtype=torch.int64, device=s0.device)
+                    hist[:, :base] = torch.from_numpy(np.repeat(ids[:, :base], takes, axis=0)).to(s0.device)
+                for c in range(C if processors else 0):
+                    view = s0 if c == 0 else s17[:, c - 1]
+                    scores = view
+                    for p in processors:
+                        scores = p(hist[:, :cur, c], scores)
+                    if scores is not view:
+                        if not torch.is_tensor(scores) or tuple(scores.shape) != tuple(view.shape):
+                            got = tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__
+                            raise ValueError(f"logits_processor returned {got} on channel {c}, expected a tensor of shape {tuple(view.shape)}")
+                        view.copy_(scores)
+                toks = eng.step_sample()
+                if cur == hist.shape[1]:
+                    hist = torch.cat([hist, torch.zeros_like(hist)], dim=1)
+                hist[:, cur] = toks
+                cur += 1
+                if streamer is not None:           # in front of this step's stopping criteria, as in the reference (:161-168)
+                    streamer.put(toks[:, 0].cpu())
+                stop = None
+                for crit in criteria:
+                    r = torch.as_tensor(crit(hist[:, :cur, 0], None)).to(device=toks.device, dtype=torch.bool)
+                    r = r.expand(R) if r.dim() == 0 else r.reshape(R)
+                    stop = r if stop is None else (stop | r)
+                eng.step_finish(stop)
+                steps, done = eng.sync_state()
+            if streamer is not None:
+                streamer.end()
+        except BaseException:
+            try:        # the run is abandoned mid-flight: end it, so that the next one may start with other settings
+                eng.sched_open(1, 8, output_scores=output_scores, top_logprobs=top_logprobs)
+            except Exception:
+                pass
+            raise
+        gen = eng.read_generated(steps)                                     # [steps, R, 8]
+        out = np.concatenate([np.repeat(ids[:, :base], takes, axis=0), np.ascontiguousarray(gen.transpose(1, 0, 2))], axis=1)
+        lp = np.ascontiguousarray(eng.read_scores(steps).transpose(1, 0, 2)) if output_scores else None
+        top = tuple(np.ascontiguousarray(np.swapaxes(a, 0, 1)) for a in eng.read_top_logprobs(steps)) if top_logprobs else None
+        return out, lp, top
 
     def _next_seed(self, seed):
         """Philox key of this call.  Explicit `seed=` / `generation_config.seed` / `model.sample_seed` win; otherwise it

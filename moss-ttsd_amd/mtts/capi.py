@@ -90,6 +90,11 @@ _SIGS = {
     "mtts_begin": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                C.POINTER(MttsSamplerCfg), C.c_uint64, C.c_void_p]),
     "mtts_step": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mtts_step_begin": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_step_sample": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_step_finish": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtts_k_scores_materialize": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(MttsSamplerCfg), C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtts_sync_state": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "mtts_read_generated": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "mtts_set_output_scores": (C.c_int32, [C.c_void_p, C.c_int32]),

@@ -367,6 +367,57 @@ class Engine:
         """Issue n decode steps on `stream` (torch.cuda.Stream; default: the device's default stream)."""
         capi.check(self.lib.mtts_step(self._h, int(n), C.c_void_p(stream.cuda_stream) if stream is not None else None))
 
+    # ---- the split step: the caller between the heads and the sampler (include/mtts.h: mtts_step_begin) --------------
+    def _split_buffers(self):
+        """The score rows of a split step, allocated by torch once per run shape and padded as the logits are."""
+        V0p, Vsp = (self.cfg["vocab_size"] + 31) // 32 * 32, (self.cfg["speech_vocab_size"] + 31) // 32 * 32
+        bufs = getattr(self, "_split", None)
+        if bufs is None or bufs[0].shape != (self._B, V0p) or bufs[1].shape != (self._B, 7, Vsp):
+            bufs = (torch.full((self._B, V0p), float("-inf"), dtype=torch.float32, device=self.device),
+                    torch.full((self._B, 7, Vsp), float("-inf"), dtype=torch.float32, device=self.device),
+                    torch.zeros((self._B, 8), dtype=torch.int64, device=self.device))
+            torch.cuda.synchronize(self.device)
+            self._split = bufs
+        return bufs
+
+    def step_begin(self, stream=None, want_rows=True):
+        """The first half of one decode step of a run started with begin(): everything in front of the sampler.
+        -> (scores0 float32 [B, vocab_size], scores17 float32 [B, 7, speech_vocab_size], rows): CUDA views of buffers that
+        live as long as the run's shape, holding for every (row, channel) the sampler evaluates this step the scores HF's
+        built-in processors leave -- the reference's two masks, the run's bans and sequence rules, the repetition penalty;
+        no temperature.  Edit them in place (on `stream`, or synchronise yourself): step_sample() samples from what they
+        hold.  rows: bool [B], the rows evaluated (finished rows that cannot come back are skipped: their score rows are
+        stale and ignored); want_rows=False: None, and no device synchronisation."""
+        s0, s17, _ = self._split_buffers()
+        rows = None
+        if want_rows:
+            st = self.slot_states()
+            rows = (st[:, 0] != 0) & ((st[:, 1] != 0) | (st[:, 0] == 2))
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        capi.check(self.lib.mtts_step_begin(self._h, s0.data_ptr(), s17.data_ptr(), sp))
+        return s0[:, :self.cfg["vocab_size"]], s17[:, :, :self.cfg["speech_vocab_size"]], rows
+
+    def step_sample(self, stream=None):
+        """Between step_begin() and step_finish(): the sampler on the score rows as they stand (temperature, the warpers, argmax
+        or the Philox draw; a row of -inf gives token 0 with a NaN score) and the state machine.  -> int64 [B, 8] CUDA tensor,
+        the tokens the step appended (padding and flushes included); overwritten by the next step_sample()."""
+        toks = self._split_buffers()[2]
+        capi.check(self.lib.mtts_step_sample(self._h, toks.data_ptr(), C.c_void_p(stream.cuda_stream) if stream is not None else None))
+        return toks
+
+    def step_finish(self, stop=None, stream=None):
+        """The rest of the step: `stop` (bool [B] or None) finishes rows as a stopping criterion of the reference does
+        (modeling_asteroid.py:166-168: a row inside its EOS flush finishes the flush first; a stopped row emits
+        (eos, speech_pad x 7) from the next step on), then the KV page bookkeeping and the forward pass.  Runs step_sample()
+        itself when the caller did not."""
+        m = None
+        if stop is not None:
+            m = np.ascontiguousarray(np.asarray(stop.cpu() if torch.is_tensor(stop) else stop).astype(bool).astype(np.uint8))
+            if m.shape != (self._B,):
+                raise ValueError(f"stop has shape {m.shape}, the run has {self._B} rows")
+        capi.check(self.lib.mtts_step_finish(self._h, None if m is None else m.ctypes.data,
+                                             C.c_void_p(stream.cuda_stream) if stream is not None else None))
+
     def sync_state(self, stream=None):
         s, d = C.c_int32(0), C.c_int32(0)
         capi.check(self.lib.mtts_sync_state(self._h, C.byref(s), C.byref(d),
